@@ -14,7 +14,10 @@ fp32 accumulation, inputs resident in HBM.  N > 1 shards independent streams ove
 scaling, no data-path collective) and gathers boxes/masks with one RCCL all_gather at the end
 of the K frames, inside the timed region.
 
-Prints ONE JSON line (driver contract) with two extra objects:
+Prints ONE JSON line (driver contract).  A plain run sets up, warms up, times the K steps and prints it:
+`value` (frames/sec) and `ms_per_step` (milliseconds per timed step) are the headline.  With --full the line also
+carries everything measured beside it (the 200-step repeat, per-frame latency, serial steps, the secondary
+workloads, the argmax statistic, the vendor baseline), among them:
   roofline     -- dominant kernel family (the MFMA implicit-GEMM convolutions: conv_igemm_kernel, its 3x3
                   patch-sharing sibling conv3x3_halo_kernel, the register-fed conv_wreg_kernel and the persistent
                   per-XCD conv_seq_kernel that runs whole ResNet stages at B = 8): algorithmic FLOPs of its
@@ -22,6 +25,8 @@ Prints ONE JSON line (driver contract) with two extra objects:
                   library's per-launch profiler (smk_profile);
   cpu_baseline -- the CPU port of the reference op sequence (oracle/torch_port.py) timed on
                   this host's cores on a bounded sample (rank 0, N=1 only).
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (dump_outputs); the inputs
+depend on the arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -125,13 +130,16 @@ class Workload(object):
                 m.template(self.z)
                 o = m.track_step(x, self.twh, refine=self.refine, stage=False)
             self.last = (o["box"], o["loc"], o["mask"], o["refine"])
+            self.outputs = o
         elif self.variant == "rpn":
             cls, loc = m.track(x)
             self.last = (cls, loc, None, None)
+            self.outputs = {"cls": cls, "loc": loc}
         else:
             cls, loc, mask = m.track_mask(x)
             ref = m.track_refine(self.pos) if self.refine else None
             self.last = (cls, loc, mask, ref)
+            self.outputs = {"cls": cls, "loc": loc, "mask": mask, "refine": ref}
         return self.last
 
     def gflop_per_frame(self):
@@ -154,7 +162,9 @@ class StubWorkload(object):
         self.ref = torch.zeros(batch, spec.REFINE_OUT ** 2)
 
     def step(self, i):
-        return self.boxes + float(i), None, None, self.ref
+        box = self.boxes + float(i)
+        self.outputs = {"box": box, "refine": self.ref}
+        return box, None, None, self.ref
 
     def gflop_per_frame(self):
         return 0.0
@@ -267,6 +277,39 @@ def timed_run(w, steps, warmup, world, gather, res=None):
     w.last_timing = {"host_enqueue_ms_per_step": round(t_enq / steps * 1e3, 4),
                      "gpu_event_ms_per_step": round(ev0.elapsed_time(ev1) / steps, 4) if cuda else None}
     return dt
+
+
+DUMP_WHOLE_BYTES = 16 << 20        # an output up to this size (as float32) is written whole ...
+DUMP_SAMPLE = 4 << 20              # ... a larger one as this many elements at fixed, seeded flat indices
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(w, out_dir):
+    """--dump-outputs: what the timed path returned to its caller in the last timed step (Workload.outputs), one
+    <name>.npy per array -- float64 where the path returns float64 (the decoded box), else float32.  An array larger than
+    DUMP_WHOLE_BYTES is written as its flattened elements at the distinct sorted indices of DUMP_SAMPLE draws from a fixed
+    seed (the same indices in every run of the same shape); <name>.npy is then that 1-D sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    w.sync()
+    written, total = {}, 0
+    for name, t in sorted(w.outputs.items()):
+        if t is None:
+            continue
+        t = t.detach()
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        entry = {"shape": list(t.shape), "dtype": str(dt).replace("torch.", "")}
+        if t.numel() * 4 > DUMP_WHOLE_BYTES:
+            g = np.random.Generator(np.random.PCG64(20261016))
+            idx = np.unique(g.integers(0, t.numel(), size=DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry["sampled_elements"] = int(idx.size)
+        a = t.to(dt).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit("--dump-outputs: the outputs exceed %d MB" % (DUMP_LIMIT_BYTES >> 20))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = entry
+    return written
 
 
 def frame_latency(w, n=40):
@@ -741,6 +784,13 @@ def main():
                     help="placement report instead of a measurement: every rank prints its device, CU count, XCD census "
                          "(is the persistent sequence kernel usable there?), PCI / NUMA node and CPU affinity; rank 0 prints one JSON line")
     ap.add_argument("--vendor-leg", action="store_true", help=argparse.SUPPRESS)     # child process of vendor_baseline_guarded
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the 200-step repeat, per-frame latency, serial steps, roofline, "
+                         "secondary workloads, argmax statistic, vendor and CPU baselines (each still subject to the --no-* options); "
+                         "without it a run sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64; arrays above 16 MB as a fixed, seeded sample of 4 Mi elements); rank 0 only")
     args = ap.parse_args()
 
     if args.vendor_leg:
@@ -785,17 +835,20 @@ def main():
     main_timing = dict(w.last_timing)
     frames = w.B * world * args.steps
     fps = frames / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(w, args.dump_outputs)
     # the same loop over 200 steps beside the driver's 20 (12 ms of GPU time is thin on a fleet whose boxes differ by +-12 %):
     # reported next to `value`, never instead of it
     long_run = None
-    if not args.stub and world == 1 and args.steps < 200 and not args.no_long:
+    if args.full and not args.stub and world == 1 and args.steps < 200 and not args.no_long:
         res200 = Results(w, 200)                    # (re-points the result ring at 200 fresh rows)
         d200 = timed_run(w, 200, 5, 1, gather, res200)
         long_run = {"steps": 200, "value": round(w.B * 200 / d200, 2), "ms_per_step": round(d200 / 200 * 1e3, 4)}
         del res200
 
     latency = serial_cmp = None
-    if not args.stub and world == 1 and w.fused:
+    if args.full and not args.stub and world == 1 and w.fused:
         try:
             latency = frame_latency(w)
             if w.pipeline and not args.no_long:
@@ -829,7 +882,7 @@ def main():
         except Exception:
             pass
     roof, recs = None, []
-    if not args.stub:
+    if args.full and not args.stub:
         try:
             roof, recs = roofline(w)
         except Exception as e:  # the profiler pass must never cost the contract line its `value`
@@ -843,7 +896,7 @@ def main():
             json.dump({"workload": args.workload, "batch": w.B, "dtype": w.dtype, "layers": recs}, f, indent=1)
 
     also = {}
-    if rank == 0 and world == 1 and not args.no_also and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.no_also and not args.stub:
         for name in ("sharp_b8_f32", "sharp_b8_f16x3", "base_b1_f32", "sharp_b1_f16", "sharp_b16_f16", "sharp_b64_f16"):
             if name == args.workload:
                 continue
@@ -863,7 +916,7 @@ def main():
                 also[name] = {"error": str(e)[:200]}
 
     agree = vendor = None
-    if rank == 0 and world == 1 and not args.no_also and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.no_also and not args.stub:
         del w.model
         torch.cuda.empty_cache()
         try:
@@ -877,7 +930,7 @@ def main():
             vendor = {"error": str(e)[:200]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stub:
         try:
             cpu = cpu_baseline()
         except Exception as e:  # noqa: BLE001 -- a reported baseline, never a reason to lose the line
@@ -917,7 +970,10 @@ def main():
             "tflops_end_to_end": round(fps / world * w.gflop_per_frame() / 1e3, 2),
             "timing": main_timing,
             "also": also or None,
+            "full": args.full,
         }
+        if args.dump_outputs:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(line), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -64,3 +64,35 @@ def test_dry_run_reports_every_rank_and_its_host_placement():
     assert len({x["pid"] for x in line["ranks"]}) == 2
     for x in line["ranks"]:
         assert x["host_placement"]["cpus"] >= 1
+
+
+def test_dump_outputs_writes_the_last_step_and_is_repeatable(tmp_path):
+    """`--dump-outputs DIR`: the arrays the timed path returned in its last step, as float32 / float64 .npy files named in
+    the line; two runs with the same arguments write the same values"""
+    import numpy as np
+    got = []
+    for k in (1, 2):
+        d = tmp_path / ("run%d" % k)
+        r = _run(["--stub", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_line(r.stdout)
+        assert line["full"] is False and line["steps"] == 3 and line["ms_per_step"] > 0
+        assert sorted(line["outputs"]["arrays"]) == ["box", "refine"]
+        arrs = {n: np.load(str(d / (n + ".npy"))) for n in line["outputs"]["arrays"]}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["box"].shape == (8, 8) and float(arrs["box"][0, 0]) == 2.0     # StubWorkload: boxes + step index 2
+        got.append(arrs)
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n]), n
+
+
+def test_plain_line_leaves_the_secondary_measurements_to_full():
+    r = _run(["--stub", "--steps", "2", "--warmup", "0"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = _json_line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["full"] is False and line["cpu_baseline"] is None and line["roofline"] is None and line["also"] is None
+    r = _run(["--stub", "--steps", "2", "--warmup", "0", "--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _json_line(r.stdout)["full"] is True

@@ -176,8 +176,18 @@ def test_tuning_knobs_read_back():
     """smk_tune / smk_tune_get need no GPU: a knob reads back what was set, unknown names and out-of-range values are errors,
     and the defaults are the measured ones (four producer waves, the layer rule fitted with them, 128-row sequence tiles)."""
     from siammask_amd import _lib
-    assert (_lib.tune_get("npw"), _lib.tune_get("wreg_policy"), _lib.tune_get("seq_tall"), _lib.tune_get("a_stage")) == (4, 1, 2, 0)
-    assert _lib.tune_get("seq_fuse") == 1 and _lib.tune_get("seq_fused_last") == 0      # conv3 + next conv1 pairs fused; nothing launched
+    # the defaults are process-wide state that earlier tests of the same process may have moved (seq_fused_last records the
+    # last sequence launched): read them in a fresh interpreter
+    import json
+    import subprocess
+    import sys
+    code = ("import json; from siammask_amd import _lib; print(json.dumps([_lib.tune_get(k) for k in "
+            "('npw', 'wreg_policy', 'seq_tall', 'a_stage', 'seq_fuse', 'seq_fused_last')]))")
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    npw, wreg_policy, seq_tall, a_stage, seq_fuse, seq_fused_last = json.loads(r.stdout.strip().splitlines()[-1])
+    assert (npw, wreg_policy, seq_tall, a_stage) == (4, 1, 2, 0)
+    assert seq_fuse == 1 and seq_fused_last == 0      # conv3 + next conv1 pairs fused; nothing launched
     old = _lib.tune_get("npw")
     try:
         _lib.tune(npw=2)

@@ -1,6 +1,7 @@
 """State-dict contract: the drop-in Custom exposes exactly the
 reference's parameter/buffer names and shapes, and a checkpoint saved for the reference loads
 through the reference's UNCHANGED utils/load_helper.load_pretrain."""
+import json
 import os
 import sys
 import tempfile
@@ -43,17 +44,19 @@ def _reference_custom(variant):
     return import_reference_custom(variant)
 
 
-@pytest.mark.reference
 @pytest.mark.parametrize("variant", spec.VARIANTS)
 def test_names_and_shapes_equal_reference(variant):
-    ref = _reference_custom(variant)(anchors={"stride": 8, "ratios": [0.33, 0.5, 1, 2, 3], "scales": [8], "round_dight": 0})
+    """against the reference's own Custom as recorded in tests/golden/reference_state_dict.json (oracle/make_spec_golden.py)"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_state_dict.json")) as f:
+        gold = json.load(f)
+    ref = gold["variants"][variant]
     ours = build(variant)
-    rsd, osd = ref.state_dict(), ours.state_dict()
-    assert list(rsd.keys()) == list(osd.keys())
-    for k in rsd:
-        assert tuple(rsd[k].shape) == tuple(osd[k].shape), k
-        assert rsd[k].dtype == osd[k].dtype, k
-    assert ours.anchors == ref.anchors and ours.anchor_num == ref.anchor_num
+    osd = ours.state_dict()
+    assert [k for k, _, _ in ref["state_dict"]] == list(osd.keys())
+    for k, shape, dtype in ref["state_dict"]:
+        assert list(osd[k].shape) == shape, k
+        assert str(osd[k].dtype) == "torch." + dtype, k
+    assert ours.anchors == ref["anchors"] == gold["anchors_cfg"] and ours.anchor_num == ref["anchor_num"]
 
 
 @pytest.mark.reference
