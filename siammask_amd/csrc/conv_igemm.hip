@@ -960,9 +960,8 @@ __global__ __launch_bounds__(512, (NPATCH == 2 ? 2 : 4)) void conv3x3_halo_kerne
 
 // host side: eligibility + launch.  Returns 1 when the geometry does not fit (caller falls back to the
 // generic kernel), 0 on success, < 0 on launch errors.  p.wgt must be the chunk-major weight pack.
-template <typename T, int WM, int WN, int WK, int AROWS, int NSLOT, int NPATCH>
-static int launch_halo_t(const ConvParams &p, hipStream_t s) {
-    constexpr int BM = 64 * WM, BN = 64 * WN;
+// activation rows (of the padded input) the patch of the worst BM-pixel workgroup spans
+static int halo_patch_rows(const ConvParams &p, int BM) {
     const int howo = p.Ho * p.Wo, Wp = p.Wl + 2 * p.pad;
     const int tpi = (howo + BM - 1) / BM;
     int worst = 0;
@@ -972,29 +971,43 @@ static int launch_halo_t(const ConvParams &p, hipStream_t s) {
         const int rows = oyl * Wp + oxl - (oy0 * Wp + ox0) + 2 * p.dil * Wp + 2 * p.dil + 1;
         if (rows > worst) worst = rows;
     }
-    if (worst > AROWS) return 1;
+    return worst;
+}
+constexpr int HALO_AROWS_128 = 320, HALO_AROWS_64 = 224;     // patch rows the BM = 128 / 64 instantiations stage
+
+template <typename T, int WM, int WN, int WK, int AROWS, int NSLOT, int NPATCH>
+static int launch_halo_t(const ConvParams &p, hipStream_t s) {
+    constexpr int BM = 64 * WM, BN = 64 * WN;
+    const int tpi = (p.Ho * p.Wo + BM - 1) / BM;
+    if (halo_patch_rows(p, BM) > AROWS) return 1;
     dim3 grid(p.B * tpi * ((p.Nst + BN - 1) / BN));
     hipLaunchKernelGGL((conv3x3_halo_kernel<T, WM, WN, WK, AROWS, NSLOT, NPATCH>), grid, dim3(512), 0, s, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-int launch_conv_halo(const ConvParams &p, int dtype, int bm, void *stream) {
-    hipStream_t s = (hipStream_t)stream;
+bool conv_halo_eligible(const ConvParams &p, int dtype, int bm) {
     const int ch = dtype == DT_F16 ? 64 : 32;
     if (p.kh != 3 || p.kw != 3 || p.stride != 1 || p.stride_x != 1 || p.ups || p.groups > 1 || p.Ci % ch != 0 ||
         p.out_mode != OUT_NHWC || !p.buf_lds || p.Wo != p.Wl + 2 * p.pad - 2 * p.dil)
-        return 1;
+        return false;
+    return halo_patch_rows(p, bm == 128 ? 128 : 64) <= (bm == 128 ? HALO_AROWS_128 : HALO_AROWS_64);
+}
+
+int launch_conv_halo(const ConvParams &p, int dtype, int bm, void *stream) {
+    hipStream_t s = (hipStream_t)stream;
+    const int ch = dtype == DT_F16 ? 64 : 32;
+    if (!conv_halo_eligible(p, dtype, bm)) return 1;
     // BM = 64 with more than one channel chunk and at most one workgroup per CU: double-buffered patch (104 KB of
     // LDS, which such a launch cannot use otherwise).  g_tune.halo_db = 0 keeps the single-buffered kernel.
     const int ch_n = p.Ci / ch;
     const long wgs64 = (long)p.B * ((p.Ho * p.Wo + 63) / 64) * ((p.Nst + 127) / 128);
     const bool db = bm == 64 && g_tune.halo_db && ch_n >= 2 && wgs64 <= 256;
     if (dtype == DT_F16) {
-        if (bm == 128) return launch_halo_t<_Float16, 2, 2, 1, 320, 2, 1>(p, s);
-        return db ? launch_halo_t<_Float16, 1, 2, 2, 224, 3, 2>(p, s) : launch_halo_t<_Float16, 1, 2, 2, 224, 3, 1>(p, s);
+        if (bm == 128) return launch_halo_t<_Float16, 2, 2, 1, HALO_AROWS_128, 2, 1>(p, s);
+        return db ? launch_halo_t<_Float16, 1, 2, 2, HALO_AROWS_64, 3, 2>(p, s) : launch_halo_t<_Float16, 1, 2, 2, HALO_AROWS_64, 3, 1>(p, s);
     }
-    if (bm == 128) return launch_halo_t<float, 2, 2, 1, 320, 2, 1>(p, s);
-    return db ? launch_halo_t<float, 1, 2, 2, 224, 3, 2>(p, s) : launch_halo_t<float, 1, 2, 2, 224, 3, 1>(p, s);
+    if (bm == 128) return launch_halo_t<float, 2, 2, 1, HALO_AROWS_128, 2, 1>(p, s);
+    return db ? launch_halo_t<float, 1, 2, 2, HALO_AROWS_64, 3, 2>(p, s) : launch_halo_t<float, 1, 2, 2, HALO_AROWS_64, 3, 1>(p, s);
 }
 
 // ---------------------------------------------------------------------------------------------

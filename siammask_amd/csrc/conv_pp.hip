@@ -346,11 +346,12 @@ void conv_pp_kernel(const ConvParams p) {
 }
 
 // f16, NHWC epilogue, one group, plain [Npad][Kpad] pack, channels a power of two >= one K tile (a K tile never straddles a tap), the
-// whole input tensor as the logical image (no window / upsampling / per-stream origin), 32-bit buffer offsets
+// whole input tensor as the logical image (no window / upsampling / per-stream origin), 32-bit buffer offsets, no split operand
 bool conv_pp_eligible(const ConvParams &p, int dtype) {
     return dtype == DT_F16 && p.out_mode == OUT_NHWC && p.wgt != nullptr && p.buf_lds && (p.Kpad % 128) == 0 && p.groups <= 1 &&
            p.ci_shift >= 6 && !p.ups && !p.pos && p.org_y == 0 && p.org_x == 0 && p.Hl == p.Hs && p.Wl == p.Ws &&
-           p.in_bytes < 0x7fff0000u && p.w_bytes < 0x7fff0000u && (p.Nst % 8) == 0 && !p.x3_out && !p.x3_res;
+           p.in_bytes < 0x7fff0000u && p.w_bytes < 0x7fff0000u && (p.Nst % 8) == 0 && !p.x3_out && !p.x3_res && !p.x3_in && !p.x3_ct &&
+           !p.oscale;
 }
 
 int launch_conv_pp(const ConvParams &p, void *stream) {

@@ -25,6 +25,7 @@
 
 #include "../../include/siammask_hip.h"
 #include "../../include/siammask_hip_test.h"
+#include "conv_plan.h"
 #include "smk_kernels.h"
 
 using namespace smk;
@@ -93,25 +94,6 @@ struct ConvPart {
     std::string bias;   // "<name>.bias" or ""
 };
 
-struct PackedConv {
-    void *w = nullptr;       // device [rows][Kpad] dtype
-    void *w_halo = nullptr;  // same weights, K ordered (chunk, kh, kw, c in chunk) for conv3x3_halo_kernel (3x3 only)
-    void *w_frag = nullptr;  // same weights in MFMA-fragment order for conv_wreg_kernel (f16 only)
-    void *w_frag_halo = nullptr;  // 3x3, f16: the chunk-major matrix (w_halo's K order) in MFMA-fragment order (wreg_halo_tile, sequences)
-    void *w_frag16 = nullptr; // small packs (<= 256 rows, K <= 640: layer1): fragment order of v_mfma_f32_16x16x32_f16 (l1_block_kernel)
-    float *bias = nullptr;   // device [rows] f32
-    int N = 0;               // real output channels per group
-    int rows = 0;            // total rows (all groups), multiple of NPAD_ALIGN
-    int group_rows = 0;      // rows per group
-    int groups = 1;
-    int Ci = 0, k = 1, K = 0, Kpad = 0;
-    int kw = 0;              // horizontal taps when != k (pixel-pair stem)
-    int alg_k = 0;           // algorithmic K (real multiply-accumulates per output) when the pack pads K
-    float *oscale = nullptr; // DT_F16X3: device [rows] f32, the inverse of the power-of-two scale each row of the split pack carries (ConvParams::oscale)
-    int x3_ct = 0, x3_nreal = 0;   // DT_F16X3, w_frag in FUSED order (ConvParams::x3_ct): channels / 64, activation tiles per K loop
-    bool x3 = false;         // DT_F16X3: K tripled -- per tap [w_hi | w_lo | w_hi] against the operand [hi | hi | lo] gathered from the stored planes [hi | lo]; Ci = 3 x channels
-};
-
 constexpr size_t KS_PART_FLOATS = 8u << 20;      // 32 MB: e.g. 256 tiles x 4 parts x 64x128
 constexpr int KS_CNT = 8192;
 constexpr size_t DEC_SCRATCH_PER_STREAM = 8 * 8 + 64 * 8 + 8 * 4 + 4;     // decode_kernel's cross-workgroup scratch
@@ -129,8 +111,6 @@ constexpr int PIPE_JOIN = 1, PIPE_SIG = 2, PIPE_EAGER = 0, PIPE_TWO_FORM = 1;
 #endif
 
 static size_t esize(int dtype) { return dtype == DT_F32 ? 4 : 2; }
-// DT_F16X3 contexts (smk_kernels.h): the KERNELS are the fp16 ones; what changes is which packs exist and how many channel planes a tensor has
-static int kdtype(int dtype) { return dtype == DT_F16X3 ? DT_F16 : dtype; }
 
 // host-side packing of ONE weight tensor [Cout][Cin][k][k] (already scaled) into rows of a
 // [rows][Kpad] matrix with K ordered (ky, kx, cin_padded)
@@ -145,10 +125,18 @@ static void pack_rows(std::vector<float> &dst, int row0, int Kpad, const float *
                 }
 }
 
+// Which derived copies of a pack exist (the packer makes them, smk_host_plan_conv fakes them from the same rules)
+static bool has_frag_pack(const PackedConv &pc, int dtype) { return dtype == DT_F16 && pc.rows % 32 == 0 && pc.Kpad % 16 == 0; }
+static bool has_frag16_pack(const PackedConv &pc, int dtype) {
+    return has_frag_pack(pc, dtype) && pc.rows <= 256 && pc.Kpad <= 640 && pc.Kpad % 32 == 0 && pc.groups == 1;
+}
+static bool has_halo_pack(const PackedConv &pc, int dtype) { return pc.k == 3 && pc.kw == 0 && pc.Ci % (dtype == DT_F16 ? 64 : 32) == 0; }
+static bool has_frag_halo_pack(const PackedConv &pc, int dtype) { return has_halo_pack(pc, dtype) && has_frag_pack(pc, dtype) && pc.Kpad == 9 * pc.Ci; }
+
 // fragment-order copy of an f16 pack for conv_wreg_kernel: one contiguous KB per (32 rows, 16 k) MFMA operand --
 // [rows/32][Kpad/16][lane 0..63][8 halves] with lane = (n % 32) + 32 * ((k % 16) / 8), element e = k % 8
 static int upload_frag_pack(PackedConv &pc, const std::vector<float> &rows_f32, int dtype) {
-    if (dtype != DT_F16 || pc.rows % 32 || pc.Kpad % 16) return 0;
+    if (!has_frag_pack(pc, dtype)) return 0;
     const int KS16 = pc.Kpad / 16;
     std::vector<_Float16> h((size_t)pc.rows * pc.Kpad);
     for (int n = 0; n < pc.rows; ++n) {
@@ -161,7 +149,7 @@ static int upload_frag_pack(PackedConv &pc, const std::vector<float> &rows_f32, 
     }
     HIPCHK(hipMalloc(&pc.w_frag, h.size() * 2));
     HIPCHK(hipMemcpy(pc.w_frag, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    if (pc.rows <= 256 && pc.Kpad <= 640 && pc.Kpad % 32 == 0 && pc.groups == 1) {
+    if (has_frag16_pack(pc, dtype)) {
         // [rows/16][Kpad/32][lane 0..63][8 halves] with lane = (n % 16) + 16 * ((k % 32) / 8), element e = k % 8
         const int KS32 = pc.Kpad / 32;
         std::vector<_Float16> g((size_t)pc.rows * pc.Kpad);
@@ -197,8 +185,8 @@ static int upload_packed(PackedConv &pc, const std::vector<float> &rows_f32, con
 
 // chunk-major copy of a 3x3 pack: k = (tap*Ci + c)  ->  k' = ((c / CH)*9 + tap)*CH + c % CH
 static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, int dtype) {
+    if (!has_halo_pack(pc, dtype)) return 0;
     const int CH = dtype == DT_F16 ? 64 : 32;
-    if (pc.k != 3 || pc.kw != 0 || pc.Ci % CH != 0) return 0;
     std::vector<float> hp(rows_f32.size(), 0.f);
     for (int n = 0; n < pc.rows; ++n)
         for (int tap = 0; tap < 9; ++tap)
@@ -206,7 +194,7 @@ static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, 
                 hp[(size_t)n * pc.Kpad + (size_t)((ci / CH) * 9 + tap) * CH + ci % CH] =
                     rows_f32[(size_t)n * pc.Kpad + (size_t)tap * pc.Ci + ci];
     const size_t cnt = hp.size();
-    if (dtype == DT_F16 && pc.rows % 32 == 0 && pc.Kpad % 16 == 0 && pc.Kpad == 9 * pc.Ci) {
+    if (has_frag_halo_pack(pc, dtype)) {
         // the same matrix in fragment order (upload_frag_pack's layout) for the patch-sharing tile of the sequences
         const int KS16 = pc.Kpad / 16;
         std::vector<_Float16> h(cnt);
@@ -235,15 +223,12 @@ static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, 
 // ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
-struct Act {
-    void *p = nullptr;
-    int H = 0, W = 0, C = 0;   // C = channel stride
-};
 
 typedef std::tuple<int, int, int, std::vector<const void *>> GraphKey;
 
 struct smk_ctx {
     int device = 0, dtype = DT_F32, variant = SMK_VARIANT_SHARP, maxB = 1;
+    long ncu = 256;           // CUs of the device (plan_conv); 256, the MI355X's, where there is none (smk_host_plan_conv)
     std::map<std::string, HostTensor> host_w;
     bool finalized = false;
     int template_B = 0;       // batch of the cached template (0 = none)
@@ -346,8 +331,6 @@ struct smk_ctx {
     unsigned *pipe_sig = nullptr;    // signal memory: main parts completed (pipe_mark_kernel); the tail's hipStreamWaitValue32 target
     unsigned pipe_sig_n = 0;         // main parts enqueued since the counter was zeroed
 };
-
-static const char *dtname(int dt) { return dt == DT_F16 ? "f16" : "f32"; }
 
 struct ProfScope {
     smk_ctx *c; hipStream_t s; int idx = -1;
@@ -748,30 +731,6 @@ static Act act(smk_ctx *c, const char *name, int H, int W, int C) {
 // ---------------------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------------------
-struct ConvOpt {
-    int stride = 1, pad = 0, dil = 1, relu = 0;
-    int stride_x = 0;         // horizontal stride when != stride (pixel-pair stem)
-    const Act *res = nullptr;
-    int res_mode = RES_NONE;
-    int res_coff = 0;
-    int cin_off = 0;          // channel slice of the input
-    int cout_off = 0;
-    int n_override = 0;       // use only the first n rows of a fused pack
-    int groups = 1;
-    // window / upsample view of the input
-    bool win = false;
-    int Hl = 0, Wl = 0, org_y = 0, org_x = 0;
-    const int *pos = nullptr;
-    int pos_mul = 0, pos_add = 0;
-    bool ups = false;
-    // NCHW f32 output
-    float *nchw_out = nullptr;
-    int algo_naive = 0;
-    int tile_code = 0;
-    int halo = 0;             // 128 / 64: force the halo kernel with this BM (per-op tests)
-    int wreg = 0;             // 1..6: force conv_wreg_kernel with this tile code (per-op tests, micro-benchmark)
-};
-
 static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, const Act *out, int B,
                        const ConvOpt &o, ConvParams &p) {
     memset(&p, 0, sizeof(p));
@@ -869,183 +828,10 @@ static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, co
     return 0;
 }
 
-// code: bits 0-3 tile (0 auto, 1 128x128, 2 128x64, 3 64x128, 4 64x64), bits 4-5 K tile
-// (0 auto, 1 128 B, 2 256 B), bits 6-7 ring depth (0 auto, 1..3 -> 2..4 stages)
-static TileChoice tile_from_code(int code, const ConvParams &p, int dtype) {
-    TileChoice t = choose_tile(p, dtype);
-    static const int tb[6][2] = {{0, 0}, {128, 128}, {128, 64}, {64, 128}, {64, 64}, {256, 128}};
-    const int tile = code & 15, kt = (code >> 4) & 3, st = (code >> 6) & 3;
-    if (tile >= 1 && tile <= 5) {
-        t.bm = tb[tile][0]; t.bn = tb[tile][1];
-        t.kt = (t.bm == 64 && t.bn == 64) ? 256 : 128;
-        t.stages = (t.bm == 128 && t.bn == 128) ? 2 : 3;
-    }
-    if (kt) t.kt = kt == 2 ? 256 : 128;
-    if (t.bm == 64 && t.bn == 64) t.kt = 256;
-    if (t.bm == 256) t.kt = 128;
-    if (st) t.stages = st + 1;
-    return t;
-}
-
-// conv3x3_halo_kernel or the generic kernel?  Returns the halo workgroup height (128 / 64) or 0.
-// Measured on MI355X (profiles/r01_v6_halo_ab.txt): the halo kernel wins on every 3x3 stride-1 layer of the
-// path except the long-K wide-N projection (l3.0.downsample, K=4608 N=1024), where the 256x128 generic tile
-// amortises the weight stream better; BM=128 once the launch has >= 300 such tiles, else BM=64.
-static int halo_choice(const PackedConv &pc, const ConvParams &p, const ConvOpt &o, int dtype) {
-    const int mode = o.halo ? o.halo : g_tune.halo;
-    if (!mode || !pc.w_halo || p.out_mode != OUT_NHWC || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.ups) return 0;
-    if (mode != 1) return mode;
-    if (dtype != DT_F16) return 0;            // fp32 (32-channel chunks, 32x32x2 MFMA): measured slower, 1.33 vs 1.09 ms at B=1
-    if (p.Ci * 9 > 2304 && p.Nst >= 512) return 0;
-    const long tiles128 = (long)p.B * ((p.Ho * p.Wo + 127) / 128) * ((p.Nst + 127) / 128);
-    return tiles128 >= 300 ? 128 : 64;
-}
-
 // ---- persistent per-XCD convolution sequences (conv_seq_kernel) ---------------------------------------------------
 // While c->seq_on, run_conv / run_conv_jobs RECORD eligible convolutions instead of launching them; seq_flush turns the
 // recorded list into persistent launches of <= SEQ_MAX layers.  Everything else (non-eligible convolutions, other
 // kernels) flushes first, so program order is preserved.
-// the patch-sharing tile of the sequences (wreg_halo_tile.inc): can this 3x3 convolution run on whole-row tiles of bm pixels?
-static bool seq_halo_ok(const ConvParams &p, int bm) {
-    if (!p.wgt_frag_halo || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.stride_x != 1 || p.pad != p.dil || p.dil < 1 || p.dil > 4) return false;
-    if (p.Hl != p.Hs || p.Wl != p.Ws || p.org_y || p.org_x || p.Ho != p.Hl || p.Wo != p.Wl) return false;
-    if (p.Ci % 128 || p.Kpad != 9 * p.Ci || p.Wo > bm) return false;       // an even number of 64-channel chunks
-    const int rpt = bm / p.Wo;
-    return (rpt + 2 * p.dil) * (p.Wl + 2 * p.dil) * 9 <= 10 * 256;         // patch pieces (HALO_NRMAX rounds of 256; 144-byte rows)
-}
-// force_halo: 0 = the rule below, 128 / 64 = that tile or fail, -1 = never (per-op tests that force another tile)
-static bool seq_layer_from(const ConvParams &p, int dtype, SeqLayer &L, int force_halo = 0) {
-    if (!conv_wreg_eligible(p, dtype) || p.groups > 1 || p.pos || p.ups || p.Kpad % 128) return false;
-    if (p.ci_shift < 0 || p.Ci < 64) return false;       // (wreg_tile compiles the general tap arithmetic out of the sequence's routines)
-    if (p.kh > 15 || p.kw > 15 || p.stride > 15 || p.pad > 15 || p.dil > 15) return false;
-    // the packed record keeps the geometry in 16-bit fields
-    const int u16[] = {p.Hs, p.Ws, p.Cs, p.cin_off, p.Ci, p.Hl, p.Wl, p.Ho, p.Wo, p.Kpad, p.Nst, p.Cos, p.cout_off, p.res_Cs, p.res_coff};
-    for (int v : u16)
-        if (v < 0 || v > 65535) return false;
-    if (p.org_y < -32768 || p.org_y > 32767 || p.org_x < -32768 || p.org_x > 32767) return false;
-    memset(&L, 0, sizeof(L));
-    L.in = p.in; L.wgt_frag = p.wgt_frag; L.bias = p.bias; L.res = p.res; L.out = p.out;
-    L.in_bytes = p.in_bytes; L.w_bytes = p.w_bytes;
-    L.Hs = (unsigned short)p.Hs; L.Ws = (unsigned short)p.Ws; L.Cs = (unsigned short)p.Cs; L.cin_off = (unsigned short)p.cin_off;
-    L.Ci = (unsigned short)p.Ci; L.Hl = (unsigned short)p.Hl; L.Wl = (unsigned short)p.Wl;
-    L.org_y = (short)p.org_y; L.org_x = (short)p.org_x; L.Ho = (unsigned short)p.Ho; L.Wo = (unsigned short)p.Wo;
-    L.Kpad = (unsigned short)p.Kpad; L.Nst = (unsigned short)p.Nst; L.Cos = (unsigned short)p.Cos;
-    L.cout_off = (unsigned short)p.cout_off; L.res_Cs = (unsigned short)p.res_Cs; L.res_coff = (unsigned short)p.res_coff;
-    L.kw_magic = p.kw_magic;
-    L.kh = (signed char)p.kh; L.kw = (signed char)p.kw; L.stride = (signed char)p.stride; L.stride_x = (signed char)p.stride_x;
-    L.pad = (signed char)p.pad; L.dil = (signed char)p.dil; L.relu = (signed char)p.relu; L.res_mode = (signed char)p.res_mode;
-    L.ci_shift = (signed char)p.ci_shift;
-    L.a_stage = (signed char)p.a_stage;
-    L.res_nt = (signed char)p.res_nt;
-    // workgroup tile: the widest that still gives the 32 workgroups of an XCD a tile each per image
-    L.cfg = p.Nst >= 512 ? 0 : (p.Nst >= 192 ? 1 : 2);
-    // Short-K layers are dominated by the fixed cost of a tile (operand first touch, residual fetch, accumulator hand-over:
-    // ~5 us against ~0.45 us per K tile, SMK_SEQ_CLK), so when the 64-row tiling needs more than one round of the team's
-    // 32 workgroups per image, ONE 128-row tile per workgroup beats two 64-row tiles in sequence
-    // (bottleneck conv3: 2 x 64x256 -> 1 x 128x256; layer2.0 conv1 on the 63x63 input: 4 rounds of 64x64 -> 1 of 128x128)
-    // (seq_tall = 2, A/B knob: also for long-K layers -- l3.0.downsample, 64 tiles of 64x256 = two rounds -- now that four
-    //  producer waves feed a 128-row tile)
-    if (g_tune.seq_tall && ((long)p.kh * p.kw * p.Ci <= 512 || g_tune.seq_tall == 2)) {
-        const int hw = p.Ho * p.Wo;
-        const int bn64 = L.cfg == 0 ? 256 : (L.cfg == 1 ? 128 : 64);
-        const int tiles64 = ((hw + 63) / 64) * ((p.Nst + bn64 - 1) / bn64);
-        if (tiles64 > 32) {
-            if (p.Nst >= 512) L.cfg = 3;
-            else if (p.Nst >= 96) L.cfg = 4;
-            else L.cfg = 9;                              // 128x64 (layer1's 64-channel convolutions on 63x63 images)
-        }
-        if (tiles64 > 64 && p.Nst >= 192 && p.Nst < 512) L.cfg = 3;      // N = 256 on 63x63 images: 128x256, one round (layer1 conv3)
-    }
-    // N = 512 with 16 row tiles (layer2.0's 3x3 stride-2 shortcut on a 31x31 output): 32 tiles either as 64x256 or as 128x128 --
-    // the square tile stages 32 KB per K tile instead of 40 KB for the same flops, and these loops run at the CU's 64 B/clk
-    // (smk_tune "seq_ds128", A/B knob)
-    if (g_tune.seq_ds128 && L.cfg == 0 && p.Nst == 512 && (long)p.kh * p.kw * p.Ci >= 1024) {
-        const int hw = p.Ho * p.Wo;
-        if (((hw + 127) / 128) * 4 <= 32) L.cfg = 4;
-    }
-    // 3x3 stride-1 layers with N <= 256 (every Bottleneck's conv2): whole-row tiles x 64 channels with the activation patch shared
-    // by the nine taps -- half the bytes per flop of the 64 x 128 / 64 x 64 im2col tiles (smk_tune "seq_halo").  128 pixels where that
-    // gives the team (nearly) a tile per workgroup (256 channels on 31 x 31: 8 x 4), else 64 (128 channels: 16 x 2).  The long-K
-    // wide-N shortcut of layer3.0 stays on 128 x 256 tiles (same bytes per flop, four times fewer tiles).
-    if (force_halo > 0 || (force_halo == 0 && g_tune.seq_halo && p.Nst <= 256)) {
-        const int tn = (p.Nst + 63) / 64;
-        int bm = force_halo > 0 ? force_halo : 0;
-        if (!bm) {
-            const bool ok128 = seq_halo_ok(p, 128), ok64 = seq_halo_ok(p, 64);
-            const int t128 = ok128 ? ((p.Ho + 128 / p.Wo - 1) / (128 / p.Wo)) * tn : 0;
-            bm = (ok128 && (t128 >= 28 || !ok64)) ? 128 : (ok64 ? 64 : 0);
-        } else if (!seq_halo_ok(p, bm)) return false;
-        if (bm) {
-            L.cfg = (signed char)(bm == 128 ? SEQ_CFG_HALO128 : SEQ_CFG_HALO64);
-            L.wgt_frag = p.wgt_frag_halo;
-        }
-    }
-    L.sync = 1;
-    // K-loop stagger (smk_tune "seq_kstag": 0 off, 1 = layers whose weights fit the XCD's L2 beside the activations, 2 = all)
-    L.kstag = (signed char)((g_tune.seq_kstag == 2 || (g_tune.seq_kstag == 1 && (size_t)p.Nst * p.Kpad * 2 <= (3u << 19))) ? 1 : 0);
-    if (g_tune.seq_deep && L.cfg == 1) L.cfg = 5;         // measurement variant (smk_tune "seq_deep")
-    {   // (smk_tune "seq_kstag_mask": which tile routines stagger -- 1 fused pairs, 2 patch-sharing tiles, 4 the im2col tiles)
-        const bool is_halo = L.cfg == SEQ_CFG_HALO128 || L.cfg == SEQ_CFG_HALO64;
-        if (is_halo && !(g_tune.seq_kstag_mask & 2)) L.kstag = 0;
-        if (!is_halo && !(g_tune.seq_kstag_mask & 4)) L.kstag = 0;
-    }
-    return true;
-}
-
-// Pairs (conv3 of a Bottleneck, the 1x1 convolution that reads its output) -> one fused tile routine (c3c1_tile.inc): the 1x1
-// needs every channel of a pixel and no neighbour, so the workgroup that owns 32 whole rows of conv3's output runs it from LDS.
-// Marks the two records of every pair the routine has a shape for; the list itself (tensors, order, barriers behind the pair)
-// stays as recorded.  smk_tune "seq_fuse" 0 leaves the list alone.
-static bool seq_pair_fusable_why(const SeqLayer *L, int i, int *code, int *why);
-static bool seq_pair_fusable(const SeqLayer *L, int i, int *code) {
-    int why = 0;
-    const bool ok = seq_pair_fusable_why(L, i, code, &why);
-    // SMK_SEQ_DEBUG=1: why is a (1x1 + residual + ReLU, 1x1) pair of records NOT fused?  (stderr, once per list walk)
-    if (!ok && why > 1 && getenv("SMK_SEQ_DEBUG"))
-        fprintf(stderr, "[seq fuse] records %d, %d: not fusable, reason %d (Kpad %d Nst %d -> Nst %d, res %p relu %d, b.relu %d b.Ho %d Hs %d)\n", i, i + 1, why,
-                (int)L[i].Kpad, (int)L[i].Nst, (int)L[i + 1].Nst, L[i].res, (int)L[i].relu, (int)L[i + 1].relu, (int)L[i + 1].Ho, (int)L[i + 1].Hs);
-    return ok;
-}
-static bool seq_pair_fusable_why(const SeqLayer *L, int i, int *code, int *why) {
-    const SeqLayer &a = L[i], &b = L[i + 1];
-    auto plain1x1 = [](const SeqLayer &l) {
-        return l.kh == 1 && l.kw == 1 && l.stride == 1 && l.stride_x == 1 && l.pad == 0 && l.org_y == 0 && l.org_x == 0 &&
-               l.Hl == l.Hs && l.Wl == l.Ws && l.Ho == l.Hs && l.Wo == l.Ws && l.Ci == l.Kpad;
-    };
-    if (!plain1x1(a) || !a.sync) { *why = 1; return false; }
-    if (!plain1x1(b)) { *why = 2; return false; }
-    if (!a.res || a.res_mode != RES_PRE_RELU || !a.relu) { *why = 1; return false; }
-    if (b.res || b.res_mode != RES_NONE) { *why = 3; return false; }
-    if (b.in != a.out) { *why = 1; return false; }
-    if (b.cin_off != a.cout_off || b.Cs != a.Cos || b.Ci != a.Nst || b.Hs != a.Ho || b.Ws != a.Wo) { *why = 4; return false; }
-    if (b.out == a.out || b.out == a.res || b.out == a.in) { *why = 5; return false; }
-    // The routine fetches the residual BEFORE it waits at its hoist point.  The barrier still pending there is the one behind
-    // the LAST layer before i that carries one (`pend`; layer i - 1 when it has sync = 1, an earlier one when smk_op_conv_seq's
-    // caller chained independent members with sync = 0).  Whoever wrote the residual inside this list must be separated from
-    // layer i by a barrier the workgroup has already PASSED, i.e. one behind a layer j' with writer <= j' < pend.
-    // (The first record of an already marked pair carries no barrier of its own.)
-    auto has_bar = [&](int k) { return L[k].sync && L[k].cfg != SEQ_CFG_C3C1_L3 && L[k].cfg != SEQ_CFG_C3C1_L2 && L[k].cfg != SEQ_CFG_C3C1P_L3 && L[k].cfg != SEQ_CFG_C3C1P_L2; };
-    int pend = -1;
-    for (int k = i - 1; k >= 0; --k)
-        if (has_bar(k)) { pend = k; break; }
-    for (int j = i - 1; j >= 0; --j)
-        if (L[j].out == a.res) {
-            bool passed = false;
-            for (int k = j; k < pend; ++k) passed = passed || has_bar(k);
-            if (!passed) { *why = 6; return false; }
-            break;
-        }
-    // conv3's own input must be behind the pending barrier too (the hoist point is the only wait in front of its loads)
-    for (int j = i - 1; j >= 0; --j)
-        if (L[j].out == a.in) {
-            if (j > pend) { *why = 7; return false; }
-            break;
-        }
-    if (a.Kpad == 256 && a.Nst == 1024 && b.Nst == 256) *code = SEQ_CFG_C3C1_L3;
-    else if (a.Kpad == 128 && a.Nst == 512 && b.Nst == 128) *code = SEQ_CFG_C3C1_L2;
-    else { *why = 8; return false; }
-    return true;
-}
 static int g_seq_fused_last = 0;          // pairs fused in the list that was launched last (smk_tune_get "seq_fused_last", a diagnostic)
 static void seq_fuse_pairs(SeqLayer *L, int n, int B, const std::vector<char> *locked = nullptr, bool have_xch = false) {
     g_seq_fused_last = 0;
@@ -1364,117 +1150,48 @@ static bool seq_wanted(const smk_ctx *c, int B) {
     return B % 8 == 0 && B <= g_tune.seq_mult_max;
 }
 
-// conv_wreg_kernel (weights global -> VGPR) or the LDS-staged kernels?  Returns the tile code 1..6
-// (64x256, 64x128, 64x64, 128x256, 128x128, 128x64) or 0.
-// CUs of the current device; host-only callers (smk_host_plan_conv on a box without a GPU) plan for the MI355X's 256
-static long device_cus() {
-    static int cached[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cached[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
-        cached[dev] = n;
-    }
-    return cached[dev];
-}
-static const int WREG_TILE[9][2] = {{0, 0}, {64, 256}, {64, 128}, {64, 64}, {128, 256}, {128, 128}, {128, 64}, {96, 256}, {32, 64}};
-static int wreg_choice(const ConvParams &p, const ConvOpt &o, int dtype) {
-    if (o.algo_naive || !conv_wreg_eligible(p, dtype)) return 0;
-    if (o.wreg) return o.wreg;
-    if (g_tune.wreg >= 2) return g_tune.wreg - 1;
-    if (!g_tune.wreg) return 0;
-    // per-shape choice, fitted to profiles/r02_wregbench_b8_b64.json (A/B against the best LDS-staged instantiation in
-    // one process): the register path wins where the weight stream is long and the tile is N-wide -- the two strided /
-    // wide 3x3 projections (l2.0.ds x1.10-1.15, l3.0.ds x1.05-1.08) and, while M is small (B <= ~16), the 1x1
-    // reductions with K >= 512 (l3.c1 x1.13, l3.0.c1 x1.10, l2.c1 x1.07) and the strided 3x3 of l2.0 (x1.06).
-    // It loses on layer1 (short K, large M: x0.5-0.9) and against the halo kernel on 3x3 stride-1 layers.
-    const long K = (long)p.kh * p.kw * p.Ci;
-    if (g_tune.wreg_policy == 1) {
-        // With four producer waves (smk_tune npw, round 2) the register-fed kernel beats the best LDS-staged instantiation on
-        // almost every fp16 NHWC layer of the path at B = 1, 8 and 64 (profiles/r02_producer_waves_2_vs_4.txt,
-        // r02_producer_waves_layers_b1_b64.json).  Exceptions, kept on the LDS-staged kernels: the 7x7 stem, the short-K 3x3
-        // stride-1 layers (the patch-sharing kernel wins or ties: l1.c2, l2.c2, Refine's small convolutions), and at
-        // large M the narrow / short-K layers (128-row LDS-staged tiles at two workgroups per CU win: layer1, l2.c1, head0,
-        // v1.0 at B = 64).
-        if (p.kh > 3) return 0;
-        if (p.kh == 3 && p.stride == 1 && K <= 1152) return 0;
-        if (p.M > 16384 && !(p.Nst >= 512 || (K >= 2304 && p.Nst >= 128) || (K >= 1024 && p.Nst >= 256) ||
-                             (p.kh == 3 && p.stride == 2)))
-            return 0;
-        // the largest workgroup shape that still hands the chip >= 150 workgroups (N-wide first: 128x256, 64x256, 64x128, 64x64)
-        static const int cand[4] = {4, 1, 2, 3};
-        const int nr = (p.Nst + 63) / 64 * 64, ng = p.groups > 0 ? p.groups : 1;
-        for (int ci = 0; ci < 4; ++ci) {
-            const int bm = WREG_TILE[cand[ci]][0], bn = WREG_TILE[cand[ci]][1];
-            if (bn > nr && bn > 64) continue;
-            if ((long)((p.M + bm - 1) / bm) * ((p.Nst + bn - 1) / bn) * ng >= 150) {
-                // 128 x 256 with 129 .. 255 workgroups leaves CUs idle for a whole tile time (conv_search at B = 8: 53 x 3 = 159
-                // tiles on 256 CUs); 96 rows (code 7) = 213 tiles, still one round, each 3/4 as long (smk_tune "wreg96", round 5)
-                if (cand[ci] == 4 && g_tune.wreg96) {
-                    const long ncu = device_cus(), tn = (p.Nst + 255) / 256 * ng;
-                    const long t128 = (long)((p.M + 127) / 128) * tn, t96 = (long)((p.M + 95) / 96) * tn;
-                    if (((t128 + ncu - 1) / ncu) * 128 > ((t96 + ncu - 1) / ncu) * 96 && t96 <= 4 * ncu) return 7;
-                }
-                return cand[ci];
-            }
-        }
-        // nothing fills the chip: 64 x 64 -- or 32 x 64 (code 8, smk_tune "wreg32") while even that leaves CUs idle: the narrow tiles' K loops wait for
-        // their activation refills (profiles/r06t_wreg_ring_depth.txt), and a 32-row workgroup asks for half of them
-        if (g_tune.wreg32 && (long)((p.M + 63) / 64) * ((p.Nst + 63) / 64) * ng < g_tune.wreg32) return 8;
-        return 3;
-    }
-    if (p.M < 4096) return 0;                  // not measured below B ~ 5: keep the fitted LDS-staged choice
-    if (p.kh == 3 && K >= 2304 && p.Nst >= 512)
-        return ((long)((p.M + 127) / 128) * ((p.Nst + 255) / 256) >= 200) ? 4 : 1;       // 128x256 once it fills the chip
-    if (p.M > 16384) return 0;
-    if (p.kh == 1 && K >= 512 && p.Nst <= 256) return p.Nst >= 192 ? 2 : 3;               // 64x128 / 64x64
-    if (p.kh == 3 && p.stride == 2 && K >= 1152 && p.Nst <= 128) return 3;
-    return 0;
-}
-// depth of conv_wreg_kernel's activation ring: three K tiles; four in split-operand contexts (their K loops are three times as long and mostly on the
-// narrow tiles: +2.3 .. 2.6 % on the B = 8 step) and for one or two streams (every layer on 64 x 64 tiles: +1.8 % on the B = 1 step).  Deeper rings (5 .. 7)
-// lose everywhere, and so does running the WEIGHT stream further ahead: profiles/r06q_x3_ring_depth_b1_levers.txt, r06t_wreg_ring_depth.txt, r06r_wreg_deep_prefetch.txt
-static int wreg_stages(const smk_ctx *c = nullptr, int B = 0) {
-    if (g_tune.wreg_stages) return g_tune.wreg_stages;
-    return (c && (c->dtype == DT_F16X3 || (B >= 1 && B <= 2))) ? 4 : 3;
-}
-// per-op entry points: bits 6-7 of the tile code -- 0 the library's choice, 1 eight k-steps ahead on every shape (conv_wreg.hip WregDepth; MEASURE builds,
-// otherwise the three-deep ring), 2 / 3 a 3- / 4-deep ring
-static int wreg_stages_from_code(int code) {
-    const int st = (code >> 6) & 3;
-    return st == 0 ? wreg_stages() : (st == 1 ? 8 : (st == 2 ? 3 : 4));
+// algorithmic work of one convolution: 2*M*N*K_real flops; bytes = activations read once + weights + output written once
+static void conv_work(const PackedConv &pc, const ConvParams &p, int B, int dtype, double &flop, double &bytes) {
+    const int ng = p.groups > 0 ? p.groups : 1;
+    const double kreal = pc.alg_k ? (double)pc.alg_k : (double)p.kh * p.kw * p.Ci;
+    const size_t es = esize(kdtype(dtype));
+    flop += 2.0 * p.M * (double)p.N * kreal * ng;
+    bytes += (double)B * (p.ups ? p.Hs * p.Ws : (double)p.Hl * p.Wl) * p.Ci * es * ng + (double)p.M * p.N * ng * (p.out_mode == OUT_NCHW_F32 ? 4 : es) +
+             (double)p.N * kreal * es * ng + (p.res ? (double)p.M * p.N * es : 0.0);
 }
 
-// conv_pp_kernel (conv_pp.hip: 256 x 256 tiles, two wave groups alternating between fetching and multiplying) takes the long-K
-// convolutions once 256-row tiles fill the chip in (nearly) whole rounds -- the 3x3 shortcuts and layer3's conv2 from B ~ 53 (BASELINE
-// configs[4]): +1.3..3.8 % per launch over the register-fed 128 x 256 tile; conv_search's 633 tiles are 2.47 rounds (0.82 of three) and
-// stay on the register-fed kernel (-6 %); profiles/r06a_pp_first_contact.txt.  Below ~200 tiles the launch is a partial round of a few
-// long tiles and the smaller tiles win (B = 32: -6..-60 %).  pp = 2 (A/B knob): any K, e.g. the Bottlenecks' 1x1 convolutions.
-static bool pp_choice(const ConvParams &p, const ConvOpt &o, int dtype) {
-    if (!g_tune.pp || o.algo_naive || o.halo || o.wreg || o.tile_code || !conv_pp_eligible(p, dtype)) return false;
-    const long K = (long)p.kh * p.kw * p.Ci;
-    const long tiles = (long)((p.M + 255) / 256) * ((p.Nst + 255) / 256), ncu = device_cus();
-    const long rounds = (tiles + ncu - 1) / ncu;
-    if (tiles < 200 || tiles * 10 < rounds * ncu * 9 || p.Nst < 256 || (p.Nst % 256) != 0) return false;
-    return g_tune.pp == 2 || K >= 2304;
+// The one place a plan becomes a launch: cb holds the planned problem (CK_PP, CK_HALO, CK_NAIVE: cb.p[0]) or the members of a
+// merged one; w_halo is the chunk-major pack of the halo kernel.  A launcher that turns down the geometry it was planned for is
+// an internal error, not a fallback.
+static int launch_plan(const ConvPlan &pl, ConvBatch &cb, const void *w_halo, int dtype, hipStream_t s, const char *what) {
+    int rc;
+    switch (pl.kind) {
+    case CK_PP: rc = launch_conv_pp(cb.p[0], s); break;
+    case CK_WREG: rc = launch_conv_wreg_batch(cb, WREG_TILE[pl.wreg][0], WREG_TILE[pl.wreg][1], pl.stages, s); break;
+    case CK_HALO: {
+        ConvParams ph = cb.p[0];
+        ph.wgt = w_halo;
+        rc = launch_conv_halo(ph, dtype, pl.halo_bm, s);
+        break;
+    }
+    case CK_NAIVE: rc = launch_conv_naive(cb.p[0], dtype, s); break;
+    default: rc = launch_conv_mfma_batch(cb, dtype, pl.tile, s);
+    }
+    if (rc == 1) return fail(SMK_E_STATE, "internal: %s is not eligible for the kernel planned for it", what);
+    if (rc) return fail(SMK_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, int B, const ConvOpt &o,
                     hipStream_t s) {
     auto it = c->conv.find(id);
     if (it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv %s not packed", id);
-    ConvParams p;
+    ConvBatch cb;
+    cb.n = 1;
+    ConvParams &p = cb.p[0];
     CHK(conv_params(c, it->second, in, out, B, o, p));
-    const TileChoice t = tile_from_code(o.tile_code, p, kdtype(c->dtype));
-    const int ng = p.groups > 0 ? p.groups : 1;
-    // algorithmic work: 2*M*N*K_real flops; bytes = activations read once + weights + output written once
-    const double kreal = it->second.alg_k ? (double)it->second.alg_k : (double)p.kh * p.kw * p.Ci;
-    const double flop = 2.0 * p.M * (double)p.N * kreal * ng;
-    const size_t es = esize(kdtype(c->dtype));
-    const double in_bytes = (double)B * (p.ups ? p.Hs * p.Ws : (double)p.Hl * p.Wl) * p.Ci * es * ng;
-    const double out_bytes = (double)p.M * p.N * ng * (p.out_mode == OUT_NCHW_F32 ? 4 : es);
-    const double bytes = in_bytes + out_bytes + (double)p.N * kreal * es * ng + (p.res ? (double)p.M * p.N * es : 0.0);
+    double flop = 0.0, bytes = 0.0;
+    conv_work(it->second, p, B, c->dtype, flop, bytes);
     if (c->seq_on) {
         SeqLayer L;
         if (!o.algo_naive && !o.halo && !o.wreg && !o.tile_code && seq_layer_from(p, kdtype(c->dtype), L)) {
@@ -1487,49 +1204,11 @@ static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, i
         }
         CHK(seq_flush(c, B, s));               // not eligible: keep program order
     }
-    char kn[64];
-    snprintf(kn, sizeof(kn), "conv_igemm<%s,%dx%dx%d,s%d,%s>", dtname(kdtype(c->dtype)), t.bm, t.bn, t.kt, t.stages,
-             p.out_mode == OUT_NCHW_F32 ? "nchw" : "nhwc");
-    int rc = 1;
-    int bm = o.algo_naive ? 0 : halo_choice(it->second, p, o, kdtype(c->dtype));
-    if (bm && !o.halo && conv_ksplit(p, kdtype(c->dtype), t) > 1) bm = 0;       // under-filled: split-K on the generic kernel wins
-    // (policy 1 decides between the register-fed and the patch-sharing kernel itself; the round-2 table only covered the
-    //  layers the patch-sharing kernel does not take)
-    if (pp_choice(p, o, kdtype(c->dtype))) {
-        ProfScope ps(c, s, id, "conv_pp<f16,256x256>", flop, bytes);
-        rc = launch_conv_pp(p, s);
-        if (rc == 1) ps.cancel();
-        else bm = 0;
-    }
-    const int wr = (rc != 1 || o.halo || (bm && !o.wreg && g_tune.wreg < 2 && g_tune.wreg_policy == 0)) ? 0 : wreg_choice(p, o, kdtype(c->dtype));
-    if (wr) {
-        // weights straight into registers, activations through LDS
-        ConvBatch cb;
-        cb.n = 1;
-        cb.p[0] = p;
-        char kw_[64];
-        snprintf(kw_, sizeof(kw_), "conv_wreg<%s,%dx%d,s%d>", dtname(kdtype(c->dtype)), WREG_TILE[wr][0], WREG_TILE[wr][1], wreg_stages(c, B));
-        ProfScope ps(c, s, id, kw_, flop, bytes);
-        rc = launch_conv_wreg_batch(cb, WREG_TILE[wr][0], WREG_TILE[wr][1], wreg_stages(c, B), s);
-        if (rc == 1) ps.cancel();
-        else bm = 0;
-    }
-    if (bm && rc == 1) {
-        // 3x3 stride-1: the activation patch is staged once per channel chunk and shared by the nine taps
-        ConvParams ph = p;
-        ph.wgt = it->second.w_halo;
-        char kh_[64];
-        snprintf(kh_, sizeof(kh_), "conv3x3_halo<%s,%dx128>", dtname(kdtype(c->dtype)), bm);
-        ProfScope ps(c, s, id, kh_, flop, bytes);
-        rc = launch_conv_halo(ph, kdtype(c->dtype), bm, s);
-        if (rc == 1) ps.cancel();
-    }
-    if (rc == 1) {
-        ProfScope ps(c, s, id, o.algo_naive ? "conv_naive" : kn, flop, bytes);
-        rc = o.algo_naive ? launch_conv_naive(p, kdtype(c->dtype), s) : launch_conv_mfma(p, kdtype(c->dtype), t, s);
-    }
-    if (rc) return fail(SMK_E_HIP, "launch of conv %s failed: %s", id, hipGetErrorString(hipGetLastError()));
-    return 0;
+    const ConvPlan pl = plan_conv(p, o, it->second, c->dtype, B, c->ncu);
+    ProfScope ps(c, s, id, plan_kernel_name(pl, c->dtype, p.out_mode), flop, bytes);
+    char what[80];
+    snprintf(what, sizeof(what), "conv %s", id);
+    return launch_plan(pl, cb, it->second.w_halo, kdtype(c->dtype), s, what);
 }
 
 // several independent convolutions as ONE launch (same dtype / epilogue mode / tile for all):
@@ -1571,42 +1250,18 @@ static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, in
     // (profile mode 2: one record for the merged launch, algorithmic work summed over its members as run_conv counts it)
     double mflop = 0.0, mbytes = 0.0;
     std::string mid;
-    if (c->prof) {
-        const size_t es = esize(kdtype(c->dtype));
-        for (int i = 0; i < cb.n; ++i) {
-            const ConvParams &q = cb.p[i];
-            const PackedConv &pc = c->conv.find(jobs[i].id)->second;
-            const int ng = q.groups > 0 ? q.groups : 1;
-            const double kreal = pc.alg_k ? (double)pc.alg_k : (double)q.kh * q.kw * q.Ci;
-            mflop += 2.0 * q.M * (double)q.N * kreal * ng;
-            mbytes += (double)B * (q.ups ? q.Hs * q.Ws : (double)q.Hl * q.Wl) * q.Ci * es * ng +
-                      (double)q.M * q.N * ng * (q.out_mode == OUT_NCHW_F32 ? 4 : es) + (double)q.N * kreal * es * ng +
-                      (q.res ? (double)q.M * q.N * es : 0.0);
-            mid += (i ? "+" : "") + std::string(jobs[i].id);
-        }
+    const ConvOpt *opts[CONV_BATCH_MAX];
+    for (int i = 0; i < cb.n; ++i) {
+        opts[i] = &jobs[i].o;
+        if (!c->prof) continue;
+        conv_work(c->conv.find(jobs[i].id)->second, cb.p[i], B, c->dtype, mflop, mbytes);
+        mid += (i ? "+" : "") + std::string(jobs[i].id);
     }
-    {
-        int wr = wreg_choice(cb.p[lead], jobs[lead].o, kdtype(c->dtype));
-        for (int i = 0; i < cb.n && wr; ++i)
-            if (!wreg_choice(cb.p[i], jobs[i].o, kdtype(c->dtype))) wr = 0;
-        if (wr) {
-            char kw_[64];
-            snprintf(kw_, sizeof(kw_), "conv_wreg<%s,%dx%d,s%d,merged%d>", dtname(kdtype(c->dtype)), WREG_TILE[wr][0], WREG_TILE[wr][1], wreg_stages(c, B), cb.n);
-            ProfScope ps(c, s, mid.c_str(), kw_, mflop, mbytes);
-            const int rc = launch_conv_wreg_batch(cb, WREG_TILE[wr][0], WREG_TILE[wr][1], wreg_stages(c, B), s);
-            if (rc == 0) return 0;
-            ps.cancel();
-            if (rc != 1) return fail(SMK_E_HIP, "launch of merged conv %s.. failed: %s", jobs[0].id, hipGetErrorString(hipGetLastError()));
-        }
-    }
-    const TileChoice t = tile_from_code(jobs[lead].o.tile_code, cb.p[lead], kdtype(c->dtype));
-    char km_[72];
-    snprintf(km_, sizeof(km_), "conv_igemm<%s,%dx%dx%d,s%d,%s,merged%d>", dtname(kdtype(c->dtype)), t.bm, t.bn, t.kt, t.stages,
-             cb.p[lead].out_mode == OUT_NCHW_F32 ? "nchw" : "nhwc", cb.n);
-    ProfScope psm(c, s, mid.c_str(), km_, mflop, mbytes);
-    if (launch_conv_mfma_batch(cb, kdtype(c->dtype), t, s))
-        return fail(SMK_E_HIP, "launch of merged conv %s.. failed: %s", jobs[0].id, hipGetErrorString(hipGetLastError()));
-    return 0;
+    const ConvPlan pl = plan_conv_batch(cb, opts, lead, c->dtype, B, c->ncu);
+    ProfScope ps(c, s, mid.c_str(), plan_kernel_name(pl, c->dtype, cb.p[lead].out_mode, cb.n), mflop, mbytes);
+    char what[80];
+    snprintf(what, sizeof(what), "merged conv %s..", jobs[0].id);
+    return launch_plan(pl, cb, nullptr, kdtype(c->dtype), s, what);
 }
 
 // A Bottleneck's conv3 (+ residual + ReLU) and the 1x1 convolution that reads its output as ONE launch (conv_pair_kernel: the
@@ -2289,6 +1944,7 @@ int smk_create(smk_ctx **out, int device, int dtype, int variant, int max_batch)
         return fail(SMK_E_NODEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
     std::unique_ptr<smk_ctx> c(new smk_ctx);
     c->device = device; c->dtype = dtype; c->variant = variant; c->maxB = max_batch;
+    c->ncu = prop.multiProcessorCount;
     const char *g = getenv("SMK_GRAPH");
     c->graph_mode = g && strcmp(g, "0") != 0;
     int rc = build_arena(c.get());
@@ -2592,154 +2248,130 @@ int smk_refine(smk_ctx *c, const int32_t *pos, int on_device, int B, float *out,
     return run_maybe_graph(c, key, s, [&](hipStream_t st) { return seq_refine(c, B, out, st); });
 }
 
+// ---- smk_tune / smk_tune_get: one table --------------------------------------------------------------------------
+// accept: the values smk_tune takes -- "*" any, else terms "a", "a..b" or ">=a" joined by '|'; nullptr: a read-only diagnostic.
+// conv: what is stored -- KNOB_RAW the value, KNOB_BOOL value != 0, > 0 value & conv.  product: a knob whose other values are
+// measured losers that only a `make MEASURE=1` library carries -- the values a product library takes (its default among them).
+enum { KNOB_RAW = 0, KNOB_BOOL = -1 };
+struct Knob { const char *name; int *slot; const char *accept; int conv; const char *product; };
+#ifdef SMK_MEASURE
+static int g_measure_build = 1;                  // smk_tune_get "measure_build": the K-loop ablation kernels are present
+#else
+static int g_measure_build = 0;
+#endif
+static const Knob KNOBS[] = {
+    {"xcd_mode", &g_tune.xcd_mode, "*", KNOB_RAW, nullptr},
+    {"force_tile", &g_tune.force_tile, "0..5", KNOB_RAW, nullptr},
+    {"min_blocks_x16", &g_tune.min_blocks_x16, "*", KNOB_RAW, nullptr},
+    {"concurrency", &g_concurrency_default, "*", KNOB_RAW, nullptr},
+    {"stages", &g_tune.stages, "0|2..4", KNOB_RAW, nullptr},
+    {"kt", &g_tune.kt, "0|128|256", KNOB_RAW, nullptr},
+    {"prio", &g_tune.prio, "-1..3", KNOB_RAW, nullptr},
+    {"nt_store", &g_tune.nt_store, "*", KNOB_BOOL, nullptr},
+    {"merge", &g_tune.merge, "0..2", KNOB_RAW, nullptr},
+    {"merge_max_batch", &g_tune.merge_max_batch, "*", KNOB_RAW, nullptr},
+    {"rf_wreg", &g_tune.rf_wreg, "*", KNOB_RAW, nullptr},           // (+ tile codes 0..8 in bits 4..7 and 8..11: smk_tune)
+    {"rf_tile2", &g_tune.rf_tile2, "0..5", KNOB_RAW, nullptr},
+    {"nchw_tn_major", &g_tune.nchw_tn_major, "*", KNOB_BOOL, nullptr},
+    {"chain", &g_tune.chain, "*", KNOB_BOOL, nullptr},
+    {"chain_mask", &g_tune.chain_mask, "*", KNOB_BOOL, nullptr},
+    {"corr_head", &g_tune.corr_head, "*", KNOB_BOOL, nullptr},
+    {"pair_launch", &g_tune.pair_launch, "0..3", KNOB_RAW, nullptr},
+    {"halo", &g_tune.halo, "0|1|64|128", KNOB_RAW, nullptr},
+    {"halo_db", &g_tune.halo_db, "*", KNOB_BOOL, nullptr},
+    {"ksplit", &g_tune.ksplit, "0|1|2|4", KNOB_RAW, nullptr},
+    {"xc_ch", &g_tune.xc_ch, "32|64", KNOB_RAW, nullptr},
+    {"xc_full", &g_tune.xc_full, "0..2", KNOB_RAW, nullptr},
+    {"stem_fused", &g_tune.stem_fused, "*", KNOB_BOOL, nullptr},
+    {"l1_fused", &g_tune.l1_fused, "*", KNOB_BOOL, nullptr},
+    {"buf_lds", &g_tune.buf_lds, "*", KNOB_BOOL, nullptr},
+    {"a_stage", &g_tune.a_stage, "*", KNOB_BOOL, nullptr},
+    {"mask_overlap", &g_tune.mask_overlap, "*", KNOB_BOOL, nullptr},
+    {"wreg", &g_tune.wreg, "0..7", KNOB_RAW, nullptr},
+    {"wreg_policy", &g_tune.wreg_policy, "0|1", KNOB_RAW, nullptr},
+    {"wreg_stages", &g_tune.wreg_stages, "0|3..8", KNOB_RAW, "0|3|4"},
+    {"wreg96", &g_tune.wreg96, "*", KNOB_BOOL, nullptr},
+    {"wreg32", &g_tune.wreg32, "0..4096", KNOB_RAW, nullptr},
+    {"npw", &g_tune.npw, "2|4", KNOB_RAW, nullptr},
+    {"res_nt", &g_tune.res_nt, "*", KNOB_BOOL, nullptr},
+    {"pp", &g_tune.pp, "0..2", KNOB_RAW, nullptr},
+    {"x3_fused", &g_tune.x3_fused, "*", KNOB_BOOL, nullptr},          // (read when a split-operand context packs its weights)
+    {"ablate", &g_tune.ablate, "*", 127, "0"},
+    {"front_occ1", &g_tune.front_occ1, "*", 3, "0"},
+    {"seq", &g_tune.seq, "*", KNOB_BOOL, nullptr},
+    {"seq_spoll", &g_tune.seq_spoll, "*", KNOB_BOOL, nullptr},
+    {"seq_kstag", &g_tune.seq_kstag, "0..2", KNOB_RAW, nullptr},
+    {"seq_kstag_mask", &g_tune.seq_kstag_mask, "*", 7, nullptr},
+    {"seq_tall", &g_tune.seq_tall, "0..2", KNOB_RAW, nullptr},
+    {"seq_fuse", &g_tune.seq_fuse, "0..3", KNOB_RAW, nullptr},
+    {"seq_fuse3", &g_tune.seq_fuse3, "0..2", KNOB_RAW, "0"},
+    {"seq_pair2d", &g_tune.seq_pair2d, "0..2", KNOB_RAW, "0"},
+    {"seq_deep", &g_tune.seq_deep, "*", KNOB_BOOL, "0"},
+    {"seq_ds128", &g_tune.seq_ds128, "*", KNOB_BOOL, nullptr},
+    {"seq_halo", &g_tune.seq_halo, "*", KNOB_BOOL, nullptr},
+    {"seq_yres", &g_tune.seq_yres, "*", KNOB_BOOL, nullptr},
+    {"seq_search", &g_tune.seq_search, "*", KNOB_BOOL, nullptr},
+    {"seq_first_stage", &g_tune.seq_first_stage, "0..3", KNOB_RAW, "1..3"},
+    {"seq_min_batch", &g_tune.seq_min_batch, ">=1", KNOB_RAW, nullptr},
+    {"seq_max_batch", &g_tune.seq_max_batch, ">=1", KNOB_RAW, nullptr},
+    {"seq_extra_batch", &g_tune.seq_extra_batch, "*", KNOB_RAW, nullptr},
+    {"seq_mult_max", &g_tune.seq_mult_max, ">=0", KNOB_RAW, nullptr},
+    {"main_prio", &g_tune.main_prio, "0..3", KNOB_RAW, nullptr},
+    {"pipe_late", &g_tune.pipe_late, "*", KNOB_BOOL, nullptr},
+    {"pipe_prio", &g_tune.pipe_prio, "0..2", KNOB_RAW, "0"},
+    {"pipe_eager", &g_tune.pipe_eager, "*", 3, "0"},
+    {"pipe_join", &g_tune.pipe_join, "*", KNOB_BOOL, "1"},
+    {"pipe_two_form", &g_tune.pipe_two_form, "0..2", KNOB_RAW, "1"},
+    {"pipe_sig", &g_tune.pipe_sig, "0..2", KNOB_RAW, "2"},
+    {"seq_fused_last", &g_seq_fused_last, nullptr, KNOB_RAW, nullptr},     // pairs fused in the sequence launched last
+    {"seq_yres_last", &g_seq_yres_last, nullptr, KNOB_RAW, nullptr},
+    {"seq_fused3_last", &g_seq_fused3_last, nullptr, KNOB_RAW, nullptr},
+    {"measure_build", &g_measure_build, nullptr, KNOB_RAW, nullptr},
+};
+
+static bool knob_accepts(const char *spec, int v) {
+    if (!strcmp(spec, "*")) return true;
+    for (const char *t = spec; t; t = strchr(t, '|') ? strchr(t, '|') + 1 : nullptr) {
+        if (t[0] == '>' && t[1] == '=') {
+            if (v >= atoi(t + 2)) return true;
+            continue;
+        }
+        char *e = nullptr;
+        const long lo = strtol(t, &e, 10), hi = (e[0] == '.' && e[1] == '.') ? strtol(e + 2, nullptr, 10) : lo;
+        if (v >= lo && v <= hi) return true;
+    }
+    return false;
+}
+
+static const Knob *find_knob(const char *key) {
+    for (const Knob &k : KNOBS)
+        if (!strcmp(key, k.name)) return &k;
+    return nullptr;
+}
+
 int smk_tune(const char *key, int value) {
     if (!key) return fail(SMK_E_ARG, "smk_tune: key is NULL");
-    if (!strcmp(key, "xcd_mode")) g_tune.xcd_mode = value;
-    else if (!strcmp(key, "force_tile")) { if (value < 0 || value > 5) return fail(SMK_E_ARG, "force_tile 0..5"); g_tune.force_tile = value; }
-    else if (!strcmp(key, "min_blocks_x16")) g_tune.min_blocks_x16 = value;
-    else if (!strcmp(key, "concurrency")) g_concurrency_default = value;
-    else if (!strcmp(key, "stages")) { if (value != 0 && (value < 2 || value > 4)) return fail(SMK_E_ARG, "stages 0|2|3|4"); g_tune.stages = value; }
-    else if (!strcmp(key, "merge")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "merge 0..2"); g_tune.merge = value; }
-    else if (!strcmp(key, "merge_max_batch")) g_tune.merge_max_batch = value;
-    else if (!strcmp(key, "seq_spoll")) g_tune.seq_spoll = value != 0;
-    else if (!strcmp(key, "rf_wreg")) g_tune.rf_wreg = value;
-    else if (!strcmp(key, "seq_fuse3")) {
-        if (value < 0 || value > 2) return fail(SMK_E_ARG, "seq_fuse3 0..2");
+    const Knob *k = find_knob(key);
+    if (!k) return fail(SMK_E_ARG, "smk_tune: unknown key %s", key);
+    if (!k->accept) return fail(SMK_E_ARG, "smk_tune: %s is a read-only diagnostic", key);
+    if (!knob_accepts(k->accept, value)) return fail(SMK_E_ARG, "smk_tune: %s takes %s, not %d", key, k->accept, value);
 #ifndef SMK_MEASURE
-        if (value) return fail(SMK_E_ARG, "seq_fuse3: the triple routine (measured a wash) is only in a library built with `make MEASURE=1`");
+    if (k->product && !knob_accepts(k->product, value))
+        return fail(SMK_E_ARG, "smk_tune: %s %d is a measured alternative, only in a library built with `make MEASURE=1` (this one takes %s)",
+                    key, value, k->product);
 #endif
-        g_tune.seq_fuse3 = value;
-    }
-    else if (!strcmp(key, "nchw_tn_major")) g_tune.nchw_tn_major = value != 0;
-    else if (!strcmp(key, "chain_mask")) g_tune.chain_mask = value != 0;
-    else if (!strcmp(key, "wreg")) { if (value < 0 || value > 7) return fail(SMK_E_ARG, "wreg 0..7"); g_tune.wreg = value; }
-    else if (!strcmp(key, "seq")) g_tune.seq = value != 0;
-    else if (!strcmp(key, "ablate")) {
-#ifdef SMK_MEASURE
-        g_tune.ablate = value & 127;
-#else
-        if (value) return fail(SMK_E_ARG, "ablate: the measurement kernels are only in a library built with `make MEASURE=1`");
-#endif
-    }
-    else if (!strcmp(key, "seq_kstag")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "seq_kstag 0|1|2"); g_tune.seq_kstag = value; }
-    else if (!strcmp(key, "seq_deep")) {
-#ifndef SMK_MEASURE
-        if (value) return fail(SMK_E_ARG, "seq_deep: the deep-ring measurement tile is only in a library built with `make MEASURE=1`");
-#endif
-        g_tune.seq_deep = value != 0;
-    }
-    else if (!strcmp(key, "corr_head")) g_tune.corr_head = value != 0;
-    else if (!strcmp(key, "pair_launch")) { if (value < 0 || value > 3) return fail(SMK_E_ARG, "pair_launch 0..3"); g_tune.pair_launch = value; }
-    else if (!strcmp(key, "rf_tile2")) { if (value < 0 || value > 5) return fail(SMK_E_ARG, "rf_tile2 0..5"); g_tune.rf_tile2 = value; }
-    else if (!strcmp(key, "seq_pair2d")) {
-        if (value < 0 || value > 2) return fail(SMK_E_ARG, "seq_pair2d 0..2");
-#ifndef SMK_MEASURE
-        if (value) return fail(SMK_E_ARG, "seq_pair2d: the pair split over two CUs (measured a wash) is only in a library built with `make MEASURE=1`");
-#endif
-        g_tune.seq_pair2d = value;
-    }
-    else if (!strcmp(key, "seq_fuse")) { if (value < 0 || value > 3) return fail(SMK_E_ARG, "seq_fuse 0..3"); g_tune.seq_fuse = value; }
-    else if (!strcmp(key, "seq_ds128")) g_tune.seq_ds128 = value != 0;
-    else if (!strcmp(key, "seq_halo")) g_tune.seq_halo = value != 0;
-    else if (!strcmp(key, "seq_kstag_mask")) g_tune.seq_kstag_mask = value & 7;
-    else if (!strcmp(key, "res_nt")) g_tune.res_nt = value != 0;
-    else if (!strcmp(key, "seq_tall")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "seq_tall 0|1|2"); g_tune.seq_tall = value; }
-    else if (!strcmp(key, "seq_first_stage")) {
-        if (value < 0 || value > 3) return fail(SMK_E_ARG, "seq_first_stage 0..3");
-#ifndef SMK_MEASURE
-        if (value == 0) return fail(SMK_E_ARG, "seq_first_stage 0 (layer1 inside the sequence: measured 140 us against 96) is only in a library built with `make MEASURE=1`");
-#endif
-        g_tune.seq_first_stage = value;
-    }
-    else if (!strcmp(key, "seq_min_batch")) { if (value < 1) return fail(SMK_E_ARG, "seq_min_batch >= 1"); g_tune.seq_min_batch = value; }
-    else if (!strcmp(key, "seq_max_batch")) { if (value < 1) return fail(SMK_E_ARG, "seq_max_batch >= 1"); g_tune.seq_max_batch = value; }
-    else if (!strcmp(key, "seq_extra_batch")) g_tune.seq_extra_batch = value;
-    else if (!strcmp(key, "seq_mult_max")) { if (value < 0) return fail(SMK_E_ARG, "seq_mult_max >= 0"); g_tune.seq_mult_max = value; }
-    else if (!strcmp(key, "wreg_stages")) { 
-#ifdef SMK_MEASURE
-        if (value != 0 && (value < 3 || value > 8)) return fail(SMK_E_ARG, "wreg_stages 0|3..8");
-#else
-        if (value != 0 && value != 3 && value != 4) return fail(SMK_E_ARG, "wreg_stages 0|3|4 (8 = eight k-steps ahead on every tile shape: measured slower, `make MEASURE=1` builds only)");
-#endif
-        g_tune.wreg_stages = value; }
-    else if (!strcmp(key, "chain")) g_tune.chain = value != 0;
-    else if (!strcmp(key, "halo_db")) g_tune.halo_db = value != 0;
-    else if (!strcmp(key, "ksplit")) { if (value != 0 && value != 1 && value != 2 && value != 4) return fail(SMK_E_ARG, "ksplit 0|1|2|4"); g_tune.ksplit = value; }
-    else if (!strcmp(key, "halo")) { if (value != 0 && value != 1 && value != 64 && value != 128) return fail(SMK_E_ARG, "halo 0|1|64|128"); g_tune.halo = value; }
-    else if (!strcmp(key, "xc_full")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "xc_full 0|1|2"); g_tune.xc_full = value; }
-    else if (!strcmp(key, "stem_fused")) g_tune.stem_fused = value != 0;
-    else if (!strcmp(key, "l1_fused")) g_tune.l1_fused = value != 0;
-    else if (!strcmp(key, "xc_ch")) { if (value != 32 && value != 64) return fail(SMK_E_ARG, "xc_ch 32|64"); g_tune.xc_ch = value; }
-    else if (!strcmp(key, "buf_lds")) g_tune.buf_lds = value != 0;
-    else if (!strcmp(key, "a_stage")) g_tune.a_stage = value != 0;
-    else if (!strcmp(key, "wreg_policy")) { if (value != 0 && value != 1) return fail(SMK_E_ARG, "wreg_policy 0|1"); g_tune.wreg_policy = value; }
-    else if (!strcmp(key, "npw")) { if (value != 2 && value != 4) return fail(SMK_E_ARG, "npw 2|4"); g_tune.npw = value; }
-    else if (!strcmp(key, "mask_overlap")) g_tune.mask_overlap = value != 0;
-#ifdef SMK_MEASURE
-    else if (!strcmp(key, "pipe_eager")) g_tune.pipe_eager = value & 3;
-    else if (!strcmp(key, "pipe_join")) g_tune.pipe_join = value != 0;
-    else if (!strcmp(key, "pipe_two_form")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "pipe_two_form 0..2"); g_tune.pipe_two_form = value; }
-    else if (!strcmp(key, "pipe_sig")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "pipe_sig 0..2"); g_tune.pipe_sig = value; }
-#else
-    else if (!strcmp(key, "pipe_eager") || !strcmp(key, "pipe_join") || !strcmp(key, "pipe_two_form") || !strcmp(key, "pipe_sig")) {
-        const int dflt = !strcmp(key, "pipe_eager") ? 0 : (!strcmp(key, "pipe_join") ? 1 : (!strcmp(key, "pipe_two_form") ? 1 : 2));
-        if (value != dflt) return fail(SMK_E_ARG, "%s: the measured alternatives of the pipelined step are only in a library built with `make MEASURE=1`", key);
-    }
-#endif
-    else if (!strcmp(key, "wreg96")) g_tune.wreg96 = value != 0;
-    else if (!strcmp(key, "main_prio")) { if (value < 0 || value > 3) return fail(SMK_E_ARG, "main_prio 0..3"); g_tune.main_prio = value; }
-    else if (!strcmp(key, "x3_fused")) g_tune.x3_fused = value != 0;          // (read when a split-operand context packs its weights)
-    else if (!strcmp(key, "pipe_prio")) {
-#ifndef SMK_MEASURE
-        if (value != 0) return fail(SMK_E_ARG, "pipe_prio: measured slower in both directions; only in a library built with `make MEASURE=1`");
-#endif
-        if (value < 0 || value > 2) return fail(SMK_E_ARG, "pipe_prio 0|1|2");
-        g_tune.pipe_prio = value;
-    }
-    else if (!strcmp(key, "wreg32")) { if (value < 0 || value > 4096) return fail(SMK_E_ARG, "wreg32 0..4096 (64x64 tile count below which 32x64 tiles are used)"); g_tune.wreg32 = value; }
-    else if (!strcmp(key, "front_occ1")) {
-#ifdef SMK_MEASURE
-        g_tune.front_occ1 = value & 3;
-#else
-        if (value) return fail(SMK_E_ARG, "front_occ1: a measured loss (profiles/r06g_front_occupancy_ab.txt), only in a library built with `make MEASURE=1`");
-#endif
-    }
-    else if (!strcmp(key, "seq_yres")) g_tune.seq_yres = value != 0;
-    else if (!strcmp(key, "seq_search")) g_tune.seq_search = value != 0;
-    else if (!strcmp(key, "pp")) { if (value < 0 || value > 2) return fail(SMK_E_ARG, "pp 0..2"); g_tune.pp = value; }
-    else if (!strcmp(key, "pipe_late")) g_tune.pipe_late = value != 0;
-    else if (!strcmp(key, "nt_store")) g_tune.nt_store = value != 0;
-    else if (!strcmp(key, "prio")) { if (value < -1 || value > 3) return fail(SMK_E_ARG, "prio -1..3"); g_tune.prio = value; }
-    else if (!strcmp(key, "kt")) { if (value != 0 && value != 128 && value != 256) return fail(SMK_E_ARG, "kt 0|128|256"); g_tune.kt = value; }
-    else return fail(SMK_E_ARG, "smk_tune: unknown key %s", key);
+    if (k->slot == &g_tune.rf_wreg && (((value >> 4) & 15) > 8 || ((value >> 8) & 15) > 8))   // (WREG_TILE has codes 1..8)
+        return fail(SMK_E_ARG, "smk_tune: rf_wreg tile codes (bits 4..7, 8..11) 0..8");
+    *k->slot = k->conv == KNOB_BOOL ? value != 0 : (k->conv > 0 ? value & k->conv : value);
     return 0;
 }
 
 int smk_tune_get(const char *key, int *value) {
     if (!key || !value) return fail(SMK_E_ARG, "smk_tune_get: null argument");
-    if (!strcmp(key, "measure_build")) {              // 1: built with `make MEASURE=1` (the K-loop ablation kernels are present)
-#ifdef SMK_MEASURE
-        *value = 1;
-#else
-        *value = 0;
-#endif
-        return 0;
-    }
-    static const struct { const char *name; int *slot; } knobs[] = {
-        {"seq_fused_last", &g_seq_fused_last}, {"seq_yres_last", &g_seq_yres_last},
-        {"xcd_mode", &g_tune.xcd_mode}, {"force_tile", &g_tune.force_tile}, {"min_blocks_x16", &g_tune.min_blocks_x16},
-        {"concurrency", &g_concurrency_default}, {"stages", &g_tune.stages}, {"merge", &g_tune.merge}, {"merge_max_batch", &g_tune.merge_max_batch}, {"seq_spoll", &g_tune.seq_spoll}, {"rf_wreg", &g_tune.rf_wreg}, {"seq_fuse3", &g_tune.seq_fuse3}, {"seq_fused3_last", &g_seq_fused3_last},
-        {"nchw_tn_major", &g_tune.nchw_tn_major}, {"chain_mask", &g_tune.chain_mask}, {"wreg", &g_tune.wreg},
-        {"seq", &g_tune.seq}, {"ablate", &g_tune.ablate}, {"seq_tall", &g_tune.seq_tall}, {"seq_kstag", &g_tune.seq_kstag},
-        {"seq_deep", &g_tune.seq_deep}, {"seq_fuse", &g_tune.seq_fuse}, {"seq_pair2d", &g_tune.seq_pair2d}, {"corr_head", &g_tune.corr_head}, {"pair_launch", &g_tune.pair_launch}, {"rf_tile2", &g_tune.rf_tile2}, {"seq_ds128", &g_tune.seq_ds128}, {"seq_halo", &g_tune.seq_halo}, {"seq_kstag_mask", &g_tune.seq_kstag_mask}, {"res_nt", &g_tune.res_nt},
-        {"seq_first_stage", &g_tune.seq_first_stage}, {"seq_min_batch", &g_tune.seq_min_batch},
-        {"seq_max_batch", &g_tune.seq_max_batch}, {"seq_extra_batch", &g_tune.seq_extra_batch}, {"seq_mult_max", &g_tune.seq_mult_max}, {"wreg_stages", &g_tune.wreg_stages}, {"chain", &g_tune.chain},
-        {"halo_db", &g_tune.halo_db}, {"ksplit", &g_tune.ksplit}, {"halo", &g_tune.halo}, {"xc_ch", &g_tune.xc_ch}, {"xc_full", &g_tune.xc_full}, {"stem_fused", &g_tune.stem_fused}, {"l1_fused", &g_tune.l1_fused},
-        {"buf_lds", &g_tune.buf_lds}, {"a_stage", &g_tune.a_stage}, {"npw", &g_tune.npw}, {"wreg_policy", &g_tune.wreg_policy}, {"mask_overlap", &g_tune.mask_overlap}, {"pipe_eager", &g_tune.pipe_eager}, {"pipe_join", &g_tune.pipe_join}, {"wreg96", &g_tune.wreg96}, {"main_prio", &g_tune.main_prio}, {"x3_fused", &g_tune.x3_fused}, {"pipe_prio", &g_tune.pipe_prio}, {"wreg32", &g_tune.wreg32}, {"pp", &g_tune.pp}, {"front_occ1", &g_tune.front_occ1}, {"seq_yres", &g_tune.seq_yres}, {"seq_search", &g_tune.seq_search}, {"pipe_late", &g_tune.pipe_late}, {"pipe_two_form", &g_tune.pipe_two_form}, {"pipe_sig", &g_tune.pipe_sig},
-        {"nt_store", &g_tune.nt_store}, {"prio", &g_tune.prio}, {"kt", &g_tune.kt}};
-    for (const auto &k : knobs)
-        if (!strcmp(key, k.name)) { *value = *k.slot; return 0; }
-    return fail(SMK_E_ARG, "smk_tune_get: unknown key %s", key);
+    const Knob *k = find_knob(key);
+    if (!k) return fail(SMK_E_ARG, "smk_tune_get: unknown key %s", key);
+    *value = *k->slot;
+    return 0;
 }
 
 int smk_profile(smk_ctx *c, int enable) {
@@ -3328,6 +2960,24 @@ static int op_ks_scratch(smk_ctx &fake) {
     return 0;
 }
 
+// The kernel a per-op entry point's algo code forces (siammask_hip_test.h: low byte 0 / 2 conv_igemm_kernel, 1 / 3 the naive
+// kernel, 4 conv3x3_halo_kernel, 5 conv_wreg_kernel, 6 conv_pp_kernel; bits 8..15 the tile code).  Returns 0, -1 for a wreg tile
+// code outside 1..8, 1 when the geometry is not eligible for the kernel.
+static int plan_from_algo(int algo, const ConvParams &p, int dtype, ConvPlan &pl) {
+    const int mode = algo & 0xff, code = (algo >> 8) & 0xff;
+    switch (mode) {
+    case 1: case 3: pl.kind = CK_NAIVE; return 0;
+    case 4:
+        pl.kind = CK_HALO; pl.halo_bm = (code & 15) == 1 ? 128 : 64;
+        return conv_halo_eligible(p, dtype, pl.halo_bm) ? 0 : 1;
+    case 5:
+        pl.kind = CK_WREG; pl.wreg = code & 15; pl.stages = wreg_stages_from_code(code);
+        if (pl.wreg < 1 || pl.wreg > 8) return -1;
+        return conv_wreg_eligible(p, dtype) ? 0 : 1;
+    case 6: pl.kind = CK_PP; return conv_pp_eligible(p, dtype) ? 0 : 1;
+    default: pl.kind = CK_IGEMM; pl.tile = tile_from_code(code, p, dtype); return 0;
+    }
+}
 
 int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x_dev, const float *w_host,
                      const float *b_host, const float *res_dev, const int32_t *pos_host, float *y_dev,
@@ -3378,15 +3028,11 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
         o.pos = pos_dev;
     }
     const int mode = algo & 0xff;
-    o.tile_code = (algo >> 8) & 0xff;
-    o.algo_naive = (mode == 1 || mode == 3);
     const bool nchw = (mode == 2 || mode == 3);
-    if (mode == 4) {                                   // halo kernel (3x3 stride 1), BM from the tile code
-        o.halo = (o.tile_code & 15) == 1 ? 128 : 64;
+    if (mode == 4) {                                   // halo kernel (3x3 stride 1): its chunk-major pack (f16: + the fragment-order copy)
         CHK(upload_halo_pack(pc, rows, dtype));
-        if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);     // (f16: upload_halo_pack also makes the fragment-order copy)
-        if (!pc.w_halo) return fail(SMK_E_ARG, "smk_op_conv2d_ex: geometry is not eligible for the halo kernel");
-        tmp.v.push_back(pc.w_halo);
+        if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);
+        if (pc.w_halo) tmp.v.push_back(pc.w_halo);
     }
     Act out, res;
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8) * (x3 ? X3_PLANES : 1);
@@ -3410,28 +3056,16 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
         CHK(tmp.alloc(&out.p, (size_t)g->B * Ho * Wo * out.C * es));
         CHK(conv_params(&fake, pc, in, &out, g->B, o, p));
     }
-    int rc;
-    if (mode == 5) {                                   // conv_wreg_kernel, tile code 1..6 in the low tile bits
-        const int wr = o.tile_code & 15;
-        if (wr < 1 || wr > 8) return fail(SMK_E_ARG, "smk_op_conv2d_ex: wreg tile code 1..8");
-        ConvBatch cb;
-        cb.n = 1;
-        cb.p[0] = p;
-        rc = launch_conv_wreg_batch(cb, WREG_TILE[wr][0], WREG_TILE[wr][1], wreg_stages_from_code(o.tile_code), s);
-        if (rc == 1) return fail(SMK_E_ARG, "smk_op_conv2d_ex: geometry / dtype is not eligible for conv_wreg_kernel");
-    } else if (mode == 6) {                            // conv_pp_kernel (256 x 256 tiles)
-        rc = dtype == DT_F16 ? launch_conv_pp(p, s) : 1;
-        if (rc == 1) return fail(SMK_E_ARG, "smk_op_conv2d_ex: geometry / dtype is not eligible for conv_pp_kernel");
-    } else if (o.halo) {
-        ConvParams ph = p;
-        ph.wgt = pc.w_halo;
-        rc = launch_conv_halo(ph, dtype, o.halo, s);
-        if (rc == 1) return fail(SMK_E_ARG, "smk_op_conv2d_ex: geometry is not eligible for the halo kernel");
-    } else {
-        rc = o.algo_naive ? launch_conv_naive(p, dtype, s)
-                          : launch_conv_mfma(p, dtype, tile_from_code(o.tile_code, p, dtype), s);
-    }
-    if (rc) return fail(SMK_E_HIP, "conv launch failed: %s", hipGetErrorString(hipGetLastError()));
+    ConvPlan pl;
+    const int prc = plan_from_algo(algo, p, dtype, pl);
+    if (prc < 0) return fail(SMK_E_ARG, "smk_op_conv2d_ex: wreg tile code 1..8");
+    if (prc)
+        return fail(SMK_E_ARG, "smk_op_conv2d_ex: %s", pl.kind == CK_HALO ? "geometry is not eligible for the halo kernel"
+                    : (pl.kind == CK_WREG ? "geometry / dtype is not eligible for conv_wreg_kernel" : "geometry / dtype is not eligible for conv_pp_kernel"));
+    ConvBatch cb;
+    cb.n = 1;
+    cb.p[0] = p;
+    CHK(launch_plan(pl, cb, pc.w_halo, dtype, s, "conv"));
     if (!nchw) {
         CvtOutParams co{out.p, y_dev, g->B, g->Cout, Ho, Wo, out.C, 0, x3 ? out.C / X3_PLANES : 0};
         if (x3 ? launch_cvt_out_x3(co, s) : launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
@@ -3755,7 +3389,7 @@ int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, in
         o.pos = pos_dev;
     }
     const int mode = algo & 0xff;
-    o.tile_code = (algo >> 8) & 0xff;
+    if (mode == 5) pc.w_frag = pc.w;                    // timing only: the fragment order is irrelevant
     Act out, res;
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8);
     float *nchw = nullptr;
@@ -3776,34 +3410,23 @@ int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, in
     CHK(op_ks_scratch(fake));
     ConvParams p;
     CHK(conv_params(&fake, pc, in, mode == 2 ? nullptr : &out, g->B, o, p));
-    const TileChoice t = tile_from_code(o.tile_code, p, dtype);
-    const int halo_bm = mode == 4 ? ((o.tile_code & 15) == 1 ? 128 : 64) : 0;     // timing only: K order is irrelevant
-    const int wr = mode == 5 ? (o.tile_code & 15) : 0;
-    if (mode == 5) {
-        if (wr < 1 || wr > 8) return fail(SMK_E_ARG, "smk_bench_conv: wreg tile code 1..8");
-        p.wgt_frag = p.wgt;                              // timing only: the fragment order is irrelevant
-        if (!conv_wreg_eligible(p, dtype)) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for conv_wreg_kernel");
-    }
-    const int wr_stages = wreg_stages_from_code(o.tile_code);
-    if (mode == 6 && !conv_pp_eligible(p, dtype)) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for conv_pp_kernel");
+    ConvPlan pl;
+    const int prc = plan_from_algo(mode == 1 || mode == 3 ? algo & ~0xff : algo, p, dtype, pl);     // (no naive kernel here: 1 / 3 time the MFMA one)
+    if (prc < 0) return fail(SMK_E_ARG, "smk_bench_conv: wreg tile code 1..8");
+    if (prc && pl.kind == CK_HALO) return fail(SMK_E_HIP, "conv launch failed or geometry not eligible");
+    if (prc) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for %s", pl.kind == CK_WREG ? "conv_wreg_kernel" : "conv_pp_kernel");
     auto launch = [&]() {
-        if (mode == 6) return launch_conv_pp(p, s);
-        if (wr) {
-            ConvBatch cb;
-            cb.n = 1;
-            cb.p[0] = p;
-            return launch_conv_wreg_batch(cb, WREG_TILE[wr][0], WREG_TILE[wr][1], wr_stages, s);
-        }
-        return halo_bm ? launch_conv_halo(p, dtype, halo_bm, s) : launch_conv_mfma(p, dtype, t, s);
+        ConvBatch cb;                                    // (a launcher writes its grid layout into the batch)
+        cb.n = 1;
+        cb.p[0] = p;
+        return launch_plan(pl, cb, p.wgt, dtype, s, "conv");     // (halo kernel, timing only: the K order is irrelevant)
     };
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i)
-        if (launch()) return fail(SMK_E_HIP, "conv launch failed or geometry not eligible");
+    for (int i = 0; i < 3; ++i) CHK(launch());
     HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i)
-        if (launch()) return fail(SMK_E_HIP, "conv launch failed");
+    for (int i = 0; i < iters; ++i) CHK(launch());
     HIPCHK(hipEventRecord(e1, s));
     HIPCHK(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -3864,9 +3487,9 @@ int smk_host_conv2d_ex(const smk_conv_geom *g, const float *x, const float *w, c
 }
 
 // Which kernel and workgroup shape does the engine pick for one convolution of this geometry?  Host only (CPU tests pin the
-// measured layer rules with it).  Mirrors the decision order of run_conv: register-fed kernel (wreg_choice), else the
-// patch-sharing kernel (halo_choice), else the generic one (tile_from_code); *seq_cfg = the conv_seq_kernel tile code the layer
-// gets inside a persistent sequence, or -1 when it cannot be part of one.
+// measured layer rules with it): plan_conv, as run_conv calls it, on a pack whose derived copies are the ones the packer would
+// make, for the MI355X's 256 CUs; *seq_cfg = the conv_seq_kernel tile code the layer gets inside a persistent sequence, or -1
+// when it cannot be part of one.
 int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *kernel, int *bm, int *bn, int *seq_cfg) {
     if (!g || !kernel || !bm || !bn || !seq_cfg) return fail(SMK_E_ARG, "smk_host_plan_conv: null argument");
     if (dtype != DT_F32 && dtype != DT_F16) return fail(SMK_E_ARG, "smk_host_plan_conv: dtype");
@@ -3875,9 +3498,10 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
     static float dummy[64];
     in.p = dummy;
     pc.w = dummy; pc.bias = dummy;
-    if (g->k == 3) pc.w_halo = dummy;
-    if (dtype == DT_F16) pc.w_frag = dummy;
-    if (dtype == DT_F16 && g->k == 3 && pc.Kpad == 9 * pc.Ci) pc.w_frag_halo = dummy;
+    if (has_frag_pack(pc, dtype)) pc.w_frag = dummy;
+    if (has_frag16_pack(pc, dtype)) pc.w_frag16 = dummy;
+    if (has_halo_pack(pc, dtype)) pc.w_halo = dummy;
+    if (has_frag_halo_pack(pc, dtype)) pc.w_frag_halo = dummy;
     Act out, res;
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8); out.p = dummy;
     res = out;
@@ -3887,14 +3511,13 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
     fake.dtype = dtype;
     ConvParams p;
     CHK(conv_params(&fake, pc, in, &out, g->B, o, p));
-    const TileChoice t = tile_from_code(0, p, dtype);
-    int hb = halo_choice(pc, p, o, dtype);
-    if (hb && conv_ksplit(p, dtype, t) > 1) hb = 0;
-    const int wr = (hb && g_tune.wreg < 2 && g_tune.wreg_policy == 0) ? 0 : wreg_choice(p, o, dtype);
-    if (pp_choice(p, o, dtype)) { *kernel = 3; *bm = 256; *bn = 256; }
-    else if (wr) { *kernel = 2; *bm = WREG_TILE[wr][0]; *bn = WREG_TILE[wr][1]; }
-    else if (hb) { *kernel = 1; *bm = hb; *bn = 128; }
-    else { *kernel = 0; *bm = t.bm; *bn = t.bn; }
+    const ConvPlan pl = plan_conv(p, o, pc, dtype, g->B, fake.ncu);
+    switch (pl.kind) {
+    case CK_PP: *kernel = 3; *bm = 256; *bn = 256; break;
+    case CK_WREG: *kernel = 2; *bm = WREG_TILE[pl.wreg][0]; *bn = WREG_TILE[pl.wreg][1]; break;
+    case CK_HALO: *kernel = 1; *bm = pl.halo_bm; *bn = 128; break;
+    default: *kernel = 0; *bm = pl.tile.bm; *bn = pl.tile.bn;
+    }
     SeqLayer L;
     *seq_cfg = seq_layer_from(p, dtype, L) ? (int)L.cfg : -1;
     return 0;

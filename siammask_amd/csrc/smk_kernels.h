@@ -207,6 +207,7 @@ struct Tuning {
                                // merge_max_batch streams (beyond it every member fills the chip by itself), 2 always
     int merge_max_batch = 32;
     int rf_wreg = 3;           // Refine's two merged front launches on the register-fed kernel's 64x64 tile: bit 0 the window convolutions + deconv, bit 1 the v*.2 launch
+                               // (tile codes 0..8 in bits 4..7 / 8..11, engine.cpp seq_refine)
     int seq_fuse3 = 0;         // conv_seq_kernel: [conv2, conv3, next 1x1] of a Bottleneck as one tile routine on image-row tiles (0 off, 1 on, 2 layer3 only)
     int seq_spoll = 1;         // conv_seq_kernel's team barrier polls with s_load_dword glc (scalar path) instead of a vector sc1 load      // measured (profiles/r04k_merge_crossover_ab.txt): merging -5 % at B = 10, -1.5 % at B = 16, 0 at B = 24, +3.3 % at B = 32, +5.1 % at B = 64
     int wreg = 1;              // fp16 NHWC convolutions through conv_wreg_kernel (weights global -> VGPR, activations
@@ -248,7 +249,7 @@ struct Tuning {
     int npw = 4;               // conv_wreg / conv_seq: producer waves per workgroup (2 or 4; measured: profiles/r02_producer_waves_2_vs_4.txt)
     int a_stage = 0;           // conv_wreg / conv_seq: activation rows through registers instead of LDS-DMA (see ConvParams::a_stage)
     int pp = 1;                // fp16 NHWC convolutions with M >= 32768 rows, K >= 2304 and >= 200 tiles of 256 x 256 through conv_pp_kernel (0 off, 1 the
-                               // rule in engine.cpp pp_choice, 2 wherever eligible)
+                               // rule in conv_plan.cpp pp_choice, 2 wherever eligible)
     int main_prio = 3;         // pipelined steps: wave priority (s_setprio 0..3) of the MAIN part's launches (stem_pool, l1_block, the per-layer convolutions) -- they share
                                // SIMDs with the previous frame's tail, whose launches stay at 0: B = 1 +1.2 %, f16x3 +1.4 .. 2.4 %, B = 8 / 64 unchanged (profiles/r06bb_main_part_wave_priority.txt)
     int front_occ1 = 0;        // MEASURE builds: bit 0 l1_block_kernel, bit 1 stem_pool_kernel limited to ONE workgroup per CU (padding LDS): does the pipelined
@@ -432,8 +433,9 @@ int launch_conv_mfma_batch(ConvBatch &cb, int dtype, TileChoice t, void *stream)
 int launch_conv_naive(const ConvParams &p, int dtype, void *stream);
 // the split-K factor launch_conv_mfma_batch would use for this problem with this tile (1 = none)
 int conv_ksplit(const ConvParams &p, int dtype, const TileChoice &t);
-// 3x3 stride-1 convolution with the activation patch shared by the nine taps (chunk-major weight pack);
-// returns 1 when the geometry is not eligible
+// 3x3 stride-1 convolution with the activation patch shared by the nine taps (chunk-major weight pack), workgroups of bm = 128 / 64
+// pixels; returns 1 when the geometry is not eligible (conv_halo_eligible, host code)
+__attribute__((visibility("hidden"))) bool conv_halo_eligible(const ConvParams &p, int dtype, int bm);
 int launch_conv_halo(const ConvParams &p, int dtype, int bm, void *stream);
 // weights straight into registers (conv_wreg.hip): f16, NHWC epilogue, p.wgt_frag set; tile bm in {64,128} x bn in
 // {64,128,256}; returns 1 when a problem of the batch is not eligible

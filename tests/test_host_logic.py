@@ -201,6 +201,30 @@ def test_tuning_knobs_read_back():
         _lib.tune_get("no_such_knob")
     with pytest.raises(RuntimeError):
         _lib.tune(no_such_knob=1)
+    # one table drives smk_tune and smk_tune_get: every knob takes back what it reads, in a fresh interpreter (the defaults)
+    src = open(os.path.join(REPO, "siammask_amd", "csrc", "engine.cpp")).read()
+    table = src[src.index("static const Knob KNOBS[] = {"):]
+    table = table[:table.index("};")]
+    names = re.findall(r'\{"(\w+)", &\w+(?:\.\w+)?, "', table)            # (read-only diagnostics have no accepted values)
+    assert len(names) > 60 and "npw" in names and "seq_fused_last" not in names
+    code = ("import json; from siammask_amd import _lib\n"
+            "for k in %r: _lib.tune(**{k: _lib.tune_get(k)})\n"
+            "_lib.tune(seq_spoll=5, seq_kstag_mask=15)\n"
+            "print(json.dumps([_lib.tune_get('seq_spoll'), _lib.tune_get('seq_kstag_mask'), _lib.tune_get('measure_build')]))" % (names,))
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=REPO, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    spoll, kstag_mask, measure_build = json.loads(r.stdout.strip().splitlines()[-1])
+    assert (spoll, kstag_mask) == (1, 7)
+    if not measure_build:
+        with pytest.raises(RuntimeError):
+            _lib.tune(seq_fuse3=1)                    # a measured alternative: only in `make MEASURE=1` libraries
+    old = _lib.tune_get("rf_wreg")
+    try:
+        with pytest.raises(RuntimeError):
+            _lib.tune(rf_wreg=(9 << 4) | 1)           # tile code 9: past conv_wreg_kernel's eight shapes
+        assert _lib.tune_get("rf_wreg") == old
+    finally:
+        _lib.tune(rf_wreg=old)
 
 
 def _plan(B, cin, hw, cout, k, stride=1, pad=0, dil=1, res=False, win=None, dtype="f16"):
@@ -259,5 +283,9 @@ def test_layer_rules_are_the_measured_ones():
     assert _plan(64, 512, 31, 128, 1)[0] == "igemm"                            # l2.c1
     assert _plan(64, 256, 63, 64, 1)[0] == "igemm"                             # l1.c1
     assert _plan(64, 128, 31, 128, 3, pad=1)[0] == "halo"                      # l2.c2
+    # Refine's h* / post* layers (fp16 3x3 stride 1 on 32 / 16 / 4 channels): no halo pack (channels not a multiple of 64), conv_igemm
+    for B in (1, 8, 64):
+        for cin, hw, cout in ((32, 15, 32), (32, 31, 16), (16, 31, 16), (16, 61, 4), (4, 61, 4), (4, 127, 1)):
+            assert _plan(B, cin, hw, cout, 3, pad=1)[0] == "igemm", (B, cin, hw, cout)
     # fp32: no register-fed kernel, no sequences
     assert _plan(8, 1024, 31, 256, 1, dtype="f32")[0] == "igemm" and _plan(8, 1024, 31, 256, 1, dtype="f32")[2] == -1
