@@ -164,6 +164,14 @@ int smk_host_conv2d_ex(const smk_conv_geom *g, const float *x, const float *w, c
  * the layer cannot be part of one.  Lets the CPU test-suite pin the measured layer rules (profiles/r02_producer_waves_*). */
 int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *kernel, int *bm, int *bn, int *seq_cfg);
 
+/* Host only: the marks the engine puts on a list of convolutions before it runs as persistent sequences, under the current
+ * smk_tune knobs -- the smk_op_conv_seq list ops[0..n) (its validation and errors; n <= 144, launched as slices of 36 layers as
+ * the engine's own lists are) on a launch grid of `grid` workgroups (256 on the MI355X).  Per layer: cfg[i] = tile / pair /
+ * triple code, sync[i] = team barrier behind it, a_stage[i] = its a_stage bits (the resident-trunk marks, smk_kernels.h
+ * SEQ_YRES_*).  A non-null y_dev means the caller reads that output after the list.  smk_tune_get's "..._last" diagnostics
+ * are not touched. */
+int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *sync, int *a_stage);
+
 #ifdef __cplusplus
 }
 #endif

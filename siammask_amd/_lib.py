@@ -28,7 +28,7 @@ SYMBOLS = (
     "smk_version", "smk_last_error", "smk_create", "smk_destroy", "smk_set_weight",
     "smk_finalize_weights", "smk_template", "smk_track", "smk_refine", "smk_set_decode_params", "smk_decode", "smk_step", "smk_set_graph_mode", "smk_seq_status", "smk_seq_sync_check", "smk_set_result_ring", "smk_result_ring_cursor", "smk_set_pipeline", "smk_pipeline_join", "smk_pipeline_observe",
     "smk_debug_read", "smk_debug_seq_inject", "smk_tune", "smk_tune_get", "smk_profile", "smk_profile_dump", "smk_op_conv2d_ex", "smk_op_conv2d", "smk_op_dw_xcorr",
-    "smk_op_maxpool3x3s2", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
+    "smk_op_maxpool3x3s2", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
     "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels",
 )
 
@@ -120,6 +120,7 @@ def lib():
     L.smk_paste_mask.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, fp, vp]
     L.smk_paste_labels.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
+    L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)

@@ -1,6 +1,8 @@
-// conv_plan.cpp -- the kernel / workgroup-shape choice for one convolution (conv_plan.h).  Host code, no HIP runtime call.
+// conv_plan.cpp -- the kernel / workgroup-shape choice for one convolution, the marks on a sequence list (conv_plan.h).  Host
+// code, no HIP runtime call.
 #include "conv_plan.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -179,6 +181,189 @@ static bool seq_pair_fusable_why(const SeqLayer *L, int i, int *code, int *why) 
     else if (a.Kpad == 128 && a.Nst == 512 && b.Nst == 128) *code = SEQ_CFG_C3C1_L2;
     else { *why = 8; return false; }
     return true;
+}
+
+bool seq_pair_fits(const SeqLayer *L, int i, int B, int *code) {
+    if (!seq_pair_fusable(L, i, code)) return false;
+    // the routine switches rows beyond the image off with a buffer offset of 0x7ffff000: every tensor must end below it
+    const size_t px = (size_t)B * L[i].Ho * L[i].Wo;
+    const size_t widest = std::max(std::max((size_t)L[i].Cs, (size_t)L[i].Cos), std::max((size_t)L[i].res_Cs, (size_t)L[i + 1].Cos));
+    return px * widest * 2 < 0x7fff0000u && L[i].in_bytes < 0x7fff0000u;
+}
+
+// ---- plan_seq: the marks on a recorded list -------------------------------------------------------------------------
+// The passes mark the records of one launch [i0, i1) of the list L[0, n).
+
+// Pairs (seq_pair_fusable).  L: the launch's first record.
+static int seq_fuse_pairs(SeqLayer *L, int n, int B, const char *locked, bool have_xch) {
+    if (!g_tune.seq_fuse) return 0;
+    int fused = 0;
+    for (int i = 0; i + 1 < n; ++i) {
+        int code = 0;
+        if (locked && (locked[i] || locked[i + 1])) continue;        // (per-op tests: the caller forced a tile)
+        if (L[i].cfg >= SEQ_CFG_C3C1_L3 || L[i + 1].cfg >= SEQ_CFG_C3C1_L3 || !seq_pair_fits(L, i, B, &code)) continue;
+        if (g_tune.seq_fuse == 2 && code != SEQ_CFG_C3C1_L3) continue;      // (2: layer3's pairs only, A/B knob)
+        // Measured (profiles/r03h_*): -4.3 .. -5.5 % on the B = 8 step, -2.0 % at B = 16, -2.7 % at B = 24.  (What looked like a race of
+        // this routine at B = 12 was a buffer shared by two layouts inside the launch, see build_arena; profiles/r03h_b12_race.txt.)
+        // smk_tune "seq_pair2d": the pair split over two CUs (needs the exchange scratch: f16 contexts / smk_op_conv_seq have it)
+        if (have_xch && g_tune.seq_pair2d && (g_tune.seq_pair2d == 1 || code == SEQ_CFG_C3C1_L3))
+            code = code == SEQ_CFG_C3C1_L3 ? SEQ_CFG_C3C1P_L3 : SEQ_CFG_C3C1P_L2;
+        L[i].cfg = (signed char)code;
+        L[i + 1].cfg = (signed char)SEQ_CFG_C3C1_2ND;
+        if (!(g_tune.seq_kstag_mask & 1)) L[i].kstag = 0;
+        ++fused;
+        ++i;
+    }
+    return fused;
+}
+
+static bool read_after_list(const std::vector<const void *> &read_after, const void *y) {
+    return std::find(read_after.begin(), read_after.end(), y) != read_after.end();
+}
+
+// Triples (round 4): [conv2 (3x3, stride 1, pad = dilation), conv3, the next 1x1] of a Bottleneck as ONE tile routine on image-row
+// tiles (c3c1_tile.inc, FRONT = 1).  Runs behind seq_fuse_pairs: a marked pair (i + 1, i + 2) whose first record reads what record i --
+// the block's 3x3 convolution -- writes, and nobody else reads it.  The barrier between conv2 and the pair disappears with the
+// tensor.  wstd[i] = the (kh, kw, cin)-ordered fragment pack of record i (the record itself carries the chunk-major pack of the
+// patch-sharing tile).  smk_tune "seq_fuse3": 0 off, 1 on, 2 layer3's blocks only.
+static int seq_fuse_triples(SeqLayer *L, int i0, int i1, int n, const void *const *wstd, const char *locked,
+                            const std::vector<const void *> &read_after) {
+    if (!g_tune.seq_fuse3) return 0;
+    auto group_has_bar = [&](int k) {            // a barrier stands behind record k (pairs / triples: behind their LAST record only)
+        const int cf = L[k].cfg;
+        if (cf == SEQ_CFG_C3C1_L3 || cf == SEQ_CFG_C3C1_L2 || cf == SEQ_CFG_C3C1P_L3 || cf == SEQ_CFG_C3C1P_L2 || cf == SEQ_CFG_C2C3C1_L3 ||
+            cf == SEQ_CFG_C2C3C1_L2 || cf == SEQ_CFG_C2C3C1_MID)
+            return false;
+        return L[k].sync != 0;
+    };
+    int fused = 0;
+    for (int i = i0; i + 2 < i1; ++i) {
+        SeqLayer &c2 = L[i], &c3 = L[i + 1], &c1 = L[i + 2];
+        if (locked && (locked[i] || locked[i + 1] || locked[i + 2])) continue;
+        if ((c3.cfg != SEQ_CFG_C3C1_L3 && c3.cfg != SEQ_CFG_C3C1_L2) || c1.cfg != SEQ_CFG_C3C1_2ND) continue;
+        if (c2.cfg != SEQ_CFG_HALO128 && c2.cfg != SEQ_CFG_HALO64 && c2.cfg > 9) continue;     // (a plain tile or the patch-sharing one)
+        const int code = c3.cfg == SEQ_CFG_C3C1_L3 ? SEQ_CFG_C2C3C1_L3 : SEQ_CFG_C2C3C1_L2;
+        if (g_tune.seq_fuse3 == 2 && code != SEQ_CFG_C2C3C1_L3) continue;
+        const int kc = c3.Kpad;                  // 256 / 128: conv2 is kc -> kc
+        if (c2.kh != 3 || c2.kw != 3 || c2.stride != 1 || c2.stride_x != 1 || c2.pad != c2.dil || c2.dil < 1 || c2.dil > 2) continue;
+        if (c2.Ci != kc || c2.Nst != kc || c2.Kpad != 9 * kc || !c2.relu || c2.res || c2.res_mode != RES_NONE || !c2.sync) continue;
+        if (c2.org_y || c2.org_x || c2.Hl != c2.Hs || c2.Wl != c2.Ws || c2.Ho != c2.Hs || c2.Wo != c2.Ws) continue;
+        if (c2.Wo > 32 || c2.Wo < 24 || c2.Wo + 2 * c2.dil > 35) continue;      // one image row per 32-row tile; short rows (the template's 15 x 15) stay pairs
+        if (c3.in != c2.out || c3.cin_off != c2.cout_off || c3.Cs != c2.Cos || c3.Hs != c2.Ho || c3.Ws != c2.Wo) continue;
+        if (!wstd[i]) continue;
+        // conv2's output never reaches memory: nobody else may read it, in this launch, a later one or behind the list, until a
+        // later record writes that buffer again (the blocks of a layer share their intermediates)
+        bool other_reader = read_after_list(read_after, c2.out);
+        for (int j = i + 2; j < n; ++j) {
+            if (L[j].in == c2.out || L[j].res == c2.out) { other_reader = true; break; }
+            if (L[j].out == c2.out) { other_reader = false; break; }
+        }
+        if (other_reader || c2.out == c3.res || c2.out == c1.out || c2.out == c3.out) continue;
+        // conv2's input must have been written in front of the barrier this routine waits for (the last one before record i)
+        int pend = -1;
+        for (int k = i - 1; k >= i0; --k)
+            if (group_has_bar(k)) { pend = k; break; }
+        bool in_ok = true;
+        for (int j = i - 1; j >= i0; --j)
+            if (L[j].out == c2.in) { in_ok = j <= pend; break; }
+        if (!in_ok) continue;
+        // the residual rows: in front of the wait when their writer is separated from record i by a barrier ALREADY passed, or when it
+        // is the previous triple's conv3 on the same row tiles (then this very workgroup wrote them); behind the wait otherwise
+        int res_late = 0;
+        for (int j = i - 1; j >= i0; --j)
+            if (L[j].out == c3.res) {
+                bool passed = false;
+                for (int k = j; k < pend; ++k) passed = passed || group_has_bar(k);
+                const bool own_rows = L[j].cfg == SEQ_CFG_C2C3C1_MID && L[j].Ho == c3.Ho && L[j].Wo == c3.Wo;
+                if (!passed && !own_rows) res_late = 1;
+                break;
+            }
+        c2.cfg = (signed char)code;
+        c2.wgt_frag = wstd[i];
+        c2.sync = 0;
+        c3.cfg = (signed char)SEQ_CFG_C2C3C1_MID;
+        c3.a_stage = (signed char)res_late;
+        ++fused;
+        i += 2;
+    }
+    return fused;
+}
+
+// Resident trunk (round 6; smk_kernels.h SEQ_YRES_*): consecutive fused pairs of one ResNet layer -- [conv3 k + conv1 k+1], conv2 k+1 on a
+// patch-sharing tile, [conv3 k+1 + conv1 k+2] -- run on the same 32-row tiles; with ONE image per team and a tile per workgroup the
+// same workgroup owns the same rows in both, and the second pair's residual is the Y image the first one left in its LDS
+// (experiments/siammask_sharp/resnet.py:80-103: `out += residual`, residual = the previous block's output).  Marks: the second
+// pair does not fetch its residual rows (64 KB per CU "usually from beyond the L2", profiles/r05_seq_phase_clocks.txt: 3.0-3.5 of a
+// layer3 pair's 17-18 us), the first one does not store Y when nobody else reads the tensor, the 3x3 convolution between them works
+// in the LDS behind the image.  Values and summation orders are unchanged: bit-identical (tests/test_gpu_seq.py).
+static int seq_mark_resident(SeqLayer *L, int i0, int i1, int n, const SeqPlanEnv &env, const std::vector<const void *> &read_after) {
+    if (!g_tune.seq_yres || env.B > 8) return 0;         // (image b runs on team b % 8: from nine images on a workgroup owns two tiles per pair)
+    int prev = -1, marked = 0;
+    for (int i = i0; i + 1 < i1; ++i) {
+        const int cfg = L[i].cfg;
+        if (cfg != SEQ_CFG_C3C1_L3 && cfg != SEQ_CFG_C3C1_L2) continue;
+        const int p = prev;
+        prev = i;
+        if (p < 0 || L[p].cfg != cfg || i != p + 3) continue;
+        const int mid = L[p + 2].cfg;
+        if (mid != SEQ_CFG_HALO64 && mid != SEQ_CFG_HALO128) continue;
+        if ((L[i].Ho * L[i].Wo + 31) / 32 > env.nslots || L[i].Ho != L[p].Ho || L[i].Wo != L[p].Wo) continue;
+        if (L[i].res != L[p].out || L[i].res_Cs != L[p].Cos || L[i].res_coff != L[p].cout_off) continue;
+        L[i].a_stage |= SEQ_YRES_IN;
+        L[p + 2].a_stage |= SEQ_LDS_HI;
+        ++marked;
+        // the store of Y: does anything but the pair's own second record (from LDS) and this residual read the tensor, anywhere in
+        // the list or behind it?  (Conservative: a reader behind a later write of the buffer counts too.)
+        bool others = read_after_list(read_after, L[p].out);
+        for (int j = 0; j < n && !others; ++j) {
+            if (j != p + 1 && L[j].in == L[p].out) others = true;
+            if (j != i && L[j].res == L[p].out) others = true;
+        }
+        if (!others) L[p].a_stage |= SEQ_YRES_NOSTORE;
+    }
+    return marked;
+}
+
+SeqPlanStats plan_seq(std::vector<SeqRec> &rec, const SeqPlanEnv &env, const char *locked, const std::vector<const void *> &read_after) {
+    const int n = (int)rec.size();
+    std::vector<SeqLayer> L(n);
+    std::vector<const void *> wstd(n);
+    for (int i = 0; i < n; ++i) { L[i] = rec[i].L; wstd[i] = rec[i].wstd; }
+    // the pair split over two CUs trades partial sums through the scratch: an even team, at most SEQ_XCH_PAIRS pairs per team
+    const bool xch = env.have_xch && env.nslots % 2 == 0 && env.nslots / 2 <= SEQ_XCH_PAIRS;
+    SeqPlanStats st;
+    for (int i0 = 0; i0 < n; i0 += SEQ_MAX) {
+        const int i1 = std::min(n, i0 + SEQ_MAX);
+        st.pairs = seq_fuse_pairs(L.data() + i0, i1 - i0, env.B, locked ? locked + i0 : nullptr, xch);
+        st.triples = seq_fuse_triples(L.data(), i0, i1, n, wstd.data(), locked, read_after);
+        st.resident = seq_mark_resident(L.data(), i0, i1, n, env, read_after);
+    }
+    for (int i = 0; i < n; ++i) rec[i].L = L[i];
+    return st;
+}
+
+double seq_fabric_bytes(const SeqLayer *L, int n, int B, const void *late_read) {
+    double ext = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const SeqLayer &l = L[i];
+        bool in_inside = false, res_inside = l.res == nullptr, out_read = false;
+        for (int j = 0; j < n; ++j) {
+            if (j < i && L[j].out == l.in) in_inside = true;
+            if (j < i && l.res && L[j].out == l.res) res_inside = true;
+            if (j > i && (L[j].in == l.out || L[j].res == l.out)) out_read = true;
+        }
+        bool in_counted = false, res_counted = false;          // a tensor several layers read is fetched once
+        for (int j = 0; j < i; ++j) {
+            if (L[j].in == l.in || L[j].res == l.in) in_counted = true;
+            if (l.res && (L[j].in == l.res || L[j].res == l.res)) res_counted = true;
+        }
+        const double px_in = (double)B * l.Hs * l.Ws, px_out = (double)B * l.Ho * l.Wo;
+        ext += (double)l.Nst * l.Kpad * 2.0;
+        if (!in_inside && !in_counted) ext += px_in * l.Cs * 2.0;
+        if (!res_inside && !res_counted) ext += px_out * l.res_Cs * 2.0;
+        if (!out_read || l.out == late_read) ext += px_out * l.Nst * 2.0;
+    }
+    return ext;
 }
 
 // conv_wreg_kernel (weights global -> VGPR) or the LDS-staged kernels?  Returns the tile code 1..8 (WREG_TILE) or 0.

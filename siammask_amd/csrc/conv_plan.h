@@ -1,9 +1,11 @@
-// conv_plan.h -- which kernel runs one convolution, and with which workgroup shape (internal to libsiammask_hip.so).
-// Host code only and no HIP runtime call (the CU count is an argument): every launch path of the engine, its per-op entry
-// points and smk_host_plan_conv plan through plan_conv, so the CPU tests pin what the GPU runs.  engine.cpp's launch_plan is
-// the only code that turns a plan into a launch.
+// conv_plan.h -- which kernel runs one convolution, and with which workgroup shape; how a recorded list of convolutions
+// becomes persistent sequence launches (internal to libsiammask_hip.so).
+// Host code only and no HIP runtime call (the CU count and the grid are arguments): every launch path of the engine, its per-op
+// entry points and smk_host_plan_conv plan through plan_conv, and seq_flush, smk_op_conv_seq and smk_host_plan_seq through
+// plan_seq, so the CPU tests pin what the GPU runs.  engine.cpp's launch_plan is the only code that turns a plan into a launch.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "smk_kernels.h"
 
@@ -89,9 +91,34 @@ ConvPlan plan_conv_batch(const smk::ConvBatch &cb, const ConvOpt *const *o, int 
 // the kernel name a profile record carries (merged > 0: members of a merged launch)
 std::string plan_kernel_name(const ConvPlan &pl, int dtype, int out_mode, int merged = 0);
 
-// ---- persistent per-XCD convolution sequences (conv_seq_kernel): shape-only decisions ----------------------------
+// ---- persistent per-XCD convolution sequences (conv_seq_kernel) ----------------------------------------------------
 bool seq_halo_ok(const smk::ConvParams &p, int bm);
 bool seq_layer_from(const smk::ConvParams &p, int dtype, smk::SeqLayer &L, int force_halo = 0);
 bool seq_pair_fusable(const smk::SeqLayer *L, int i, int *code);
+// records i, i + 1 as one pair routine at batch B: seq_pair_fusable, and every tensor ends below the routine's out-of-range offset
+bool seq_pair_fits(const smk::SeqLayer *L, int i, int B, int *code);
+
+// One recorded convolution of a sequence list.  wstd: the (kh, kw, cin)-ordered fragment pack (the triples need it where the
+// record carries the chunk-major one of the patch-sharing tile).
+struct SeqRec {
+    smk::SeqLayer L;
+    const void *wstd = nullptr;
+    std::string id;
+};
+struct SeqPlanEnv {
+    int B = 0;
+    int nslots = 0;            // workgroups per team: the launch grid / 8
+    bool have_xch = false;     // the pair-split exchange scratch exists
+};
+struct SeqPlanStats { int pairs = 0, triples = 0, resident = 0; };   // of the LAST launch of the list
+
+// The marks on a recorded list, launched as fixed slices of SEQ_MAX records: pairs (cfg), triples (cfg, sync, a_stage) and the
+// resident trunk (a_stage).  Pairs and triples never cross a slice, and the backward scans for writers stay inside it (a launch
+// boundary orders every earlier write); the forward scans for readers see the whole list and read_after, the buffers read
+// after the list ends.  locked (may be null): records whose tile the caller forced.
+SeqPlanStats plan_seq(std::vector<SeqRec> &rec, const SeqPlanEnv &env, const char *locked, const std::vector<const void *> &read_after);
+// what one launch of n records must move across the fabric if every tensor produced AND consumed inside it stays in the XCD's
+// L2: tensors read but not produced here, every weight pack once, tensors produced here and not read here, and late_read
+double seq_fabric_bytes(const smk::SeqLayer *L, int n, int B, const void *late_read);
 
 #pragma GCC visibility pop

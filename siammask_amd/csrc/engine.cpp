@@ -263,15 +263,16 @@ struct smk_ctx {
     std::map<GraphKey, bool> graph_has_seq;
     unsigned long long *seq_clk = nullptr, *seq_clk2 = nullptr;   // SMK_SEQ_CLK stamps (measurement aid), per context
     int seq_grid = 0;                // workgroups of a sequence launch (= CUs) when the placement check passed, else 0
-    bool seq_on = false;             // run_conv records into seq_rec instead of launching
+    bool seq_on = false;             // run_conv records into seq instead of launching
     // fused frame step: the mask head is handed to the Refine chain launch (chain_mask_kernel) instead of its own launch
     bool defer_mask_req = false, have_deferred_mask = false;
     ConvParams deferred_mask;
     double deferred_mask_flop = 0.0, deferred_mask_bytes = 0.0;
-    std::vector<SeqLayer> seq_rec;
-    std::vector<const void *> seq_wstd;      // per record: the (kh, kw, cin)-ordered fragment pack (seq_fuse_triples needs it where the record carries the chunk-major one)
-    std::vector<std::string> seq_ids;
-    double seq_flop = 0.0, seq_bytes = 0.0;
+    struct SeqList {                 // what run_conv recorded while seq_on (conv_plan.h SeqRec), algorithmic work summed over it
+        std::vector<SeqRec> rec;
+        double flop = 0.0, bytes = 0.0;
+        void clear() { rec.clear(); flop = bytes = 0.0; }
+    } seq;
 
     // result ring (smk_set_result_ring): caller-owned rows, library-owned cursor
     double *ring_box = nullptr;
@@ -829,142 +830,17 @@ static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, co
 }
 
 // ---- persistent per-XCD convolution sequences (conv_seq_kernel) ---------------------------------------------------
-// While c->seq_on, run_conv / run_conv_jobs RECORD eligible convolutions instead of launching them; seq_flush turns the
-// recorded list into persistent launches of <= SEQ_MAX layers.  Everything else (non-eligible convolutions, other
-// kernels) flushes first, so program order is preserved.
-static int g_seq_fused_last = 0;          // pairs fused in the list that was launched last (smk_tune_get "seq_fused_last", a diagnostic)
-static void seq_fuse_pairs(SeqLayer *L, int n, int B, const std::vector<char> *locked = nullptr, bool have_xch = false) {
-    g_seq_fused_last = 0;
-    if (!g_tune.seq_fuse) return;
-    for (int i = 0; i + 1 < n; ++i) {
-        int code = 0;
-        if (locked && ((*locked)[i] || (*locked)[i + 1])) continue;        // (per-op tests: the caller forced a tile)
-        if (L[i].cfg >= SEQ_CFG_C3C1_L3 || L[i + 1].cfg >= SEQ_CFG_C3C1_L3 || !seq_pair_fusable(L, i, &code)) continue;
-        if (g_tune.seq_fuse == 2 && code != SEQ_CFG_C3C1_L3) continue;      // (2: layer3's pairs only, A/B knob)
-        // Measured (profiles/r03h_*): -4.3 .. -5.5 % on the B = 8 step, -2.0 % at B = 16, -2.7 % at B = 24.  (What looked like a race of
-        // this routine at B = 12 was a buffer shared by two layouts inside the launch, see build_arena; profiles/r03h_b12_race.txt.)
-        // the routine switches rows beyond the image off with a buffer offset of 0x7ffff000: every tensor must end below it
-        const size_t px = (size_t)B * L[i].Ho * L[i].Wo;
-        const size_t widest = std::max(std::max((size_t)L[i].Cs, (size_t)L[i].Cos), std::max((size_t)L[i].res_Cs, (size_t)L[i + 1].Cos));
-        if (px * widest * 2 >= 0x7fff0000u || L[i].in_bytes >= 0x7fff0000u) continue;
-        // smk_tune "seq_pair2d": the pair split over two CUs (needs the exchange scratch: f16 contexts / smk_op_conv_seq have it)
-        if (have_xch && g_tune.seq_pair2d && (g_tune.seq_pair2d == 1 || code == SEQ_CFG_C3C1_L3))
-            code = code == SEQ_CFG_C3C1_L3 ? SEQ_CFG_C3C1P_L3 : SEQ_CFG_C3C1P_L2;
-        L[i].cfg = (signed char)code;
-        L[i + 1].cfg = (signed char)SEQ_CFG_C3C1_2ND;
-        if (!(g_tune.seq_kstag_mask & 1)) L[i].kstag = 0;
-        ++g_seq_fused_last;
-        ++i;
-    }
-}
-
-// Resident trunk (round 6; smk_kernels.h SEQ_YRES_*): consecutive fused pairs of one ResNet layer -- [conv3 k + conv1 k+1], conv2 k+1 on a
-// patch-sharing tile, [conv3 k+1 + conv1 k+2] -- run on the same 32-row tiles; with ONE image per team and a tile per workgroup the
-// same workgroup owns the same rows in both, and the second pair's residual is the Y image the first one left in its LDS
-// (experiments/siammask_sharp/resnet.py:80-103: `out += residual`, residual = the previous block's output).  Marks: the second
-// pair does not fetch its residual rows (64 KB per CU "usually from beyond the L2", profiles/r05_seq_phase_clocks.txt: 3.0-3.5 of a
-// layer3 pair's 17-18 us), the first one does not store Y when nobody else reads the tensor, the 3x3 convolution between them works
-// in the LDS behind the image.  Values and summation orders are unchanged: bit-identical (tests/test_gpu_seq.py).
-// `keep` (per-op tests): records whose output the caller reads back.
-static int g_seq_yres_last = 0;           // pairs that found their residual resident in the list launched last (smk_tune_get "seq_yres_last")
-static void seq_mark_resident(SeqLayer *L, int n, int B, int nslots, const void *extern_read = nullptr, const std::vector<char> *keep = nullptr) {
-    g_seq_yres_last = 0;
-    if (!g_tune.seq_yres || B > 8) return;               // (image b runs on team b % 8: from nine images on a workgroup owns two tiles per pair)
-    int prev = -1;
-    for (int i = 0; i + 1 < n; ++i) {
-        const int cfg = L[i].cfg;
-        if (cfg != SEQ_CFG_C3C1_L3 && cfg != SEQ_CFG_C3C1_L2) continue;
-        const int p = prev;
-        prev = i;
-        if (p < 0 || L[p].cfg != cfg || i != p + 3) continue;
-        const int mid = L[p + 2].cfg;
-        if (mid != SEQ_CFG_HALO64 && mid != SEQ_CFG_HALO128) continue;
-        if ((L[i].Ho * L[i].Wo + 31) / 32 > nslots || L[i].Ho != L[p].Ho || L[i].Wo != L[p].Wo) continue;
-        if (L[i].res != L[p].out || L[i].res_Cs != L[p].Cos || L[i].res_coff != L[p].cout_off) continue;
-        L[i].a_stage |= SEQ_YRES_IN;
-        L[p + 2].a_stage |= SEQ_LDS_HI;
-        ++g_seq_yres_last;
-        // the store of Y: only the pair's own second record (from LDS) and this residual read the tensor?
-        bool others = L[p].out == extern_read || (keep && (*keep)[p]);
-        for (int j = 0; j < n && !others; ++j) {
-            if (j != p + 1 && L[j].in == L[p].out) others = true;
-            if (j != i && L[j].res == L[p].out) others = true;
-        }
-        if (!others) L[p].a_stage |= SEQ_YRES_NOSTORE;
-    }
-}
-
-// Triples (round 4): [conv2 (3x3, stride 1, pad = dilation), conv3, the next 1x1] of a Bottleneck as ONE tile routine on image-row
-// tiles (c3c1_tile.inc, FRONT = 1).  Runs behind seq_fuse_pairs: a marked pair (i + 1, i + 2) whose first record reads what record i --
-// the block's 3x3 convolution -- writes, and nobody else reads it.  The barrier between conv2 and the pair disappears with the
-// tensor.  wstd[i] = the (kh, kw, cin)-ordered fragment pack of record i (the record itself carries the chunk-major pack of the
-// patch-sharing tile).  smk_tune "seq_fuse3": 0 off, 1 on, 2 layer3's blocks only.
-static int g_seq_fused3_last = 0;
-static void seq_fuse_triples(SeqLayer *L, int n, int B, const void *const *wstd, const std::vector<char> *locked = nullptr) {
-    g_seq_fused3_last = 0;
-    if (!g_tune.seq_fuse3 || !wstd) return;
-    auto group_has_bar = [&](int k) {            // a barrier stands behind record k (pairs / triples: behind their LAST record only)
-        const int cf = L[k].cfg;
-        if (cf == SEQ_CFG_C3C1_L3 || cf == SEQ_CFG_C3C1_L2 || cf == SEQ_CFG_C3C1P_L3 || cf == SEQ_CFG_C3C1P_L2 || cf == SEQ_CFG_C2C3C1_L3 ||
-            cf == SEQ_CFG_C2C3C1_L2 || cf == SEQ_CFG_C2C3C1_MID)
-            return false;
-        return L[k].sync != 0;
-    };
-    for (int i = 0; i + 2 < n; ++i) {
-        SeqLayer &c2 = L[i], &c3 = L[i + 1], &c1 = L[i + 2];
-        if (locked && ((*locked)[i] || (*locked)[i + 1] || (*locked)[i + 2])) continue;
-        if ((c3.cfg != SEQ_CFG_C3C1_L3 && c3.cfg != SEQ_CFG_C3C1_L2) || c1.cfg != SEQ_CFG_C3C1_2ND) continue;
-        if (c2.cfg != SEQ_CFG_HALO128 && c2.cfg != SEQ_CFG_HALO64 && c2.cfg > 9) continue;     // (a plain tile or the patch-sharing one)
-        const int code = c3.cfg == SEQ_CFG_C3C1_L3 ? SEQ_CFG_C2C3C1_L3 : SEQ_CFG_C2C3C1_L2;
-        if (g_tune.seq_fuse3 == 2 && code != SEQ_CFG_C2C3C1_L3) continue;
-        const int kc = c3.Kpad;                  // 256 / 128: conv2 is kc -> kc
-        if (c2.kh != 3 || c2.kw != 3 || c2.stride != 1 || c2.stride_x != 1 || c2.pad != c2.dil || c2.dil < 1 || c2.dil > 2) continue;
-        if (c2.Ci != kc || c2.Nst != kc || c2.Kpad != 9 * kc || !c2.relu || c2.res || c2.res_mode != RES_NONE || !c2.sync) continue;
-        if (c2.org_y || c2.org_x || c2.Hl != c2.Hs || c2.Wl != c2.Ws || c2.Ho != c2.Hs || c2.Wo != c2.Ws) continue;
-        if (c2.Wo > 32 || c2.Wo < 24 || c2.Wo + 2 * c2.dil > 35) continue;      // one image row per 32-row tile; short rows (the template's 15 x 15) stay pairs
-        if (c3.in != c2.out || c3.cin_off != c2.cout_off || c3.Cs != c2.Cos || c3.Hs != c2.Ho || c3.Ws != c2.Wo) continue;
-        if (!wstd[i]) continue;
-        bool other_reader = false;               // conv2's output never reaches memory: nobody else may read it ...
-        for (int j = i + 2; j < n; ++j) {        // ... until a later record writes that buffer again (the blocks of a layer share their intermediates)
-            if (L[j].in == c2.out || L[j].res == c2.out) { other_reader = true; break; }
-            if (L[j].out == c2.out) break;
-        }
-        if (other_reader || c2.out == c3.res || c2.out == c1.out || c2.out == c3.out) continue;
-        // conv2's input must have been written in front of the barrier this routine waits for (the last one before record i)
-        int pend = -1;
-        for (int k = i - 1; k >= 0; --k)
-            if (group_has_bar(k)) { pend = k; break; }
-        bool in_ok = true;
-        for (int j = i - 1; j >= 0; --j)
-            if (L[j].out == c2.in) { in_ok = j <= pend; break; }
-        if (!in_ok) continue;
-        // the residual rows: in front of the wait when their writer is separated from record i by a barrier ALREADY passed, or when it
-        // is the previous triple's conv3 on the same row tiles (then this very workgroup wrote them); behind the wait otherwise
-        int res_late = 0;
-        for (int j = i - 1; j >= 0; --j)
-            if (L[j].out == c3.res) {
-                bool passed = false;
-                for (int k = j; k < pend; ++k) passed = passed || group_has_bar(k);
-                const bool own_rows = L[j].cfg == SEQ_CFG_C2C3C1_MID && L[j].Ho == c3.Ho && L[j].Wo == c3.Wo;
-                if (!passed && !own_rows) res_late = 1;
-                break;
-            }
-        c2.cfg = (signed char)code;
-        c2.wgt_frag = wstd[i];
-        c2.sync = 0;
-        c3.cfg = (signed char)SEQ_CFG_C2C3C1_MID;
-        c3.a_stage = (signed char)res_late;
-        ++g_seq_fused3_last;
-        i += 2;
-    }
-}
+// While c->seq_on, run_conv / run_conv_jobs RECORD eligible convolutions instead of launching them; seq_flush plans the whole
+// recorded list (plan_seq, conv_plan.cpp) and turns it into persistent launches of <= SEQ_MAX layers.  Everything else
+// (non-eligible convolutions, other kernels) flushes first, so program order is preserved.
+static SeqPlanStats g_seq_last;   // marks of the launch issued last (smk_tune_get "seq_fused_last" / "seq_fused3_last" / "seq_yres_last", diagnostics)
 
 // SMK_SEQ_CLK (measurement aid, eager runs only): print what (team 0, slot 0) stamped
-static void seq_print_clk(const SeqArgs &a, const std::vector<std::string> &ids, const char *idn, const unsigned long long *h,
+static void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, const unsigned long long *h,
                           const unsigned long long *h2) {
     fprintf(stderr, "[seq clk] %s total %.2f us\n", idn, (h[2 * a.n] - h[0]) / 100.0);
     for (int i = 0; i < a.n; ++i)
-        fprintf(stderr, "[seq clk]   %-10s cfg %d sync %d kstag %d  tiles %.2f us  arrive %.2f us\n", ids[i].c_str(), a.L[i].cfg,
+        fprintf(stderr, "[seq clk]   %-10s cfg %d sync %d kstag %d  tiles %.2f us  arrive %.2f us\n", r[i].id.c_str(), a.L[i].cfg,
                 a.L[i].sync, a.L[i].kstag, (h[1 + 2 * i] - h[2 * i]) / 100.0, (h[2 + 2 * i] - h[1 + 2 * i]) / 100.0);
     if (!h2) return;
     // arrival of team 0's 32 workgroups at the barrier behind each layer (SMK_SEQ_CLK=2): how much of a team wait is SKEW (the last
@@ -982,7 +858,7 @@ static void seq_print_clk(const SeqArgs &a, const std::vector<std::string> &ids,
         unsigned long long rel = 0;                      // slot 0 past the wait: stamp 7 of its first tile in the next record that has one
         for (int j = i + 1; j < a.n && !rel; ++j) rel = h2[12 * j + 7];
         fprintf(stderr, "[seq arrive] %-10s %2d workgroups: first -> last arrival %.2f us, mean wait for the last one %.2f us, last arrival -> slot 0 "
-                "released %.2f us\n", ids[i].c_str(), nz, (mx - mn) / 100.0, sum / nz / 100.0, rel > mx ? (rel - mx) / 100.0 : -1.0);
+                "released %.2f us\n", r[i].id.c_str(), nz, (mx - mn) / 100.0, sum / nz / 100.0, rel > mx ? (rel - mx) / 100.0 : -1.0);
     }
     for (int i = 0; i < a.n; ++i) {
         const unsigned long long *t = h2 + 12 * i;
@@ -992,26 +868,26 @@ static void seq_print_clk(const SeqArgs &a, const std::vector<std::string> &ids,
             fprintf(stderr, "[seq clk2]  %-10s first tile (pair split, fused with the next 1x1): team wait %.2f | activation rows -> LDS %.2f | "
                     "conv3 K loop %.2f | residual -> Y %.2f | Y = relu(..) %.2f | Y stores + second K loop + slab + arrive %.2f | partner wait + add %.2f | "
                     "stores %.2f us | %.0f MHz\n",
-                    ids[i].c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
+                    r[i].id.c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
                     (t[4] - t[3]) / 100.0, (t[5] - t[4]) / 100.0, (t[10] - t[5]) / 100.0, (t[6] - t[10]) / 100.0, us > 0 ? (double)(t[9] - t[8]) / us : 0.0);
             continue;
         }
         if (a.L[i].cfg == SEQ_CFG_C2C3C1_L3 || a.L[i].cfg == SEQ_CFG_C2C3C1_L2) {   // a triple: c3c1_tile's phases with conv2 in front
             fprintf(stderr, "[seq clk2]  %-10s first tile (3x3 + conv3 + the next 1x1): prologue + team wait %.2f | patch -> LDS + conv2 %.2f | "
                     "conv3 K loop %.2f | residual -> Y %.2f | Y = relu(..) %.2f | Y stores + second K loop %.2f | its epilogue + stores %.2f us | %.0f MHz\n",
-                    ids[i].c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
+                    r[i].id.c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
                     (t[4] - t[3]) / 100.0, (t[5] - t[4]) / 100.0, (t[6] - t[5]) / 100.0, us > 0 ? (double)(t[9] - t[8]) / us : 0.0);
             continue;
         }
         if (a.L[i].cfg == SEQ_CFG_C3C1_L3 || a.L[i].cfg == SEQ_CFG_C3C1_L2) {       // a fused pair: c3c1_tile's phases
             fprintf(stderr, "[seq clk2]  %-10s first tile (fused with the next 1x1): team wait %.2f | activation rows -> LDS %.2f | "
                     "conv3 K loop %.2f | residual -> Y %.2f | Y = relu(..) %.2f | Y stores + second K loop %.2f | its epilogue + stores %.2f us | %.0f MHz\n",
-                    ids[i].c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
+                    r[i].id.c_str(), (t[7] - t[0]) / 100.0, (t[1] - t[7]) / 100.0, (t[2] - t[1]) / 100.0, (t[3] - t[2]) / 100.0,
                     (t[4] - t[3]) / 100.0, (t[5] - t[4]) / 100.0, (t[6] - t[5]) / 100.0, us > 0 ? (double)(t[9] - t[8]) / us : 0.0);
             continue;
         }
         fprintf(stderr, "[seq clk2]  %-10s first tile: prologue %.2f | team wait %.2f | first operands %.2f | K loop %.2f | other waves %.2f | "
-                "acc -> LDS %.2f | bias/res/stores %.2f | end sync %.2f us | %.0f MHz\n", ids[i].c_str(),
+                "acc -> LDS %.2f | bias/res/stores %.2f | end sync %.2f us | %.0f MHz\n", r[i].id.c_str(),
                 t[7] ? (t[7] - t[0]) / 100.0 : 0.0, 0.0, t[7] ? (t[1] - t[7]) / 100.0 : (t[1] - t[0]) / 100.0, (t[2] - t[1]) / 100.0,
                 (t[3] - t[2]) / 100.0, (t[4] - t[3]) / 100.0, (t[5] - t[4]) / 100.0, (t[6] - t[5]) / 100.0,
                 us > 0 ? (double)(t[9] - t[8]) / us : 0.0);
@@ -1019,7 +895,14 @@ static void seq_print_clk(const SeqArgs &a, const std::vector<std::string> &ids,
 }
 
 static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
-    const size_t n = c->seq_rec.size();
+    const size_t n = c->seq.rec.size();
+    if (!n) return 0;
+    auto buf = [c](const char *name) -> const void * { auto it = c->buf.find(name); return it == c->buf.end() ? nullptr : it->second; };
+    // read behind the list: p2 (Refine) and what smk_debug_read can name
+    std::vector<const void *> read_after;
+    for (const char *name : {"p2", c->p3_buf, "search", "zf", "xs"})
+        if (buf(name)) read_after.push_back(buf(name));
+    g_seq_last = plan_seq(c->seq.rec, {B, c->seq_grid >> 3, c->seq_xch != nullptr}, nullptr, read_after);
     for (size_t i0 = 0; i0 < n; i0 += SEQ_MAX) {
         SeqArgs a;
         memset(&a, 0, sizeof(a));
@@ -1033,10 +916,8 @@ static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
         // pipelined step, depth 2: the last launch of the list tells the previous frame's chain / mask-head launch that the chip is free
         a.exit_sem = (c->pipe_seq_exit && i0 + SEQ_MAX >= n) ? c->pipe_cnt + 7 : nullptr;
         if (a.exit_sem) c->pipe_seq_exit_done = true;
-        for (int i = 0; i < a.n; ++i) a.L[i] = c->seq_rec[i0 + i];
-        seq_fuse_pairs(a.L, a.n, B, nullptr, c->seq_xch != nullptr && (c->seq_grid >> 3) % 2 == 0 && (c->seq_grid >> 4) <= SEQ_XCH_PAIRS);   // (a pair never straddles two launches)
-        seq_fuse_triples(a.L, a.n, B, c->seq_wstd.data() + i0);
-        seq_mark_resident(a.L, a.n, B, c->seq_grid >> 3, c->buf.count("p2") ? c->buf.at("p2") : nullptr);
+        const SeqRec *r = c->seq.rec.data() + i0;
+        for (int i = 0; i < a.n; ++i) a.L[i] = r[i].L;
         const char *ck = getenv("SMK_SEQ_CLK");
         const bool want_clk = ck != nullptr && !c->graph_mode;
         // SMK_SEQ_CLK=2: additionally the phases INSIDE the first tile of every layer (a separate kernel build with the stamps)
@@ -1047,34 +928,10 @@ static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
         a.clk = want_clk ? c->seq_clk : nullptr;
         a.clk2 = want_clk2 ? c->seq_clk2 : nullptr;
         char idn[96];
-        snprintf(idn, sizeof(idn), "seq[%s..%s]", c->seq_ids[i0].c_str(), c->seq_ids[i0 + a.n - 1].c_str());
+        snprintf(idn, sizeof(idn), "seq[%s..%s]", r[0].id.c_str(), r[a.n - 1].id.c_str());
         const double fr = (double)a.n / (double)n;
-        ProfScope ps(c, s, idn, "conv_seq", c->seq_flop * fr, c->seq_bytes * fr);
-        {   // what must cross the fabric if every tensor produced AND consumed inside the launch stays in the XCD's L2:
-            // tensors read but not produced here, every weight pack once, tensors produced here and not read here (+ p2,
-            // which Refine reads later)
-            double ext = 0.0;
-            for (int i = 0; i < a.n; ++i) {
-                const SeqLayer &L = a.L[i];
-                bool in_inside = false, res_inside = L.res == nullptr, out_read = false;
-                for (int j = 0; j < a.n; ++j) {
-                    if (j < i && a.L[j].out == L.in) in_inside = true;
-                    if (j < i && L.res && a.L[j].out == L.res) res_inside = true;
-                    if (j > i && (a.L[j].in == L.out || a.L[j].res == L.out)) out_read = true;
-                }
-                bool in_counted = false, res_counted = false;          // a tensor several layers read is fetched once
-                for (int j = 0; j < i; ++j) {
-                    if (a.L[j].in == L.in || a.L[j].res == L.in) in_counted = true;
-                    if (L.res && (a.L[j].in == L.res || a.L[j].res == L.res)) res_counted = true;
-                }
-                const double px_in = (double)B * L.Hs * L.Ws, px_out = (double)B * L.Ho * L.Wo;
-                ext += (double)L.Nst * L.Kpad * 2.0;
-                if (!in_inside && !in_counted) ext += px_in * L.Cs * 2.0;
-                if (!res_inside && !res_counted) ext += px_out * L.res_Cs * 2.0;
-                if (!out_read || L.out == c->buf.at("p2")) ext += px_out * L.Nst * 2.0;
-            }
-            ps.ext_bytes(ext);
-        }
+        ProfScope ps(c, s, idn, "conv_seq", c->seq.flop * fr, c->seq.bytes * fr);
+        ps.ext_bytes(seq_fabric_bytes(a.L, a.n, B, buf("p2")));          // (p2: Refine reads it later)
         if (launch_conv_seq(a, c->seq_grid, s))
             return fail(SMK_E_HIP, "launch of %s failed: %s", idn, hipGetErrorString(hipGetLastError()));
         c->seq_pending = c->cap_has_seq = true;          // (smk_seq_sync_check: the flag is worth a look once this has drained)
@@ -1083,14 +940,10 @@ static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
             HIPCHK(hipStreamSynchronize(s));
             HIPCHK(hipMemcpy(h, c->seq_clk, sizeof(h), hipMemcpyDeviceToHost));
             if (want_clk2) HIPCHK(hipMemcpy(h2, c->seq_clk2, sizeof(h2), hipMemcpyDeviceToHost));
-            std::vector<std::string> ids(c->seq_ids.begin() + i0, c->seq_ids.begin() + i0 + a.n);
-            seq_print_clk(a, ids, idn, h, want_clk2 ? h2 : nullptr);
+            seq_print_clk(a, r, idn, h, want_clk2 ? h2 : nullptr);
         }
     }
-    c->seq_rec.clear();
-    c->seq_wstd.clear();
-    c->seq_ids.clear();
-    c->seq_flop = c->seq_bytes = 0.0;
+    c->seq.clear();
     return 0;
 }
 
@@ -1195,11 +1048,9 @@ static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, i
     if (c->seq_on) {
         SeqLayer L;
         if (!o.algo_naive && !o.halo && !o.wreg && !o.tile_code && seq_layer_from(p, kdtype(c->dtype), L)) {
-            c->seq_rec.push_back(L);
-            c->seq_wstd.push_back(p.wgt_frag);
-            c->seq_ids.push_back(id);
-            c->seq_flop += flop;
-            c->seq_bytes += bytes;
+            c->seq.rec.push_back({L, p.wgt_frag, id});
+            c->seq.flop += flop;
+            c->seq.bytes += bytes;
             return 0;
         }
         CHK(seq_flush(c, B, s));               // not eligible: keep program order
@@ -1219,10 +1070,10 @@ static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, in
     if (jobs.empty() || (int)jobs.size() > CONV_BATCH_MAX) return fail(SMK_E_ARG, "internal: bad conv job count");
     if (c->seq_on) {
         // independent members: no team barrier between them, one after the last
-        const size_t n0 = c->seq_rec.size();
+        const size_t n0 = c->seq.rec.size();
         for (auto &j : jobs) CHK(run_conv(c, j.id, *j.in, j.out, B, j.o, s));
-        if (c->seq_rec.size() == n0 + jobs.size())
-            for (size_t i = n0; i + 1 < c->seq_rec.size(); ++i) c->seq_rec[i].sync = 0;
+        if (c->seq.rec.size() == n0 + jobs.size())
+            for (size_t i = n0; i + 1 < c->seq.rec.size(); ++i) c->seq.rec[i].L.sync = 0;
         return 0;
     }
     ConvBatch cb;
@@ -1285,16 +1136,12 @@ static int run_conv_pair(smk_ctx *c, const char *id3, const Act &in3, const Act 
     SeqLayer L[2];
     if (!seq_layer_from(p3, c->dtype, L[0], -1) || !seq_layer_from(p1, c->dtype, L[1], -1)) return 1;
     int code = 0;
-    if (!seq_pair_fusable(L, 0, &code)) return 1;
-    const size_t px = (size_t)p3.M;
-    const size_t widest = std::max(std::max((size_t)L[0].Cs, (size_t)L[0].Cos), std::max((size_t)L[0].res_Cs, (size_t)L[1].Cos));
-    if (px * widest * 2 >= 0x7fff0000u || L[0].in_bytes >= 0x7fff0000u) return 1;     // (the routine's out-of-range offset: see seq_fuse_pairs)
+    if (!seq_pair_fits(L, 0, B, &code)) return 1;
     const size_t es = esize(c->dtype);
     const double flop = 2.0 * p3.M * ((double)p3.N * p3.Ci + (double)p1.N * p1.Ci);
     const double bytes = ((double)p3.M * (p3.Ci + 2.0 * p3.N + p1.N) + (double)p3.N * p3.Ci + (double)p1.N * p1.Ci) * es;
     char kn[48];
     snprintf(kn, sizeof(kn), "conv_pair<f16,%d-%d-%d>", p3.Ci, p3.N, p1.N);
-    (void)pair_rows;
     const std::string pid = std::string(id3) + "+" + id1;
     ProfScope ps(c, s, pid.c_str(), kn, flop, bytes);
     if (launch_conv_pair(L[0], L[1], code, p3.M, s, pair_rows)) return fail(SMK_E_HIP, "launch of pair %s failed: %s", pid.c_str(), hipGetErrorString(hipGetLastError()));
@@ -1371,7 +1218,7 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
     struct SeqScope {
         smk_ctx *c;
         SeqScope(smk_ctx *c_, bool on) : c(c_) { c->seq_on = on; }
-        ~SeqScope() { c->seq_on = false; c->seq_rec.clear(); c->seq_wstd.clear(); c->seq_ids.clear(); c->seq_flop = c->seq_bytes = 0.0; }
+        ~SeqScope() { c->seq_on = false; c->seq.clear(); }
     } seq_scope(c, false);
     const bool seq_ok = seq_wanted(c, B) && !parallel_ok(c);
     bool c1_done = false;                     // the previous block's conv3 launch already computed this block's conv1 (run_conv_pair)
@@ -1501,7 +1348,7 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
         Act se = act(c, "search", sp, sp, X(256));
         CHK(run_conv(c, "adjust", cur, &se, B, oa, s));
     }
-    if (c->seq_on && search_nb > 0 && sp >= 20 && g_tune.seq_search && c->seq_rec.size() < (size_t)SEQ_MAX) {
+    if (c->seq_on && search_nb > 0 && sp >= 20 && g_tune.seq_search && c->seq.rec.size() < (size_t)SEQ_MAX) {
         Act se = act(c, "search", sp, sp, X(256));
         Act xs = act(c, "xs", sp - 2, sp - 2, X(256 * search_nbt));
         ConvOpt o; o.relu = 1; o.n_override = 256 * search_nb;
@@ -2323,9 +2170,9 @@ static const Knob KNOBS[] = {
     {"pipe_join", &g_tune.pipe_join, "*", KNOB_BOOL, "1"},
     {"pipe_two_form", &g_tune.pipe_two_form, "0..2", KNOB_RAW, "1"},
     {"pipe_sig", &g_tune.pipe_sig, "0..2", KNOB_RAW, "2"},
-    {"seq_fused_last", &g_seq_fused_last, nullptr, KNOB_RAW, nullptr},     // pairs fused in the sequence launched last
-    {"seq_yres_last", &g_seq_yres_last, nullptr, KNOB_RAW, nullptr},
-    {"seq_fused3_last", &g_seq_fused3_last, nullptr, KNOB_RAW, nullptr},
+    {"seq_fused_last", &g_seq_last.pairs, nullptr, KNOB_RAW, nullptr},     // pairs fused in the sequence launched last
+    {"seq_yres_last", &g_seq_last.resident, nullptr, KNOB_RAW, nullptr},
+    {"seq_fused3_last", &g_seq_last.triples, nullptr, KNOB_RAW, nullptr},
     {"measure_build", &g_measure_build, nullptr, KNOB_RAW, nullptr},
 };
 
@@ -3074,6 +2921,71 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
     return 0;
 }
 
+// The layers of an smk_seq_op list as sequence records, with smk_op_conv_seq's validation and errors (smk_host_plan_seq shares
+// them): layer i's weights come from pack(i, pc), every output tensor from alloc(&p, bytes); xin is the list input.
+static int seq_op_records(const smk_seq_op *ops, int n, const Act &xin, int device, const std::function<int(int, PackedConv &)> &pack,
+                          const std::function<int(void **, size_t)> &alloc, std::vector<SeqRec> &rec, std::vector<Act> &outs) {
+    const int dtype = DT_F16, B = ops[0].g.B;
+    smk_ctx fake;
+    fake.dtype = dtype;
+    fake.device = device;
+    rec.assign(n, SeqRec());
+    outs.assign(n, Act());
+    for (int i = 0; i < n; ++i) {
+        const smk_seq_op &op = ops[i];
+        if (!op.w_host) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d has no weights", i);
+        if (op.src >= i || op.res_src >= i) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d reads a later layer", i);
+        if (op.g.B != B || op.g.win || op.g.ups) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: one batch, no windows", i);
+        const Act &in = op.src < 0 ? xin : outs[op.src];
+        const int cin_have = op.src < 0 ? ops[0].g.Cin : ops[op.src].g.Cout;
+        if (op.g.H != in.H || op.g.W != in.W || op.g.Cin != cin_have)
+            return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d geometry does not match its source", i);
+        PackedConv pc; Act gin; ConvOpt o; int Ho, Wo;
+        CHK(fill_geom(&op.g, pc, gin, o, Ho, Wo));
+        CHK(pack(i, pc));
+        outs[i].H = Ho; outs[i].W = Wo; outs[i].C = rup(op.g.Cout, 8);
+        CHK(alloc(&outs[i].p, (size_t)B * Ho * Wo * outs[i].C * esize(dtype)));
+        Act res;
+        if (op.g.res_mode) {
+            if (op.res_src < -1) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d wants a residual without a source", i);
+            res = op.res_src < 0 ? xin : outs[op.res_src];
+            if (res.H != Ho || res.W != Wo || res.C != outs[i].C)
+                return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: residual shape differs from the output", i);
+            o.res = &res; o.res_mode = op.g.res_mode;
+        }
+        ConvParams p;
+        CHK(conv_params(&fake, pc, in, &outs[i], B, o, p));
+        SeqLayer &L = rec[i].L;
+        const int force_halo = op.cfg == SEQ_CFG_HALO128 ? 128 : (op.cfg == SEQ_CFG_HALO64 ? 64 : (op.cfg >= 0 ? -1 : 0));
+        if (!seq_layer_from(p, dtype, L, force_halo)) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d cannot run inside a sequence%s", i, force_halo > 0 ? " on the patch-sharing tile" : "");
+        if (op.cfg >= 0 && force_halo <= 0) {
+#ifdef SMK_MEASURE
+            if (op.cfg > 18) return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..18");
+#else
+            if (op.cfg > 9 || (op.cfg >= 6 && op.cfg <= 8))
+                return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..5, 9 (6..8, 10..18 are measurement tiles: `make MEASURE=1`)");
+#endif
+            L.cfg = (signed char)op.cfg;
+        }
+        if (op.kstag >= 0) L.kstag = (signed char)(op.kstag != 0);
+        L.sync = (signed char)(op.sync != 0);
+        rec[i].wstd = pc.w_frag;
+        rec[i].id = "op" + std::to_string(i);
+    }
+    return 0;
+}
+
+// plan_seq on an smk_seq_op list: a layer with a cfg of its own is locked, the outputs the caller reads back are read behind the list
+static SeqPlanStats plan_seq_ops(const smk_seq_op *ops, std::vector<SeqRec> &rec, const std::vector<Act> &outs, int grid) {
+    std::vector<char> locked(rec.size());
+    std::vector<const void *> read_after;
+    for (size_t i = 0; i < rec.size(); ++i) {
+        locked[i] = ops[i].cfg >= 0;
+        if (ops[i].y_dev) read_after.push_back(outs[i].p);
+    }
+    return plan_seq(rec, {ops[0].g.B, grid >> 3, true}, locked.data(), read_after);
+}
+
 // A sequence of convolutions through conv_seq_kernel on caller-described layers (unit parity of the persistent kernel:
 // every tile configuration, residual and independent-member cases; micro-benchmarks of its K loop).  fp16 only.
 int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters, float *usec_out, float *clk_us_out,
@@ -3095,30 +3007,9 @@ int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters,
     CHK(tmp.alloc(&xin.p, (size_t)B * xin.H * xin.W * xin.C * es));
     CvtInParams ci{x_dev, xin.p, B, ops[0].g.Cin, xin.H, xin.W, xin.C, 0};
     if (launch_cvt_in(ci, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    smk_ctx fake;
-    fake.dtype = dtype;
-    fake.device = dev;
-    std::vector<Act> outs(n);
-    std::vector<int> couts(n);
     std::vector<PackedConv> packs(n);
-    SeqArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n; a.B = B;
-    a.flags = g_tune.seq_spoll ? 1 : 0;
-    std::vector<std::string> ids;
-    std::vector<char> locked(n, 0);
-    for (int i = 0; i < n; ++i) {
+    auto pack = [&](int i, PackedConv &pc) -> int {
         const smk_seq_op &op = ops[i];
-        locked[i] = op.cfg >= 0;
-        if (!op.w_host) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d has no weights", i);
-        if (op.src >= i || op.res_src >= i) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d reads a later layer", i);
-        if (op.g.B != B || op.g.win || op.g.ups) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: one batch, no windows", i);
-        const Act &in = op.src < 0 ? xin : outs[op.src];
-        const int cin_have = op.src < 0 ? ops[0].g.Cin : couts[op.src];
-        if (op.g.H != in.H || op.g.W != in.W || op.g.Cin != cin_have)
-            return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d geometry does not match its source", i);
-        PackedConv pc; Act gin; ConvOpt o; int Ho, Wo;
-        CHK(fill_geom(&op.g, pc, gin, o, Ho, Wo));
         int same = -1;                                    // a layer that names the SAME host weights re-uses the device copy
         for (int j = 0; j < i && same < 0; ++j)           // (micro-benchmarks: L2-warm weights)
             if (ops[j].w_host == op.w_host && ops[j].b_host == op.b_host && ops[j].g.Cout == op.g.Cout &&
@@ -3137,38 +3028,17 @@ int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters,
             if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);
         }
         packs[i] = pc;
-        outs[i].H = Ho; outs[i].W = Wo; outs[i].C = rup(op.g.Cout, 8);
-        couts[i] = op.g.Cout;
-        CHK(tmp.alloc(&outs[i].p, (size_t)B * Ho * Wo * outs[i].C * es));
-        Act res;
-        if (op.g.res_mode) {
-            if (op.res_src < -1) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d wants a residual without a source", i);
-            res = op.res_src < 0 ? xin : outs[op.res_src];
-            if (res.H != Ho || res.W != Wo || res.C != outs[i].C)
-                return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: residual shape differs from the output", i);
-            o.res = &res; o.res_mode = op.g.res_mode;
-        }
-        ConvParams p;
-        CHK(conv_params(&fake, pc, in, &outs[i], B, o, p));
-        SeqLayer L;
-        const int force_halo = op.cfg == SEQ_CFG_HALO128 ? 128 : (op.cfg == SEQ_CFG_HALO64 ? 64 : (op.cfg >= 0 ? -1 : 0));
-        if (!seq_layer_from(p, dtype, L, force_halo)) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d cannot run inside a sequence%s", i, force_halo > 0 ? " on the patch-sharing tile" : "");
-        if (op.cfg >= 0 && force_halo <= 0) {
-#ifdef SMK_MEASURE
-            if (op.cfg > 18) return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..18");
-#else
-            if (op.cfg > 9 || (op.cfg >= 6 && op.cfg <= 8))
-                return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..5, 9 (6..8, 10..18 are measurement tiles: `make MEASURE=1`)");
-#endif
-            L.cfg = (signed char)op.cfg;
-        }
-        if (op.kstag >= 0) L.kstag = (signed char)(op.kstag != 0);
-        L.sync = (signed char)(op.sync != 0);
-        a.L[i] = L;
-        char nm[16];
-        snprintf(nm, sizeof(nm), "op%d", i);
-        ids.push_back(nm);
-    }
+        return 0;
+    };
+    std::vector<SeqRec> rec;
+    std::vector<Act> outs;
+    CHK(seq_op_records(ops, n, xin, dev, pack, [&](void **p, size_t bytes) { return tmp.alloc(p, bytes); }, rec, outs));
+    g_seq_last = plan_seq_ops(ops, rec, outs, grid);          // what the engine does with its own lists (smk_tune "seq_fuse", ...)
+    SeqArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n = n; a.B = B;
+    a.flags = g_tune.seq_spoll ? 1 : 0;
+    for (int i = 0; i < n; ++i) a.L[i] = rec[i].L;
     unsigned *bar = nullptr;
     int *err = nullptr;
     unsigned long long *clk = nullptr, *clk2 = nullptr;
@@ -3181,15 +3051,6 @@ int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters,
     float *xch = nullptr;
     CHK(tmp.alloc((void **)&xch, SEQ_XCH_BYTES));
     a.bar = bar; a.xch = xch; a.err = err; a.err_host = nullptr; a.clk = clk; a.clk2 = clk2;
-    seq_fuse_pairs(a.L, a.n, B, &locked, (grid >> 3) % 2 == 0 && (grid >> 4) <= SEQ_XCH_PAIRS);                   // what the engine does with its own lists (smk_tune "seq_fuse")
-    {
-        std::vector<const void *> wstd(n);
-        for (int i = 0; i < n; ++i) wstd[i] = packs[i].w_frag;
-        seq_fuse_triples(a.L, a.n, B, wstd.data(), &locked);
-        std::vector<char> keep(n, 0);
-        for (int i = 0; i < n; ++i) keep[i] = ops[i].y_dev != nullptr;
-        seq_mark_resident(a.L, a.n, B, grid >> 3, nullptr, &keep);
-    }
     if (n_fused_out) {
         *n_fused_out = 0;
         for (int i = 0; i < n; ++i) *n_fused_out += a.L[i].cfg == SEQ_CFG_C3C1_2ND;
@@ -3225,12 +3086,12 @@ int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters,
             }
         if (ck) {
             if (want2) HIPCHK(hipMemcpy(h2, clk2, sizeof(h2), hipMemcpyDeviceToHost));
-            seq_print_clk(a, ids, "smk_op_conv_seq", h, want2 ? h2 : nullptr);
+            seq_print_clk(a, rec.data(), "smk_op_conv_seq", h, want2 ? h2 : nullptr);
         }
     }
     for (int i = 0; i < n; ++i)
         if (ops[i].y_dev) {
-            CvtOutParams co{outs[i].p, ops[i].y_dev, B, couts[i], outs[i].H, outs[i].W, outs[i].C, 0};
+            CvtOutParams co{outs[i].p, ops[i].y_dev, B, ops[i].g.Cout, outs[i].H, outs[i].W, outs[i].C, 0};
             if (launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
         }
     HIPCHK(hipStreamSynchronize(s));
@@ -3486,6 +3347,16 @@ int smk_host_conv2d_ex(const smk_conv_geom *g, const float *x, const float *w, c
     return 0;
 }
 
+// the pack the packer would make, with every derived copy it would make (host-only planning: nothing is dereferenced)
+static void fake_pack(PackedConv &pc, int dtype) {
+    static float dummy[64];
+    pc.w = dummy; pc.bias = dummy;
+    if (has_frag_pack(pc, dtype)) pc.w_frag = dummy;
+    if (has_frag16_pack(pc, dtype)) pc.w_frag16 = dummy;
+    if (has_halo_pack(pc, dtype)) pc.w_halo = dummy;
+    if (has_frag_halo_pack(pc, dtype)) pc.w_frag_halo = dummy;
+}
+
 // Which kernel and workgroup shape does the engine pick for one convolution of this geometry?  Host only (CPU tests pin the
 // measured layer rules with it): plan_conv, as run_conv calls it, on a pack whose derived copies are the ones the packer would
 // make, for the MI355X's 256 CUs; *seq_cfg = the conv_seq_kernel tile code the layer gets inside a persistent sequence, or -1
@@ -3497,11 +3368,7 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
     CHK(fill_geom(g, pc, in, o, Ho, Wo));
     static float dummy[64];
     in.p = dummy;
-    pc.w = dummy; pc.bias = dummy;
-    if (has_frag_pack(pc, dtype)) pc.w_frag = dummy;
-    if (has_frag16_pack(pc, dtype)) pc.w_frag16 = dummy;
-    if (has_halo_pack(pc, dtype)) pc.w_halo = dummy;
-    if (has_frag_halo_pack(pc, dtype)) pc.w_frag_halo = dummy;
+    fake_pack(pc, dtype);
     Act out, res;
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8); out.p = dummy;
     res = out;
@@ -3520,6 +3387,29 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
     }
     SeqLayer L;
     *seq_cfg = seq_layer_from(p, dtype, L) ? (int)L.cfg : -1;
+    return 0;
+}
+
+// The marks plan_seq puts on an smk_op_conv_seq list of up to 4 * SEQ_MAX layers (launched as SEQ_MAX slices) on a grid of
+// `grid` workgroups.  Host only: the records are smk_op_conv_seq's, on distinct fake tensors and fake packs with the copies the
+// packer would make.  The "last launch" diagnostics are left alone.
+int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *sync, int *a_stage) {
+    if (!ops || n < 1 || n > 4 * SEQ_MAX || grid < 8 || grid % 8 || !cfg || !sync || !a_stage)
+        return fail(SMK_E_ARG, "smk_host_plan_seq: bad argument (1..%d layers, a grid of whole teams)", 4 * SEQ_MAX);
+    static char tensors[4 * SEQ_MAX + 1];             // one address per tensor: the list input, then the layers' outputs
+    Act xin;
+    xin.H = ops[0].g.H; xin.W = ops[0].g.W; xin.C = rup(ops[0].g.Cin, 8); xin.p = tensors;
+    int next = 1;
+    std::vector<SeqRec> rec;
+    std::vector<Act> outs;
+    CHK(seq_op_records(ops, n, xin, -1, [](int, PackedConv &pc) { fake_pack(pc, DT_F16); return 0; },
+                       [&](void **p, size_t) { *p = tensors + next++; return 0; }, rec, outs));
+    plan_seq_ops(ops, rec, outs, grid);
+    for (int i = 0; i < n; ++i) {
+        cfg[i] = rec[i].L.cfg;
+        sync[i] = rec[i].L.sync;
+        a_stage[i] = rec[i].L.a_stage;
+    }
     return 0;
 }
 

@@ -120,7 +120,7 @@ struct SeqLayer {
     signed char cfg;       // workgroup tile: 0 = 64x256, 1 = 64x128, 2 = 64x64, 3 = 128x256, 4 = 128x128, 9 = 128x64;
                            //   measurement variants: 5 = 64x128 with a 5-deep ring and weights 4 K tiles ahead, 6..8 ablations
     signed char sync;      // 1: the next layer reads what this one (or an earlier one since the last barrier) wrote
-    signed char a_stage;   // bit 0: see ConvParams::a_stage; bits 1-3 (engine.cpp seq_mark_resident, round 6): SEQ_YRES_IN / _NOSTORE / SEQ_LDS_HI
+    signed char a_stage;   // bit 0: see ConvParams::a_stage; bits 1-3 (conv_plan.cpp plan_seq, round 6): SEQ_YRES_IN / _NOSTORE / SEQ_LDS_HI
     signed char kstag;     // 1: every workgroup starts its K loop at another K tile (see wreg_tile kt0)
     signed char res_nt;    // 1: residual rows are fetched non-temporally (the tensor is dead after this layer)
     // features of ConvParams the sequences never use (compile-time constants for the shared tile routine)
@@ -130,7 +130,7 @@ struct SeqLayer {
     static constexpr const float *oscale = nullptr;
 };
 static_assert(sizeof(SeqLayer) == 104, "SeqLayer packing");
-// pair codes (engine.cpp seq_fuse_pairs, c3c1_tile.inc): a Bottleneck's conv3 and the 1x1 convolution that reads its output run as
+// pair codes (conv_plan.cpp plan_seq, c3c1_tile.inc): a Bottleneck's conv3 and the 1x1 convolution that reads its output run as
 // ONE tile routine; the first record carries the shape code, the second one is consumed with it
 constexpr int SEQ_CFG_C3C1_L3 = 20;    // K 256 -> N 1024 (+ residual, ReLU) -> N 256   (layer3 conv3 -> next conv1 / adjust)
 constexpr int SEQ_CFG_C3C1_L2 = 21;    // K 128 -> N 512  (+ residual, ReLU) -> N 128   (layer2 conv3 -> next conv1)
@@ -139,7 +139,7 @@ constexpr int SEQ_CFG_C3C1_2ND = 22;   // the pair's second record
 // matching K half of the second convolution, fp32 partial sums exchanged through SeqArgs::xch; second record = 22 as well
 constexpr int SEQ_CFG_C3C1P_L3 = 26;
 constexpr int SEQ_CFG_C3C1P_L2 = 27;
-// triples (c3c1_tile.inc FRONT = 1; engine.cpp seq_fuse_triples): a Bottleneck's 3x3 convolution, its conv3 and the next 1x1 as ONE tile
+// triples (c3c1_tile.inc FRONT = 1; conv_plan.cpp plan_seq): a Bottleneck's 3x3 convolution, its conv3 and the next 1x1 as ONE tile
 // routine on image-row tiles; records: conv2 = 28 / 29, conv3 = 30, the 1x1 = 22
 constexpr int SEQ_CFG_C2C3C1_L3 = 28;  // 3x3 256 -> 256, then the layer3 pair
 constexpr int SEQ_CFG_C2C3C1_L2 = 29;  // 3x3 128 -> 128, then the layer2 pair

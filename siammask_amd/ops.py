@@ -76,23 +76,13 @@ SEQ_CFG = {None: -1, (64, 256): 0, (64, 128): 1, (64, 64): 2, (128, 256): 3, (12
            "halo128": 24, "halo64": 25}     # 3x3 stride-1: whole-row tiles (128 / 64 pixels x 64 channels), activation patch shared by the nine taps
 
 
-def conv_seq(x, layers, iters=1, want_outputs=True, info=None):
-    """smk_op_conv_seq: a list of convolutions as ONE persistent conv_seq_kernel launch (fp16).
-
-    x: [B,C,H,W] float32 CUDA tensor.  layers: dicts with w [Cout,Cin,k,k] (numpy), optional b, stride, pad, dil, relu,
-    src (-1 = x, j = output of layer j; default: the previous layer), res (source index of the residual, -1 = x) with
-    res_mode 1 (before the ReLU) / 2 (after), sync (default True), tile ((bm, bn), "deep" or None), kstag (-1 engine's choice).
-    Returns (outputs [list of float32 NCHW tensors], usec per launch, per-layer (tiles_us, arrive_us) array); info (a dict,
-    optional) receives "fused_pairs" = the (conv3, next 1x1) pairs the launch ran as one tile routine (smk_tune "seq_fuse").
-    want_outputs: True (all layers), False, or a collection of layer indices (the returned list then holds None elsewhere)."""
-    _chk_cuda(x)
-    x = x.contiguous().float()
-    B = x.shape[0]
-    n = len(layers)
-    arr = (_lib.SeqOp * n)()
+def seq_ops(x_shape, layers):
+    """The smk_seq_op array of a conv_seq list on an input of shape x_shape [B,C,H,W], without tensors (layers: see conv_seq).
+    Returns (array, the host arrays it points to -- keep them alive while it is used, the (C, H, W) of every layer's output)."""
+    B = x_shape[0]
+    arr = (_lib.SeqOp * len(layers))()
     keep = []
-    shapes = [tuple(x.shape[1:])]          # shape of x, then of every output
-    outs = []
+    shapes = [tuple(x_shape[1:])]          # shape of x, then of every output
     for i, l in enumerate(layers):
         w = np.ascontiguousarray(l["w"], dtype=np.float32)
         b = None if l.get("b") is None else np.ascontiguousarray(l["b"], dtype=np.float32)
@@ -115,14 +105,35 @@ def conv_seq(x, layers, iters=1, want_outputs=True, info=None):
         arr[i].kstag = l.get("kstag", -1)
         arr[i].w_host = w.ctypes.data
         arr[i].b_host = b.ctypes.data if b is not None else None
-        if want_outputs is True or (want_outputs not in (False, None) and i in want_outputs):
-            y = torch.empty((B, w.shape[0], Ho, Wo), dtype=torch.float32, device=x.device)
+    return arr, keep, shapes[1:]
+
+
+def _wanted(want_outputs, i):
+    return want_outputs is True or (want_outputs not in (False, None) and i in want_outputs)
+
+
+def conv_seq(x, layers, iters=1, want_outputs=True, info=None):
+    """smk_op_conv_seq: a list of convolutions as ONE persistent conv_seq_kernel launch (fp16).
+
+    x: [B,C,H,W] float32 CUDA tensor.  layers: dicts with w [Cout,Cin,k,k] (numpy), optional b, stride, pad, dil, relu,
+    src (-1 = x, j = output of layer j; default: the previous layer), res (source index of the residual, -1 = x) with
+    res_mode 1 (before the ReLU) / 2 (after), sync (default True), tile ((bm, bn), "deep" or None), kstag (-1 engine's choice).
+    Returns (outputs [list of float32 NCHW tensors], usec per launch, per-layer (tiles_us, arrive_us) array); info (a dict,
+    optional) receives "fused_pairs" = the (conv3, next 1x1) pairs the launch ran as one tile routine (smk_tune "seq_fuse").
+    want_outputs: True (all layers), False, or a collection of layer indices (the returned list then holds None elsewhere)."""
+    _chk_cuda(x)
+    x = x.contiguous().float()
+    B = x.shape[0]
+    n = len(layers)
+    arr, keep, shapes = seq_ops(x.shape, layers)
+    outs = []
+    for i, shape in enumerate(shapes):
+        if _wanted(want_outputs, i):
+            y = torch.empty((B,) + shape, dtype=torch.float32, device=x.device)
             outs.append(y)
             arr[i].y_dev = y.data_ptr()
-        else:
-            if want_outputs not in (True, False, None):
-                outs.append(None)              # (a collection of layer indices: the other layers' outputs are not read back)
-            arr[i].y_dev = None
+        elif want_outputs not in (True, False, None):
+            outs.append(None)              # (a collection of layer indices: the other layers' outputs are not read back)
     us = ctypes.c_float(0.0)
     clk = np.zeros(2 * n, dtype=np.float32)
     nfused = ctypes.c_int(0)
@@ -132,6 +143,20 @@ def conv_seq(x, layers, iters=1, want_outputs=True, info=None):
     if info is not None:
         info["fused_pairs"] = nfused.value
     return outs, us.value, clk.reshape(n, 2)
+
+
+def plan_seq(x_shape, layers, want_outputs=True, grid=256):
+    """smk_host_plan_seq (host only, no GPU): the marks the engine puts on the conv_seq list of layers on an input of shape
+    x_shape (up to 144 layers, launched as slices of 36), on a launch grid of `grid` workgroups.  want_outputs as in conv_seq:
+    the outputs read after the list.  Returns one (cfg, sync, a_stage) per layer."""
+    arr, keep, _ = seq_ops(x_shape, layers)
+    n = len(layers)
+    for i in range(n):
+        if _wanted(want_outputs, i):
+            arr[i].y_dev = 1               # (only whether it is set counts: nothing is written)
+    out = [(ctypes.c_int * n)() for _ in range(3)]
+    _lib.check(_lib.lib().smk_host_plan_seq(arr, n, grid, *out))
+    return list(zip(*[list(o) for o in out]))
 
 
 def dw_xcorr(x, k, dtype="f32"):

@@ -33,3 +33,33 @@ def assert_close(got, ref, tol, what):
     e = rel_err(got, ref)
     assert e <= tol, "%s: rel-to-max error %.3e > %.1e" % (what, e, tol)
     return e
+
+
+# ---- conv_seq lists (ops.conv_seq / ops.plan_seq layer dicts) ----------------------------------------------------------
+
+def seq_weight(rng, cout, cin, k):
+    return (rng.uniform(-1, 1, size=(cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
+
+
+def seq_bottleneck(rng, cin, planes, k2=3, dil=2, tile=None, kstag=-1):
+    """conv1 1x1 -> conv2 3x3 (dilated, same size) -> conv3 1x1 + input, ReLU: resnet.py:80-103"""
+    return [
+        dict(w=seq_weight(rng, planes, cin, 1), b=rng.uniform(-1, 1, planes).astype(np.float32), relu=True, tile=tile, kstag=kstag),
+        dict(w=seq_weight(rng, planes, planes, k2), b=rng.uniform(-1, 1, planes).astype(np.float32), pad=dil * (k2 // 2), dil=dil,
+             relu=True, tile=tile, kstag=kstag),
+        dict(w=seq_weight(rng, cin, planes, 1), b=rng.uniform(-1, 1, cin).astype(np.float32), relu=True, res=-1, res_mode=1,
+             tile=tile, kstag=kstag),
+    ]
+
+
+def seq_chain(rng, cin, planes, nblocks, dil, adjust=True):
+    """nblocks identity Bottlenecks, each reading the previous one's output, then a 1x1 cin -> planes (adjust: no ReLU)"""
+    layers = []
+    for b in range(nblocks):
+        blk = seq_bottleneck(rng, cin, planes, dil=dil)
+        if b:
+            blk[0]["src"] = len(layers) - 1
+            blk[2]["res"] = len(layers) - 1
+        layers += blk
+    layers.append(dict(w=seq_weight(rng, planes, cin, 1), b=rng.uniform(-1, 1, planes).astype(np.float32), relu=not adjust))
+    return layers

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from oracle import np_oracle as O
-from helpers import rel_err
+from helpers import rel_err, seq_bottleneck as _bottleneck, seq_chain as _chain, seq_weight as _w
 
 pytestmark = pytest.mark.gpu
 TOL = 2e-3
@@ -26,10 +26,6 @@ def _ops():
 
 def _q(a):
     return np.asarray(a, dtype=np.float32).astype(np.float16).astype(np.float64)
-
-
-def _w(rng, cout, cin, k):
-    return (rng.uniform(-1, 1, size=(cout, cin, k, k)) / np.sqrt(cin * k * k)).astype(np.float32)
 
 
 def _check(x, layers, outs, what):
@@ -51,17 +47,6 @@ def _check(x, layers, outs, what):
     bad = {i: e for i, e in errs.items() if not e <= TOL}
     assert not bad, "%s: layers %s over %.0e (all %s)" % (what, bad, TOL, errs)
     return errs
-
-
-def _bottleneck(rng, cin, planes, k2=3, dil=2, tile=None, kstag=-1):
-    """conv1 1x1 -> conv2 3x3 (dilated, same size) -> conv3 1x1 + input, ReLU: resnet.py:80-103"""
-    return [
-        dict(w=_w(rng, planes, cin, 1), b=rng.uniform(-1, 1, planes).astype(np.float32), relu=True, tile=tile, kstag=kstag),
-        dict(w=_w(rng, planes, planes, k2), b=rng.uniform(-1, 1, planes).astype(np.float32), pad=dil * (k2 // 2), dil=dil,
-             relu=True, tile=tile, kstag=kstag),
-        dict(w=_w(rng, cin, planes, 1), b=rng.uniform(-1, 1, cin).astype(np.float32), relu=True, res=-1, res_mode=1,
-             tile=tile, kstag=kstag),
-    ]
 
 
 @pytest.mark.parametrize("kstag", [0, 1])
@@ -524,18 +509,6 @@ def test_side_stream_work_during_a_step_stays_correct_or_raises():
     print("side stream: failure path taken %d times of 4" % raised)
 
 
-def _chain(rng, cin, planes, nblocks, dil, adjust=True):
-    layers = []
-    for b in range(nblocks):
-        blk = _bottleneck(rng, cin, planes, dil=dil)
-        if b:
-            blk[0]["src"] = len(layers) - 1
-            blk[2]["res"] = len(layers) - 1
-        layers += blk
-    layers.append(dict(w=_w(rng, planes, cin, 1), b=rng.uniform(-1, 1, planes).astype(np.float32), relu=not adjust))
-    return layers
-
-
 @pytest.mark.parametrize("shape,dil", [((1024, 256), 2), ((1024, 256), 1), ((512, 128), 1)])
 @pytest.mark.parametrize("B,S", [(8, 31), (3, 29), (10, 31)])
 def test_conv_seq_fused_triples(shape, dil, B, S):
@@ -554,19 +527,19 @@ def test_conv_seq_fused_triples(shape, dil, B, S):
     layers = _chain(rng, cin, planes, 3, dil)
     xd = torch.from_numpy(x).cuda()
     info = {}
-    old = _lib.tune_get("seq_fuse3")
+    keep = [i for i in range(len(layers)) if i % 3 != 1 or i == len(layers) - 1]       # every record but the conv2s (never stored:
+    old = _lib.tune_get("seq_fuse3")                                                    # a conv2 output read back keeps its triple off)
     try:
         _lib.tune(seq_fuse3=1)
-        outs, _, _ = ops.conv_seq(xd, layers, info=info)
+        outs, _, _ = ops.conv_seq(xd, layers, want_outputs=keep, info=info)
         assert info["fused_pairs"] == 3 and _lib.tune_get("seq_fused3_last") == 3, (info, _lib.tune_get("seq_fused3_last"))
-        again, _, _ = ops.conv_seq(xd, layers, info=info)
+        again, _, _ = ops.conv_seq(xd, layers, want_outputs=keep, info=info)
         _lib.tune(seq_fuse3=0)
         plain, _, _ = ops.conv_seq(xd, layers, info=info)
         assert _lib.tune_get("seq_fused3_last") == 0
     finally:
         _lib.tune(seq_fuse3=old)
     _check(x, layers, plain, "unfused chain %s" % (shape,))
-    keep = [i for i in range(len(layers)) if i % 3 != 1 or i == len(layers) - 1]       # every record but the conv2s (never stored)
     for i in keep:
         assert torch.equal(outs[i], again[i]), "layer %d differs between two launches" % i
         e = rel_err(outs[i].cpu().numpy(), plain[i].cpu().numpy().astype(np.float64))

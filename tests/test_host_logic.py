@@ -289,3 +289,134 @@ def test_layer_rules_are_the_measured_ones():
             assert _plan(B, cin, hw, cout, 3, pad=1)[0] == "igemm", (B, cin, hw, cout)
     # fp32: no register-fed kernel, no sequences
     assert _plan(8, 1024, 31, 256, 1, dtype="f32")[0] == "igemm" and _plan(8, 1024, 31, 256, 1, dtype="f32")[2] == -1
+
+
+# ---- persistent sequences: the marks plan_seq puts on a recorded list (smk_host_plan_seq) ----------------------------------
+SEQ_PAIR_L3, SEQ_PAIR_L2, SEQ_PAIR_2ND = 20, 21, 22                 # smk_kernels.h SEQ_CFG_C3C1_*
+SEQ_TRIPLE_L3, SEQ_TRIPLE_L2, SEQ_TRIPLE_MID = 28, 29, 30           # SEQ_CFG_C2C3C1_*
+YRES_IN, YRES_NOSTORE, LDS_HI = 2, 4, 8                             # SEQ_YRES_IN, SEQ_YRES_NOSTORE, SEQ_LDS_HI
+
+
+class _knobs:
+    """smk_tune for the duration of a with-block, then back to what was there"""
+    def __init__(self, **kw):
+        self.kw = kw
+
+    def __enter__(self):
+        self.old = {k: _lib.tune_get(k) for k in self.kw}
+        _lib.tune(**self.kw)
+
+    def __exit__(self, *exc):
+        _lib.tune(**self.old)
+
+
+def _plan_seq(B, S, layers, want_outputs=True):
+    from siammask_amd import ops
+    return ops.plan_seq((B, layers[0]["w"].shape[1], S, S), layers, want_outputs)
+
+
+@pytest.mark.parametrize("shape,B,S", [((1024, 256), 8, 31), ((1024, 256), 3, 15), ((512, 128), 8, 31), ((512, 128), 5, 15)])
+def test_seq_plan_resident_trunk(shape, B, S):
+    """The lists of tests/test_gpu_seq.py test_conv_seq_resident_trunk_gives_the_same_bits: three Bottlenecks + adjust fuse into
+    three pairs, and the second and third pair find their residual resident (the conv2 between them works above it in LDS).
+    The first two pairs skip the store of their output only while nobody reads it back; with two images on a team (B = 10) or
+    smk_tune seq_yres 0 nothing is marked."""
+    from helpers import seq_chain
+    cin, planes = shape
+    layers = seq_chain(np.random.default_rng(0), cin, planes, 3, 2 if cin == 1024 else 1)
+    last = len(layers) - 1
+    pair = SEQ_PAIR_L3 if cin == 1024 else SEQ_PAIR_L2
+    every = _plan_seq(B, S, layers)
+    cfg = [c for c, _, _ in every]
+    assert [cfg[i] for i in (2, 3, 5, 6, 8, 9)] == [pair, SEQ_PAIR_2ND] * 3, cfg
+    assert cfg.count(SEQ_PAIR_2ND) == 3
+    marks = {i: a for i, (_, _, a) in enumerate(every) if a}
+    assert marks == {4: LDS_HI, 5: YRES_IN, 7: LDS_HI, 8: YRES_IN}, marks
+    only = {i: a for i, (_, _, a) in enumerate(_plan_seq(B, S, layers, want_outputs=(last,))) if a}
+    assert only == {2: YRES_NOSTORE, 4: LDS_HI, 5: YRES_IN | YRES_NOSTORE, 7: LDS_HI, 8: YRES_IN}, only
+    first = {i: a for i, (_, _, a) in enumerate(_plan_seq(B, S, layers, want_outputs=(2, last))) if a}
+    assert first == {4: LDS_HI, 5: YRES_IN | YRES_NOSTORE, 7: LDS_HI, 8: YRES_IN}, first
+    assert not any(a for _, _, a in _plan_seq(10, 15, layers, want_outputs=(last,)))
+    with _knobs(seq_yres=0):
+        plain = _plan_seq(B, S, layers, want_outputs=(last,))
+    assert [c for c, _, _ in plain] == cfg and not any(a for _, _, a in plain)
+
+
+def test_seq_plan_no_pairs_without_seq_fuse():
+    """smk_tune seq_fuse 0: no pairs, hence nothing resident; planning on the host leaves the "..._last" diagnostics alone"""
+    from helpers import seq_chain
+    layers = seq_chain(np.random.default_rng(1), 1024, 256, 3, 2)
+    last = [_lib.tune_get(k) for k in ("seq_fused_last", "seq_fused3_last", "seq_yres_last")]
+    with _knobs(seq_fuse=0):
+        got = _plan_seq(8, 31, layers)
+    assert not {SEQ_PAIR_L3, SEQ_PAIR_L2, SEQ_PAIR_2ND} & {c for c, _, _ in got} and not any(a for _, _, a in got), got
+    assert _plan_seq(8, 31, layers)[2][0] == SEQ_PAIR_L3
+    assert [_lib.tune_get(k) for k in ("seq_fused_last", "seq_fused3_last", "seq_yres_last")] == last
+
+
+def test_seq_plan_reader_in_a_later_launch_keeps_the_store():
+    """A list longer than one launch (36 records): twelve layer2 Bottlenecks + adjust, then a 1x1 convolution in the second launch
+    that reads the output of the first pair.  That pair's Y must reach memory; without the late reader it need not.  Pairs stay
+    inside their launch: the last Bottleneck's conv3 (record 35) and adjust (record 36) are not fused."""
+    from helpers import seq_chain, seq_weight
+    rng = np.random.default_rng(2)
+    layers = seq_chain(rng, 512, 128, 12, 1)
+    assert len(layers) == 37
+    alone = _plan_seq(8, 31, layers, want_outputs=(36,))
+    late = layers + [dict(w=seq_weight(rng, 128, 512, 1), relu=True, src=2)]
+    got = _plan_seq(8, 31, late, want_outputs=(37,))
+    for plan in (alone, got):
+        cfg = [c for c, _, _ in plan]
+        assert [i for i, c in enumerate(cfg) if c == SEQ_PAIR_L2] == list(range(2, 33, 3)), cfg
+        assert cfg[35] != SEQ_PAIR_L2 and cfg[36] != SEQ_PAIR_2ND
+        assert [i for i, (_, _, a) in enumerate(plan) if a & YRES_IN] == list(range(5, 33, 3))
+    assert [i for i, (_, _, a) in enumerate(alone) if a & YRES_NOSTORE] == list(range(2, 30, 3))
+    assert [i for i, (_, _, a) in enumerate(got) if a & YRES_NOSTORE] == list(range(5, 30, 3))
+
+
+def _needs_measure_build():
+    if not _lib.tune_get("measure_build"):
+        pytest.skip("the triple routine (seq_fuse3) is only in a library built with `make MEASURE=1`")
+
+
+@pytest.mark.parametrize("shape,dil", [((1024, 256), 2), ((1024, 256), 1), ((512, 128), 1)])
+@pytest.mark.parametrize("B,S", [(8, 31), (3, 29), (10, 31)])
+def test_seq_plan_triples(shape, dil, B, S):
+    """The lists of tests/test_gpu_seq.py test_conv_seq_fused_triples: with seq_fuse3 every Bottleneck's [conv2, conv3, next 1x1]
+    is one triple, without a barrier behind conv2, each residual in front of the wait (the list input, then the previous triple's
+    conv3 on the same rows).  A conv2 output that is read back keeps its triple off."""
+    _needs_measure_build()
+    from helpers import seq_chain
+    cin, planes = shape
+    layers = seq_chain(np.random.default_rng(3), cin, planes, 3, dil)
+    keep = [i for i in range(len(layers)) if i % 3 != 1 or i == len(layers) - 1]
+    code = SEQ_TRIPLE_L3 if cin == 1024 else SEQ_TRIPLE_L2
+    with _knobs(seq_fuse3=1):
+        got = _plan_seq(B, S, layers, want_outputs=keep)
+        read_back = _plan_seq(B, S, layers)
+    assert [c for c, _, _ in got][1:] == [code, SEQ_TRIPLE_MID, SEQ_PAIR_2ND] * 3, got
+    assert [got[i][1] for i in (1, 4, 7)] == [0, 0, 0] and [got[i][2] for i in (2, 5, 8)] == [0, 0, 0]
+    assert SEQ_TRIPLE_MID not in [c for c, _, _ in read_back]
+    assert [c for c, _, _ in read_back].count(SEQ_PAIR_2ND) == 3
+    with _knobs(seq_fuse3=0):
+        assert SEQ_TRIPLE_MID not in [c for c, _, _ in _plan_seq(B, S, layers, want_outputs=keep)]
+
+
+def test_seq_plan_triples_leave_short_rows_and_shared_conv2_outputs_alone():
+    """tests/test_gpu_seq.py test_conv_seq_triples_leave_short_rows_and_shared_conv2_outputs_alone, and the same across a launch
+    boundary: the 15 x 15 template rows keep the pairs; a conv2 output that another record reads -- in the same launch or in
+    the next one -- reaches memory"""
+    _needs_measure_build()
+    from helpers import seq_chain, seq_weight
+    rng = np.random.default_rng(4)
+    with _knobs(seq_fuse3=1):
+        got = _plan_seq(8, 15, seq_chain(rng, 1024, 256, 2, 2), want_outputs=False)
+        assert [c for c, _, _ in got].count(SEQ_PAIR_2ND) == 2 and SEQ_TRIPLE_MID not in [c for c, _, _ in got]
+        layers = seq_chain(rng, 1024, 256, 1, 2)
+        layers.append(dict(w=seq_weight(rng, 256, 256, 1), relu=True, src=1))
+        assert SEQ_TRIPLE_MID not in [c for c, _, _ in _plan_seq(8, 31, layers, want_outputs=False)]
+        layers = seq_chain(rng, 1024, 256, 12, 2)
+        alone = _plan_seq(8, 31, layers, want_outputs=False)
+        assert [c for c, _, _ in alone][1:4] == [SEQ_TRIPLE_L3, SEQ_TRIPLE_MID, SEQ_PAIR_2ND]
+        late = _plan_seq(8, 31, layers + [dict(w=seq_weight(rng, 256, 256, 1), relu=True, src=1)], want_outputs=False)
+        assert late[1][0] != SEQ_TRIPLE_L3 and late[2][0] == SEQ_PAIR_L3
