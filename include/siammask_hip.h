@@ -27,6 +27,7 @@
 #ifndef SIAMMASK_HIP_H
 #define SIAMMASK_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -229,6 +230,28 @@ int smk_paste_mask(const float *logits_dev, int mask_size, const double *inv_map
  * (argmax_o prob_o + 1) * (max_o prob_o > seg_thr) over n_obj objects that share the frame */
 int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W,
                      int H, float seg_thr, float border, uint8_t *labels_out_dev, void *stream);
+
+/* ---- rotated box of the mask (tools/test.py:283-300; ABI 1.7, additive) ----------------------
+ * smk_mask_rbox: for each of B uint8 masks [B][H][W] (a pixel is set when its byte is non-zero; pixel (x, y) is the
+ * lattice point (x, y)) what the tool derives with cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_NONE) -> the largest
+ * cv2.contourArea -> cv2.minAreaRect -> cv2.boxPoints:
+ *   - the 8-connected components of the set pixels; the contour of a component is its outer border followed from its first
+ *     pixel in raster order (Suzuki-Abe, every visit of a border pixel a vertex; holes do not matter); its area is the
+ *     shoelace sum over that vertex list (a multiple of 1/2; a w x h rectangle gives (w-1)(h-1), a one-pixel line 0);
+ *   - the component of largest contour area is selected; on equal areas the one whose first raster pixel comes first
+ *     (OpenCV's own order among equal areas is not pinned: do not depend on it);
+ *   - the rectangle is the minimum-area enclosing rectangle of the selected component's pixel centres (rotating calipers
+ *     over its convex hull, in float64).
+ * out_dev: float64 [B][12] = x0 y0 x1 y1 x2 y2 x3 y3 (four corners in cyclic order; starting corner and direction are
+ * not pinned), area (contour area of the selected component, 0 without one), found (1: area > min_area -- the tool uses
+ * 100, the comparison is strict; 0: not, the corners then still describe the selected component, zeros without one;
+ * -1: an internal loop bound was exceeded, the row is invalid), n_components, n_hull (hull vertices of the selected one).
+ * W, H in 1..4096; min_area >= 0.  ws_dev: scratch of at least smk_mask_rbox_workspace(B, W, H) bytes (sized for the
+ * worst case of ceil(W/2)*H runs per mask; 0 for a bad geometry), 16-byte aligned, owned by the call until it has completed
+ * on `stream`.  No context; asynchronous on `stream`, no host synchronisation. */
+size_t smk_mask_rbox_workspace(int B, int W, int H);
+int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev,
+                  size_t ws_bytes, double *out_dev, void *stream);
 
 #ifdef __cplusplus
 }

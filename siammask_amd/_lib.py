@@ -29,7 +29,7 @@ SYMBOLS = (
     "smk_finalize_weights", "smk_template", "smk_track", "smk_refine", "smk_set_decode_params", "smk_decode", "smk_step", "smk_set_graph_mode", "smk_seq_status", "smk_seq_sync_check", "smk_set_result_ring", "smk_result_ring_cursor", "smk_set_pipeline", "smk_pipeline_join", "smk_pipeline_observe",
     "smk_debug_read", "smk_debug_seq_inject", "smk_tune", "smk_tune_get", "smk_profile", "smk_profile_dump", "smk_op_conv2d_ex", "smk_op_conv2d", "smk_op_dw_xcorr",
     "smk_op_maxpool3x3s2", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
-    "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels",
+    "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels", "smk_mask_rbox_workspace", "smk_mask_rbox",
 )
 
 
@@ -119,13 +119,15 @@ def lib():
     L.smk_crop_resize.argtypes = [vp, ctypes.c_int64, ci, ci, vp, vp, ci, ci, fp, vp]
     L.smk_paste_mask.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, fp, vp]
     L.smk_paste_labels.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp]
+    L.smk_mask_rbox_workspace.argtypes = [ci, ci, ci]
+    L.smk_mask_rbox.argtypes = [vp, ci, ci, ci, ctypes.c_double, vp, ctypes.c_size_t, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
-            fn.restype = ci
+            fn.restype = ctypes.c_size_t if name == "smk_mask_rbox_workspace" else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

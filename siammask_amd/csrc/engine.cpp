@@ -1769,7 +1769,7 @@ static int seq_grid_for(int ncu) {
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
-int smk_version(void) { return (1 << 16) | 6; }   // 1.6: SMK_DTYPE_F16X3 (split-operand fp16 contexts)
+int smk_version(void) { return (1 << 16) | 7; }   // 1.7: smk_mask_rbox (1.6: SMK_DTYPE_F16X3, split-operand fp16 contexts)
 //   // 1.2: smk_decode / smk_step take float64 target_wh and write a float64 box; 1.3: smk_op_conv_seq,
                                                   // sequence failures reported at the next entry point
 
@@ -3207,6 +3207,47 @@ int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_m
     for (int i = 0; i < n_obj; ++i)
         for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
     if (launch_paste_labels(p, n_obj, stream)) return fail(SMK_E_HIP, "paste_labels launch failed");
+    return 0;
+}
+
+// ---- rotated box of the largest external contour (tools/test.py:283-300; mask_rbox.hip) ---------
+static const int RBOX_MAX_DIM = 4096;
+static inline size_t rup256(size_t x) { return (x + 255) / 256 * 256; }
+
+size_t smk_mask_rbox_workspace(int B, int W, int H) {
+    if (B < 1 || W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM) return 0;
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+    return rup256(b * sizeof(RboxHdr)) + rup256(b * H * 2 * sizeof(int)) + rup256(b * H * Wq * 8) + rup256(b * H * Wh * sizeof(int));
+}
+
+int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev, size_t ws_bytes,
+                  double *out_dev, void *stream) {
+    if (!mask_dev || !ws_dev || !out_dev) return fail(SMK_E_ARG, "smk_mask_rbox: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_mask_rbox: batch %d", B);
+    if (W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_mask_rbox: frame %d x %d outside 1..%d", W, H, RBOX_MAX_DIM);
+    if (!(min_area >= 0)) return fail(SMK_E_ARG, "smk_mask_rbox: min_area must be >= 0");
+    const size_t need = smk_mask_rbox_workspace(B, W, H);
+    if (ws_bytes < need) return fail(SMK_E_ARG, "smk_mask_rbox: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if ((uintptr_t)ws_dev % 16) return fail(SMK_E_ARG, "smk_mask_rbox: workspace must be 16-byte aligned");
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+    char *w = (char *)ws_dev;
+    RboxHdr *hdr = (RboxHdr *)w;                       w += rup256(b * sizeof(RboxHdr));
+    int *rows = (int *)w;                              w += rup256(b * H * 2 * sizeof(int));
+    unsigned long long *bits = (unsigned long long *)w; w += rup256(b * H * Wq * 8);
+    int *parent = (int *)w;
+    const int GRID_Y = 32768;                          // streams per launch (grid.y)
+    for (int b0 = 0; b0 < B; b0 += GRID_Y) {
+        RboxParams p;
+        p.mask = mask_dev + (size_t)b0 * H * W;
+        p.B = B - b0 < GRID_Y ? B - b0 : GRID_Y;
+        p.W = W; p.H = H; p.Wq = (int)Wq; p.Wh = (int)Wh;
+        p.min_area = min_area;
+        p.hdr = hdr + b0; p.rows = rows + (size_t)b0 * H * 2; p.bits = bits + (size_t)b0 * H * Wq;
+        p.parent = parent + (size_t)b0 * H * Wh;
+        p.out = out_dev + (size_t)b0 * 12;
+        if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
+    }
     return 0;
 }
 

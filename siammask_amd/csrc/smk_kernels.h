@@ -514,6 +514,21 @@ int launch_pipe_mark(unsigned *sig, void *stream);          // sig: signal memor
 int launch_crop_resize(const CropParams &p, int B, void *stream);
 int launch_paste_mask(const PasteParams &p, int B, void *stream);
 int launch_paste_labels(const PasteParams &p, int n_obj, void *stream);
+// mask_rbox.hip: rotated box of the largest external contour of each of B masks.  Workspace, per call: hdr [B], rows [B][H][2]
+// (min / max x of the winner per row), bits [B][H][Wq] (Wq = ceil(W/64) packed words per row), parent [B][H][Wh] (Wh = ceil(W/2):
+// one union-find slot per possible run of a row)
+struct RboxHdr {
+    unsigned long long best;           // ((2*area << 24 | 0xffffff - root slot) + 1) of the winner, 0: no component
+    int ncomp, err;
+};
+struct RboxParams {
+    const unsigned char *mask;
+    int B, W, H, Wq, Wh;
+    double min_area;
+    RboxHdr *hdr; int *rows; unsigned long long *bits; int *parent;
+    double *out;                       // [B][12]
+};
+int launch_mask_rbox(const RboxParams &p, void *stream);
 const void *zero_page();   // device-resident 8 KB of zeros (allocated on first use, per device)
 
 }  // namespace smk

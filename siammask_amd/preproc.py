@@ -5,6 +5,7 @@ arguments but a frame that already lives on the MI355X.
   get_subwindow_tracking <- tools/test.py:67-110   (crop + mean-colour pad + cv2.resize INTER_LINEAR)
   crop_batch              the same for B streams in one launch
   paste_masks            <- tools/test.py:257-284  (sigmoid + crop_back/cv2.warpAffine + threshold)
+  mask_rboxes            <- tools/test.py:285-294  (findContours -> largest contourArea -> minAreaRect -> boxPoints)
 No CPU fallback: CPU tensors raise."""
 import ctypes
 
@@ -116,3 +117,33 @@ def paste_labels(logits, back_boxes, im_wh, seg_thr=0.35, padding=-1.0):
                                                float(seg_thr), float(padding), labels.data_ptr(),
                                                _lib.current_stream_ptr()))
     return labels
+
+
+_rbox_ws = {}      # (device, stream, B, W, H) -> scratch of smk_mask_rbox (sized for the worst case of ceil(W/2)*H runs per mask)
+
+
+def mask_rboxes(mask, min_area=100.0):
+    """The rotated rectangle of the largest external contour of each mask (tools/test.py:285-294), on the device.
+    mask: uint8 CUDA tensor [B,H,W] or [H,W] (a pixel is set when non-zero), H and W up to 4096.
+    -> float64 CUDA tensor [B,12]: x0 y0 x1 y1 x2 y2 x3 y3 (corners in cyclic order), contour area of the selected component,
+    found (1: area > min_area; 0: not; -1: the row is invalid), n_components, n_hull (include/siammask_hip.h: smk_mask_rbox)."""
+    _need_cuda(mask, "mask")
+    if mask.dtype != torch.uint8 or mask.dim() not in (2, 3):
+        raise ValueError("mask must be uint8 [B,H,W] or [H,W]")
+    m = mask.contiguous()
+    if m.dim() == 2:
+        m = m[None]
+    B, H, W = (int(v) for v in m.shape)
+    L = _lib.lib()
+    need = L.smk_mask_rbox_workspace(B, W, H)
+    if need == 0:
+        raise ValueError("mask_rboxes: B >= 1 and H, W in 1..4096, got %s" % (tuple(m.shape),))
+    with torch.cuda.device(m.device):
+        stream = _lib.current_stream_ptr()
+        key = (m.device.index, stream.value, B, W, H)
+        ws = _rbox_ws.get(key)
+        if ws is None:
+            ws = _rbox_ws[key] = torch.empty(need, dtype=torch.uint8, device=m.device)
+        out = torch.empty((B, 12), dtype=torch.float64, device=m.device)
+        _lib.check(L.smk_mask_rbox(m.data_ptr(), B, W, H, float(min_area), ws.data_ptr(), need, out.data_ptr(), stream))
+    return out

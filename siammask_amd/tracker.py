@@ -1,13 +1,15 @@
 """Device-resident tracker loop for B streams in lock-step: the host logic of tools/test.py
 (`siamese_init` :132-170, `siamese_track` :173-311) with every image-sized operation on the MI355X
-(crop+resize, network, decode, Refine, mask paste-back).  The host keeps the per-stream scalar state
-(target_pos / target_sz update, :241-250 and :302-305); contours / minAreaRect (:285-294) are left to the
-caller.  Additive: the reference's tools keep running their own functions through the drop-in Custom.
+(crop+resize, network, decode, Refine, mask paste-back, and on request the rotated box of the mask: contours / minAreaRect,
+:285-294).  The host keeps the per-stream scalar state (target_pos / target_sz update, :241-250 and :302-305) and the box of
+an empty mask (:298-303).  Additive: the reference's tools keep running their own functions through the drop-in Custom.
 
     tr = DeviceTracker(model, hp={'penalty_k': 0.04, 'window_influence': 0.4, 'lr': 1.0, 'seg_thr': 0.35})
     tr.init(frame_u8_cuda, [(cx, cy), ...], [(w, h), ...])         # siamese_init per stream
     st = tr.track(next_frame_u8_cuda)                              # siamese_track(mask_enable, refine_enable)
     st['target_pos'], st['target_sz'], st['score'], st['mask']     # [B,2], [B,2], [B], uint8 [B,im_h,im_w]
+    st = tr.track(next_frame_u8_cuda, want_polygon=True)           # + state['ploygon'] of the reference (:294-303):
+    st['polygon'], st['polygon_found']                             # float64 [B,4,2], bool [B] (False: the box of an empty mask)
 """
 import numpy as np
 import torch
@@ -77,8 +79,13 @@ class DeviceTracker(object):
         return self.state
 
     # -- siamese_track (tools/test.py:173-311) ---------------------------------------------------
-    def track(self, frame, want_mask=True, keep_crop=False):
+    def track(self, frame, want_mask=True, keep_crop=False, want_polygon=False):
+        """want_polygon: also the rotated rectangle the reference returns as state['ploygon'] (variants with a mask branch, and
+        want_mask): st['polygon'] float64 [B,4,2], st['polygon_found'] bool [B]; the only extra device -> host traffic is
+        [B,12] float64.  Without it the returned state has exactly the keys and values it always had."""
         p, st = self.p, self.state
+        st.pop("polygon", None)                                       # (of an earlier step that asked for it)
+        st.pop("polygon_found", None)
         want_mask = want_mask and self.model.variant != "rpn"         # siamrpn has no mask branch (mask_enable=False)
         pos, sz = st["target_pos"], st["target_sz"]
         B = pos.shape[0]
@@ -119,6 +126,8 @@ class DeviceTracker(object):
                 idx = torch.arange(B, device=m.device)
                 logits = m[idx, :, torch.as_tensor(delta_y, device=m.device), torch.as_tensor(delta_x, device=m.device)]
             masks = preproc.paste_masks(logits, bbs, (st["im_w"], st["im_h"]), seg_thr=p.seg_thr)
+            if want_polygon:                                          # same stream, behind the paste-back (:285-303)
+                st["polygon"], st["polygon_found"] = rotated_boxes(masks, new_pos, new_sz)
         new_pos[:, 0] = np.clip(new_pos[:, 0], 0, st["im_w"])         # (:302-305)
         new_pos[:, 1] = np.clip(new_pos[:, 1], 0, st["im_h"])
         new_sz[:, 0] = np.clip(new_sz[:, 0], 10, st["im_w"])
@@ -126,6 +135,21 @@ class DeviceTracker(object):
         st.update(target_pos=new_pos, target_sz=new_sz, score=box[:, 4].copy(), mask=masks, best_id=best,
                   delta_yx=np.stack([delta_y, delta_x], 1), crop_box=crop_box, x_crop=x.clone() if keep_crop else None)
         return st
+
+
+def rotated_boxes(masks, target_pos, target_sz, min_area=100.0):
+    """tools/test.py:285-303: minAreaRect of the largest contour where its area exceeds 100, else the axis-aligned box of
+    cxy_wh_2_rect(target_pos, target_sz) (the updated state before it is clipped) -> float64 [B,4,2], bool [B]"""
+    rows = preproc.mask_rboxes(masks, min_area=min_area).cpu().numpy()
+    if (rows[:, 9] < 0).any():
+        raise RuntimeError("mask_rboxes: a loop bound was exceeded for streams %s" % np.nonzero(rows[:, 9] < 0)[0].tolist())
+    found = rows[:, 9] > 0
+    poly = rows[:, :8].reshape(-1, 4, 2).copy()
+    for b in np.nonzero(~found)[0]:
+        x, y = target_pos[b, 0] - target_sz[b, 0] / 2, target_pos[b, 1] - target_sz[b, 1] / 2
+        w, h = target_sz[b]
+        poly[b] = [[x, y], [x + w, y], [x + w, y + h], [x, y + h]]
+    return poly, found
 
 
 def preproc_back_box(crop_box, delta_yx, im_wh, p, mask_size):
