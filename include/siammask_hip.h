@@ -253,6 +253,65 @@ size_t smk_mask_rbox_workspace(int B, int W, int H);
 int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev,
                   size_t ws_bytes, double *out_dev, void *stream);
 
+/* ---- tracker state on the device (tools/test.py:173-311 siamese_track; ABI 1.8, additive) ------
+ * The float64 scalars that connect one frame to the next live in a caller-owned device block, so that a tracker loop is
+ * a sequence of launches on one stream with no host read-back between frames (siammask_amd.tracker.DeviceTracker.enqueue).
+ * Block layout: B records `smk_trk_stream`, then target_wh [B][2] f64 (what smk_step takes as target_wh_dev):
+ *     smk_trk_state_bytes(B) = B * sizeof(smk_trk_stream) + B * 16;   target_wh = (double *)((char *)state + B * sizeof(smk_trk_stream))
+ * 8-byte aligned.  No smk_ctx; every entry is asynchronous on `stream` and checks its arguments before it touches the device.
+ * Every scalar operation is an IEEE float64 basic operation in the order of the reference's host code (no contraction): the
+ * records hold the bits the host loop computes. */
+typedef struct smk_trk_cfg {       /* utils/tracker_config.py:10-47 + hp of config_*.json */
+    double context_amount;         /* 0.5                                                                        */
+    double lr;                     /* hp 'lr' (tools/test.py:241)                                                */
+    int exemplar_size, instance_size, total_stride, base_size;   /* 127, 255, 8, 8                               */
+    int score_size;                /* 25: best_id -> delta_y / delta_x (:253-254)                                */
+    int mask_size;                 /* side of the mask that is pasted back: 127 (Refine) or 63 (mask head), :278 */
+} smk_trk_cfg;
+
+typedef struct smk_trk_stream {
+    /* persistent: written by smk_trk_set, updated by smk_trk_advance */
+    double target_pos[2];          /* clipped (:302-305), frame pixels (x, y)                                    */
+    double target_sz[2];           /* clipped, (w, h)                                                            */
+    /* per frame: written by the plan of the frame (:181-198) */
+    double scale_x, s_x;           /* exemplar_size / sqrt(wc_x * hc_x); s_x before rounding                     */
+    double crop_box[4];            /* pos - round(s_x) / 2 (x, y), round(s_x), round(s_x)  (:191)                */
+    /* per frame: written by the advance of the frame; slot = the `slot` argument (two frames can be in flight) */
+    double inv_map[2][6];          /* dst -> src affine map of the paste-back (:263-279, cv::invertAffineTransform) */
+    int im_w, im_h;
+    int xmin, ymin, sz;            /* integer crop window (:70-76) of the planned frame                          */
+    int best_id;                   /* of the frame advanced last                                                 */
+    int delta_yx[2][2];            /* [slot] = (delta_y, delta_x) (:253-254)                                     */
+    unsigned char avg_bgr[4];      /* mean colour, truncated to uint8 as the numpy assignment does (:92-99)      */
+    int reserved;
+} smk_trk_stream;
+
+size_t smk_trk_state_bytes(int B);
+/* init: target_pos / target_sz [B][2] f64, avg_bgr [B][3] uint8 are HOST values; they travel as kernel arguments (nothing of the
+ * caller's memory is read after the call returns).  The derived fields are zeroed. */
+int smk_trk_set(void *state_dev, int B, const double *target_pos, const double *target_sz, const uint8_t *avg_bgr,
+                int im_w, int im_h, void *stream);
+/* plan (:181-198,230 + :70-76): scale_x, s_x, crop_box, the integer window and target_wh of the NEXT frame from target_pos / target_sz */
+int smk_trk_plan(void *state_dev, int B, const smk_trk_cfg *cfg, void *stream);
+/* advance (:240-254,263-279,302-305) from smk_step's box_out [B][8]: pred / scale_x, lr = penalty * score * lr, new position and
+ * size, delta_y / delta_x, back box -> crop_back map -> its inverse into inv_map[slot] (slot 0 | 1), the clip.  result_row_dev
+ * (may be NULL) [B][16] f64: target_pos (2), target_sz (2) clipped, score, best_id, delta_y, delta_x, position (2) and size (2)
+ * BEFORE the clip (:298-303 builds the box of an empty mask from them), crop_box x, y, side, scale_x.  A best_id outside
+ * 0 .. 5 * score_size^2 - 1 (an invalid frame) is clamped so that delta_y / delta_x stay inside the head.
+ * plan_next != 0: the plan of the next frame in the same launch. */
+int smk_trk_advance(void *state_dev, int B, const smk_trk_cfg *cfg, const double *box_dev, int slot,
+                    double *result_row_dev, int plan_next, void *stream);
+/* smk_crop_resize with the window (xmin, ymin, sz) and the mean colour read from the state block by the kernel.  A window side
+ * outside 1..32768 (smk_crop_resize's range; only an invalid state has one) gives the mean colour. */
+int smk_crop_resize_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev,
+                        int B, int model_sz, float *out_dev, void *stream);
+/* smk_paste_mask with inv_map[slot] read from the state block.  head_dev == NULL: logits_dev [B][ms*ms] as for smk_paste_mask.
+ * head_dev != NULL (logits_dev ignored): the mask head's output [B][ms*ms][score_size][score_size]; the logits of stream b are
+ * its column at delta_yx[slot] of the state (tools/test.py:259-260). */
+int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                       int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev,
+                       float *prob_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,14 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
  * are not touched. */
 int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *sync, int *a_stage);
 
+/* Host only: the scalar stage of the tracker (smk_trk_plan / smk_trk_advance) on HOST memory -- the very inline functions the
+ * device kernels compile (csrc/tracker_state.h), so that the CPU test-suite can hold them bit for bit against the host loop of
+ * siammask_amd.tracker.DeviceTracker.track.  state: B records smk_trk_stream followed by target_wh [B][2], as on the device;
+ * box [B][8] and result_row [B][16] (may be NULL) as for smk_trk_advance. */
+int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg);
+int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const double *box, int slot, double *result_row,
+                         int plan_next);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,8 @@ SYMBOLS = (
     "smk_debug_read", "smk_debug_seq_inject", "smk_tune", "smk_tune_get", "smk_profile", "smk_profile_dump", "smk_op_conv2d_ex", "smk_op_conv2d", "smk_op_dw_xcorr",
     "smk_op_maxpool3x3s2", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
     "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels", "smk_mask_rbox_workspace", "smk_mask_rbox",
+    "smk_trk_state_bytes", "smk_trk_set", "smk_trk_plan", "smk_trk_advance", "smk_crop_resize_dev", "smk_paste_mask_dev",
+    "smk_host_trk_plan", "smk_host_trk_advance",
 )
 
 
@@ -44,6 +46,12 @@ class SeqOp(ctypes.Structure):
     _fields_ = [("g", ConvGeom), ("src", ctypes.c_int), ("res_src", ctypes.c_int), ("sync", ctypes.c_int),
                 ("cfg", ctypes.c_int), ("kstag", ctypes.c_int), ("w_host", ctypes.c_void_p), ("b_host", ctypes.c_void_p),
                 ("y_dev", ctypes.c_void_p)]
+
+
+class TrkCfg(ctypes.Structure):
+    """smk_trk_cfg: the tracker's configuration for the scalar kernels (utils/tracker_config.py + hp)"""
+    _fields_ = [("context_amount", ctypes.c_double), ("lr", ctypes.c_double)] + [(n, ctypes.c_int) for n in (
+        "exemplar_size", "instance_size", "total_stride", "base_size", "score_size", "mask_size")]
 
 
 class SmkError(RuntimeError):
@@ -121,13 +129,22 @@ def lib():
     L.smk_paste_labels.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp]
     L.smk_mask_rbox_workspace.argtypes = [ci, ci, ci]
     L.smk_mask_rbox.argtypes = [vp, ci, ci, ci, ctypes.c_double, vp, ctypes.c_size_t, vp, vp]
+    cp = ctypes.POINTER(TrkCfg)
+    L.smk_trk_state_bytes.argtypes = [ci]
+    L.smk_trk_set.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp]
+    L.smk_trk_plan.argtypes = [vp, ci, cp, vp]
+    L.smk_trk_advance.argtypes = [vp, ci, cp, vp, ci, vp, ci, vp]
+    L.smk_host_trk_plan.argtypes = [vp, ci, cp]
+    L.smk_host_trk_advance.argtypes = [vp, ci, cp, vp, ci, vp, ci]
+    L.smk_crop_resize_dev.argtypes = [vp, ctypes.c_int64, ci, ci, vp, ci, ci, fp, vp]
+    L.smk_paste_mask_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, fp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
-            fn.restype = ctypes.c_size_t if name == "smk_mask_rbox_workspace" else ci
+            fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_trk_state_bytes") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

@@ -27,6 +27,7 @@
 #include "../../include/siammask_hip_test.h"
 #include "conv_plan.h"
 #include "smk_kernels.h"
+#include "tracker_state.h"
 
 using namespace smk;
 
@@ -1769,7 +1770,7 @@ static int seq_grid_for(int ncu) {
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
-int smk_version(void) { return (1 << 16) | 7; }   // 1.7: smk_mask_rbox (1.6: SMK_DTYPE_F16X3, split-operand fp16 contexts)
+int smk_version(void) { return (1 << 16) | 8; }   // 1.8: tracker state on the device, smk_trk_* / smk_*_dev (1.7: smk_mask_rbox; 1.6: SMK_DTYPE_F16X3)
 //   // 1.2: smk_decode / smk_step take float64 target_wh and write a float64 box; 1.3: smk_op_conv_seq,
                                                   // sequence failures reported at the next entry point
 
@@ -3248,6 +3249,118 @@ int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min
         p.out = out_dev + (size_t)b0 * 12;
         if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
     }
+    return 0;
+}
+
+// ---- tracker state on the device (tools/test.py:173-311; tracker_state.hip / tracker_state.h) ---------------------------
+size_t smk_trk_state_bytes(int B) { return B < 1 ? 0 : (size_t)B * (sizeof(smk_trk_stream) + 2 * sizeof(double)); }
+
+static int trk_cfg_check(const char *who, const smk_trk_cfg *cfg) {
+    if (!cfg) return fail(SMK_E_ARG, "%s: null configuration", who);
+    if (cfg->exemplar_size < 1 || cfg->instance_size < cfg->exemplar_size || cfg->total_stride < 1 || cfg->base_size < 0 ||
+        cfg->score_size < 1 || cfg->score_size > 1024 || cfg->mask_size < 1)
+        return fail(SMK_E_ARG, "%s: bad configuration", who);
+    return 0;
+}
+
+int smk_trk_set(void *state_dev, int B, const double *target_pos, const double *target_sz, const uint8_t *avg_bgr, int im_w,
+                int im_h, void *stream) {
+    if (!state_dev || !target_pos || !target_sz || !avg_bgr) return fail(SMK_E_ARG, "smk_trk_set: null argument");
+    if (B < 1 || im_w < 1 || im_h < 1) return fail(SMK_E_ARG, "smk_trk_set: bad geometry");
+    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_set: the state block must be 8-byte aligned");
+    for (int b0 = 0; b0 < B; b0 += TRK_SET_MAX_B) {
+        TrkSetArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = B - b0 < TRK_SET_MAX_B ? B - b0 : TRK_SET_MAX_B;
+        a.im_w = im_w; a.im_h = im_h;
+        for (int i = 0; i < a.n; ++i)
+            for (int k = 0; k < 2; ++k) {
+                a.pos[i][k] = target_pos[2 * (b0 + i) + k];
+                a.sz[i][k] = target_sz[2 * (b0 + i) + k];
+            }
+        for (int i = 0; i < a.n; ++i)
+            for (int k = 0; k < 3; ++k) a.avg[i][k] = avg_bgr[3 * (b0 + i) + k];
+        if (launch_trk_set((smk_trk_stream *)state_dev + b0, a, stream)) return fail(SMK_E_HIP, "trk_set launch failed");
+    }
+    return 0;
+}
+
+int smk_trk_plan(void *state_dev, int B, const smk_trk_cfg *cfg, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_trk_plan: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_trk_plan: batch %d", B);
+    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_plan: the state block must be 8-byte aligned");
+    CHK(trk_cfg_check("smk_trk_plan", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_step(st, (double *)(st + B), B, *cfg, nullptr, 0, nullptr, 2, stream)) return fail(SMK_E_HIP, "trk_step launch failed");
+    return 0;
+}
+
+int smk_trk_advance(void *state_dev, int B, const smk_trk_cfg *cfg, const double *box_dev, int slot, double *result_row_dev,
+                    int plan_next, void *stream) {
+    if (!state_dev || !box_dev) return fail(SMK_E_ARG, "smk_trk_advance: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_trk_advance: batch %d", B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_trk_advance: slot %d (0 or 1)", slot);
+    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_advance: the state block must be 8-byte aligned");
+    CHK(trk_cfg_check("smk_trk_advance", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_step(st, (double *)(st + B), B, *cfg, box_dev, slot, result_row_dev, plan_next ? 3 : 1, stream))
+        return fail(SMK_E_HIP, "trk_step launch failed");
+    return 0;
+}
+
+int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg) {
+    if (!state) return fail(SMK_E_ARG, "smk_host_trk_plan: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_plan: batch %d", B);
+    CHK(trk_cfg_check("smk_host_trk_plan", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) trk_plan(st[b], *cfg, twh + 2 * b);
+    return 0;
+}
+
+int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const double *box, int slot, double *result_row,
+                         int plan_next) {
+    if (!state || !box) return fail(SMK_E_ARG, "smk_host_trk_advance: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_advance: batch %d", B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_host_trk_advance: slot %d (0 or 1)", slot);
+    CHK(trk_cfg_check("smk_host_trk_advance", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) {
+        trk_advance(st[b], *cfg, box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
+        if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
+    }
+    return 0;
+}
+
+int smk_crop_resize_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev, int B,
+                        int model_sz, float *out_dev, void *stream) {
+    if (!frames_dev || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev: null argument");
+    if (H < 1 || W < 1 || model_sz < 1 || B < 1 || B > 65535 || frame_stride_bytes < 0)
+        return fail(SMK_E_ARG, "smk_crop_resize_dev: bad geometry");
+    CropDevParams p;
+    p.frames = frames_dev; p.frame_stride = frame_stride_bytes; p.out = out_dev;
+    p.H = H; p.W = W; p.model_sz = model_sz;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_crop_resize_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev launch failed");
+    return 0;
+}
+
+int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                       int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev, float *prob_out_dev,
+                       void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev || (!mask_out_dev && !prob_out_dev))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev: null argument");
+    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || B < 1 || B > 65535 || (head_dev && (score_size < 1 || score_size > 1024)))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev: slot %d (0 or 1)", slot);
+    PasteDevParams p;
+    p.logits = head_dev ? head_dev : logits_dev;
+    p.mask_out = mask_out_dev; p.prob_out = prob_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.seg_thr = seg_thr; p.border = border;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_paste_mask_dev(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev launch failed");
     return 0;
 }
 

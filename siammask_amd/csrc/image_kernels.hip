@@ -11,6 +11,7 @@
 // coordinates are bit-identical to the host restatement in oracle/cv_ops.py.
 #include <hip/hip_runtime.h>
 #include "smk_kernels.h"
+#include "tracker_state.h"
 
 namespace smk {
 
@@ -32,11 +33,11 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int ssize, double scale) {
     return c;
 }
 
-__global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
-    const int b = blockIdx.z;
-    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
-    if (dx >= p.model_sz) return;
-    const int xmin = p.box[b][0], ymin = p.box[b][1], sz = p.box[b][2];
+// one output pixel (dx, dy) of stream b; P = CropParams (window and mean colour in the kernarg) or CropDevParams (read from the
+// tracker's state block): the same per-pixel code for both, the resize branch is uniform per stream either way
+template <class P>
+__device__ __forceinline__ void crop_pixel(const P &p, int b, int dx, int dy, int xmin, int ymin, int sz, int avg0, int avg1,
+                                           int avg2) {
     const unsigned char *im = p.frames + (size_t)b * p.frame_stride;
     const int H = p.H, W = p.W;
     // patch pixel (py, px) -> frame pixel or the mean colour (tools/test.py:89-100)
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
             const unsigned char *q = im + ((size_t)y * W + x) * 3;
             v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
         } else {
-            v[0] = p.avg[b][0]; v[1] = p.avg[b][1]; v[2] = p.avg[b][2];
+            v[0] = avg0; v[1] = avg1; v[2] = avg2;
         }
     };
     int o[3];
@@ -78,6 +79,36 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
     out[2 * plane] = (float)o[2];
 }
 
+__global__ __launch_bounds__(256) void crop_resize_kernel(const CropParams p) {
+    const int b = blockIdx.z;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+    if (dx >= p.model_sz) return;
+    crop_pixel(p, b, dx, dy, p.box[b][0], p.box[b][1], p.box[b][2], p.avg[b][0], p.avg[b][1], p.avg[b][2]);
+}
+
+// the same with the window and the mean colour of the tracker's device state (smk_crop_resize_dev)
+__global__ __launch_bounds__(256) void crop_resize_dev_kernel(const CropDevParams p) {
+    const int b = blockIdx.z;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+    if (dx >= p.model_sz) return;
+    const smk_trk_stream *s = p.st + b;
+    const int sz = s->sz, a0 = s->avg_bgr[0], a1 = s->avg_bgr[1], a2 = s->avg_bgr[2];
+    if (sz < 1 || sz > 32768) {                           // (an invalid state; the host entry refuses such a window)
+        const size_t plane = (size_t)p.model_sz * p.model_sz;
+        float *out = p.out + (size_t)b * 3 * plane + (size_t)dy * p.model_sz + dx;
+        out[0] = (float)a0; out[plane] = (float)a1; out[2 * plane] = (float)a2;
+        return;
+    }
+    crop_pixel(p, b, dx, dy, s->xmin, s->ymin, sz, a0, a1, a2);
+}
+
+int launch_crop_resize_dev(const CropDevParams &p, int B, void *stream) {
+    if (B < 1 || B > 65535) return -1;
+    dim3 grid((p.model_sz + 255) / 256, p.model_sz, B);
+    hipLaunchKernelGGL(crop_resize_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_crop_resize(const CropParams &p, int B, void *stream) {
     if (B < 1 || B > CROP_MAX_B) return -1;
     dim3 grid((p.model_sz + 255) / 256, p.model_sz, B);
@@ -87,8 +118,9 @@ int launch_crop_resize(const CropParams &p, int B, void *stream) {
 
 // ------------------------------------------------------------------------------------------
 // warped probability of stream b at frame pixel (x, y): WarpAffineInvoker + remapBilinear<float>
-__device__ __forceinline__ float warped_prob(const PasteParams &p, int b, int x, int y) {
-    const double *M = p.inv_map[b];
+// M: the stream's inverse map; lg / ls: its logits and their element stride (1, or S * S for a column of the mask head)
+template <class P>
+__device__ __forceinline__ float warped_prob(const P &p, const double *M, const float *lg, int ls, int x, int y) {
     constexpr int AB_BITS = 10, INTER_BITS = 5, TAB = 1 << INTER_BITS;
     constexpr double AB_SCALE = 1024.0;
     // X = (X0(y) + adelta(x)) >> (AB_BITS - INTER_BITS), round_delta = AB_SCALE / TAB / 2 = 16
@@ -104,10 +136,9 @@ __device__ __forceinline__ float warped_prob(const PasteParams &p, int b, int x,
     const float fx = __fmul_rn((float)(X & (TAB - 1)), 1.f / TAB), fy = __fmul_rn((float)(Y & (TAB - 1)), 1.f / TAB);
     const float w00 = __fmul_rn(__fsub_rn(1.f, fy), __fsub_rn(1.f, fx)), w01 = __fmul_rn(__fsub_rn(1.f, fy), fx);
     const float w10 = __fmul_rn(fy, __fsub_rn(1.f, fx)), w11 = __fmul_rn(fy, fx);
-    const float *lg = p.logits + (size_t)b * p.ms * p.ms;
     auto tap = [&](int yy, int xx) -> float {
         if ((unsigned)yy < (unsigned)p.ms && (unsigned)xx < (unsigned)p.ms) {
-            const float v = lg[yy * p.ms + xx];
+            const float v = lg[(yy * p.ms + xx) * ls];
             return __fdiv_rn(1.f, __fadd_rn(1.f, expf(-v)));        // .sigmoid() (tools/test.py:256)
         }
         return p.border;
@@ -124,10 +155,37 @@ __global__ __launch_bounds__(256) void paste_mask_kernel(const PasteParams p) {
     const int b = blockIdx.z;
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= p.W) return;
-    const float v = warped_prob(p, b, x, y);
+    const float v = warped_prob(p, p.inv_map[b], p.logits + (size_t)b * p.ms * p.ms, 1, x, y);
     const size_t o = ((size_t)b * p.H + y) * p.W + x;
     if (p.prob_out) p.prob_out[o] = v;
     if (p.mask_out) p.mask_out[o] = v > p.seg_thr ? 1 : 0;
+}
+
+// the same with inv_map[slot] of the tracker's device state; head_S != 0: the logits are the column (delta_y, delta_x) of the
+// mask head [B][ms*ms][S][S] (tools/test.py:259-260)
+__global__ __launch_bounds__(256) void paste_mask_dev_kernel(const PasteDevParams p) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= p.W) return;
+    const smk_trk_stream *s = p.st + b;
+    const float *lg = p.logits + (size_t)b * p.ms * p.ms;
+    int ls = 1;
+    if (p.head_S) {
+        ls = p.head_S * p.head_S;
+        const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1), dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+        lg = p.logits + (size_t)b * p.ms * p.ms * ls + dy * p.head_S + dx;
+    }
+    const float v = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y);
+    const size_t o = ((size_t)b * p.H + y) * p.W + x;
+    if (p.prob_out) p.prob_out[o] = v;
+    if (p.mask_out) p.mask_out[o] = v > p.seg_thr ? 1 : 0;
+}
+
+int launch_paste_mask_dev(const PasteDevParams &p, int B, void *stream) {
+    if (B < 1 || B > 65535) return -1;
+    dim3 grid((p.W + 255) / 256, p.H, B);
+    hipLaunchKernelGGL(paste_mask_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 // multi-object fusion (tools/test.py:521-523): label = (argmax_o prob_o + 1) * (max_o prob_o > thr);
@@ -135,10 +193,10 @@ __global__ __launch_bounds__(256) void paste_mask_kernel(const PasteParams p) {
 __global__ __launch_bounds__(256) void paste_labels_kernel(const PasteParams p, int n_obj) {
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= p.W) return;
-    float best = warped_prob(p, 0, x, y);
+    float best = warped_prob(p, p.inv_map[0], p.logits, 1, x, y);
     int arg = 0;
     for (int o = 1; o < n_obj; ++o) {
-        const float v = warped_prob(p, o, x, y);
+        const float v = warped_prob(p, p.inv_map[o], p.logits + (size_t)o * p.ms * p.ms, 1, x, y);
         if (v > best) { best = v; arg = o; }
     }
     p.mask_out[(size_t)y * p.W + x] = best > p.seg_thr ? (unsigned char)(arg + 1) : 0;

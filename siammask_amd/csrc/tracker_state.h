@@ -1,0 +1,157 @@
+// tracker_state.h -- the scalar stage of the tracker loop (tools/test.py:173-311 siamese_track, as restated by
+// siammask_amd/tracker.py DeviceTracker.track) written ONCE for host and device: tracker_state.hip runs it one lane per stream,
+// smk_host_trk_plan / smk_host_trk_advance (engine.cpp) run the same functions on the CPU for the bit-exact host tests.
+// Every operation is an IEEE float64 basic operation (+ - * /, sqrt, round half to even, compare) in the host loop's order; the
+// operators are compiled under `fp contract(off)` on both sides.
+#ifndef SMK_TRACKER_STATE_H
+#define SMK_TRACKER_STATE_H
+
+#include <hip/hip_runtime.h>
+#include "../../include/siammask_hip.h"
+
+namespace smk {
+
+static_assert(sizeof(smk_trk_stream) == 224 && sizeof(smk_trk_stream) % 8 == 0, "smk_trk_stream is part of the ABI");
+
+// `fp contract(off)` on every operation, host AND device: hipcc compiles device code with -ffp-contract=fast, and the __d*_rn
+// "intrinsics" of this toolchain's __clang_hip_math.h are the plain operators (`return __x * __y;`), so that
+// __dadd_rn(__dmul_rn(a, b), __dmul_rn(c, d)) is contracted into v_fma_f64 once inlined -- it was, and target_sz came out one ulp
+// off the host loop.  The pragma removes the `contract` flag from the operation itself.
+#define SMK_TRK_OP(expr) { _Pragma("clang fp contract(off)") return expr; }
+#define SMK_TRK_HD __host__ __device__ __forceinline__
+SMK_TRK_HD double t_add(double a, double b) SMK_TRK_OP(a + b)
+SMK_TRK_HD double t_sub(double a, double b) SMK_TRK_OP(a - b)
+SMK_TRK_HD double t_mul(double a, double b) SMK_TRK_OP(a * b)
+SMK_TRK_HD double t_div(double a, double b) SMK_TRK_OP(a / b)
+SMK_TRK_HD double t_sqrt(double a) {
+#if defined(__HIP_DEVICE_COMPILE__) && __HIP_DEVICE_COMPILE__
+    return __dsqrt_rn(a);
+#else
+    return __builtin_sqrt(a);
+#endif
+}
+// Python's round() of a np.float64 / np.round: half to even (the default rounding mode on both sides)
+SMK_TRK_HD double t_rint(double a) { return __builtin_rint(a); }
+// float64 -> int32 for values that are integers already; an invalid state (NaN, huge) gives a defined value on both sides
+SMK_TRK_HD int t_int(double a) {
+    if (!(a == a)) return 0;
+    if (a > 1073741824.0) return 1073741824;
+    if (a < -1073741824.0) return -1073741824;
+    return (int)a;
+}
+// np.clip (numpy/_core/src/umath/clip.cpp): min(max(x, lo), hi) with x > lo ? x : lo and v < hi ? v : hi; NaN stays
+SMK_TRK_HD double t_clip(double x, double lo, double hi) {
+    if (!(x == x)) return x;
+    const double v = x > lo ? x : lo;
+    return v < hi ? v : hi;
+}
+
+// tracker.py:124-133 (tools/test.py:181-198,230) + preproc.subwindow_box (:70-76)
+SMK_TRK_HD void trk_plan(smk_trk_stream &s, const smk_trk_cfg &c, double *twh) {
+    const double ctx = t_mul(c.context_amount, t_add(s.target_sz[0], s.target_sz[1]));
+    const double wc_x = t_add(s.target_sz[1], ctx);                       // (w / h swapped as in the reference)
+    const double hc_x = t_add(s.target_sz[0], ctx);
+    const double sq = t_sqrt(t_mul(wc_x, hc_x));
+    const double scale_x = t_div((double)c.exemplar_size, sq);
+    const double pad = t_div(t_div((double)(c.instance_size - c.exemplar_size), 2.0), scale_x);
+    const double s_x = t_add(sq, t_mul(2.0, pad));
+    const double r = t_rint(s_x);
+    const double half = t_div(r, 2.0);
+    s.scale_x = scale_x;
+    s.s_x = s_x;
+    s.crop_box[0] = t_sub(s.target_pos[0], half);
+    s.crop_box[1] = t_sub(s.target_pos[1], half);
+    s.crop_box[2] = r;
+    s.crop_box[3] = r;
+    const double cc = t_div(t_add(r, 1.0), 2.0);                          // subwindow_box: (original_sz + 1) / 2
+    s.xmin = t_int(t_rint(t_sub(s.target_pos[0], cc)));
+    s.ymin = t_int(t_rint(t_sub(s.target_pos[1], cc)));
+    s.sz = t_int(r);
+    twh[0] = t_mul(s.target_sz[0], scale_x);                              // target_sz_in_crop (:230)
+    twh[1] = t_mul(s.target_sz[1], scale_x);
+}
+
+// tracker.py:136-144,159-162 (tools/test.py:240-254,302-305) + preproc_back_box (:275-279), preproc.crop_back_map (:263-268),
+// preproc.invert_affine (cv::invertAffineTransform); box = cx cy w h score penalty pscore best_id of smk_step
+SMK_TRK_HD void trk_advance(smk_trk_stream &s, const smk_trk_cfg &c, const double *box, int slot, double *row) {
+    const double pred0 = t_div(box[0], s.scale_x), pred1 = t_div(box[1], s.scale_x);
+    const double pred2 = t_div(box[2], s.scale_x), pred3 = t_div(box[3], s.scale_x);
+    const double lr = t_mul(t_mul(box[5], box[4]), c.lr);
+    const double keep = t_sub(1.0, lr);
+    const double pos0 = t_add(pred0, s.target_pos[0]), pos1 = t_add(pred1, s.target_pos[1]);
+    const double sz0 = t_add(t_mul(s.target_sz[0], keep), t_mul(pred2, lr));
+    const double sz1 = t_add(t_mul(s.target_sz[1], keep), t_mul(pred3, lr));
+    const int ss = c.score_size, n_best = 5 * ss * ss;
+    int best = t_int(box[7]);
+    best = best < 0 ? 0 : (best >= n_best ? n_best - 1 : best);
+    const int delta_y = (best % (ss * ss)) / ss, delta_x = best % ss;
+    // back box
+    const double sc = t_div(s.crop_box[2], (double)c.instance_size);
+    const double hb = t_div((double)c.base_size, 2.0);
+    const double sub0 = t_add(s.crop_box[0], t_mul(t_mul(t_sub((double)delta_x, hb), (double)c.total_stride), sc));
+    const double sub1 = t_add(s.crop_box[1], t_mul(t_mul(t_sub((double)delta_y, hb), (double)c.total_stride), sc));
+    const double sub2 = t_mul(sc, (double)c.exemplar_size);
+    const double sb = t_div((double)c.mask_size, sub2);
+    const double bb0 = t_mul(-sub0, sb), bb1 = t_mul(-sub1, sb);
+    const double bb2 = t_mul((double)s.im_w, sb), bb3 = t_mul((double)s.im_h, sb);
+    // forward map [[a, 0, -a * bb0], [0, b, -b * bb1]] and its inverse
+    const double a = t_div((double)(s.im_w - 1), bb2), b = t_div((double)(s.im_h - 1), bb3);
+    const double m02 = t_mul(-a, bb0), m12 = t_mul(-b, bb1);
+    double d = t_sub(t_mul(a, b), t_mul(0.0, 0.0));
+    d = d != 0 ? t_div(1.0, d) : 0.0;
+    const double a11 = t_mul(b, d), a22 = t_mul(a, d);
+    const double a12 = t_mul(-0.0, d), a21 = t_mul(-0.0, d);
+    double *im = s.inv_map[slot];
+    im[0] = a11;
+    im[1] = a12;
+    im[2] = t_sub(t_mul(-a11, m02), t_mul(a12, m12));
+    im[3] = a21;
+    im[4] = a22;
+    im[5] = t_sub(t_mul(-a21, m02), t_mul(a22, m12));
+    s.best_id = best;
+    s.delta_yx[slot][0] = delta_y;
+    s.delta_yx[slot][1] = delta_x;
+    // the clip (:302-305)
+    const double cp0 = t_clip(pos0, 0.0, (double)s.im_w), cp1 = t_clip(pos1, 0.0, (double)s.im_h);
+    const double cs0 = t_clip(sz0, 10.0, (double)s.im_w), cs1 = t_clip(sz1, 10.0, (double)s.im_h);
+    if (row) {
+        row[0] = cp0; row[1] = cp1; row[2] = cs0; row[3] = cs1;
+        row[4] = box[4]; row[5] = (double)best; row[6] = (double)delta_y; row[7] = (double)delta_x;
+        row[8] = pos0; row[9] = pos1; row[10] = sz0; row[11] = sz1;
+        row[12] = s.crop_box[0]; row[13] = s.crop_box[1]; row[14] = s.crop_box[2]; row[15] = s.scale_x;
+    }
+    s.target_pos[0] = cp0; s.target_pos[1] = cp1;
+    s.target_sz[0] = cs0; s.target_sz[1] = cs1;
+}
+
+// ---- launchers (tracker_state.hip, image_kernels.hip) ----------------------------------------------------------------
+constexpr int TRK_SET_MAX_B = 32;
+struct TrkSetArgs {                 // smk_trk_set: the host's values travel in the kernarg
+    double pos[TRK_SET_MAX_B][2], sz[TRK_SET_MAX_B][2];
+    unsigned char avg[TRK_SET_MAX_B][4];
+    int im_w, im_h, n;
+};
+int launch_trk_set(smk_trk_stream *st, const TrkSetArgs &a, void *stream);
+// flags: bit 0 advance (box, slot, row), bit 1 plan
+int launch_trk_step(smk_trk_stream *st, double *twh, int B, const smk_trk_cfg &cfg, const double *box, int slot,
+                    double *row, int flags, void *stream);
+struct CropDevParams {
+    const unsigned char *frames;
+    long frame_stride;
+    float *out;
+    int H, W, model_sz;
+    const smk_trk_stream *st;
+};
+struct PasteDevParams {
+    const float *logits;            // [B][ms*ms], or the head [B][ms*ms][S][S] when head_S != 0
+    unsigned char *mask_out;
+    float *prob_out;
+    int ms, W, H, head_S, slot;
+    float seg_thr, border;
+    const smk_trk_stream *st;
+};
+int launch_crop_resize_dev(const CropDevParams &p, int B, void *stream);
+int launch_paste_mask_dev(const PasteDevParams &p, int B, void *stream);
+
+}  // namespace smk
+#endif

@@ -403,7 +403,7 @@ class Custom(nn.Module):
                                             twh.data_ptr(), pos.data_ptr(), box.data_ptr(), _lib.current_stream_ptr()))
         return pos, box
 
-    def track_step(self, search, target_wh, refine=None, mask_head=True, stage=True):
+    def track_step(self, search, target_wh, refine=None, mask_head=True, stage=True, out_set=0):
         """One frame for B streams without leaving the device: track(_mask) -> decode -> refine at
         the decoded positions, replayed as ONE captured graph.
         -> dict(cls, loc, mask, box [B,8], refine [B,16129] or None).  With graph replay the
@@ -411,7 +411,10 @@ class Custom(nn.Module):
         ``box`` is float64 [B,8] (cx, cy, w, h, score, penalty, pscore, best_id), target_wh float64 (:230).
         stage=False: ``search`` (float32) / ``target_wh`` (float64) are caller-owned persistent CUDA buffers
         (e.g. a ring of pre-staged crops); they are read in place (no staging copy) and the
-        captured graph is keyed on their addresses."""
+        captured graph is keyed on their addresses.
+        out_set=1: ``refine`` is written to a second persistent buffer (the graphs are keyed on the I/O pointers: one more
+        cached graph).  A caller that keeps pipelined frames in flight alternates the two, so that the tail of frame f + 1
+        does not write the logits the paste-back of frame f still has to read (tracker.DeviceTracker.enqueue)."""
         if self.zf is None:
             raise RuntimeError("template() must be called before track_step()")
         B = search.shape[0]
@@ -421,7 +424,7 @@ class Custom(nn.Module):
             raise ValueError("the result ring was set for batch %d, got %d" % (self._ring[2], B))
         if not stage:
             # serving fast path: everything about this call is cached per (input buffers, options)
-            key = (search.data_ptr(), target_wh.data_ptr(), B, bool(refine), bool(mask_head))
+            key = (search.data_ptr(), target_wh.data_ptr(), B, bool(refine), bool(mask_head), int(out_set))
             hit = self._fast.get(key) if self._ctx is not None and not self._weights_dirty and not self._hp_dirty else None
             if hit is not None:
                 self._fast[key] = self._fast.pop(key)    # most recently used last
@@ -454,7 +457,7 @@ class Custom(nn.Module):
             loc = self._out("loc", (B, 4 * A, S, S), dev)
             mask = self._out("mask", (B, spec.MASK_OUT ** 2, S, S), dev) if want_mask else None
             box = self._out("box", (B, 8), dev, torch.float64)
-            ref = self._out("refine", (B, spec.REFINE_OUT ** 2), dev) if refine else None
+            ref = self._out("refine1" if out_set else "refine", (B, spec.REFINE_OUT ** 2), dev) if refine else None
             args = (x.data_ptr(), B, flags, twh.data_ptr(), cls.data_ptr(), loc.data_ptr(),
                     mask.data_ptr() if mask is not None else None, box.data_ptr(),
                     ref.data_ptr() if ref is not None else None)

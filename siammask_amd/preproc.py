@@ -100,6 +100,60 @@ def paste_masks(logits, back_boxes, im_wh, seg_thr=0.35, padding=-1.0, want_prob
     return (mask, prob) if want_prob else mask
 
 
+def crop_batch_dev(frames, state, B, model_sz, out=None):
+    """crop_batch with each stream's window and mean colour read on the device from the tracker's state block (uint8 CUDA
+    tensor of smk_trk_state_bytes(B) bytes, include/siammask_hip.h: smk_trk_stream); nothing about the window is on the host.
+    out: a contiguous float32 CUDA tensor [B,3,model_sz,model_sz] to write into (a persistent network input)."""
+    _need_cuda(frames, "frames")
+    _need_cuda(state, "state")
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [H,W,3] or [B,H,W,3]")
+    if frames.dim() == 4 and frames.shape[0] != B:
+        raise ValueError("frames batch %d != %d streams" % (frames.shape[0], B))
+    frames = frames.contiguous()
+    H, W = int(frames.shape[-3]), int(frames.shape[-2])
+    stride = H * W * 3 if frames.dim() == 4 else 0
+    if out is None:
+        out = torch.empty((B, 3, model_sz, model_sz), dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.lib().smk_crop_resize_dev(frames.data_ptr(), stride, H, W, state.data_ptr(), B, int(model_sz),
+                                                  out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
+def paste_masks_dev(logits, state, slot, im_wh, seg_thr=0.35, padding=-1.0, head=None, mask_size=None, out=None, want_prob=False):
+    """paste_masks with the inverse map inv_map[slot] of the tracker's state block read on the device.  logits: float32 CUDA
+    [B, ms*ms]; or head: the mask head's output float32 CUDA [B, ms*ms, S, S] whose column at the state's (delta_y, delta_x)
+    of that slot is pasted (tools/test.py:259-260).  out: uint8 CUDA [B,im_h,im_w] to write into."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = src.shape[0]
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    mask = out if out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=src.device)
+    if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (B, H, W):
+        raise ValueError("out must be a contiguous uint8 CUDA tensor [%d,%d,%d]" % (B, H, W))
+    prob = torch.empty((B, H, W), dtype=torch.float32, device=src.device) if want_prob else None
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().smk_paste_mask_dev(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, W, H, float(seg_thr), float(padding), mask.data_ptr(),
+            prob.data_ptr() if prob is not None else None, _lib.current_stream_ptr()))
+    return (mask, prob) if want_prob else mask
+
+
 def paste_labels(logits, back_boxes, im_wh, seg_thr=0.35, padding=-1.0):
     """Multi-object VOS fusion (tools/test.py:521-523) fused with the paste-back: the O objects of one
     frame -> uint8 label map [im_h, im_w] = (argmax_o prob_o + 1) * (max_o prob_o > seg_thr)."""
@@ -122,11 +176,12 @@ def paste_labels(logits, back_boxes, im_wh, seg_thr=0.35, padding=-1.0):
 _rbox_ws = {}      # (device, stream, B, W, H) -> scratch of smk_mask_rbox (sized for the worst case of ceil(W/2)*H runs per mask)
 
 
-def mask_rboxes(mask, min_area=100.0):
+def mask_rboxes(mask, min_area=100.0, out=None):
     """The rotated rectangle of the largest external contour of each mask (tools/test.py:285-294), on the device.
     mask: uint8 CUDA tensor [B,H,W] or [H,W] (a pixel is set when non-zero), H and W up to 4096.
     -> float64 CUDA tensor [B,12]: x0 y0 x1 y1 x2 y2 x3 y3 (corners in cyclic order), contour area of the selected component,
-    found (1: area > min_area; 0: not; -1: the row is invalid), n_components, n_hull (include/siammask_hip.h: smk_mask_rbox)."""
+    found (1: area > min_area; 0: not; -1: the row is invalid), n_components, n_hull (include/siammask_hip.h: smk_mask_rbox).
+    out: a contiguous float64 CUDA tensor of B * 12 elements to write the rows into instead of a new one."""
     _need_cuda(mask, "mask")
     if mask.dtype != torch.uint8 or mask.dim() not in (2, 3):
         raise ValueError("mask must be uint8 [B,H,W] or [H,W]")
@@ -144,6 +199,9 @@ def mask_rboxes(mask, min_area=100.0):
         ws = _rbox_ws.get(key)
         if ws is None:
             ws = _rbox_ws[key] = torch.empty(need, dtype=torch.uint8, device=m.device)
-        out = torch.empty((B, 12), dtype=torch.float64, device=m.device)
+        if out is None:
+            out = torch.empty((B, 12), dtype=torch.float64, device=m.device)
+        elif out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.numel() != B * 12:
+            raise ValueError("mask_rboxes: out must be a contiguous float64 CUDA tensor of %d elements" % (B * 12))
         _lib.check(L.smk_mask_rbox(m.data_ptr(), B, W, H, float(min_area), ws.data_ptr(), need, out.data_ptr(), stream))
     return out

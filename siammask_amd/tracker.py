@@ -10,11 +10,36 @@ an empty mask (:298-303).  Additive: the reference's tools keep running their ow
     st['target_pos'], st['target_sz'], st['score'], st['mask']     # [B,2], [B,2], [B], uint8 [B,im_h,im_w]
     st = tr.track(next_frame_u8_cuda, want_polygon=True)           # + state['ploygon'] of the reference (:294-303):
     st['polygon'], st['polygon_found']                             # float64 [B,4,2], bool [B] (False: the box of an empty mask)
+
+Free-running mode: the same loop with the per-stream scalar state in device memory (include/siammask_hip.h: smk_trk_stream,
+csrc/tracker_state.hip) -- any number of frames is enqueued without a host synchronisation and read back once:
+    tr.enqueue(frame)                                              # crop -> step -> advance + plan -> paste: launches only
+    res = tr.collect()                                             # ONE synchronisation: host arrays [T,B,...] + device masks
+    res = tr.run(frames)                                           # frames uint8 CUDA [T,H,W,3] or [T,B,H,W,3]
+track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
 """
+import ctypes
+
 import numpy as np
 import torch
 
-from . import preproc
+from . import _lib, preproc
+
+# numpy view of one record of the device state block (include/siammask_hip.h: smk_trk_stream); the block is B records followed
+# by target_wh [B,2] float64
+STREAM_DTYPE = np.dtype([
+    ("target_pos", "<f8", (2,)), ("target_sz", "<f8", (2,)), ("scale_x", "<f8"), ("s_x", "<f8"), ("crop_box", "<f8", (4,)),
+    ("inv_map", "<f8", (2, 6)), ("im_w", "<i4"), ("im_h", "<i4"), ("xmin", "<i4"), ("ymin", "<i4"), ("sz", "<i4"),
+    ("best_id", "<i4"), ("delta_yx", "<i4", (2, 2)), ("avg_bgr", "u1", (4,)), ("reserved", "<i4")])
+RESULT_ROW = 16        # float64 per stream and frame (smk_trk_advance)
+_ROWS_PER_BLOCK = 128
+
+
+def state_records(block, B):
+    """(records [B] of STREAM_DTYPE, target_wh [B,2]) of a state block given as bytes / uint8 array"""
+    a = np.frombuffer(bytes(block), dtype=np.uint8)
+    n = B * STREAM_DTYPE.itemsize
+    return a[:n].view(STREAM_DTYPE).copy(), a[n:n + B * 16].view(np.float64).reshape(B, 2).copy()
 
 
 class TrackerConfig(object):
@@ -54,6 +79,7 @@ class DeviceTracker(object):
         self.mask_size = int(hp["out_size"]) if hp and "out_size" in hp else (127 if self.refine else 63)
         model.set_tracker_hp(self.p.penalty_k, self.p.window_influence)
         self.state = None
+        self._fr = None               # free-running mode: device state, persistent buffers, the pending chunk
 
     # -- siamese_init (tools/test.py:132-170) ---------------------------------------------------
     def init(self, frame, target_pos, target_sz):
@@ -76,6 +102,8 @@ class DeviceTracker(object):
         H, W = int(frame.shape[-3]), int(frame.shape[-2])
         self.state = {"im_h": H, "im_w": W, "avg_chans": avg, "target_pos": pos.copy(), "target_sz": sz.copy(),
                       "score": np.zeros(B), "mask": None}
+        self._fr_setup(frame.device, B, H, W)
+        self._fr_upload()
         return self.state
 
     # -- siamese_track (tools/test.py:173-311) ---------------------------------------------------
@@ -135,6 +163,229 @@ class DeviceTracker(object):
         st.update(target_pos=new_pos, target_sz=new_sz, score=box[:, 4].copy(), mask=masks, best_id=best,
                   delta_yx=np.stack([delta_y, delta_x], 1), crop_box=crop_box, x_crop=x.clone() if keep_crop else None)
         return st
+
+    # -- free-running mode: the scalar state on the device (smk_trk_*), no host synchronisation per frame ------------------
+    def _fr_setup(self, device, B, H, W):
+        p, L = self.p, _lib.lib()
+        fr = self._fr = {"B": B, "H": H, "W": W, "device": device, "pending": 0, "deferred": None, "rows": [], "rbox": [],
+                         "masks": [], "poly": [], "synced": None}
+        n = int(L.smk_trk_state_bytes(B))
+        with torch.cuda.device(device):
+            fr["dev"] = torch.zeros(n, dtype=torch.uint8, device=device)
+            fr["snap"] = torch.zeros(n, dtype=torch.uint8, device=device)
+            fr["x"] = torch.zeros((B, 3, p.instance_size, p.instance_size), dtype=torch.float32, device=device)
+        fr["twh"] = fr["dev"][B * STREAM_DTYPE.itemsize:].view(torch.float64).view(B, 2)
+        fr["cfg"] = _lib.TrkCfg(float(p.context_amount), float(p.lr), int(p.exemplar_size), int(p.instance_size),
+                                int(p.total_stride), int(p.base_size), int(p.score_size), int(self.mask_size))
+        assert STREAM_DTYPE.itemsize * B + 16 * B == n, "STREAM_DTYPE does not match smk_trk_stream"
+
+    def _fr_upload(self):
+        """the host's state -> the device block (values as kernel arguments), then the plan of the next frame"""
+        fr, st, L = self._fr, self.state, _lib.lib()
+        pos = np.ascontiguousarray(st["target_pos"], dtype=np.float64)
+        sz = np.ascontiguousarray(st["target_sz"], dtype=np.float64)
+        # numpy assignment of the float mean into a uint8 image truncates (tools/test.py:92-99), as in preproc.crop_batch
+        avg = np.ascontiguousarray(np.asarray(st["avg_chans"], dtype=np.float64).reshape(fr["B"], 3).astype(np.uint8))
+        with torch.cuda.device(fr["device"]):
+            sp = _lib.current_stream_ptr()
+            _lib.check(L.smk_trk_set(fr["dev"].data_ptr(), fr["B"], pos.ctypes.data, sz.ctypes.data, avg.ctypes.data,
+                                     st["im_w"], st["im_h"], sp))
+            _lib.check(L.smk_trk_plan(fr["dev"].data_ptr(), fr["B"], ctypes.byref(fr["cfg"]), sp))
+        fr["synced"] = (st["target_pos"], st["target_sz"])        # track() replaces these arrays: identity tells who is ahead
+
+    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None):
+        """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
+        advance + plan -> paste-back (map from the device state) [-> rotated box].  No host synchronisation of any kind.
+        mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.  -> the frame's index in the
+        chunk that collect() returns."""
+        fr, st = self._fr, self.state
+        if st is None or fr is None:
+            raise RuntimeError("DeviceTracker.enqueue(): init() first")
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        if not isinstance(frame, torch.Tensor) or not frame.is_cuda:
+            raise RuntimeError("siammask_amd.tracker runs on the MI355X only: frame must be a CUDA(HIP) tensor")
+        if frame.dtype != torch.uint8 or tuple(frame.shape) not in ((H, W, 3), (B, H, W, 3)):
+            raise ValueError("frame must be uint8 [%d,%d,3] or [%d,%d,%d,3] as given to init(), got %s %s"
+                             % (H, W, B, H, W, frame.dtype, tuple(frame.shape)))
+        want_mask = want_mask and self.model.variant != "rpn"
+        want_polygon = want_polygon and want_mask
+        if mask_out is not None and (not want_mask or mask_out.dtype != torch.uint8 or not mask_out.is_cuda or
+                                     not mask_out.is_contiguous() or tuple(mask_out.shape) != (B, H, W)):
+            raise ValueError("mask_out must be a contiguous uint8 CUDA tensor [%d,%d,%d] (and the variant has a mask)" % (B, H, W))
+        frame = frame.contiguous()
+        L, model = _lib.lib(), self.model
+        try:
+            with torch.cuda.device(fr["device"]):
+                sp = _lib.current_stream_ptr()
+                if fr["synced"] is None or st["target_pos"] is not fr["synced"][0] or st["target_sz"] is not fr["synced"][1]:
+                    self._fr_upload()                                 # a track() in between: the host is ahead
+                if fr["pending"] == 0:                                # chunk start: what a reported sequence failure rewinds to
+                    fr["snap"].copy_(fr["dev"])
+                    fr["start"] = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}
+                t = fr["pending"]
+                slot = t & 1
+                blk, i = divmod(t, _ROWS_PER_BLOCK)
+                if i == 0 and blk == len(fr["rows"]):
+                    fr["rows"].append(torch.empty((_ROWS_PER_BLOCK, B, RESULT_ROW), dtype=torch.float64, device=fr["device"]))
+                    fr["rbox"].append(None)
+                if want_polygon and fr["rbox"][blk] is None:
+                    fr["rbox"][blk] = torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=fr["device"])
+                dev_ptr = fr["dev"].data_ptr()
+                _lib.check(L.smk_crop_resize_dev(frame.data_ptr(), H * W * 3 if frame.dim() == 4 else 0, H, W, dev_ptr, B,
+                                                 self.p.instance_size, fr["x"].data_ptr(), sp))
+                refine = self.refine and want_mask
+                out = model.track_step(fr["x"], fr["twh"], refine=refine, mask_head=not self.refine, stage=False,
+                                       out_set=slot if refine else 0)
+                _lib.check(L.smk_trk_advance(dev_ptr, B, ctypes.byref(fr["cfg"]), out["box"].data_ptr(), slot,
+                                             fr["rows"][blk].data_ptr() + i * B * RESULT_ROW * 8, 1, sp))
+                depth = int(getattr(model, "_pipeline", 0) or 0) if self.refine else 0     # (the model's, whoever set it)
+                prev, fr["deferred"] = fr["deferred"], None
+                if prev is not None:
+                    # pipelined: the Refine logits of the previous frame are complete behind this step's decode (smk_set_pipeline,
+                    # depth 1); a step without Refine has no gate, and depth 2 completes them one step later -- join explicitly
+                    if not refine or depth != 1:
+                        model.pipeline_join()
+                    self._fr_paste(prev, sp)
+                mask = None
+                if want_mask:
+                    mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=fr["device"])
+                    job = (out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
+                           fr["rbox"][blk][i] if want_polygon else None)
+                    if depth:
+                        fr["deferred"] = job                          # pasted behind the NEXT step (or by collect())
+                    else:
+                        self._fr_paste(job, sp)
+                fr["masks"].append(mask)
+                fr["poly"].append(bool(want_polygon))
+                fr["pending"] = t + 1
+        except _lib.SmkError as e:
+            if e.code == _lib.E_SEQ:
+                self._fr_rewind()
+            raise
+        return t
+
+    def _fr_paste(self, job, sp):
+        logits, head, slot, mask, rbox = job
+        fr, p = self._fr, self.p
+        _lib.check(_lib.lib().smk_paste_mask_dev(
+            logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
+            int(head.shape[-1]) if head is not None else 0, self.mask_size, fr["dev"].data_ptr(), slot, fr["B"], fr["W"], fr["H"],
+            float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))
+        if rbox is not None:                                          # same stream, behind the paste-back (:285-303)
+            preproc.mask_rboxes(mask, out=rbox)
+
+    def _fr_rewind(self):
+        """a persistent-sequence failure was reported (SMK_E_SEQ): every frame of the pending chunk is invalid and so is the
+        device state.  Back to the chunk's start on both sides; the library has dropped the cached template -- re-establish it
+        from the model's replay record (Custom._guarded), on the per-layer kernels the context has switched to."""
+        fr, model = self._fr, self.model
+        torch.cuda.synchronize(fr["device"])
+        if fr.get("start") is not None:
+            fr["dev"].copy_(fr["snap"])
+            self.state = fr["start"]
+            fr["synced"] = (self.state["target_pos"], self.state["target_sz"])
+        fr["start"] = None
+        fr["pending"], fr["deferred"], fr["masks"], fr["poly"] = 0, None, [], []
+        fr.pop("whole", None)
+        replay = model._replay.get("template")
+        if replay is not None:
+            with torch.cuda.device(fr["device"]):
+                replay()
+                _lib.check(_lib.lib().smk_seq_sync_check(model._ctx, _lib.current_stream_ptr(), None))
+
+    def collect(self):
+        """Join the frames enqueued since the last collect() -- ONE synchronisation -- and return host arrays
+        target_pos [T,B,2], target_sz [T,B,2], score [T,B] (float64), best_id [T,B], delta_yx [T,B,2] (int64), crop_box [T,B,4],
+        mask (uint8 CUDA [T,B,H,W], None without masks), and for frames enqueued with want_polygon polygon [T,B,4,2] /
+        polygon_found [T,B].  Leaves tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the
+        tracker to the chunk's start when a persistent-sequence failure was reported: re-run the chunk."""
+        fr, st = self._fr, self.state
+        if st is None or fr is None:
+            raise RuntimeError("DeviceTracker.collect(): init() first")
+        T, B = fr["pending"], fr["B"]
+        whole = fr.pop("whole", None)                                 # run() (or its caller) gave one [T,B,H,W] mask tensor
+        if T == 0:
+            return None
+        try:
+            with torch.cuda.device(fr["device"]):
+                sp = _lib.current_stream_ptr()
+                if fr["deferred"] is not None:
+                    self.model.pipeline_join()
+                    job, fr["deferred"] = fr["deferred"], None
+                    self._fr_paste(job, sp)
+                _lib.check(_lib.lib().smk_seq_sync_check(self.model._ctx, sp, None))
+                nblk = (T + _ROWS_PER_BLOCK - 1) // _ROWS_PER_BLOCK
+                rows = torch.cat(fr["rows"][:nblk])[:T] if nblk > 1 else fr["rows"][0][:T]
+                any_poly = any(fr["poly"])
+                if any_poly:
+                    rb = [b if b is not None else torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=fr["device"])
+                          for b in fr["rbox"][:nblk]]
+                    rows = torch.cat([rows, torch.cat(rb)[:T]], dim=2)
+                host = rows.cpu().numpy()                             # the one synchronisation
+        except _lib.SmkError as e:
+            if e.code == _lib.E_SEQ:
+                self._fr_rewind()
+            raise
+        r = host[:, :, :RESULT_ROW]
+        res = {"target_pos": r[:, :, 0:2].copy(), "target_sz": r[:, :, 2:4].copy(), "score": r[:, :, 4].copy(),
+               "best_id": r[:, :, 5].astype(np.int64), "delta_yx": r[:, :, 6:8].astype(np.int64),
+               "crop_box": np.stack([r[:, :, 12], r[:, :, 13], r[:, :, 14], r[:, :, 14]], axis=2), "mask": None}
+        masks = fr["masks"]
+        if all(m is not None for m in masks):
+            res["mask"] = whole if whole is not None and whole.shape[0] == T else torch.stack(masks)
+        elif any(m is not None for m in masks):
+            res["mask"] = masks                                       # mixed chunk: per frame, None where no mask was asked for
+        if any_poly:
+            q = host[:, :, RESULT_ROW:]
+            asked = np.asarray(fr["poly"], dtype=bool)
+            if (q[asked][:, :, 9] < 0).any():
+                raise RuntimeError("mask_rboxes: a loop bound was exceeded for (frame, stream) %s"
+                                   % np.argwhere(q[:, :, 9] < 0).tolist())
+            found = q[:, :, 9] > 0
+            poly = q[:, :, :8].reshape(T, B, 4, 2).copy()
+            for t, b in np.argwhere(~found):                          # the box of the state before the clip (:298-303)
+                pos, sz = r[t, b, 8:10], r[t, b, 10:12]
+                x, y = pos[0] - sz[0] / 2, pos[1] - sz[1] / 2
+                w, h = sz
+                poly[t, b] = [[x, y], [x + w, y], [x + w, y + h], [x, y + h]]
+            res["polygon"], res["polygon_found"] = poly, found
+        # tr.state as the last track() would have left it
+        st.pop("polygon", None)
+        st.pop("polygon_found", None)
+        last = masks[-1]
+        st.update(target_pos=res["target_pos"][-1].copy(), target_sz=res["target_sz"][-1].copy(), score=res["score"][-1].copy(),
+                  mask=last, best_id=res["best_id"][-1].copy(), delta_yx=res["delta_yx"][-1].copy(),
+                  crop_box=[[float(v[0]), float(v[1]), int(v[2]), int(v[3])] for v in res["crop_box"][-1]], x_crop=None)
+        if fr["poly"][-1]:
+            st["polygon"], st["polygon_found"] = res["polygon"][-1].copy(), res["polygon_found"][-1].copy()
+        fr["synced"] = (st["target_pos"], st["target_sz"])            # the device holds exactly these values
+        fr["pending"], fr["masks"], fr["poly"], fr["start"] = 0, [], [], None
+        return res
+
+    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None):
+        """enqueue every frame of ``frames`` (uint8 CUDA [T,H,W,3], or [T,B,H,W,3] for per-stream frames), then collect().
+        mask_out: uint8 CUDA [T,B,H,W] to receive the masks."""
+        fr = self._fr
+        if self.state is None or fr is None:
+            raise RuntimeError("DeviceTracker.run(): init() first")
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise RuntimeError("siammask_amd.tracker runs on the MI355X only: frames must be a CUDA(HIP) tensor")
+        if frames.dim() not in (4, 5):
+            raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
+        T = int(frames.shape[0])
+        masks = None
+        if want_mask and self.model.variant != "rpn":
+            shape = (T, fr["B"], fr["H"], fr["W"])
+            if mask_out is None:
+                masks = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+            elif mask_out.dtype != torch.uint8 or not mask_out.is_cuda or not mask_out.is_contiguous() or tuple(mask_out.shape) != shape:
+                raise ValueError("mask_out must be a contiguous uint8 CUDA tensor %s" % (shape,))
+            else:
+                masks = mask_out
+        for t in range(T):
+            self.enqueue(frames[t], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[t] if masks is not None else None)
+        fr["whole"] = masks
+        return self.collect()
 
 
 def rotated_boxes(masks, target_pos, target_sz, min_area=100.0):
