@@ -99,18 +99,6 @@ constexpr size_t KS_PART_FLOATS = 8u << 20;      // 32 MB: e.g. 256 tiles x 4 pa
 constexpr int KS_CNT = 8192;
 constexpr size_t DEC_SCRATCH_PER_STREAM = 8 * 8 + 64 * 8 + 8 * 4 + 4;     // decode_kernel's cross-workgroup scratch
 
-// The forms of the pipelined step that measured slower than the default (a cross-queue event join, hipStreamWaitValue32, eager launches,
-// the two other depth-2 forms; profiles/r05a/e/f/j/o_*) are A/B arms of measurement builds only: in the product library the four knobs are
-// compile-time constants, so the arms are not even compiled.
-#ifdef SMK_MEASURE
-#define PIPE_JOIN (g_tune.pipe_join)
-#define PIPE_SIG (g_tune.pipe_sig)
-#define PIPE_EAGER (g_tune.pipe_eager)
-#define PIPE_TWO_FORM (g_tune.pipe_two_form)
-#else
-constexpr int PIPE_JOIN = 1, PIPE_SIG = 2, PIPE_EAGER = 0, PIPE_TWO_FORM = 1;
-#endif
-
 static size_t esize(int dtype) { return dtype == DT_F32 ? 4 : 2; }
 
 // host-side packing of ONE weight tensor [Cout][Cin][k][k] (already scaled) into rows of a
@@ -226,10 +214,11 @@ static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, 
 // ---------------------------------------------------------------------------------------------
 
 typedef std::tuple<int, int, int, std::vector<const void *>> GraphKey;
+constexpr long MI355X_CUS = 256;     // what host-only planning (smk_host_plan_conv) plans for
 
 struct smk_ctx {
     int device = 0, dtype = DT_F32, variant = SMK_VARIANT_SHARP, maxB = 1;
-    long ncu = 256;           // CUs of the device (plan_conv); 256, the MI355X's, where there is none (smk_host_plan_conv)
+    long ncu = MI355X_CUS;    // CUs of the device (plan_conv)
     std::map<std::string, HostTensor> host_w;
     bool finalized = false;
     int template_B = 0;       // batch of the cached template (0 = none)
@@ -260,15 +249,10 @@ struct smk_ctx {
     int *seq_err_hdev = nullptr;     // device address of seq_err_host
     int seq_fail = 0;                // last failure code taken from the flag (sticky, reported by smk_seq_status)
     bool seq_pending = false;        // a sequence launch has been enqueued since the flag was last checked behind a synchronisation
-    bool cap_has_seq = false;        // the graph being captured contains a sequence launch
     std::map<GraphKey, bool> graph_has_seq;
     unsigned long long *seq_clk = nullptr, *seq_clk2 = nullptr;   // SMK_SEQ_CLK stamps (measurement aid), per context
     int seq_grid = 0;                // workgroups of a sequence launch (= CUs) when the placement check passed, else 0
     bool seq_on = false;             // run_conv records into seq instead of launching
-    // fused frame step: the mask head is handed to the Refine chain launch (chain_mask_kernel) instead of its own launch
-    bool defer_mask_req = false, have_deferred_mask = false;
-    ConvParams deferred_mask;
-    double deferred_mask_flop = 0.0, deferred_mask_bytes = 0.0;
     struct SeqList {                 // what run_conv recorded while seq_on (conv_plan.h SeqRec), algorithmic work summed over it
         std::vector<SeqRec> rec;
         double flop = 0.0, bytes = 0.0;
@@ -281,9 +265,6 @@ struct smk_ctx {
     int ring_rows = 0;
     int *ring_cursor = nullptr;      // device [4]: [0] frames committed, [1] arrival counter of the launch that advances it; [2] / [3] the same for the box
                                      // rows alone while frame steps are pipelined two deep (decode then runs ahead of the previous frame's chain)
-    bool ring_in_step = false;       // smk_step is recording: decode / the Refine chain take the ring writes with them
-    bool ring_step_refine = false;   // ... and a Refine launch follows the decode launch
-    bool ring_ref_folded = false;    // the chain launch took the fp16 logits + the cursor
 
     // decode (tools/test.py:205-254 on device)
     float anchor_w[8] = {104, 88, 64, 40, 32}, anchor_h[8] = {32, 40, 64, 80, 96};   // utils/anchors.py:40-50
@@ -304,8 +285,6 @@ struct smk_ctx {
     std::vector<ProfRec> prof_recs;
     std::vector<hipEvent_t> prof_pool;
     size_t prof_pool_next = 0;
-    bool mask_join_pending = false;
-    bool prof_split_l1 = false;      // (reserved) per-layer attribution of layer1 while profiling
 
     // software-pipelined frame steps (smk_set_pipeline): the Refine / mask tail of frame f runs on pipe_stream beside the
     // stem + layer1 launches of frame f + 1, which write the OTHER copy of p0 / p1 (the only tensors both sides touch)
@@ -319,19 +298,37 @@ struct smk_ctx {
     bool tail_pending = false;       // a tail has been enqueued on pipe_stream and nothing has been ordered behind it yet
     hipEvent_t tail_ev = nullptr;
     int ring_batch = 0;              // batch the result ring was sized for (smk_set_result_ring)
-    bool pipe_tail_has_mask = false; // (A/B knob pipe_eager bit 1) mid's capture handed the mask head to the tail
     unsigned *pipe_cnt = nullptr;    // device [16] u32: [0] semaphore "tails completed" (starts at 1), [2] semaphore "main parts completed",
                                      // [4] / [5] arrival counters of decode's streams / chain_mask's workgroups, [8] "this step's main part is running" (arms the tail gate's clock; misc_kernels.hip pipe_*)
-    bool pipe_two = false;           // (recording a depth-2 pipelined step) decode keeps its own ring cursor
-    bool pipe_corr_sem = false;      // ... or corr_head's first workgroup does (form 2)
-    bool pipe_seq_exit = false, pipe_seq_exit_done = false;   // ... and the sequence launch raises the "chip is free" semaphore when it leaves
     bool tail2_pending = false;      // depth 2: the second part of the last frame's tail (chain + mask head) has not been launched yet
     GraphKey tail2_key, tail2_gated_key;   // ... its graph without / with the gate (flush form / the form the next step launches)
     int wave_prio_now = 0;           // (recording a pipelined step's main part) the wave priority its launches carry: smk_tune main_prio
-    bool pipe_gate_late = false;     // (recording a pipelined step) seq_track launches the main gate in front of the heads
-    bool pipe_mark_fold = false, pipe_tail_fold = false, pipe_done_folded = false;   // (while a pipelined step's parts are being recorded)
-    unsigned *pipe_sig = nullptr;    // signal memory: main parts completed (pipe_mark_kernel); the tail's hipStreamWaitValue32 target
-    unsigned pipe_sig_n = 0;         // main parts enqueued since the counter was zeroed
+};
+
+// One recording of a frame step or of a part of one (a serial step, a pipelined step's main part, one part of its tail): made by
+// whoever records it and passed down the path by reference.  The serial entry points pass a fresh one.
+struct StepRec {
+    // what the recorder asks of the launches below it
+    bool gate_late = false;          // pipelined step: seq_track launches the main gate in front of the heads
+    bool mark_fold = false;          // pipelined step: the decode launch carries the main part's completion mark (the tail's gate waits for it)
+    bool two = false;                // depth-2 pipelined step: the tail's first part launches the mask head
+    bool seq_exit = false;           // ... and the sequence's last launch raises the "chip is free" semaphore when it leaves
+    bool tail_fold = false;          // pipelined step: a chain_mask launch ends the tail, its last workgroup is the "done" mark
+    bool defer_mask = false;         // the mask head is handed to the Refine chain launch (chain_mask_kernel) instead of its own launch
+    bool ring = false;               // result ring: decode / the Refine chain take the ring writes with them
+    bool ring_refine = false;        // ... and a Refine launch follows the decode launch
+    // what those launches report back
+    bool seq_exit_done = false;      // a sequence launch took the exit semaphore
+    bool done_folded = false;        // the chain_mask launch took the tail's "done" mark
+    bool ring_ref_folded = false;    // the chain launch took the fp16 logits + the ring cursor
+    bool has_seq = false;            // a sequence or gate launch was recorded (both report through the sequence failure flag)
+    bool mask_join_pending = false;  // the mask head runs on a side stream that the end of the step joins
+    // handed over from the main part (seq_track) to the tail (seq_refine, step_tail): the deferred mask head
+    struct DeferredMask {
+        bool have = false;
+        ConvParams p = {};
+        double flop = 0.0, bytes = 0.0;
+    } deferred_mask;
 };
 
 struct ProfScope {
@@ -733,7 +730,16 @@ static Act act(smk_ctx *c, const char *name, int H, int W, int C) {
 // ---------------------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------------------
-static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, const Act *out, int B,
+// what conv_params takes from its surroundings: a context's (conv_env) or a context-free entry point's own
+struct ConvEnv {
+    int dtype = DT_F32, device = 0;      // device < 0: host-side walk (CPU tests)
+    float *ks_part = nullptr;            // split-K scratch (KS_PART_FLOATS) and arrival counters (KS_CNT), or none
+    unsigned *ks_cnt = nullptr;
+    int wave_prio = 0;
+};
+static ConvEnv conv_env(const smk_ctx *c) { return {c->dtype, c->device, c->ks_part, c->ks_cnt, c->wave_prio_now}; }
+
+static int conv_params(const ConvEnv &env, const PackedConv &pc, const Act &in, const Act *out, int B,
                        const ConvOpt &o, ConvParams &p) {
     memset(&p, 0, sizeof(p));
     p.in = in.p;
@@ -799,9 +805,9 @@ static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, co
     // (measured, profiles/r02_tail_ab.txt: B=64 -1.3 % on the step, B=8 / B=1 within noise -> large launches only)
     if (o.nchw_out && g_tune.nchw_tn_major && p.xcd_mode == 1 && p.M >= 20000 && (double)p.M * p.N * 4 >= 4.0e6) p.xcd_mode = 2;
     p.prio = g_tune.prio;
-    p.wave_prio = c->wave_prio_now;
+    p.wave_prio = env.wave_prio;
     {
-        const double ib = (double)B * in.H * in.W * in.C * esize(c->dtype), wb = (double)pc.rows * pc.Kpad * esize(c->dtype);
+        const double ib = (double)B * in.H * in.W * in.C * esize(env.dtype), wb = (double)pc.rows * pc.Kpad * esize(env.dtype);
         p.buf_lds = (g_tune.buf_lds && ib < 2.0e9 && wb < 2.0e9) ? 1 : 0;
         p.a_stage = g_tune.a_stage;
         p.res_nt = g_tune.res_nt;
@@ -813,8 +819,8 @@ static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, co
     for (int sh = 0; sh < 16; ++sh)
         if ((1 << sh) == p.Ci) p.ci_shift = sh;
     p.kw_magic = 65536 / p.kw + 1;                        // exact for tap < 4096 and kw <= 15
-    p.zero = c->device >= 0 ? zero_page() : nullptr;      // device < 0: host-side walk (CPU tests)
-    if (c->device >= 0 && !p.zero) return fail(SMK_E_HIP, "could not allocate the zero page");
+    p.zero = env.device >= 0 ? zero_page() : nullptr;
+    if (env.device >= 0 && !p.zero) return fail(SMK_E_HIP, "could not allocate the zero page");
     if (o.res) {
         p.res = o.res->p;
         p.res_Cs = o.res->C;
@@ -823,10 +829,10 @@ static int conv_params(const smk_ctx *c, const PackedConv &pc, const Act &in, co
         if (pc.x3) p.x3_res = o.res->C / X3_PLANES;
     }
     p.ksplit = 1;
-    p.ks_part = c->ks_part;
-    p.ks_cnt = c->ks_cnt;
-    p.ks_part_cap = c->ks_part ? KS_PART_FLOATS : 0;
-    p.ks_cnt_cap = c->ks_cnt ? KS_CNT : 0;
+    p.ks_part = env.ks_part;
+    p.ks_cnt = env.ks_cnt;
+    p.ks_part_cap = env.ks_part ? KS_PART_FLOATS : 0;
+    p.ks_cnt_cap = env.ks_cnt ? KS_CNT : 0;
     return 0;
 }
 
@@ -895,7 +901,7 @@ static void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, co
     }
 }
 
-static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
+static int seq_flush(smk_ctx *c, StepRec &rec, int B, hipStream_t s) {
     const size_t n = c->seq.rec.size();
     if (!n) return 0;
     auto buf = [c](const char *name) -> const void * { auto it = c->buf.find(name); return it == c->buf.end() ? nullptr : it->second; };
@@ -915,8 +921,8 @@ static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
         a.err = c->seq_err;
         a.err_host = c->seq_err_hdev;
         // pipelined step, depth 2: the last launch of the list tells the previous frame's chain / mask-head launch that the chip is free
-        a.exit_sem = (c->pipe_seq_exit && i0 + SEQ_MAX >= n) ? c->pipe_cnt + 7 : nullptr;
-        if (a.exit_sem) c->pipe_seq_exit_done = true;
+        a.exit_sem = (rec.seq_exit && i0 + SEQ_MAX >= n) ? c->pipe_cnt + 7 : nullptr;
+        if (a.exit_sem) rec.seq_exit_done = true;
         const SeqRec *r = c->seq.rec.data() + i0;
         for (int i = 0; i < a.n; ++i) a.L[i] = r[i].L;
         const char *ck = getenv("SMK_SEQ_CLK");
@@ -935,7 +941,7 @@ static int seq_flush(smk_ctx *c, int B, hipStream_t s) {
         ps.ext_bytes(seq_fabric_bytes(a.L, a.n, B, buf("p2")));          // (p2: Refine reads it later)
         if (launch_conv_seq(a, c->seq_grid, s))
             return fail(SMK_E_HIP, "launch of %s failed: %s", idn, hipGetErrorString(hipGetLastError()));
-        c->seq_pending = c->cap_has_seq = true;          // (smk_seq_sync_check: the flag is worth a look once this has drained)
+        c->seq_pending = rec.has_seq = true;             // (smk_seq_sync_check: the flag is worth a look once this has drained)
         if (want_clk) {                                  // per-layer spans of (team 0, slot 0), eager mode only
             unsigned long long h[2 * SEQ_MAX + 1], h2[(12 + 32) * SEQ_MAX];
             HIPCHK(hipStreamSynchronize(s));
@@ -965,7 +971,6 @@ static int seq_health(smk_ctx *c) {
         const unsigned init[16] = {1u, 0u};
         (void)hipMemcpy(c->pipe_cnt, init, sizeof(init), hipMemcpyHostToDevice);
     }
-    if (c->pipe_sig) { (void)hipMemset(c->pipe_sig, 0, 8); c->pipe_sig_n = 0; }
     *(volatile int *)c->seq_err_host = 0;
     (void)hipMemset(c->seq_err, 0, sizeof(int));
     (void)hipMemset(c->seq_bar, 0, 8 * 32 * sizeof(unsigned));
@@ -1036,14 +1041,15 @@ static int launch_plan(const ConvPlan &pl, ConvBatch &cb, const void *w_halo, in
     return 0;
 }
 
+// rec: the step record of a caller that may be recording a sequence (run_backbone); a flush fills it
 static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, int B, const ConvOpt &o,
-                    hipStream_t s) {
+                    hipStream_t s, StepRec *rec = nullptr) {
     auto it = c->conv.find(id);
     if (it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv %s not packed", id);
     ConvBatch cb;
     cb.n = 1;
     ConvParams &p = cb.p[0];
-    CHK(conv_params(c, it->second, in, out, B, o, p));
+    CHK(conv_params(conv_env(c), it->second, in, out, B, o, p));
     double flop = 0.0, bytes = 0.0;
     conv_work(it->second, p, B, c->dtype, flop, bytes);
     if (c->seq_on) {
@@ -1054,7 +1060,8 @@ static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, i
             c->seq.bytes += bytes;
             return 0;
         }
-        CHK(seq_flush(c, B, s));               // not eligible: keep program order
+        if (!rec) return fail(SMK_E_STATE, "internal: conv %s recorded into a sequence without a step record", id);
+        CHK(seq_flush(c, *rec, B, s));         // not eligible: keep program order
     }
     const ConvPlan pl = plan_conv(p, o, it->second, c->dtype, B, c->ncu);
     ProfScope ps(c, s, id, plan_kernel_name(pl, c->dtype, p.out_mode), flop, bytes);
@@ -1067,12 +1074,12 @@ static int run_conv(smk_ctx *c, const char *id, const Act &in, const Act *out, i
 // removes launch boundaries and fills the chip when the single problems are small
 struct ConvJob { const char *id; const Act *in; const Act *out; ConvOpt o; };
 
-static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, int lead, hipStream_t s) {
+static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, int lead, hipStream_t s, StepRec *rec = nullptr) {
     if (jobs.empty() || (int)jobs.size() > CONV_BATCH_MAX) return fail(SMK_E_ARG, "internal: bad conv job count");
     if (c->seq_on) {
         // independent members: no team barrier between them, one after the last
         const size_t n0 = c->seq.rec.size();
-        for (auto &j : jobs) CHK(run_conv(c, j.id, *j.in, j.out, B, j.o, s));
+        for (auto &j : jobs) CHK(run_conv(c, j.id, *j.in, j.out, B, j.o, s, rec));
         if (c->seq.rec.size() == n0 + jobs.size())
             for (size_t i = n0; i + 1 < c->seq.rec.size(); ++i) c->seq.rec[i].L.sync = 0;
         return 0;
@@ -1086,7 +1093,7 @@ static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, in
     for (int i = 0; i < cb.n; ++i) {
         auto it = c->conv.find(jobs[i].id);
         if (it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv %s not packed", jobs[i].id);
-        CHK(conv_params(c, it->second, *jobs[i].in, jobs[i].out, B, jobs[i].o, cb.p[i]));
+        CHK(conv_params(conv_env(c), it->second, *jobs[i].in, jobs[i].out, B, jobs[i].o, cb.p[i]));
         const int bm = halo_choice(it->second, cb.p[i], jobs[i].o, kdtype(c->dtype));
         if (bm) ++n_halo;
         if (bm == 64 || (bm == 0 && cb.p[i].kh == 3)) split_for_halo = false;
@@ -1133,7 +1140,7 @@ static int run_conv_pair(smk_ctx *c, const char *id3, const Act &in3, const Act 
     auto i3 = c->conv.find(id3), i1 = c->conv.find(id1);
     if (i3 == c->conv.end() || i1 == c->conv.end() || o1.win || o1.ups || o1.pos) return 1;
     ConvParams p3, p1;
-    if (conv_params(c, i3->second, in3, &out3, B, o3, p3) || conv_params(c, i1->second, out3, &out1, B, o1, p1)) return 1;
+    if (conv_params(conv_env(c), i3->second, in3, &out3, B, o3, p3) || conv_params(conv_env(c), i1->second, out3, &out1, B, o1, p1)) return 1;
     SeqLayer L[2];
     if (!seq_layer_from(p3, c->dtype, L[0], -1) || !seq_layer_from(p1, c->dtype, L[1], -1)) return 1;
     int code = 0;
@@ -1161,8 +1168,8 @@ enum { PH_FRONT = 1, PH_BACK = 2, PH_ALL = 3 };
 // and in front of the sequence's flush, so that it becomes the persistent launch's last record (round 6, smk_tune "seq_search"): no kernel
 // boundary, no cold start, the weights behind the team's own L2 -- the register-fed 128 x 256 tiles run at 0.58 us per K tile inside the
 // sequence where the stand-alone launch needs 0.9.  *search_done tells the caller that conv_search has been issued (recorded or launched).
-static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s, int phase = PH_ALL, int search_nb = 0, int search_nbt = 0,
-                        bool *search_done = nullptr) {
+static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, hipStream_t s, int phase = PH_ALL, int search_nb = 0,
+                        int search_nbt = 0, bool *search_done = nullptr) {
     // DT_F16X3: the trunk's tensors are stored as [hi | lo] planes -- twice the channels (smk_kernels.h)
     auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
     const int s0 = (S - 7) / 2 + 1;          // conv1 7x7 s2 p0
@@ -1239,7 +1246,7 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
             const int dil = (st == 2 && b > 0) ? 2 : 1;
             const int pad2 = dil > 1 ? dil : 2 - stride;
             const int so = stride == 2 ? s2 : sp;
-            if (st == 0 && c->dtype == DT_F16 && g_tune.l1_fused && !c->seq_on && !c->prof_split_l1) {
+            if (st == 0 && c->dtype == DT_F16 && g_tune.l1_fused && !c->seq_on) {
                 // layer1: the whole Bottleneck in one launch, weights in registers, intermediates in LDS (l1_block.hip)
                 auto f1 = c->conv.find(id + "c1"), f2 = c->conv.find(id + "c2"), f3 = c->conv.find(id + "c3");
                 auto fd = c->conv.find(id + "ds");
@@ -1296,17 +1303,17 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
                 if (par) {
                     hipStream_t sd = c->side[0];
                     CHK(stream_dep(c, s, sd));
-                    CHK(run_conv(c, id_ds.c_str(), cur, &r, B, od, sd));
-                    CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s));
+                    CHK(run_conv(c, id_ds.c_str(), cur, &r, B, od, sd, &rec));
+                    CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s, &rec));
                 } else {
-                    CHK(run_conv_jobs(c, {{id_ds.c_str(), &cur, &r, od}, {id_c1.c_str(), &cur, &t1, o1}}, B, 0, s));
+                    CHK(run_conv_jobs(c, {{id_ds.c_str(), &cur, &r, od}, {id_c1.c_str(), &cur, &t1, o1}}, B, 0, s, &rec));
                 }
                 res = r;
             } else if (!c1_done) {
-                CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s));
+                CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s, &rec));
             }
             c1_done = false;
-            CHK(run_conv(c, (id + "c2").c_str(), t1, &t2, B, o2, s));
+            CHK(run_conv(c, (id + "c2").c_str(), t1, &t2, B, o2, s, &rec));
             if (b == 0 && par) CHK(stream_dep(c, c->side[0], s));
             const bool last = b == STAGE_BLOCKS[st] - 1;
             const char *oname = last ? (st == 0 ? "p1" : st == 1 ? "p2" : AN[2]) : ((b & 1) ? BN[st] : AN[st]);
@@ -1334,7 +1341,7 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
                     if (paired == 0) adjust_done = true;
                 }
             }
-            if (paired == 1) CHK(run_conv(c, (id + "c3").c_str(), t2, &out, B, o3, s));
+            if (paired == 1) CHK(run_conv(c, (id + "c3").c_str(), t2, &out, B, o3, s, &rec));
             cur = out;
             sp = so;
         }
@@ -1344,26 +1351,26 @@ static int run_backbone(smk_ctx *c, const float *x, int B, int S, hipStream_t s,
     if (sp < 20) {
         Act zf = act(c, "zf", sp - 8, sp - 8, X(256));
         oa.win = true; oa.Hl = oa.Wl = sp - 8; oa.org_y = oa.org_x = 4;
-        CHK(run_conv(c, "adjust", cur, &zf, B, oa, s));
+        CHK(run_conv(c, "adjust", cur, &zf, B, oa, s, &rec));
     } else if (!adjust_done) {
         Act se = act(c, "search", sp, sp, X(256));
-        CHK(run_conv(c, "adjust", cur, &se, B, oa, s));
+        CHK(run_conv(c, "adjust", cur, &se, B, oa, s, &rec));
     }
     if (c->seq_on && search_nb > 0 && sp >= 20 && g_tune.seq_search && c->seq.rec.size() < (size_t)SEQ_MAX) {
         Act se = act(c, "search", sp, sp, X(256));
         Act xs = act(c, "xs", sp - 2, sp - 2, X(256 * search_nbt));
         ConvOpt o; o.relu = 1; o.n_override = 256 * search_nb;
-        CHK(run_conv(c, "conv_search", se, &xs, B, o, s));         // (not eligible for the sequence: flushed + launched, still done)
+        CHK(run_conv(c, "conv_search", se, &xs, B, o, s, &rec));         // (not eligible for the sequence: flushed + launched, still done)
         if (search_done) *search_done = true;
     }
-    if (c->seq_on) CHK(seq_flush(c, B, s));
+    if (c->seq_on) CHK(seq_flush(c, rec, B, s));
     c->last_B = B; c->last_S = S;
     return 0;
 }
 
-static int seq_template(smk_ctx *c, const float *z, int B, hipStream_t s) {
+static int seq_template(smk_ctx *c, StepRec &rec, const float *z, int B, hipStream_t s) {
     auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
-    CHK(run_backbone(c, z, B, 127, s));
+    CHK(run_backbone(c, rec, z, B, 127, s));
     const int nb = nbranch(c);
     Act zf = act(c, "zf", 7, 7, X(256));
     Act zk = act(c, "zk", 5, 5, X(256 * nb));
@@ -1375,24 +1382,24 @@ static int seq_template(smk_ctx *c, const float *z, int B, hipStream_t s) {
 // defer_mask_join: the 63x63 mask head (HBM-write bound, nothing on the device reads it) is forked
 // to a side stream and only joined by the caller at the end of the frame step, so that it runs
 // beside the small decode / Refine launches instead of in front of them
-static int seq_track(smk_ctx *c, const float *x, int B, int flags, float *cls, float *loc, float *mask,
+static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags, float *cls, float *loc, float *mask,
                      hipStream_t s, bool defer_mask_join = false, int phase = PH_ALL) {
     auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
     const bool x3 = c->dtype == DT_F16X3;
     const int nbt = nbranch(c);                                   // branches laid out in the buffers
     const int nb = (flags & SMK_TRACK_MASK) ? nbt : 2;            // branches computed
     bool search_done = false;
-    CHK(run_backbone(c, x, B, 255, s, phase, nb, nbt, &search_done));
+    CHK(run_backbone(c, rec, x, B, 255, s, phase, nb, nbt, &search_done));
     Act se = act(c, "search", 31, 31, X(256));
     Act xs = act(c, "xs", 29, 29, X(256 * nbt));
     ConvOpt o; o.relu = 1; o.n_override = 256 * nb;               // conv_search x nb as one N-fused GEMM
     if (!search_done) CHK(run_conv(c, "conv_search", se, &xs, B, o, s));
-    if (c->pipe_gate_late) {
+    if (rec.gate_late) {
         // pipelined step without the persistent sequence: nothing up to here writes what the previous frame's tail reads (p0 / p1 / p2
         // exist twice), so the gate sits HERE -- the tail has the whole backbone of this frame to finish beside -- and the heads below
         // (corr, head0, the decoded position) are the first writers it protects
         if (launch_pipe_gate(c->pipe_cnt, c->seq_err, c->seq_err_hdev, s, 0, nullptr, c->pipe_cnt + 8)) return fail(SMK_E_HIP, "pipe_gate launch failed");
-        c->cap_has_seq = true;
+        rec.has_seq = true;
     }
     Act corr = act(c, "corr", 25, 25, X(256 * nbt));
     Act h0 = act(c, "head0", 25, 25, X(256 * nbt));
@@ -1415,7 +1422,6 @@ static int seq_track(smk_ctx *c, const float *x, int B, int flags, float *cls, f
             hp.w3_bytes[0] = (unsigned)((size_t)ic->second.rows * ic->second.Kpad * 2);
             hp.w3_bytes[1] = (unsigned)((size_t)il->second.rows * il->second.Kpad * 2);
             hp.B = B; hp.nb = nb; hp.Cs = 256 * nbt;
-            if (c->pipe_corr_sem) { hp.start_sem = c->pipe_cnt + 7; c->pipe_seq_exit_done = true; }
             const double flop = 2.0 * B * nb * 256.0 * 625 * 25 + 2.0 * B * nb * 625.0 * 256 * 256 + 2.0 * B * 625.0 * 256 * 30;
             const double bytes = (double)B * nb * 256.0 * (29 * 29 + 25 + 2 * 625) * 2 + 3.0 * 256 * 256 * 2 + (double)B * 30 * 625 * 4;
             ProfScope ps(c, s, "dw_xcorr+head0+cls3+loc3", "corr_head", flop, bytes);
@@ -1447,19 +1453,19 @@ static int seq_track(smk_ctx *c, const float *x, int B, int flags, float *cls, f
     }
     if (want_mask) {
         ConvOpt om; om.nchw_out = mask; om.cin_off = x3 ? 2 * X3_PLANES * 256 : 512;      // (x3: plain fp16 pack on the hi plane of the mask branch)
-        if (c->defer_mask_req && !par) {
+        if (rec.defer_mask && !par) {
             // handed to seq_refine: it runs inside the chain launch, beside the (B-workgroup) Refine chain
             auto it = c->conv.find("mask3");
             if (it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv mask3 not packed");
-            CHK(conv_params(c, it->second, h0, nullptr, B, om, c->deferred_mask));
-            const ConvParams &mp = c->deferred_mask;
-            c->deferred_mask_flop = 2.0 * mp.M * (double)mp.N * mp.kh * mp.kw * mp.Ci;
-            c->deferred_mask_bytes = (double)mp.M * mp.Ci * esize(c->dtype) + (double)mp.M * mp.N * 4 + (double)mp.N * mp.Ci * esize(c->dtype);
-            c->have_deferred_mask = true;
+            CHK(conv_params(conv_env(c), it->second, h0, nullptr, B, om, rec.deferred_mask.p));
+            const ConvParams &mp = rec.deferred_mask.p;
+            rec.deferred_mask.flop = 2.0 * mp.M * (double)mp.N * mp.kh * mp.kw * mp.Ci;
+            rec.deferred_mask.bytes = (double)mp.M * mp.Ci * esize(c->dtype) + (double)mp.M * mp.N * 4 + (double)mp.N * mp.Ci * esize(c->dtype);
+            rec.deferred_mask.have = true;
         } else if (defer_mask_join && !par && !c->prof && g_tune.mask_overlap && c->side[0]) {
             CHK(stream_dep(c, s, c->side[0]));
             CHK(run_conv(c, "mask3", h0, nullptr, B, om, c->side[0]));
-            c->mask_join_pending = true;
+            rec.mask_join_pending = true;
         } else {
             CHK(run_conv(c, "mask3", h0, nullptr, B, om, s));
         }
@@ -1475,7 +1481,7 @@ static int seq_track(smk_ctx *c, const float *x, int B, int flags, float *cls, f
 static bool refine_splittable(const smk_ctx *c, int B) {
     return kdtype(c->dtype) == DT_F16 && g_tune.chain && !parallel_ok(c) && g_tune.merge && (g_tune.merge == 2 || B <= g_tune.merge_max_batch);
 }
-static int seq_refine(smk_ctx *c, int B, float *out, hipStream_t s, int part = 0) {
+static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s, int part = 0) {
     const int *pos = c->pos_dev;
     // (DT_F16X3: Refine runs in plain fp16 on the hi planes of the kept trunk tensors -- channel stride 2 C, first C channels)
     auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
@@ -1557,10 +1563,10 @@ static int seq_refine(smk_ctx *c, int B, float *out, hipStream_t s, int part = 0
         rp.clk = nullptr;
         rp.ring = nullptr; rp.ring_cursor = nullptr; rp.ring_done = nullptr; rp.ring_rows = 0;
         rp.tail_sem = nullptr;
-        if (c->ring_in_step && c->ring_ref) {            // the frame's fp16 logits go to the result ring from post2 itself
+        if (rec.ring && c->ring_ref) {                   // the frame's fp16 logits go to the result ring from post2 itself
             rp.ring = (_Float16 *)c->ring_ref; rp.ring_cursor = c->ring_cursor; rp.ring_done = (unsigned *)(c->ring_cursor + 1);
             rp.ring_rows = c->ring_rows;
-            c->ring_ref_folded = true;
+            rec.ring_ref_folded = true;
         }
         // SMK_CHAIN_CLK=1 (eager runs only): print the time workgroup 0 spends in each of the nine layers
         static const bool want_clk = getenv("SMK_CHAIN_CLK") != nullptr;
@@ -1571,17 +1577,17 @@ static int seq_refine(smk_ctx *c, int B, float *out, hipStream_t s, int part = 0
             rp.clk = clk_dev;
         }
         const double cbytes = B * (2.0 * (7200 + 225 * 32 + 961 * 16 + 3721 * 4) + 4.0 * 16129) + wbytes;
-        if (c->have_deferred_mask && !rp.clk) {
+        if (rec.deferred_mask.have && !rp.clk) {
             ConvBatch cb;
             cb.n = 1;
-            cb.p[0] = c->deferred_mask;
-            ProfScope ps(c, s, "refine_chain+mask3", "chain_mask", flop + c->deferred_mask_flop, cbytes + c->deferred_mask_bytes);
-            if (c->pipe_tail_fold) rp.tail_sem = c->pipe_cnt;      // pipelined step: this launch ends the tail, its last workgroup is the "done" mark
+            cb.p[0] = rec.deferred_mask.p;
+            ProfScope ps(c, s, "refine_chain+mask3", "chain_mask", flop + rec.deferred_mask.flop, cbytes + rec.deferred_mask.bytes);
+            if (rec.tail_fold) rp.tail_sem = c->pipe_cnt;      // pipelined step: this launch ends the tail, its last workgroup is the "done" mark
             const int rc = launch_chain_mask(rp, cb, s);
             rp.tail_sem = nullptr;
             if (rc == 0) {
-                c->have_deferred_mask = false;
-                if (c->pipe_tail_fold) c->pipe_done_folded = true;
+                rec.deferred_mask.have = false;
+                if (rec.tail_fold) rec.done_folded = true;
                 return 0;
             }
             if (rc != 1) return fail(SMK_E_HIP, "chain_mask launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1643,15 +1649,13 @@ static int seq_refine(smk_ctx *c, int B, float *out, hipStream_t s, int part = 0
 // ---------------------------------------------------------------------------------------------
 // graph capture / replay
 // ---------------------------------------------------------------------------------------------
-// capture `body` into an instantiated graph under `key` (LRU-bounded cache); no launch
+// capture `body` into an instantiated graph under `key` (LRU-bounded cache); no launch.  rec: the step record `body` fills
 template <typename F>
-static int capture_graph(smk_ctx *c, const GraphKey &key, F &&body) {
+static int capture_graph(smk_ctx *c, const GraphKey &key, const StepRec &rec, F &&body) {
     if (!c->cap_stream) HIPCHK(hipStreamCreateWithFlags(&c->cap_stream, hipStreamNonBlocking));
     HIPCHK(hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal));
     const bool pend0 = c->seq_pending;
-    c->cap_has_seq = false;
     int rc = body(c->cap_stream);
-    const bool has_seq = c->cap_has_seq;
     c->seq_pending = pend0;                          // captured, not enqueued
     hipGraph_t g = nullptr;
     hipError_t e = hipStreamEndCapture(c->cap_stream, &g);
@@ -1674,7 +1678,7 @@ static int capture_graph(smk_ctx *c, const GraphKey &key, F &&body) {
         c->graph_used.erase(lru);
     }
     c->graphs.emplace(key, ex);
-    c->graph_has_seq[key] = has_seq;
+    c->graph_has_seq[key] = rec.has_seq;
     c->graph_used[key] = ++c->graph_tick;
     return 0;
 }
@@ -1689,9 +1693,9 @@ static int launch_graph(smk_ctx *c, const GraphKey &key, hipStream_t s) {
 }
 
 template <typename F>
-static int run_maybe_graph(smk_ctx *c, const GraphKey &key, hipStream_t s, F &&body) {
+static int run_maybe_graph(smk_ctx *c, const GraphKey &key, hipStream_t s, const StepRec &rec, F &&body) {
     if (!c->graph_mode || c->prof) return body(s);
-    if (c->graphs.find(key) == c->graphs.end()) CHK(capture_graph(c, key, body));
+    if (c->graphs.find(key) == c->graphs.end()) CHK(capture_graph(c, key, rec, body));
     return launch_graph(c, key, s);
 }
 
@@ -1707,11 +1711,9 @@ static int pipe_reset_counters(smk_ctx *c) {
     if (!c->pipe_cnt) return 0;
     unsigned init[16] = {1u, 0u};
     HIPCHK(hipMemcpy(c->pipe_cnt, init, sizeof(init), hipMemcpyHostToDevice));
-    if (c->pipe_sig) { HIPCHK(hipMemset(c->pipe_sig, 0, 8)); c->pipe_sig_n = 0; }
     return 0;
 }
 
-static int launch_graph(smk_ctx *c, const GraphKey &key, hipStream_t s);
 // depth-2 pipelining: the second part of the last frame's tail waits for a next frame that may never come -- whoever needs the
 // results (or is about to drop the graphs) launches it without its gate
 static int pipe_flush(smk_ctx *c) {
@@ -1844,7 +1846,6 @@ int smk_destroy(smk_ctx *c) {
     for (auto &e : c->pipe_ev) hipEventDestroy(e);
     if (c->pipe_stream) hipStreamDestroy(c->pipe_stream);
     if (c->pipe_cnt) hipFree(c->pipe_cnt);
-    if (c->pipe_sig) hipFree(c->pipe_sig);
     delete c;
     return 0;
 }
@@ -2045,7 +2046,8 @@ int smk_template(smk_ctx *c, const float *z, int B, void *stream) {
     CHK(pipe_join(c, s, true));
     c->parity_now = c->last_parity = 0;
     GraphKey key{0, B, 0, {z}};
-    int rc = run_maybe_graph(c, key, s, [&](hipStream_t st) { return seq_template(c, z, B, st); });
+    StepRec rec;
+    int rc = run_maybe_graph(c, key, s, rec, [&](hipStream_t st) { return seq_template(c, rec, z, B, st); });
     if (rc) return rc;
     c->template_B = B;
     c->track_B = 0;
@@ -2069,7 +2071,8 @@ int smk_track(smk_ctx *c, const float *x, int B, int flags, float *cls, float *l
     CHK(pipe_join(c, s, true));
     c->parity_now = c->last_parity = 0;
     GraphKey key{1, B, flags, {x, cls, loc, mask}};
-    int rc = run_maybe_graph(c, key, s, [&](hipStream_t st) { return seq_track(c, x, B, flags, cls, loc, mask, st); });
+    StepRec rec;
+    int rc = run_maybe_graph(c, key, s, rec, [&](hipStream_t st) { return seq_track(c, rec, x, B, flags, cls, loc, mask, st); });
     if (rc) return rc;
     c->track_B = (flags & SMK_TRACK_MASK) ? B : 0;
     return 0;
@@ -2093,7 +2096,8 @@ int smk_refine(smk_ctx *c, const int32_t *pos, int on_device, int B, float *out,
         HIPCHK(hipMemcpyAsync(c->pos_dev, pos, sizeof(int) * 2 * B, hipMemcpyDeviceToDevice, s));
     }
     GraphKey key{2, B, c->parity_now, {out}};
-    return run_maybe_graph(c, key, s, [&](hipStream_t st) { return seq_refine(c, B, out, st); });
+    StepRec rec;
+    return run_maybe_graph(c, key, s, rec, [&](hipStream_t st) { return seq_refine(c, rec, B, out, st); });
 }
 
 // ---- smk_tune / smk_tune_get: one table --------------------------------------------------------------------------
@@ -2166,11 +2170,6 @@ static const Knob KNOBS[] = {
     {"seq_mult_max", &g_tune.seq_mult_max, ">=0", KNOB_RAW, nullptr},
     {"main_prio", &g_tune.main_prio, "0..3", KNOB_RAW, nullptr},
     {"pipe_late", &g_tune.pipe_late, "*", KNOB_BOOL, nullptr},
-    {"pipe_prio", &g_tune.pipe_prio, "0..2", KNOB_RAW, "0"},
-    {"pipe_eager", &g_tune.pipe_eager, "*", 3, "0"},
-    {"pipe_join", &g_tune.pipe_join, "*", KNOB_BOOL, "1"},
-    {"pipe_two_form", &g_tune.pipe_two_form, "0..2", KNOB_RAW, "1"},
-    {"pipe_sig", &g_tune.pipe_sig, "0..2", KNOB_RAW, "2"},
     {"seq_fused_last", &g_seq_last.pairs, nullptr, KNOB_RAW, nullptr},     // pairs fused in the sequence launched last
     {"seq_yres_last", &g_seq_last.resident, nullptr, KNOB_RAW, nullptr},
     {"seq_fused3_last", &g_seq_last.triples, nullptr, KNOB_RAW, nullptr},
@@ -2268,31 +2267,6 @@ int smk_profile_dump(smk_ctx *c, char *buf, int cap) {
 }
 
 static void fill_decode_params(smk_ctx *c, const float *cls, const float *loc, int B, const double *target_wh, int *pos_out,
-                               double *box_out, DecodeParams &p);
-
-static int seq_decode(smk_ctx *c, const float *cls, const float *loc, int B, const double *target_wh, int *pos_out,
-                      double *box_out, hipStream_t s) {
-    DecodeParams p;
-    fill_decode_params(c, cls, loc, B, target_wh, pos_out, box_out, p);
-    if (c->ring_in_step && c->ring_box && box_out) {     // result ring: the box goes to the ring from the decode launch itself
-        p.ring_box = c->ring_box; p.ring_cursor = c->ring_cursor; p.ring_done = (unsigned *)(c->ring_cursor + 1);
-        p.ring_rows = c->ring_rows; p.ring_advance = 1;
-        if (c->ring_step_refine) {
-            // A Refine launch follows and commits the frame (cursor [0]).  With frame steps pipelined two deep this launch runs BEFORE the
-            // previous frame's chain has done so, so the box rows follow their own cursor ([2], arrivals [3]) in every mode; both cursors
-            // advance once per frame whatever mix of step forms a caller uses.
-            p.ring_cursor = c->ring_cursor + 2; p.ring_done = (unsigned *)(c->ring_cursor + 3);
-        } else {
-            p.ring_also = c->ring_cursor + 2;          // no Refine launch: this one commits the frame and keeps the box cursor level
-        }
-    }
-    if (c->pipe_mark_fold) { p.mark = c->pipe_cnt + 2; p.mark_arrived = c->pipe_cnt + 4; }     // pipelined step: the tail's gate waits for this launch
-    ProfScope ps(c, s, "decode", "decode", 0.0, (double)B * 30 * 625 * 4);
-    if (launch_decode(p, s)) return fail(SMK_E_HIP, "decode launch failed");
-    return 0;
-}
-
-static void fill_decode_params(smk_ctx *c, const float *cls, const float *loc, int B, const double *target_wh, int *pos_out,
                                double *box_out, DecodeParams &p) {
     memset(&p, 0, sizeof(p));
     p.cls = cls; p.loc = loc; p.target_wh = target_wh; p.window = c->window_dev;
@@ -2307,6 +2281,28 @@ static void fill_decode_params(smk_ctx *c, const float *cls, const float *loc, i
     p.B = B; p.A = 5; p.S = 25; p.stride = c->anchor_stride;
     for (int i = 0; i < 5; ++i) { p.anchor_w[i] = c->anchor_w[i]; p.anchor_h[i] = c->anchor_h[i]; }
     p.penalty_k = c->penalty_k; p.window_influence = c->window_influence;
+}
+
+static int seq_decode(smk_ctx *c, const StepRec &rec, const float *cls, const float *loc, int B, const double *target_wh, int *pos_out,
+                      double *box_out, hipStream_t s) {
+    DecodeParams p;
+    fill_decode_params(c, cls, loc, B, target_wh, pos_out, box_out, p);
+    if (rec.ring && c->ring_box && box_out) {            // result ring: the box goes to the ring from the decode launch itself
+        p.ring_box = c->ring_box; p.ring_cursor = c->ring_cursor; p.ring_done = (unsigned *)(c->ring_cursor + 1);
+        p.ring_rows = c->ring_rows; p.ring_advance = 1;
+        if (rec.ring_refine) {
+            // A Refine launch follows and commits the frame (cursor [0]).  With frame steps pipelined two deep this launch runs BEFORE the
+            // previous frame's chain has done so, so the box rows follow their own cursor ([2], arrivals [3]) in every mode; both cursors
+            // advance once per frame whatever mix of step forms a caller uses.
+            p.ring_cursor = c->ring_cursor + 2; p.ring_done = (unsigned *)(c->ring_cursor + 3);
+        } else {
+            p.ring_also = c->ring_cursor + 2;          // no Refine launch: this one commits the frame and keeps the box cursor level
+        }
+    }
+    if (rec.mark_fold) { p.mark = c->pipe_cnt + 2; p.mark_arrived = c->pipe_cnt + 4; }     // pipelined step: the tail's gate waits for this launch
+    ProfScope ps(c, s, "decode", "decode", 0.0, (double)B * 30 * 625 * 4);
+    if (launch_decode(p, s)) return fail(SMK_E_HIP, "decode launch failed");
+    return 0;
 }
 
 int smk_set_decode_params(smk_ctx *c, const float *anchor_wh, int n_anchor, int stride, double penalty_k,
@@ -2332,62 +2328,50 @@ int smk_decode(smk_ctx *c, const float *cls, const float *loc, int B, const doub
     if (B < 1 || B > c->maxB) return fail(SMK_E_ARG, "smk_decode: batch %d not in [1,%d]", B, c->maxB);
     HIPCHK(hipSetDevice(c->device));
     CHK(pipe_join(c, (hipStream_t)stream, true));     // (a tail in flight reads the ctx-internal position)
-    return seq_decode(c, cls, loc, B, target_wh, pos_out ? pos_out : c->pos_dev, box_out, (hipStream_t)stream);
+    return seq_decode(c, StepRec(), cls, loc, B, target_wh, pos_out ? pos_out : c->pos_dev, box_out, (hipStream_t)stream);
+}
+
+// The record of a frame step, or of one of its parts, with the result ring's asks (smk_set_result_ring): the decode launch writes
+// the box row, the Refine chain launch the fp16 logits and advances the cursor; only a Refine that does NOT end in the chain
+// kernel (fp32, smk_tune chain = 0) needs the stand-alone commit launch for its logits (step_tail)
+static StepRec step_rec(const smk_ctx *c, const float *refine_out) {
+    StepRec rec;
+    rec.ring = c->ring_rows > 0;
+    rec.ring_refine = refine_out != nullptr && c->ring_ref != nullptr;
+    return rec;
 }
 
 // the part of a frame step that feeds the NEXT frame (its crop depends on the decoded box only, tools/test.py:240-250,302-308):
-// layer2 .. decode; `phase` = PH_ALL with the front end in front of it (serial step) or PH_BACK behind a front graph
-static int step_track_decode(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
+// layer2 .. decode; `phase` = PH_ALL with the front end in front of it (serial step) or PH_BACK behind the front end of a pipelined step
+static int step_track_decode(smk_ctx *c, StepRec &rec, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
                              float *mask, double *box_out, float *refine_out, hipStream_t st, bool defer_mask_join, int phase) {
     // sharp fp16 with Refine: the mask head rides in the Refine chain launch (see chain_mask_kernel)
-    c->have_deferred_mask = false;
-    c->defer_mask_req = refine_out && mask && (flags & SMK_TRACK_MASK) && !(flags & SMK_TRACK_NO_MASK_HEAD) &&
-                        kdtype(c->dtype) == DT_F16 && g_tune.chain && g_tune.chain_mask && !parallel_ok(c) &&
-                        (B <= 16 ||   // measured (profiles/r02_chain_mask_ab.txt): B=8 -6.6 %, B=1 -2 %, B=64 +1 % (64 chain workgroups)
-                         (c->pipe_two && PIPE_TWO_FORM == 1));      // depth-2 pipelining, form 1: the tail's first part launches it (step_tail)
-    int rc2 = seq_track(c, x, B, flags, cls, loc, mask, st, defer_mask_join, phase);
-    c->defer_mask_req = false;
-    CHK(rc2);
-    // result ring (smk_set_result_ring): the decode launch writes the box row, the Refine chain launch the fp16 logits and
-    // advances the cursor; only a Refine that does NOT end in the chain kernel (fp32, smk_tune chain = 0) needs the
-    // stand-alone commit launch for its logits
-    c->ring_in_step = c->ring_rows > 0;
-    c->ring_step_refine = refine_out != nullptr && c->ring_ref != nullptr;
-    c->ring_ref_folded = false;
-    int rcd = seq_decode(c, cls, loc, B, target_wh, c->pos_dev, box_out, st);
-    c->ring_in_step = false;
-    return rcd;
+    rec.defer_mask = refine_out && mask && (flags & SMK_TRACK_MASK) && !(flags & SMK_TRACK_NO_MASK_HEAD) &&
+                     kdtype(c->dtype) == DT_F16 && g_tune.chain && g_tune.chain_mask && !parallel_ok(c) &&
+                     (B <= 16 ||   // measured (profiles/r02_chain_mask_ab.txt): B=8 -6.6 %, B=1 -2 %, B=64 +1 % (64 chain workgroups)
+                      rec.two);    // depth-2 pipelining: the tail's first part launches it (step_tail)
+    CHK(seq_track(c, rec, x, B, flags, cls, loc, mask, st, defer_mask_join, phase));
+    return seq_decode(c, rec, cls, loc, B, target_wh, c->pos_dev, box_out, st);
 }
 
 // the part nothing on the device waits for (tools/test.py:257-284: the mask is an output): Refine at the decoded positions
 // (+ the 63x63 mask head when the chain launch carries it) and the ring row's logits
-static int step_tail(smk_ctx *c, int B, float *mask, double *box_out, float *refine_out, hipStream_t st, int part = 0) {
-    c->ring_in_step = c->ring_rows > 0;
-    c->ring_step_refine = refine_out != nullptr && c->ring_ref != nullptr;
-    if (part == 1 && c->have_deferred_mask && PIPE_TWO_FORM == 1) {
-        // depth-2 pipelining: the 63x63 mask head FIRST (it needs head0 only) -- as its own launch beside the next frame's front end; inside
-        // the chain launch of part 2 its 640 tiles would take the CUs from that frame's conv_search (measured: 67 instead of 32 us,
-        // profiles/r05j_depth2_chain_mask_beside_heads.txt); the chain alone (one workgroup per stream) runs there for free
-        c->have_deferred_mask = false;
+static int step_tail(smk_ctx *c, StepRec &rec, int B, float *mask, double *box_out, float *refine_out, hipStream_t st, int part = 0) {
+    auto mask3 = [&]() {                         // the handed-over mask head as its own launch
+        rec.deferred_mask.have = false;
         Act h0 = act(c, "head0", 25, 25, 256 * nbranch(c));
         ConvOpt om; om.nchw_out = mask; om.cin_off = 512;
-        CHK(run_conv(c, "mask3", h0, nullptr, B, om, st));
-    }
-    int rcd = refine_out ? seq_refine(c, B, refine_out, st, part) : 0;
-    c->ring_in_step = false;
-    CHK(rcd);
+        return run_conv(c, "mask3", h0, nullptr, B, om, st);
+    };
+    // depth-2 pipelining: the 63x63 mask head FIRST (it needs head0 only) -- as its own launch beside the next frame's front end; inside
+    // the chain launch of part 2 its 640 tiles would take the CUs from that frame's conv_search (measured: 67 instead of 32 us,
+    // profiles/r05j_depth2_chain_mask_beside_heads.txt); the chain alone (one workgroup per stream) runs there for free
+    if (part == 1 && rec.deferred_mask.have) CHK(mask3());
+    if (refine_out) CHK(seq_refine(c, rec, B, refine_out, st, part));
     if (part == 1) return 0;
-    if (c->have_deferred_mask) {                 // the chain launch did not take it (timing aid on, ...): its own launch
-        c->have_deferred_mask = false;
-        Act h0 = act(c, "head0", 25, 25, 256 * nbranch(c));
-        ConvOpt om; om.nchw_out = mask; om.cin_off = 512;
-        CHK(run_conv(c, "mask3", h0, nullptr, B, om, st));
-    }
-    if (c->mask_join_pending) {
-        c->mask_join_pending = false;
-        CHK(stream_dep(c, c->side[0], st));
-    }
-    if (c->ring_rows > 0 && refine_out && c->ring_ref && !c->ring_ref_folded) {      // (the box row was written by the decode launch)
+    if (rec.deferred_mask.have) CHK(mask3());    // the chain launch did not take it (timing aid on, ...)
+    if (rec.mask_join_pending) CHK(stream_dep(c, c->side[0], st));
+    if (c->ring_rows > 0 && refine_out && c->ring_ref && !rec.ring_ref_folded) {      // (the box row was written by the decode launch)
         RingParams rg{box_out, refine_out, nullptr, (_Float16 *)c->ring_ref, c->ring_cursor,
                       (unsigned *)(c->ring_cursor + 1), c->ring_rows, B, 127 * 127};
         ProfScope ps(c, st, "ring_commit", "ring_commit", 0.0, (double)B * (64.0 * 2 + (refine_out ? 127.0 * 127 * 6 : 0.0)));
@@ -2398,26 +2382,12 @@ static int step_tail(smk_ctx *c, int B, float *mask, double *box_out, float *ref
 
 // Pipelined frame step (smk_set_pipeline(ctx, 1)): two linear graphs per frame --
 //   caller's stream:  main(f) = stem + layer1 into copy f % 2 of p0 / p1 | gate: wait for tail(f-1) | layer2 .. heads .. decode
-//   side stream:      wait (event) for main(f) | tail(f) = Refine (+ mask head) at the decoded positions | completion mark
+//   side stream:      gate: wait for decode(f) | tail(f) = Refine (+ mask head) at the decoded positions | completion mark
 // tail(f) (small launches, low occupancy) shares the chip with the front end of frame f + 1 (bandwidth-bound); the persistent
 // layer2 .. adjust launch of frame f + 1 sits behind the gate so that it still owns every CU.  The front end of f + 1 is ordered behind
 // decode(f) by the caller's stream, as a tracker that crops frame f + 1 at the decoded box needs it.  Everything both sides touch is
-// either written behind the gate or exists twice (p0, p1).  The join is an in-stream gate kernel (misc_kernels.hip pipe_gate_kernel),
-// not an event: a cross-queue event wait on the critical path costs 15-22 us here (smk_tune "pipe_join" = 0 keeps that form --
-// three graphs, front | event wait | mid -- for the A/B).
-static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
-                                  float *mask, double *box_out, float *refine_out, hipStream_t s);
-static int step_pipelined(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
-                          float *mask, double *box_out, float *refine_out, hipStream_t s) {
-    const int rc = step_pipelined_enqueue(c, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, s);
-    if (rc) {
-        // a main part without its tail (or the reverse) would leave the semaphores unbalanced: drain and start over
-        (void)hipDeviceSynchronize();
-        (void)pipe_reset_counters(c);
-        c->tail_pending = false;
-    }
-    return rc;
-}
+// either written behind the gate or exists twice (p0, p1).  Both joins are in-stream gate kernels (misc_kernels.hip pipe_gate_kernel),
+// not events: a cross-queue event wait on the critical path costs 15-22 us here (DESIGN.md names the forms that were measured and dropped).
 static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
                                   float *mask, double *box_out, float *refine_out, hipStream_t s) {
     const int par = c->pipe_parity;
@@ -2426,111 +2396,67 @@ static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, 
     memcpy(&pk, &c->penalty_k, 8); memcpy(&wi, &c->window_influence, 8);
     const std::vector<const void *> io{x, target_wh, cls, loc, mask, box_out, refine_out, (const void *)pk, (const void *)wi};
     const bool graphs = c->graph_mode;
-    const bool gate = PIPE_JOIN != 0;
-    const bool sig = gate && PIPE_SIG == 1 && c->pipe_sig;
-    const bool tgate = gate && PIPE_SIG == 2;      // the tail's start is a gate kernel too (A/B)
     // where the main gate sits: in front of layer2 when that is the persistent sequence (it must own every CU), else in front of the
     // heads -- the first launches that write what the tail reads (smk_tune pipe_late = 0 keeps it in front of layer2 for the A/B)
-    const bool late = gate && g_tune.pipe_late && !(seq_wanted(c, B) && !parallel_ok(c));
-    // depth 2 (the persistent sequence's batches, fp16 chain path, graph replay): the tail in TWO parts.  Part 1 (window convolutions,
-    // deconv, v*.2: everything that reads the kept features and the position) runs beside the next frame's front end as before; part 2
-    // (the Refine chain + the mask head: one low-occupancy launch of ~50 us that only reads part 1's outputs and head0) waits for the
+    const bool late = g_tune.pipe_late && !(seq_wanted(c, B) && !parallel_ok(c));
+    // depth 2 (the persistent sequence's batches, fp16 chain path, graph replay): the tail in TWO parts.  Part 1 (the mask head, the
+    // window convolutions, deconv, v*.2: everything that reads head0, the kept features and the position) runs beside the next frame's
+    // front end as before; part 2 (the Refine chain: one low-occupancy launch that only reads part 1's outputs) waits for the
     // next frame's persistent launch to LEAVE and runs beside that frame's heads (conv_search / corr_head / decode leave 40-200 CUs
     // idle) -- it is launched by the NEXT smk_step, or without its gate by whatever joins the pipeline first.
-    const bool two = c->pipe_depth >= 2 && graphs && gate && tgate && !late && !sig && refine_splittable(c, B) && !PIPE_EAGER;
-    const int fl = flags | (par << 16) | (gate ? 1 << 17 : 0) | (sig ? 1 << 18 : 0) | (tgate ? 1 << 19 : 0) | (late ? 1 << 20 : 0) | (two ? 1 << 21 : 0) |
-                   ((two && PIPE_TWO_FORM == 1) ? 1 << 22 : 0) | ((two && PIPE_TWO_FORM == 2) ? 1 << 23 : 0);
-    const GraphKey kf{10, B, fl, io}, km{11, B, fl, io}, kt{12, B, fl, io}, kt2g{13, B, fl, io}, kt2n{14, B, fl, io};
-    auto front = [&](hipStream_t st) { return run_backbone(c, x, B, 255, st, PH_FRONT); };
-    auto mid = [&](hipStream_t st) { return step_track_decode(c, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, false, PH_BACK); };
-    auto main_ = [&](hipStream_t st) {
+    const bool two = c->pipe_depth >= 2 && graphs && !late && refine_splittable(c, B);
+    const int fl = flags | (par << 16) | (late ? 1 << 17 : 0) | (two ? 1 << 18 : 0);
+    const GraphKey km{11, B, fl, io}, kt{12, B, fl, io}, kt2g{13, B, fl, io}, kt2n{14, B, fl, io};
+    auto main_ = [&](hipStream_t st, StepRec &rec) {
         struct PrioScope { smk_ctx *c; PrioScope(smk_ctx *c_) : c(c_) { c->wave_prio_now = g_tune.main_prio; } ~PrioScope() { c->wave_prio_now = 0; } } prio_scope(c);
-        CHK(front(st));
+        CHK(run_backbone(c, rec, x, B, 255, st, PH_FRONT));
         if (!late) {
             if (launch_pipe_gate(c->pipe_cnt, c->seq_err, c->seq_err_hdev, st, 0, nullptr, c->pipe_cnt + 8)) return fail(SMK_E_HIP, "pipe_gate launch failed");
-            c->cap_has_seq = true;          // (the gate reports through the sequence failure flag: checked like a sequence launch)
+            rec.has_seq = true;             // (the gate reports through the sequence failure flag: checked like a sequence launch)
         }
-        c->pipe_gate_late = late;           // ... else seq_track places it in front of the heads
-        c->pipe_mark_fold = tgate;          // the decode launch's last writer is the main part's completion mark
-        c->pipe_two = two;
-        // the "chip is free for the previous frame's second tail part" semaphore: raised by the persistent launch's last leaving team
-        // (forms 0 / 1) or by corr_head's first workgroup, i.e. behind conv_search (form 2)
-        c->pipe_seq_exit = two && PIPE_TWO_FORM != 2; c->pipe_corr_sem = two && PIPE_TWO_FORM == 2; c->pipe_seq_exit_done = false;
-        const int rcm = mid(st);
-        c->pipe_corr_sem = false;
-        c->pipe_mark_fold = false;
-        c->pipe_gate_late = false;
-        c->pipe_two = false;
-        const bool exit_ok = c->pipe_seq_exit_done;
-        c->pipe_seq_exit = false;
-        CHK(rcm);
-        if (two && !exit_ok && launch_pipe_done(c->pipe_cnt + 7, st)) return fail(SMK_E_HIP, "pipe_done launch failed");   // (no sequence launch took the mark)
-        if (sig && launch_pipe_mark(c->pipe_sig, st)) return fail(SMK_E_HIP, "pipe_mark launch failed");
+        rec.gate_late = late;               // ... else seq_track places it in front of the heads
+        rec.mark_fold = true;               // the decode launch's last writer is the main part's completion mark
+        rec.two = two;
+        rec.seq_exit = two;                 // the "chip is free for the previous frame's second tail part" semaphore: raised by the persistent launch's last leaving team
+        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, false, PH_BACK));
+        if (two && !rec.seq_exit_done && launch_pipe_done(c->pipe_cnt + 7, st)) return fail(SMK_E_HIP, "pipe_done launch failed");   // (no sequence launch took the mark)
         return 0;
     };
     // part: 0 = the whole tail (depth 1), 1 / 2 = its two parts (depth 2); gated: with the gate at its head
-    auto tail = [&](hipStream_t st, int part, bool gated) {
-        if (gated && tgate && launch_pipe_gate(c->pipe_cnt + (part == 2 ? 7 : 2), c->seq_err, c->seq_err_hdev, st, 1, part == 2 ? nullptr : c->pipe_cnt + 8)) return fail(SMK_E_HIP, "pipe_gate launch failed");
-        c->pipe_tail_fold = gate && part == 0;      // a whole tail that ends in chain_mask_kernel lets its last workgroup be the "done" mark
-        c->pipe_done_folded = false;
-        const int rct = step_tail(c, B, mask, box_out, refine_out, st, part);
-        c->pipe_tail_fold = false;
-        CHK(rct);
+    auto tail = [&](hipStream_t st, StepRec &rec, int part, bool gated) {
+        if (gated && launch_pipe_gate(c->pipe_cnt + (part == 2 ? 7 : 2), c->seq_err, c->seq_err_hdev, st, 1, part == 2 ? nullptr : c->pipe_cnt + 8)) return fail(SMK_E_HIP, "pipe_gate launch failed");
+        rec.tail_fold = part == 0;          // a whole tail that ends in chain_mask_kernel lets its last workgroup be the "done" mark
+        CHK(step_tail(c, rec, B, mask, box_out, refine_out, st, part));
         // what the next frame's main gate waits for: the whole tail (depth 1) / part 1 (depth 2: part 2 of the PREVIOUS frame precedes it in this stream)
-        if (gate && part != 2 && !c->pipe_done_folded && launch_pipe_done(c->pipe_cnt, st)) return fail(SMK_E_HIP, "pipe_done launch failed");
+        if (part != 2 && !rec.done_folded && launch_pipe_done(c->pipe_cnt, st)) return fail(SMK_E_HIP, "pipe_done launch failed");
         return 0;
     };
+    // one record per recorded part; the main part's hands the mask head over to the tail part that launches it (the whole tail, or part 1 of two)
+    const StepRec tail_rec = step_rec(c, refine_out);
+    StepRec main_rec = tail_rec;
     bool have = c->graphs.count(km) && c->graphs.count(kt);
-    if (!gate) have = have && c->graphs.count(kf);
     if (two) have = have && c->graphs.count(kt2g) && c->graphs.count(kt2n);
     if (graphs && !have) {
-        // captured together: the middle part hands the mask head over to the tail at capture time
-        drop_graph(c, kf); drop_graph(c, km); drop_graph(c, kt); drop_graph(c, kt2g); drop_graph(c, kt2n);
-        if (gate) CHK(capture_graph(c, km, main_));
-        else { CHK(capture_graph(c, kf, front)); CHK(capture_graph(c, km, mid)); }
-        const bool hm = c->have_deferred_mask;
-        c->pipe_tail_has_mask = hm;
+        // captured together: the hand-over happens at capture time
+        drop_graph(c, km); drop_graph(c, kt); drop_graph(c, kt2g); drop_graph(c, kt2n);
+        CHK(capture_graph(c, km, main_rec, [&](hipStream_t st) { return main_(st, main_rec); }));
+        StepRec t = tail_rec;
+        t.deferred_mask = main_rec.deferred_mask;
+        CHK(capture_graph(c, kt, t, [&](hipStream_t st) { return tail(st, t, two ? 1 : 0, true); }));
         if (two) {
-            // (pipe_two_form 1: part 1 launches the mask head itself and part 2 is the bare chain; 0: the chain launch of part 2 carries it)
-            CHK(capture_graph(c, kt, [&](hipStream_t st) { return tail(st, 1, true); }));
-            c->have_deferred_mask = hm && PIPE_TWO_FORM != 1;
-            CHK(capture_graph(c, kt2g, [&](hipStream_t st) { return tail(st, 2, true); }));
-            c->have_deferred_mask = hm && PIPE_TWO_FORM != 1;
-            CHK(capture_graph(c, kt2n, [&](hipStream_t st) { return tail(st, 2, false); }));
-            c->have_deferred_mask = false;
-        } else {
-            CHK(capture_graph(c, kt, [&](hipStream_t st) { return tail(st, 0, true); }));
+            StepRec t2g = tail_rec, t2n = tail_rec;
+            CHK(capture_graph(c, kt2g, t2g, [&](hipStream_t st) { return tail(st, t2g, 2, true); }));
+            CHK(capture_graph(c, kt2n, t2n, [&](hipStream_t st) { return tail(st, t2n, 2, false); }));
         }
         bool ok = c->graphs.count(km) && c->graphs.count(kt);
         if (two) ok = ok && c->graphs.count(kt2g) && c->graphs.count(kt2n);
         if (!ok) return fail(SMK_E_STATE, "internal: pipelined step graphs evicted while capturing");
     }
     if (!two && c->tail2_pending) CHK(pipe_flush(c));       // (the mode changed under a pending second part: launch it now)
-    if (gate) {
-        CHK(graphs ? launch_graph(c, km, s) : main_(s));
-        if (!graphs) c->seq_pending = true;
-        // (no event wait on `s`: the gate inside main(f) is the join; tail_ev stays for the serial entry points and smk_pipeline_join)
-        c->tail_pending = false;
-    } else {
-        CHK((graphs && !(PIPE_EAGER & 1)) ? launch_graph(c, kf, s) : front(s));
-        CHK(pipe_join(c, s, true));
-        CHK(graphs ? launch_graph(c, km, s) : mid(s));
-    }
-    hipEvent_t e_dec = c->pipe_ev[c->pipe_ev_next++ % c->pipe_ev.size()];
-    hipEvent_t e_tail = c->pipe_ev[c->pipe_ev_next++ % c->pipe_ev.size()];
-    if (sig) {
-        // the side stream's command processor polls the counter the main graph's last kernel advances: nothing is enqueued on `s`
-        if (c->pipe_sig_n >= 0x7fff0000u) {                   // (every 2^31 frames: start the count over)
-            HIPCHK(hipDeviceSynchronize());
-            HIPCHK(hipMemset(c->pipe_sig, 0, 8));
-            c->pipe_sig_n = 0;
-            return fail(SMK_E_STATE, "internal: pipelined frame counter wrapped; re-submit the frame");
-        }
-        HIPCHK(hipStreamWaitValue32(c->pipe_stream, c->pipe_sig, ++c->pipe_sig_n, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    } else if (!tgate) {
-        HIPCHK(hipEventRecord(e_dec, s));
-        HIPCHK(hipStreamWaitEvent(c->pipe_stream, e_dec, 0));
-    }
+    CHK(graphs ? launch_graph(c, km, s) : main_(s, main_rec));
+    if (!graphs) c->seq_pending = true;
+    // (no event wait on `s`: the gate inside main(f) is the join; tail_ev stays for the serial entry points and smk_pipeline_join)
+    c->tail_pending = false;
     if (two) {
         // the side stream, in the order things happen on the device: [sequence of THIS frame has left] part 2 of the previous frame |
         // [decode of this frame] part 1 of this frame.  Every step takes exactly one count of the "sequence has left" semaphore: with
@@ -2541,18 +2467,30 @@ static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, 
         c->tail2_pending = true;
         c->tail2_key = kt2n;
         c->tail2_gated_key = kt2g;
-    } else if (graphs && !(PIPE_EAGER & 2)) CHK(launch_graph(c, kt, c->pipe_stream));
+    } else if (graphs) CHK(launch_graph(c, kt, c->pipe_stream));
     else {
-        // (eager: the capture-time hand-over of the mask head is replayed from the context, see step_track_decode)
-        if (graphs) c->have_deferred_mask = c->pipe_tail_has_mask;
-        CHK(tail(c->pipe_stream, 0, true));
+        StepRec t = tail_rec;
+        t.deferred_mask = main_rec.deferred_mask;
+        CHK(tail(c->pipe_stream, t, 0, true));
     }
+    hipEvent_t e_tail = c->pipe_ev[c->pipe_ev_next++ % c->pipe_ev.size()];
     HIPCHK(hipEventRecord(e_tail, c->pipe_stream));
     c->tail_ev = e_tail;
     c->tail_pending = true;
     c->last_parity = par;
     c->pipe_parity = par ^ 1;
     return 0;
+}
+static int step_pipelined(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
+                          float *mask, double *box_out, float *refine_out, hipStream_t s) {
+    const int rc = step_pipelined_enqueue(c, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, s);
+    if (rc) {
+        // a main part without its tail (or the reverse) would leave the semaphores unbalanced: drain and start over
+        (void)hipDeviceSynchronize();
+        (void)pipe_reset_counters(c);
+        c->tail_pending = false;
+    }
+    return rc;
 }
 
 int smk_step(smk_ctx *c, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
@@ -2585,9 +2523,10 @@ int smk_step(smk_ctx *c, const float *x, int B, int flags, const double *target_
     int64_t pk, wi;
     memcpy(&pk, &c->penalty_k, 8); memcpy(&wi, &c->window_influence, 8);
     GraphKey key{3, B, flags, {x, target_wh, cls, loc, mask, box_out, refine_out, (const void *)pk, (const void *)wi}};
-    int rc = run_maybe_graph(c, key, s, [&](hipStream_t st) {
-        CHK(step_track_decode(c, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, true, PH_ALL));
-        return step_tail(c, B, mask, box_out, refine_out, st);
+    StepRec rec = step_rec(c, refine_out);
+    int rc = run_maybe_graph(c, key, s, rec, [&](hipStream_t st) {
+        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, true, PH_ALL));
+        return step_tail(c, rec, B, mask, box_out, refine_out, st);
     });
     if (rc) return rc;
     c->track_B = (flags & SMK_TRACK_MASK) ? B : 0;
@@ -2624,23 +2563,11 @@ int smk_set_pipeline(smk_ctx *c, int depth) {
         // (the box rows' own cursor of depth 2 starts where the shared one stands)
         if (c->ring_cursor) HIPCHK(hipMemcpy(c->ring_cursor + 2, c->ring_cursor, sizeof(int), hipMemcpyDeviceToDevice));
         if (!c->pipe_stream) {
-            // A queue priority for the side stream (lowest: the tail's workgroups dispatched behind the next frame's front end) was measured in round 6
-            // (profiles/r06z_side_stream_priority.txt): ANY priority other than the default -- lowest or highest -- costs +50 % per B = 8 step and x4.4 at
-            // B = 1; queues of unequal priority are not arbitrated workgroup by workgroup.  The arm lives in `make MEASURE=1` builds (smk_tune pipe_prio).
-#ifdef SMK_MEASURE
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);          // (numerically: lo >= hi, lower value = higher priority)
-            if (g_tune.pipe_prio) HIPCHK(hipStreamCreateWithPriority(&c->pipe_stream, hipStreamNonBlocking, g_tune.pipe_prio == 1 ? lo : hi));
-            else
-#endif
+            // default queue priority: ANY other -- lowest or highest -- costs +50 % per B = 8 step and x4.4 at B = 1, queues of unequal
+            // priority are not arbitrated workgroup by workgroup (profiles/r06z_side_stream_priority.txt)
             HIPCHK(hipStreamCreateWithFlags(&c->pipe_stream, hipStreamNonBlocking));
         }
         if (!c->pipe_cnt) HIPCHK(hipMalloc((void **)&c->pipe_cnt, 64));
-        if (!c->pipe_sig) {
-            int can = 0;
-            (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device);
-            if (can && hipExtMallocWithFlags((void **)&c->pipe_sig, 8, hipMallocSignalMemory) != hipSuccess) { c->pipe_sig = nullptr; (void)hipGetLastError(); }
-        }
         CHK(pipe_reset_counters(c));
         if (c->pipe_ev.empty()) {
             c->pipe_ev.resize(16);
@@ -2793,18 +2720,18 @@ static void pack_host(const smk_conv_geom *g, const PackedConv &pc, const float 
 }
 
 // split-K scratch of the context-free entry points (per-op tests, smk_bench_conv): one per device, lazily
-static int op_ks_scratch(smk_ctx &fake) {
+static int op_ks_scratch(ConvEnv &env) {
     static float *part[64] = {nullptr};
     static unsigned *cnt[64] = {nullptr};
-    const int d = fake.device;
+    const int d = env.device;
     if (d < 0 || d >= 64) return 0;
     if (!part[d]) {
         HIPCHK(hipMalloc((void **)&part[d], KS_PART_FLOATS * sizeof(float)));
         HIPCHK(hipMalloc((void **)&cnt[d], KS_CNT * sizeof(unsigned)));
         HIPCHK(hipMemset(cnt[d], 0, KS_CNT * sizeof(unsigned)));
     }
-    fake.ks_part = part[d];
-    fake.ks_cnt = cnt[d];
+    env.ks_part = part[d];
+    env.ks_cnt = cnt[d];
     return 0;
 }
 
@@ -2892,17 +2819,17 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
         if (x3 ? launch_cvt_in_x3(cr, s) : launch_cvt_in(cr, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
         o.res = &res; o.res_mode = g->res_mode;
     }
-    smk_ctx fake;
-    fake.dtype = ctx_dtype;
-    HIPCHK(hipGetDevice(&fake.device));
-    CHK(op_ks_scratch(fake));
+    ConvEnv env;
+    env.dtype = ctx_dtype;
+    HIPCHK(hipGetDevice(&env.device));
+    CHK(op_ks_scratch(env));
     ConvParams p;
     if (nchw) {
         o.nchw_out = y_dev;
-        CHK(conv_params(&fake, pc, in, nullptr, g->B, o, p));
+        CHK(conv_params(env, pc, in, nullptr, g->B, o, p));
     } else {
         CHK(tmp.alloc(&out.p, (size_t)g->B * Ho * Wo * out.C * es));
-        CHK(conv_params(&fake, pc, in, &out, g->B, o, p));
+        CHK(conv_params(env, pc, in, &out, g->B, o, p));
     }
     ConvPlan pl;
     const int prc = plan_from_algo(algo, p, dtype, pl);
@@ -2927,9 +2854,9 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
 static int seq_op_records(const smk_seq_op *ops, int n, const Act &xin, int device, const std::function<int(int, PackedConv &)> &pack,
                           const std::function<int(void **, size_t)> &alloc, std::vector<SeqRec> &rec, std::vector<Act> &outs) {
     const int dtype = DT_F16, B = ops[0].g.B;
-    smk_ctx fake;
-    fake.dtype = dtype;
-    fake.device = device;
+    ConvEnv env;
+    env.dtype = dtype;
+    env.device = device;
     rec.assign(n, SeqRec());
     outs.assign(n, Act());
     for (int i = 0; i < n; ++i) {
@@ -2955,7 +2882,7 @@ static int seq_op_records(const smk_seq_op *ops, int n, const Act &xin, int devi
             o.res = &res; o.res_mode = op.g.res_mode;
         }
         ConvParams p;
-        CHK(conv_params(&fake, pc, in, &outs[i], B, o, p));
+        CHK(conv_params(env, pc, in, &outs[i], B, o, p));
         SeqLayer &L = rec[i].L;
         const int force_halo = op.cfg == SEQ_CFG_HALO128 ? 128 : (op.cfg == SEQ_CFG_HALO64 ? 64 : (op.cfg >= 0 ? -1 : 0));
         if (!seq_layer_from(p, dtype, L, force_halo)) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d cannot run inside a sequence%s", i, force_halo > 0 ? " on the patch-sharing tile" : "");
@@ -3419,12 +3346,12 @@ int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, in
             o.res = &res; o.res_mode = RES_PRE_RELU;
         }
     }
-    smk_ctx fake;
-    fake.dtype = dtype;
-    HIPCHK(hipGetDevice(&fake.device));
-    CHK(op_ks_scratch(fake));
+    ConvEnv env;
+    env.dtype = dtype;
+    HIPCHK(hipGetDevice(&env.device));
+    CHK(op_ks_scratch(env));
     ConvParams p;
-    CHK(conv_params(&fake, pc, in, mode == 2 ? nullptr : &out, g->B, o, p));
+    CHK(conv_params(env, pc, in, mode == 2 ? nullptr : &out, g->B, o, p));
     ConvPlan pl;
     const int prc = plan_from_algo(mode == 1 || mode == 3 ? algo & ~0xff : algo, p, dtype, pl);     // (no naive kernel here: 1 / 3 time the MFMA one)
     if (prc < 0) return fail(SMK_E_ARG, "smk_bench_conv: wreg tile code 1..8");
@@ -3475,10 +3402,10 @@ int smk_host_conv2d_ex(const smk_conv_geom *g, const float *x, const float *w, c
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8);
     std::vector<float> obuf((size_t)g->B * Ho * Wo * out.C, 0.f);
     out.p = obuf.data();
-    smk_ctx fake;
-    fake.device = -1;
+    ConvEnv env;
+    env.device = -1;
     ConvParams p;
-    CHK(conv_params(&fake, pc, in, &out, g->B, o, p));
+    CHK(conv_params(env, pc, in, &out, g->B, o, p));
     for (int m = 0; m < p.M; ++m) {
         const RowInfo r = row_info(p, m, p.pos);
         for (int n = 0; n < g->Cout; ++n) {
@@ -3527,12 +3454,12 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8); out.p = dummy;
     res = out;
     if (with_res) { o.res = &res; o.res_mode = RES_PRE_RELU; }
-    smk_ctx fake;
-    fake.device = -1;
-    fake.dtype = dtype;
+    ConvEnv env;
+    env.device = -1;
+    env.dtype = dtype;
     ConvParams p;
-    CHK(conv_params(&fake, pc, in, &out, g->B, o, p));
-    const ConvPlan pl = plan_conv(p, o, pc, dtype, g->B, fake.ncu);
+    CHK(conv_params(env, pc, in, &out, g->B, o, p));
+    const ConvPlan pl = plan_conv(p, o, pc, dtype, g->B, MI355X_CUS);
     switch (pl.kind) {
     case CK_PP: *kernel = 3; *bm = 256; *bn = 256; break;
     case CK_WREG: *kernel = 2; *bm = WREG_TILE[pl.wreg][0]; *bn = WREG_TILE[pl.wreg][1]; break;

@@ -698,15 +698,6 @@ __global__ __launch_bounds__(64) void pipe_gate_kernel(unsigned *sem, int *err, 
 __global__ __launch_bounds__(64) void pipe_done_kernel(unsigned *sem) {
     if (threadIdx.x == 0) __hip_atomic_fetch_add(sem, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
-// (smk_tune pipe_sig = 1: the main part's completion mark in SIGNAL memory for a hipStreamWaitValue32 on the side stream -- 3-4 us in
-//  the two-kernel probe, +50 % per step in the real loop: kept as the measured alternative, profiles/r05e_pipe_sig_ab.txt)
-__global__ __launch_bounds__(64) void pipe_mark_kernel(unsigned *sig) {
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(sig, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-int launch_pipe_mark(unsigned *sig, void *stream) {
-    hipLaunchKernelGGL(pipe_mark_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sig);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 int launch_pipe_gate(unsigned *sem, int *err, int *err_host, void *stream, int long_wait, unsigned *started_wait, unsigned *started_set) {
     hipLaunchKernelGGL(pipe_gate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sem, err, err_host,
                        long_wait ? 500000000ull : 20000000ull, started_wait, started_set);             // 5 s / 0.2 s at 100 MHz

@@ -258,21 +258,8 @@ struct Tuning {
     int x3_fused = 1;          // split-operand contexts: conv_wreg_kernel's fragment packs in fused order (a hi activation tile staged once for its two products)
     int wreg32 = 140;          // conv_wreg tile choice: 32 x 64 tiles where fewer than this many 64 x 64 tiles exist (0 = never): -8..15 % per under-filled
                                // launch, -2 % on the B = 1 step (profiles/r06w_wreg_32_row_tiles.txt)
-    int pipe_join = 1;         // pipelined frame step: 1 = the join with the previous frame's tail is an in-stream gate kernel (two graphs per
-                               // frame), 0 = a cross-queue event wait (three graphs; measured 15-22 us of latency on the critical path)
-    int pipe_two_form = 1;     // depth-2 pipelining: 1 = the mask head as its own launch at the head of the tail's first part, the bare Refine chain beside
-                               // the next frame's heads; 0 = chain + mask head as one launch beside the heads (measured: it starves conv_search);
-                               // 2 = chain + mask head as one launch behind conv_search (beside corr_head + decode: 136-216 idle CUs)
-    int pipe_prio = 0;         // (MEASURE builds) queue priority of the pipelined step's side stream (0 default, 1 lowest, 2 highest): read when the stream is created
     int pipe_late = 1;         // pipelined frame step outside the persistent sequence's batches: the main gate in front of the heads instead of in front of
                                // layer2 (the tail overlaps the whole backbone of the next frame; p2 exists twice as well)
-    int pipe_sig = 2;          // pipelined frame step, how the side stream learns that decode(f) is done: 2 (default) = a one-wave gate kernel at the head of
-                               // the tail polls a semaphore the decode launch's last writer raises (it polls through the next frame's persistent launch,
-                               // beside it: 0.531-0.541 ms per step against 0.556 for 0 and 0.563-0.565 serial, profiles/r05f_pipe_sig_ab.txt);
-                               // 0 = hipEventRecord in the step's stream + hipStreamWaitEvent; 1 = hipStreamWaitValue32 on signal memory (3-4 us in the
-                               // two-kernel probe, 0.85 ms per step in the real loop, profiles/r05e_pipe_sig_ab.txt)
-    int pipe_eager = 0;        // pipelined frame step, A/B knob: bit 0 = the front end (stem + layer1) as eager launches instead of a graph,
-                               // bit 1 = the Refine / mask tail as eager launches
 };
 extern Tuning g_tune;
 
@@ -510,7 +497,6 @@ int launch_ring_commit(const RingParams &p, void *stream);
 // P: poll until *sem > 0, take one; gives up after 0.2 s (long_wait: 5 s, counted from the moment *started_wait is non-zero); then *started_wait = 0, *started_set = 1
 int launch_pipe_gate(unsigned *sem, int *err, int *err_host, void *stream, int long_wait = 0, unsigned *started_wait = nullptr, unsigned *started_set = nullptr);
 int launch_pipe_done(unsigned *sem, void *stream);                             // V
-int launch_pipe_mark(unsigned *sig, void *stream);          // sig: signal memory (hipMallocSignalMemory), waited for with hipStreamWaitValue32
 int launch_crop_resize(const CropParams &p, int B, void *stream);
 int launch_paste_mask(const PasteParams &p, int B, void *stream);
 int launch_paste_labels(const PasteParams &p, int n_obj, void *stream);

@@ -206,7 +206,7 @@ def test_tuning_knobs_read_back():
     table = src[src.index("static const Knob KNOBS[] = {"):]
     table = table[:table.index("};")]
     names = re.findall(r'\{"(\w+)", &\w+(?:\.\w+)?, "', table)            # (read-only diagnostics have no accepted values)
-    assert len(names) > 60 and "npw" in names and "seq_fused_last" not in names
+    assert len(names) == 58 and "npw" in names and "seq_fused_last" not in names
     code = ("import json; from siammask_amd import _lib\n"
             "for k in %r: _lib.tune(**{k: _lib.tune_get(k)})\n"
             "_lib.tune(seq_spoll=5, seq_kstag_mask=15)\n"
@@ -225,6 +225,19 @@ def test_tuning_knobs_read_back():
         assert _lib.tune_get("rf_wreg") == old
     finally:
         _lib.tune(rf_wreg=old)
+
+
+@pytest.mark.parametrize("name", ["pipe_join", "pipe_sig", "pipe_eager", "pipe_two_form", "pipe_prio"])
+def test_settled_pipeline_knobs_are_gone(name):
+    """the measured and dropped forms of the pipelined step (cross-queue event join, event / hipStreamWaitValue32 start of the tail,
+    eager parts, depth-2 forms 0 / 2, a side-stream priority; profiles/r05a_*, r05e_*, r05f_*, r05j_*, r05o_*, r06z_*) left the library
+    with their knobs: no kind of build sets or reads them any more"""
+    from siammask_amd import _lib
+    for value in (0, 1, 2):
+        with pytest.raises(RuntimeError):
+            _lib.tune(**{name: value})
+    with pytest.raises(RuntimeError):
+        _lib.tune_get(name)
 
 
 def _plan(B, cin, hw, cout, k, stride=1, pad=0, dil=1, res=False, win=None, dtype="f16"):
