@@ -312,6 +312,35 @@ int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score
                        int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev,
                        float *prob_out_dev, void *stream);
 
+/* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
+ * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
+ * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:
+ *   prob_o = bit o of alive_mask ? the warped probability smk_paste_mask writes to prob_out (the same bits) : -1.0f
+ *            (:480: pred_masks is -1 outside an object's lifetime);
+ *   best = max_o prob_o, arg = the first o attaining it (:434-435 np.argmax / np.max over the objects);
+ *   for each of the n_thr (1..8) thresholds k, above = (double)best > thrs[k] -- a FLOAT64 comparison, as :437 compares the
+ *   float64 `outputs` with the float64 values of np.arange(0.3, 0.5, 0.05) -- and for each object j (:439, :447-450):
+ *     pred = above && arg == j;  tgt = gt[y][x] == object_ids[j];
+ *     counts[j][k][0] += pred && tgt (intersection);  counts[j][k][1] += pred || tgt (union).
+ * gt_dev: uint8 [H][W]; object_ids (host): n_obj uint8 values -- any values, they need not occur in gt, and gt may hold values
+ * that match none; thrs (host): n_thr doubles in any order.  counts_out_dev: int32 [n_obj][n_thr][2], fully defined by the
+ * call (zeroed on `stream` by the call itself), exact and reproducible (integer sums).  labels_out_dev (may be NULL): uint8
+ * [H][W] = best > seg_thr ? arg + 1 : 0 with the float32 comparison of smk_paste_labels (:521-523) -- the same bytes when all
+ * objects are alive.  W * H < 2^31, H <= 65535.  inv_map (host): n_obj x 6 doubles as for smk_paste_mask.  Host arrays travel
+ * as kernel arguments: nothing of the caller's host memory is read after the call returns.  No context; asynchronous on
+ * `stream`, no host synchronisation; bad arguments give SMK_E_ARG before anything is enqueued.
+ * The mean over a video's frames (:441-455) is left to the host: siammask_amd.vos.mean_iou. */
+int smk_vos_score(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                  const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                  float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, void *stream);
+/* smk_vos_score with inv_map[slot] -- and, with head_dev != NULL (logits_dev ignored), the column delta_yx[slot] of the mask
+ * head [n_obj][ms*ms][score_size][score_size] (:259-260) -- of stream o read from the tracker's state block, exactly as
+ * smk_paste_mask_dev reads them: behind smk_trk_advance on the same stream it scores the frame that was just advanced. */
+int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                      uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                      uint8_t *labels_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

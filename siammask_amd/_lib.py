@@ -31,7 +31,7 @@ SYMBOLS = (
     "smk_op_maxpool3x3s2", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
     "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels", "smk_mask_rbox_workspace", "smk_mask_rbox",
     "smk_trk_state_bytes", "smk_trk_set", "smk_trk_plan", "smk_trk_advance", "smk_crop_resize_dev", "smk_paste_mask_dev",
-    "smk_host_trk_plan", "smk_host_trk_advance",
+    "smk_vos_score", "smk_vos_score_dev", "smk_host_trk_plan", "smk_host_trk_advance",
 )
 
 
@@ -138,6 +138,9 @@ def lib():
     L.smk_host_trk_advance.argtypes = [vp, ci, cp, vp, ci, vp, ci]
     L.smk_crop_resize_dev.argtypes = [vp, ctypes.c_int64, ci, ci, vp, ci, ci, fp, vp]
     L.smk_paste_mask_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, fp, vp]
+    cf, u32 = ctypes.c_float, ctypes.c_uint32
+    L.smk_vos_score.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, vp, u32, vp, ci, cf, vp, vp, vp]
+    L.smk_vos_score_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, vp, vp, u32, vp, ci, cf, vp, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

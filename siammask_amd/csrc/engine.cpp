@@ -1772,7 +1772,7 @@ static int seq_grid_for(int ncu) {
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
-int smk_version(void) { return (1 << 16) | 8; }   // 1.8: tracker state on the device, smk_trk_* / smk_*_dev (1.7: smk_mask_rbox; 1.6: SMK_DTYPE_F16X3)
+int smk_version(void) { return (1 << 16) | 9; }   // 1.9: smk_vos_score / smk_vos_score_dev (1.8: tracker state on the device, smk_trk_* / smk_*_dev; 1.7: smk_mask_rbox; 1.6: SMK_DTYPE_F16X3)
 //   // 1.2: smk_decode / smk_step take float64 target_wh and write a float64 box; 1.3: smk_op_conv_seq,
                                                   // sequence failures reported at the next entry point
 
@@ -3288,6 +3288,56 @@ int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score
     p.seg_thr = seg_thr; p.border = border;
     p.st = (const smk_trk_stream *)state_dev;
     if (launch_paste_mask_dev(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev launch failed");
+    return 0;
+}
+
+// ---- VOS scoring (tools/test.py:421-456 MultiBatchIouMeter per frame, fused with the paste-back; image_kernels.hip) ------------
+static_assert(VOS_MAX_OBJ == CROP_MAX_B, "smk_vos_score takes as many objects as smk_paste_labels");
+
+// the checks and the fields both entries share; everything is refused here, before anything is enqueued
+static int vos_fill(const char *who, VosParams &p, const float *src, int mask_size, int n_obj, int W, int H, float border,
+                    const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                    float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev) {
+    if (!src || !gt_dev || !object_ids || !thrs || !counts_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (n_obj < 1 || n_obj > VOS_MAX_OBJ) return fail(SMK_E_ARG, "%s: %d objects (1..%d)", who, n_obj, VOS_MAX_OBJ);
+    if (n_thr < 1 || n_thr > VOS_MAX_THR) return fail(SMK_E_ARG, "%s: %d thresholds (1..%d)", who, n_thr, VOS_MAX_THR);
+    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || (int64_t)W * H > INT32_MAX)
+        return fail(SMK_E_ARG, "%s: bad geometry (%d x %d frame, mask %d)", who, W, H, mask_size);
+    memset(&p, 0, sizeof(p));
+    p.logits = src; p.gt = gt_dev; p.counts = counts_out_dev; p.labels = labels_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.n_obj = n_obj; p.n_thr = n_thr;
+    p.seg_thr = seg_thr; p.border = border; p.alive = alive_mask;
+    for (int k = 0; k < n_thr; ++k) p.thr[k] = thrs[k];
+    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
+    return 0;
+}
+
+int smk_vos_score(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                  const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                  float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_score: null argument");
+    VosParams p;
+    CHK(vos_fill("smk_vos_score", p, logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
+                 seg_thr, counts_out_dev, labels_out_dev));
+    for (int i = 0; i < n_obj; ++i)
+        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
+    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
+    return 0;
+}
+
+int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                      uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                      uint8_t *labels_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_score_dev: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_score_dev: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_score_dev: score_size %d", score_size);
+    VosParams p;
+    CHK(vos_fill("smk_vos_score_dev", p, head_dev ? head_dev : logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids,
+                 alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
     return 0;
 }
 

@@ -202,6 +202,109 @@ __global__ __launch_bounds__(256) void paste_labels_kernel(const PasteParams p, 
     p.mask_out[(size_t)y * p.W + x] = best > p.seg_thr ? (unsigned char)(arg + 1) : 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// VOS scoring (tools/test.py:421-456 MultiBatchIouMeter, the per-frame part): the O objects of one frame are fused per pixel
+// (max + first argmax over warped_prob, -1 for an object outside its lifetime, :480) and every threshold k counts, per object j,
+//   intersection += (best > thr[k] && arg == j) && gt == id[j],   union += (best > thr[k] && arg == j) || gt == id[j].
+// `best > thr[k]` is a FLOAT64 comparison (the reference's outputs and thrs are float64); the label map, when asked for, uses
+// the float32 comparison of paste_labels_kernel.  A pixel touches only object `arg` and the objects whose id equals gt, so the
+// wave groups its lanes by arg (then by gt), counts each group with ballot + popcount and lane 0 adds to the workgroup's LDS
+// counters; one global atomic add per non-zero counter per workgroup.  Integer sums: the result does not depend on the order.
+// A workgroup covers 256 pixels of VOS_ROWS consecutive rows (fewer workgroups -> fewer global atomics on the O*K*2 counters).
+constexpr int VOS_ROWS = 4;
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void vos_score_kernel(const VosParams p) {
+    __shared__ int cnt[VOS_MAX_OBJ * VOS_MAX_THR * 2];
+    __shared__ int sid[VOS_MAX_OBJ];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int O = p.n_obj, K = p.n_thr, n = O * K * 2;
+    for (int i = tid; i < n; i += 256) cnt[i] = 0;
+    if (tid < O) sid[tid] = p.ids[tid];
+    __syncthreads();
+    const int x = blockIdx.x * 256 + tid;
+    const bool in_x = x < p.W;
+    const int y0 = blockIdx.y * VOS_ROWS, y1 = min(y0 + VOS_ROWS, p.H);
+    for (int y = y0; y < y1; ++y) {
+        float best = -1.f;
+        int arg = 0, g = -1;
+        unsigned abv = 0;                                             // bit k: (double)best > thr[k]
+        if (in_x) {
+            for (int o = 0; o < O; ++o) {
+                float v = -1.f;
+                if ((p.alive >> o) & 1) {
+                    if constexpr (DEV) {
+                        const smk_trk_stream *s = p.st + o;
+                        const float *lg = p.logits + (size_t)o * p.ms * p.ms;
+                        int ls = 1;
+                        if (p.head_S) {
+                            ls = p.head_S * p.head_S;
+                            const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1);
+                            const int dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+                            lg = p.logits + (size_t)o * p.ms * p.ms * ls + dy * p.head_S + dx;
+                        }
+                        v = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y);
+                    } else {
+                        v = warped_prob(p, p.inv_map[o], p.logits + (size_t)o * p.ms * p.ms, 1, x, y);
+                    }
+                }
+                if (o == 0 || v > best) { best = v; arg = o; }        // np.argmax keeps the first maximum
+            }
+            const size_t px = (size_t)y * p.W + x;
+            g = p.gt[px];
+            for (int k = 0; k < K; ++k) abv |= ((double)best > p.thr[k] ? 1u : 0u) << k;
+            if (p.labels) p.labels[px] = best > p.seg_thr ? (unsigned char)(arg + 1) : 0;
+        }
+        // predictions: the lanes above some threshold, grouped by arg
+        const bool hit = in_x && abv != 0;
+        unsigned long long todo = __ballot(hit);
+        while (todo) {
+            const int a = __builtin_amdgcn_readfirstlane(__shfl(arg, __ffsll((long long)todo) - 1));
+            const bool same = hit && arg == a;
+            todo &= ~__ballot(same);
+            const bool tgt = g == sid[a];
+            for (int k = 0; k < K; ++k) {
+                const bool pred = same && ((abv >> k) & 1);
+                const int u = __popcll(__ballot(pred)), it = __popcll(__ballot(pred && tgt));
+                if (lane == 0 && u) {
+                    atomicAdd(&cnt[(a * K + k) * 2 + 1], u);
+                    if (it) atomicAdd(&cnt[(a * K + k) * 2], it);
+                }
+            }
+        }
+        // targets: the lanes grouped by gt; every object with that id takes the pixels its prediction has not counted
+        todo = __ballot(in_x);
+        while (todo) {
+            const int gg = __builtin_amdgcn_readfirstlane(__shfl(g, __ffsll((long long)todo) - 1));
+            const bool same = in_x && g == gg;
+            todo &= ~__ballot(same);
+            for (int j = 0; j < O; ++j) {
+                if (sid[j] != gg) continue;
+                for (int k = 0; k < K; ++k) {
+                    const int u = __popcll(__ballot(same && !(((abv >> k) & 1) && arg == j)));
+                    if (lane == 0 && u) atomicAdd(&cnt[(j * K + k) * 2 + 1], u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int v = cnt[i];
+        if (v) atomicAdd(p.counts + i, v);
+    }
+}
+
+int launch_vos_score(const VosParams &p, void *stream) {
+    if (p.n_obj < 1 || p.n_obj > VOS_MAX_OBJ || p.n_thr < 1 || p.n_thr > VOS_MAX_THR || !p.logits || !p.gt || !p.counts) return -1;
+    if (p.W < 1 || p.H < 1 || p.H > 65535 * VOS_ROWS) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * p.n_obj * p.n_thr, s) != hipSuccess) return -4;
+    dim3 grid((p.W + 255) / 256, (p.H + VOS_ROWS - 1) / VOS_ROWS, 1);
+    if (p.st) hipLaunchKernelGGL(vos_score_kernel<true>, grid, dim3(256), 0, s, p);
+    else      hipLaunchKernelGGL(vos_score_kernel<false>, grid, dim3(256), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_paste_mask(const PasteParams &p, int B, void *stream) {
     if (B < 1 || B > CROP_MAX_B) return -1;
     dim3 grid((p.W + 255) / 256, p.H, B);

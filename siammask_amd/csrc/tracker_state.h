@@ -152,6 +152,22 @@ struct PasteDevParams {
 };
 int launch_crop_resize_dev(const CropDevParams &p, int B, void *stream);
 int launch_paste_mask_dev(const PasteDevParams &p, int B, void *stream);
+// smk_vos_score / smk_vos_score_dev: the per-frame counts of MultiBatchIouMeter (tools/test.py:421-456) fused with the paste-back
+constexpr int VOS_MAX_OBJ = 32, VOS_MAX_THR = 8;
+struct VosParams {
+    const float *logits;            // [O][ms*ms], or the head [O][ms*ms][S][S] when head_S != 0
+    const unsigned char *gt;        // [H][W] object id per pixel
+    int *counts;                    // [O][K][2] (intersection, union), zeroed in-stream before the launch
+    unsigned char *labels;          // [H][W] or nullptr
+    int ms, W, H, n_obj, n_thr, head_S, slot;
+    float seg_thr, border;
+    unsigned alive;                 // bit o: object o is inside its lifetime (else its probability is -1, tools/test.py:480)
+    const smk_trk_stream *st;       // != nullptr: inv_map[slot] / delta_yx[slot] of the state block, inv_map below unused
+    double thr[VOS_MAX_THR];
+    unsigned char ids[VOS_MAX_OBJ];
+    double inv_map[VOS_MAX_OBJ][6];
+};
+int launch_vos_score(const VosParams &p, void *stream);
 
 }  // namespace smk
 #endif

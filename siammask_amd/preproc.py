@@ -6,6 +6,7 @@ arguments but a frame that already lives on the MI355X.
   crop_batch              the same for B streams in one launch
   paste_masks            <- tools/test.py:257-284  (sigmoid + crop_back/cv2.warpAffine + threshold)
   mask_rboxes            <- tools/test.py:285-294  (findContours -> largest contourArea -> minAreaRect -> boxPoints)
+  vos_score              <- tools/test.py:421-456  (MultiBatchIouMeter: per-frame intersection / union counts, fused with the paste-back)
 No CPU fallback: CPU tensors raise."""
 import ctypes
 
@@ -171,6 +172,96 @@ def paste_labels(logits, back_boxes, im_wh, seg_thr=0.35, padding=-1.0):
                                                float(seg_thr), float(padding), labels.data_ptr(),
                                                _lib.current_stream_ptr()))
     return labels
+
+
+def _vos_args(O, gt, object_ids, thrs, alive, W, H, device):
+    """the checked arguments vos_score / vos_score_dev share -> (ids uint8 [O], thrs float64 [K], alive bit mask)"""
+    _need_cuda(gt, "gt")
+    if gt.dtype != torch.uint8 or tuple(gt.shape) != (H, W) or not gt.is_contiguous() or gt.device != device:
+        raise ValueError("gt must be a contiguous uint8 CUDA tensor [%d,%d] on the logits' device" % (H, W))
+    if not 1 <= O <= 32:
+        raise ValueError("1..32 objects, got %d" % O)
+    ids = np.asarray(object_ids)
+    if ids.shape != (O,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+        raise ValueError("object_ids must be %d integers in 0..255" % O)
+    thr = np.ascontiguousarray(thrs, dtype=np.float64)
+    if thr.ndim != 1 or not 1 <= thr.size <= 8:
+        raise ValueError("thrs must be 1..8 values")
+    if alive is None:
+        bits = (1 << O) - 1
+    else:
+        al = np.asarray(alive)
+        if al.shape != (O,):
+            raise ValueError("alive must be %d booleans" % O)
+        bits = sum(1 << o for o in range(O) if al[o])
+    return np.ascontiguousarray(ids.astype(np.uint8)), thr, bits
+
+
+def vos_score(logits, back_boxes, im_wh, gt, object_ids, thrs, alive=None, seg_thr=0.35, padding=-1.0, want_labels=False):
+    """The per-frame counts of MultiBatchIouMeter (tools/test.py:421-456) fused with the paste-back: the O objects of one frame
+    (logits / back_boxes as for paste_labels) against gt (uint8 CUDA [im_h, im_w] of object ids) at every threshold of thrs
+    (1..8 float64 values; the comparison is in float64).  alive: O booleans, False = the object is outside its lifetime on this
+    frame (probability -1, :480).  -> int32 CUDA [O, K, 2] = (intersection, union) [, uint8 label map [im_h, im_w] =
+    paste_labels at seg_thr].  siammask_amd.vos.mean_iou turns the counts of a video into the meter's result."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    O = logits.shape[0]
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != O:
+        raise ValueError("logits must be [O, ms*ms] with one back_box per object")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    ids, thr, bits = _vos_args(O, gt, object_ids, thrs, alive, W, H, logits.device)
+    inv = np.ascontiguousarray(np.stack([invert_affine(crop_back_map(bb, (W, H))) for bb in back_boxes]))
+    counts = torch.empty((O, thr.size, 2), dtype=torch.int32, device=logits.device)
+    labels = torch.empty((H, W), dtype=torch.uint8, device=logits.device) if want_labels else None
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.lib().smk_vos_score(
+            logits.data_ptr(), ms, inv.ctypes.data_as(ctypes.c_void_p), O, W, H, float(padding), gt.data_ptr(),
+            ids.ctypes.data_as(ctypes.c_void_p), bits, thr.ctypes.data_as(ctypes.c_void_p), int(thr.size), float(seg_thr),
+            counts.data_ptr(), labels.data_ptr() if labels is not None else None, _lib.current_stream_ptr()))
+    return (counts, labels) if want_labels else counts
+
+
+def vos_score_dev(logits, state, slot, im_wh, gt, object_ids, thrs, alive=None, seg_thr=0.35, padding=-1.0, head=None,
+                  mask_size=None, out=None, labels_out=None, want_labels=False):
+    """vos_score with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of each object read on the device
+    from the tracker's state block, as paste_masks_dev reads them.  out: int32 CUDA [O, K, 2] to write the counts into;
+    labels_out: uint8 CUDA [im_h, im_w] to write the label map into (implies want_labels)."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    O = src.shape[0]
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [O, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [O, ms*ms]")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    ids, thr, bits = _vos_args(O, gt, object_ids, thrs, alive, W, H, src.device)
+    K = int(thr.size)
+    counts = out if out is not None else torch.empty((O, K, 2), dtype=torch.int32, device=src.device)
+    if counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or tuple(counts.shape) != (O, K, 2):
+        raise ValueError("out must be a contiguous int32 CUDA tensor [%d,%d,2]" % (O, K))
+    labels = labels_out
+    if labels is None and want_labels:
+        labels = torch.empty((H, W), dtype=torch.uint8, device=src.device)
+    if labels is not None and (labels.dtype != torch.uint8 or not labels.is_cuda or not labels.is_contiguous() or
+                               tuple(labels.shape) != (H, W)):
+        raise ValueError("labels_out must be a contiguous uint8 CUDA tensor [%d,%d]" % (H, W))
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().smk_vos_score_dev(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), O, W, H, float(padding), gt.data_ptr(), ids.ctypes.data_as(ctypes.c_void_p), bits,
+            thr.ctypes.data_as(ctypes.c_void_p), K, float(seg_thr), counts.data_ptr(),
+            labels.data_ptr() if labels is not None else None, _lib.current_stream_ptr()))
+    return (counts, labels) if labels is not None else counts
 
 
 _rbox_ws = {}      # (device, stream, B, W, H) -> scratch of smk_mask_rbox (sized for the worst case of ceil(W/2)*H runs per mask)

@@ -16,6 +16,8 @@ csrc/tracker_state.hip) -- any number of frames is enqueued without a host synch
     tr.enqueue(frame)                                              # crop -> step -> advance + plan -> paste: launches only
     res = tr.collect()                                             # ONE synchronisation: host arrays [T,B,...] + device masks
     res = tr.run(frames)                                           # frames uint8 CUDA [T,H,W,3] or [T,B,H,W,3]
+    res = tr.run(frames, gt=gt_u8_cuda, vos={'object_ids': ids, 'thrs': vos.THRS})   # B objects on a shared frame, scored
+    res['vos_counts'], res['labels']                               # against gt on the device (tools/test.py:421-456, 521-523)
 track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
 """
 import ctypes
@@ -168,7 +170,7 @@ class DeviceTracker(object):
     def _fr_setup(self, device, B, H, W):
         p, L = self.p, _lib.lib()
         fr = self._fr = {"B": B, "H": H, "W": W, "device": device, "pending": 0, "deferred": None, "rows": [], "rbox": [],
-                         "masks": [], "poly": [], "synced": None}
+                         "masks": [], "poly": [], "synced": None, "vos": [], "labels": [], "vos_k": None}
         n = int(L.smk_trk_state_bytes(B))
         with torch.cuda.device(device):
             fr["dev"] = torch.zeros(n, dtype=torch.uint8, device=device)
@@ -193,11 +195,55 @@ class DeviceTracker(object):
             _lib.check(L.smk_trk_plan(fr["dev"].data_ptr(), fr["B"], ctypes.byref(fr["cfg"]), sp))
         fr["synced"] = (st["target_pos"], st["target_sz"])        # track() replaces these arrays: identity tells who is ahead
 
-    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None):
+    def _vos_spec(self, frame_dim, want_mask, gt, vos, labels_out=None):
+        """the checked VOS request of one frame (before anything is launched) -> None, or (gt, ids, thrs, alive bits) with the
+        host arrays the C entry takes"""
+        if gt is None and vos is None:
+            if labels_out is not None:
+                raise ValueError("labels_out comes with gt= and vos=")
+            return None
+        fr = self._fr
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        if gt is None or vos is None:
+            raise ValueError("gt= and vos= come together")
+        if frame_dim != 3 or not want_mask or self.model.variant == "rpn":
+            raise ValueError("VOS scoring needs one frame shared by the B objects, want_mask and a variant with a mask branch")
+        if not isinstance(gt, torch.Tensor) or not gt.is_cuda or gt.dtype != torch.uint8 or tuple(gt.shape) != (H, W):
+            raise ValueError("gt must be a uint8 CUDA tensor [%d,%d]" % (H, W))
+        if B > 32:
+            raise ValueError("VOS scoring takes up to 32 objects, the tracker has %d" % B)
+        unknown = set(vos) - {"object_ids", "thrs", "alive"}
+        if unknown or "object_ids" not in vos or "thrs" not in vos:
+            raise ValueError("vos = {'object_ids': B ids, 'thrs': 1..8 thresholds[, 'alive': B booleans]}")
+        ids = np.asarray(vos["object_ids"])
+        if ids.shape != (B,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+            raise ValueError("vos['object_ids'] must be %d integers in 0..255" % B)
+        thrs = np.ascontiguousarray(vos["thrs"], dtype=np.float64)
+        if thrs.ndim != 1 or not 1 <= thrs.size <= 8:
+            raise ValueError("vos['thrs'] must be 1..8 values")
+        if fr["pending"] and fr["vos_k"] != thrs.size:
+            raise ValueError("every frame of a chunk is scored at the same number of thresholds, or none is")
+        alive = vos.get("alive")
+        bits = (1 << B) - 1
+        if alive is not None:
+            alive = np.asarray(alive)
+            if alive.shape != (B,):
+                raise ValueError("vos['alive'] must be %d booleans" % B)
+            bits = sum(1 << b for b in range(B) if alive[b])
+        if labels_out is not None and (labels_out.dtype != torch.uint8 or not labels_out.is_cuda or
+                                       not labels_out.is_contiguous() or tuple(labels_out.shape) != (H, W)):
+            raise ValueError("labels_out must be a contiguous uint8 CUDA tensor [%d,%d]" % (H, W))
+        return gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits
+
+    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
-        advance + plan -> paste-back (map from the device state) [-> rotated box].  No host synchronisation of any kind.
-        mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.  -> the frame's index in the
-        chunk that collect() returns."""
+        advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
+        any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
+        gt (uint8 CUDA [im_h,im_w] of object ids) and vos ({'object_ids': B ids, 'thrs': 1..8 float64 thresholds[, 'alive': B
+        booleans]}): the B streams are the objects of one shared frame; behind the frame's paste-back the intersection / union
+        counts of tools/test.py:421-456 and the fused label map (:521-523, at the tracker's seg_thr; labels_out: uint8 CUDA
+        [im_h,im_w] to receive it) are computed on the device and come back from collect().
+        -> the frame's index in the chunk that collect() returns."""
         fr, st = self._fr, self.state
         if st is None or fr is None:
             raise RuntimeError("DeviceTracker.enqueue(): init() first")
@@ -212,6 +258,9 @@ class DeviceTracker(object):
         if mask_out is not None and (not want_mask or mask_out.dtype != torch.uint8 or not mask_out.is_cuda or
                                      not mask_out.is_contiguous() or tuple(mask_out.shape) != (B, H, W)):
             raise ValueError("mask_out must be a contiguous uint8 CUDA tensor [%d,%d,%d] (and the variant has a mask)" % (B, H, W))
+        if fr["pending"] and (fr["vos_k"] is not None) != (vos is not None or gt is not None):
+            raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
+        spec = self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = frame.contiguous()
         L, model = _lib.lib(), self.model
         try:
@@ -230,6 +279,15 @@ class DeviceTracker(object):
                     fr["rbox"].append(None)
                 if want_polygon and fr["rbox"][blk] is None:
                     fr["rbox"][blk] = torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=fr["device"])
+                score = None
+                if spec is not None:
+                    K = int(spec[2].size)
+                    if i == 0 and blk == len(fr["vos"]):              # count rows per block, like fr["rows"]
+                        fr["vos"].append(torch.empty((_ROWS_PER_BLOCK, B, 8, 2), dtype=torch.int32, device=fr["device"]))
+                    labels = labels_out if labels_out is not None else torch.empty((H, W), dtype=torch.uint8, device=fr["device"])
+                    score = spec + (fr["vos"][blk][i], labels)
+                    fr["vos_k"] = K
+                    fr["labels"].append(labels)
                 dev_ptr = fr["dev"].data_ptr()
                 _lib.check(L.smk_crop_resize_dev(frame.data_ptr(), H * W * 3 if frame.dim() == 4 else 0, H, W, dev_ptr, B,
                                                  self.p.instance_size, fr["x"].data_ptr(), sp))
@@ -250,7 +308,7 @@ class DeviceTracker(object):
                 if want_mask:
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=fr["device"])
                     job = (out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
-                           fr["rbox"][blk][i] if want_polygon else None)
+                           fr["rbox"][blk][i] if want_polygon else None, score)
                     if depth:
                         fr["deferred"] = job                          # pasted behind the NEXT step (or by collect())
                     else:
@@ -265,7 +323,7 @@ class DeviceTracker(object):
         return t
 
     def _fr_paste(self, job, sp):
-        logits, head, slot, mask, rbox = job
+        logits, head, slot, mask, rbox, score = job
         fr, p = self._fr, self.p
         _lib.check(_lib.lib().smk_paste_mask_dev(
             logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
@@ -273,6 +331,13 @@ class DeviceTracker(object):
             float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))
         if rbox is not None:                                          # same stream, behind the paste-back (:285-303)
             preproc.mask_rboxes(mask, out=rbox)
+        if score is not None:                                         # the same slot of the same state block, same stream
+            gt, ids, thrs, bits, row, labels = score
+            _lib.check(_lib.lib().smk_vos_score_dev(
+                logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
+                int(head.shape[-1]) if head is not None else 0, self.mask_size, fr["dev"].data_ptr(), slot, fr["B"], fr["W"],
+                fr["H"], -1.0, gt.data_ptr(), ids.ctypes.data, bits, thrs.ctypes.data, int(thrs.size), float(p.seg_thr),
+                row.data_ptr(), labels.data_ptr(), sp))
 
     def _fr_rewind(self):
         """a persistent-sequence failure was reported (SMK_E_SEQ): every frame of the pending chunk is invalid and so is the
@@ -286,7 +351,9 @@ class DeviceTracker(object):
             fr["synced"] = (self.state["target_pos"], self.state["target_sz"])
         fr["start"] = None
         fr["pending"], fr["deferred"], fr["masks"], fr["poly"] = 0, None, [], []
+        fr["labels"], fr["vos_k"] = [], None
         fr.pop("whole", None)
+        fr.pop("whole_labels", None)
         replay = model._replay.get("template")
         if replay is not None:
             with torch.cuda.device(fr["device"]):
@@ -297,13 +364,15 @@ class DeviceTracker(object):
         """Join the frames enqueued since the last collect() -- ONE synchronisation -- and return host arrays
         target_pos [T,B,2], target_sz [T,B,2], score [T,B] (float64), best_id [T,B], delta_yx [T,B,2] (int64), crop_box [T,B,4],
         mask (uint8 CUDA [T,B,H,W], None without masks), and for frames enqueued with want_polygon polygon [T,B,4,2] /
-        polygon_found [T,B].  Leaves tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the
+        polygon_found [T,B]; for a chunk enqueued with gt= / vos=, vos_counts int64 [T,B,K,2] = (intersection, union) per frame,
+        object and threshold and labels (uint8 CUDA [T,H,W]).  Leaves tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the
         tracker to the chunk's start when a persistent-sequence failure was reported: re-run the chunk."""
         fr, st = self._fr, self.state
         if st is None or fr is None:
             raise RuntimeError("DeviceTracker.collect(): init() first")
         T, B = fr["pending"], fr["B"]
         whole = fr.pop("whole", None)                                 # run() (or its caller) gave one [T,B,H,W] mask tensor
+        whole_labels = fr.pop("whole_labels", None)
         if T == 0:
             return None
         try:
@@ -321,12 +390,20 @@ class DeviceTracker(object):
                     rb = [b if b is not None else torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=fr["device"])
                           for b in fr["rbox"][:nblk]]
                     rows = torch.cat([rows, torch.cat(rb)[:T]], dim=2)
+                K = fr["vos_k"]
+                if K is not None:                                     # int32 counts ride along as float64 (exact): [T,B,K*2]
+                    vc = torch.cat(fr["vos"][:nblk])[:T] if nblk > 1 else fr["vos"][0][:T]
+                    n_row = rows.shape[2]
+                    vc = vc.reshape(T, B * 16)[:, :B * K * 2].reshape(T, B, K * 2)      # a frame's row is packed [B][K][2]
+                    rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
                 host = rows.cpu().numpy()                             # the one synchronisation
         except _lib.SmkError as e:
             if e.code == _lib.E_SEQ:
                 self._fr_rewind()
             raise
         r = host[:, :, :RESULT_ROW]
+        if K is not None:
+            host, counts = host[:, :, :n_row], host[:, :, n_row:]
         res = {"target_pos": r[:, :, 0:2].copy(), "target_sz": r[:, :, 2:4].copy(), "score": r[:, :, 4].copy(),
                "best_id": r[:, :, 5].astype(np.int64), "delta_yx": r[:, :, 6:8].astype(np.int64),
                "crop_box": np.stack([r[:, :, 12], r[:, :, 13], r[:, :, 14], r[:, :, 14]], axis=2), "mask": None}
@@ -335,6 +412,10 @@ class DeviceTracker(object):
             res["mask"] = whole if whole is not None and whole.shape[0] == T else torch.stack(masks)
         elif any(m is not None for m in masks):
             res["mask"] = masks                                       # mixed chunk: per frame, None where no mask was asked for
+        if K is not None:
+            res["vos_counts"] = counts.astype(np.int64).reshape(T, B, K, 2)
+            labels = fr["labels"]
+            res["labels"] = whole_labels if whole_labels is not None and whole_labels.shape[0] == T else torch.stack(labels)
         if any_poly:
             q = host[:, :, RESULT_ROW:]
             asked = np.asarray(fr["poly"], dtype=bool)
@@ -360,11 +441,15 @@ class DeviceTracker(object):
             st["polygon"], st["polygon_found"] = res["polygon"][-1].copy(), res["polygon_found"][-1].copy()
         fr["synced"] = (st["target_pos"], st["target_sz"])            # the device holds exactly these values
         fr["pending"], fr["masks"], fr["poly"], fr["start"] = 0, [], [], None
+        fr["labels"], fr["vos_k"] = [], None
         return res
 
-    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None):
+    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None):
         """enqueue every frame of ``frames`` (uint8 CUDA [T,H,W,3], or [T,B,H,W,3] for per-stream frames), then collect().
-        mask_out: uint8 CUDA [T,B,H,W] to receive the masks."""
+        mask_out: uint8 CUDA [T,B,H,W] to receive the masks.
+        gt (uint8 CUDA [T,im_h,im_w]) and vos (as for enqueue(); 'alive' may be [T,B]): every frame is scored against its
+        annotation -> res['vos_counts'] int64 [T,B,K,2] (siammask_amd.vos.mean_iou takes it) and res['labels'] uint8 CUDA
+        [T,im_h,im_w]."""
         fr = self._fr
         if self.state is None or fr is None:
             raise RuntimeError("DeviceTracker.run(): init() first")
@@ -373,6 +458,18 @@ class DeviceTracker(object):
         if frames.dim() not in (4, 5):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T = int(frames.shape[0])
+        labels, alive = None, None
+        if gt is not None or vos is not None:                         # checked for the whole run before the first launch
+            if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T or not isinstance(vos, dict):
+                raise ValueError("VOS scoring: frames [T,H,W,3] shared by the objects, gt uint8 CUDA [T,H,W] and a vos spec")
+            alive = vos.get("alive")
+            if alive is not None:
+                alive = np.asarray(alive)
+                if alive.shape not in ((fr["B"],), (T, fr["B"])):
+                    raise ValueError("vos['alive'] must be [B] or [T,B] booleans")
+            for t in range(T):
+                self._vos_spec(3, want_mask, gt[t], self._vos_at(vos, alive, t))
+            labels = torch.empty((T, fr["H"], fr["W"]), dtype=torch.uint8, device=frames.device)
         masks = None
         if want_mask and self.model.variant != "rpn":
             shape = (T, fr["B"], fr["H"], fr["W"])
@@ -383,9 +480,20 @@ class DeviceTracker(object):
             else:
                 masks = mask_out
         for t in range(T):
-            self.enqueue(frames[t], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[t] if masks is not None else None)
+            self.enqueue(frames[t], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[t] if masks is not None else None,
+                         gt=gt[t] if gt is not None else None, vos=self._vos_at(vos, alive, t) if vos is not None else None,
+                         labels_out=labels[t] if labels is not None else None)
         fr["whole"] = masks
+        if labels is not None:
+            fr["whole_labels"] = labels
         return self.collect()
+
+    @staticmethod
+    def _vos_at(vos, alive, t):
+        """the spec of frame t of a run: a [T,B] 'alive' is cut to its row"""
+        if alive is None or alive.ndim == 1:
+            return vos
+        return dict(vos, alive=alive[t])
 
 
 def rotated_boxes(masks, target_pos, target_sz, min_area=100.0):
