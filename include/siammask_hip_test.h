@@ -34,9 +34,7 @@ extern "C" {
  *   default 1)   "stem_fused" 0|1 (fp16: frame -> conv1 + BN + ReLU -> p0 -> maxpool -> x1 as one launch, stem_pool_kernel; default 1)
  *   "xc_full" 0|1|2 (dw-xcorr: 0 = 5-row bands (default, fastest), 1 = 13-row bands (input read 1.14x instead of 1.8x, slower),
  *   2 = 5-row bands with batched loads (measurement))
- *   "prio" -1..3 (s_setprio of the consumer waves; measured null)   "mask_overlap" 0|1 (mask head on a graph side
- *   branch; measured slower)   "concurrency" 0|1 (fork/join between independent launches; measured slower; applies to
- *   contexts created afterwards)
+ *   "prio" -1..3 (s_setprio of the consumer waves; measured null)
  *   "halo" 0|1|64|128 (3x3 stride-1 convolutions through conv3x3_halo_kernel: off | per-shape choice (default, fp16) |
  *   force that workgroup height)   "halo_db" 0|1 (double-buffered patch for launches of <= one workgroup per CU)
  *   "chain" 0|1 (fp16: Refine's nine sequential convolutions as one launch,
@@ -169,6 +167,11 @@ int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *ker
  * SEQ_YRES_*).  A non-null y_dev means the caller reads that output after the list.  smk_tune_get's "..._last" diagnostics
  * are not touched. */
 int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *sync, int *a_stage);
+
+/* Host only: the activation arena a context of this dtype / variant holds at this pipeline depth (smk_set_pipeline), summed over the
+ * engine's table of arena tensors the way smk_create allocates it -- elements per image, one plane (a split-operand context stores
+ * two), aliased buffers counted once.  Lets the CPU test-suite pin the sizes. */
+int smk_host_arena_elems(int dtype, int variant, int pipe_depth, uint64_t *elems_per_image);
 
 /* Host only: the scalar stage of the tracker (smk_trk_plan / smk_trk_advance) on HOST memory -- the very inline functions the
  * device kernels compile (csrc/tracker_state.h), so that the CPU test-suite can hold them bit for bit against the host loop of

@@ -18,7 +18,6 @@
 #include <cstring>
 #include <functional>
 #include <map>
-#include <set>
 #include <memory>
 #include <string>
 #include <vector>
@@ -35,7 +34,6 @@ using namespace smk;
 // errors
 // ---------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int g_concurrency_default = 0;   // measured slower on MI355X (cross-stream graph edges), see DESIGN.md
 
 static int fail(int code, const char *fmt, ...) {
     char buf[1024];
@@ -210,6 +208,96 @@ static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// arena: ONE row per activation tensor -- what build_arena sizes, what act() hands to the launches, what smk_debug_read names
+// ---------------------------------------------------------------------------------------------
+enum {
+    T_XIN, T_P0, T_X1, T_T1, T_T2, T_R, T_A, T_B, T_P1,
+    T_T1_S, T_T1_2, T_T2_2, T_R_2, T_A_2, T_B_2, T_T1_3, T_T2_3, T_R_3, T_A_3, T_B_3,
+    T_P2, T_SEARCH, T_ZF, T_ZK, T_XS, T_CORR, T_HEAD0,
+    T_RF_D, T_RF_H2A, T_RF_H2B, T_RF_V2A, T_RF_S2, T_RF_U0, T_RF_H1A, T_RF_H1B, T_RF_V1A, T_RF_S1, T_RF_U1, T_RF_H0A, T_RF_H0B, T_RF_V0A, T_RF_S0,
+    T_COUNT
+};
+struct ArenaRow {
+    const char *name;
+    int H, W, C;            // largest per-image shape, one plane
+    bool per_branch;        // C is per branch: x nbranch (cls, loc[, mask] side by side)
+    bool refine;            // a Refine buffer: the sharp variant only, and plain fp16 in a split-operand context (no plane factor in the view)
+    int alias;              // the buffer whose allocation it shares in contexts that cannot run the persistent sequence, or -1
+    int twice_from;         // the pipeline depth (smk_set_pipeline) from which it exists twice, 0 = never
+};
+// layer2 / layer3 have their OWN intermediates (t1_s .. b_3), one layout per buffer (run_backbone): inside the persistent sequence the eight
+// teams are not synchronised with each other, and a buffer that changes its image pitch between layers lets a team that is ahead
+// write over the images of a team that is behind (found at B = 9..14: profiles/r03h_b12_race.txt).  Only f16 contexts can run
+// the sequence kernel; an f32 context launches layer after layer on one stream, where re-using a / b / t1 / t2 / r is safe, so
+// there the stage-private rows are ALIASES of the shared buffers (5.7 M elements per image saved: 1.45 GB at max_batch 64).
+// p0 / p1 / p2 exist twice while frame steps are pipelined (the tail of frame f reads one copy, the front of f + 1 writes the other);
+// head0 from depth 2 (the mask head of frame f runs beside corr_head of f + 1).
+static const ArenaRow ARENA[T_COUNT] = {
+    {"xin", 255, 255, 8, false, false, -1, 0},
+    {"p0", 125, 125, 64, false, false, -1, 1},
+    {"x1", 63, 63, 64, false, false, -1, 0},
+    {"t1", 63, 63, 128, false, false, -1, 0},          // (layer1 uses 64 channels of t1 / t2: the room is t1_s's, which aliases t1)
+    {"t2", 63, 63, 128, false, false, -1, 0},
+    {"r", 63, 63, 256, false, false, -1, 0},
+    {"a", 63, 63, 256, false, false, -1, 0},
+    {"b", 63, 63, 256, false, false, -1, 0},
+    {"p1", 63, 63, 256, false, false, -1, 1},
+    {"t1_s", 63, 63, 128, false, false, T_T1, 0},      // layer2.0's conv1 output in front of the stride
+    {"t1_2", 31, 31, 128, false, false, T_T1, 0},
+    {"t2_2", 31, 31, 128, false, false, T_T2, 0},
+    {"r_2", 31, 31, 512, false, false, T_R, 0},
+    {"a_2", 31, 31, 512, false, false, T_A, 0},
+    {"b_2", 31, 31, 512, false, false, T_B, 0},
+    {"t1_3", 31, 31, 256, false, false, T_T1, 0},
+    {"t2_3", 31, 31, 256, false, false, T_T2, 0},
+    {"r_3", 31, 31, 1024, false, false, T_R, 0},
+    {"a_3", 31, 31, 1024, false, false, T_A, 0},
+    {"b_3", 31, 31, 1024, false, false, T_B, 0},
+    {"p2", 31, 31, 512, false, false, -1, 1},
+    {"search", 31, 31, 256, false, false, -1, 0},
+    {"zf", 7, 7, 256, false, false, -1, 0},
+    {"zk", 5, 5, 256, true, false, -1, 0},
+    {"xs", 29, 29, 256, true, false, -1, 0},
+    {"corr", 25, 25, 256, true, false, -1, 0},
+    {"head0", 25, 25, 256, true, false, -1, 2},
+    {"rf_d", 15, 15, 32, false, true, -1, 0},
+    {"rf_h2a", 15, 15, 32, false, true, -1, 0},
+    {"rf_h2b", 15, 15, 32, false, true, -1, 0},
+    {"rf_v2a", 15, 15, 128, false, true, -1, 0},
+    {"rf_s2", 15, 15, 32, false, true, -1, 0},
+    {"rf_u0", 31, 31, 16, false, true, -1, 0},
+    {"rf_h1a", 31, 31, 16, false, true, -1, 0},
+    {"rf_h1b", 31, 31, 16, false, true, -1, 0},
+    {"rf_v1a", 31, 31, 64, false, true, -1, 0},
+    {"rf_s1", 31, 31, 16, false, true, -1, 0},
+    {"rf_u1", 61, 61, 8, false, true, -1, 0},
+    {"rf_h0a", 61, 61, 8, false, true, -1, 0},
+    {"rf_h0b", 61, 61, 8, false, true, -1, 0},
+    {"rf_v0a", 61, 61, 16, false, true, -1, 0},
+    {"rf_s0", 61, 61, 8, false, true, -1, 0},
+};
+
+static int nbranch_of(int variant) { return variant == SMK_VARIANT_RPN ? 2 : 3; }
+static size_t row_elems(const ArenaRow &t, int variant) { return (size_t)t.H * t.W * t.C * (t.per_branch ? nbranch_of(variant) : 1); }
+static bool row_aliased(const ArenaRow &t, int dtype) { return t.alias >= 0 && dtype != DT_F16; }
+
+// sizing: the elements per image, one plane, of everything a context of this kind allocates at this pipeline depth (aliases counted
+// once, second copies twice); an alias that does not fit the buffer it shares is an error
+static int arena_elems(int dtype, int variant, int depth, uint64_t *total) {
+    uint64_t n = 0;
+    for (const ArenaRow &t : ARENA) {
+        if (t.refine && variant != SMK_VARIANT_SHARP) continue;
+        if (row_aliased(t, dtype)) {
+            if (row_elems(t, variant) > row_elems(ARENA[t.alias], variant)) return fail(SMK_E_STATE, "arena alias %s", t.name);
+            continue;
+        }
+        n += row_elems(t, variant) * ((t.twice_from && depth >= t.twice_from) ? 2 : 1);
+    }
+    *total = n;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------------
 
@@ -224,7 +312,7 @@ struct smk_ctx {
     int template_B = 0;       // batch of the cached template (0 = none)
     int track_B = 0;          // batch of the last track with SMK_TRACK_MASK
     int last_B = 0, last_S = 0, last_nb = 0;
-    const char *p3_buf = "a";   // arena buffer that holds the layer3 output of the last backbone run (debug read-back)
+    int p3_id = T_A;            // arena tensor that holds the layer3 output of the last backbone run (debug read-back)
     bool graph_mode = false;
     hipStream_t cap_stream = nullptr;
     std::map<GraphKey, hipGraphExec_t> graphs;
@@ -234,9 +322,7 @@ struct smk_ctx {
     // packed convolutions
     std::map<std::string, PackedConv> conv;   // keyed by short layer id
     // arena (sized for maxB)
-    std::map<std::string, void *> buf;
-    std::map<std::string, size_t> buf_elems;  // per item
-    std::set<std::string> buf_alias;          // names that share another entry's allocation (never freed themselves)
+    void *buf[T_COUNT][2] = {};               // per ARENA row; [1]: the second copy pipelined steps alternate with
     int *pos_dev = nullptr;
     void *dec_scratch = nullptr;     // decode: per-stream winners of the A workgroups + arrival counters
     float *ks_part = nullptr;        // split-K: f32 partial tiles (KS_PART_FLOATS) and per-tile arrival counters
@@ -271,12 +357,6 @@ struct smk_ctx {
     int anchor_stride = 8;
     double *window_dev = nullptr;        // [25*25] outer(hanning(25), hanning(25))
     double penalty_k = 0.04, window_influence = 0.4;   // config_davis.json hp
-
-    // fork/join concurrency between independent launches (side streams + event pool)
-    bool concurrency = true;
-    hipStream_t side[2] = {nullptr, nullptr};
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_next = 0;
 
     // per-launch profiling (smk_profile): HIP events around every kernel, eager mode only
     bool prof = false;
@@ -322,7 +402,6 @@ struct StepRec {
     bool done_folded = false;        // the chain_mask launch took the tail's "done" mark
     bool ring_ref_folded = false;    // the chain launch took the fp16 logits + the ring cursor
     bool has_seq = false;            // a sequence or gate launch was recorded (both report through the sequence failure flag)
-    bool mask_join_pending = false;  // the mask head runs on a side stream that the end of the step joins
     // handed over from the main part (seq_track) to the tail (seq_refine, step_tail): the deferred mask head
     struct DeferredMask {
         bool have = false;
@@ -352,16 +431,7 @@ struct ProfScope {
     void cancel() { if (idx >= 0 && idx == (int)c->prof_recs.size() - 1) { c->prof_recs.pop_back(); c->prof_pool_next -= 2; } idx = -1; }
 };
 
-// make `to` wait for everything enqueued so far on `from` (captured as a graph dependency)
-static int stream_dep(smk_ctx *c, hipStream_t from, hipStream_t to) {
-    hipEvent_t e = c->ev_pool[c->ev_next++ % c->ev_pool.size()];
-    HIPCHK(hipEventRecord(e, from));
-    HIPCHK(hipStreamWaitEvent(to, e, 0));
-    return 0;
-}
-static bool parallel_ok(const smk_ctx *c) { return c->concurrency && !c->prof && c->side[0] && c->side[1]; }
-
-static int nbranch(const smk_ctx *c) { return c->variant == SMK_VARIANT_RPN ? 2 : 3; }
+static int nbranch(const smk_ctx *c) { return nbranch_of(c->variant); }
 
 static const HostTensor *find_w(const smk_ctx *c, const std::string &name) {
     auto it = c->host_w.find(name);
@@ -630,69 +700,29 @@ static int build_weights(smk_ctx *c) {
 // ---------------------------------------------------------------------------------------------
 // arena
 // ---------------------------------------------------------------------------------------------
-static int alloc_buf(smk_ctx *c, const char *name, size_t elems_per_item) {
-    void *p = nullptr;
+static int alloc_buf(smk_ctx *c, int id, int copy) {
     // (DT_F16X3: two channel planes [hi | lo] per tensor of the trunk; the Refine buffers get them too -- small, and one rule)
-    const size_t bytes = elems_per_item * (c->dtype == DT_F16X3 ? X3_PLANES : 1) * (size_t)c->maxB * esize(c->dtype) + 256;
-    HIPCHK(hipMalloc(&p, bytes));
-    HIPCHK(hipMemset(p, 0, bytes));
-    c->buf[name] = p;
-    c->buf_elems[name] = elems_per_item;
+    const size_t bytes = row_elems(ARENA[id], c->variant) * (c->dtype == DT_F16X3 ? X3_PLANES : 1) * (size_t)c->maxB * esize(c->dtype) + 256;
+    HIPCHK(hipMalloc(&c->buf[id][copy], bytes));
+    HIPCHK(hipMemset(c->buf[id][copy], 0, bytes));
+    return 0;
+}
+
+// the second copies a pipeline depth needs (allocated once, kept for the context's life)
+static int alloc_copies(smk_ctx *c, int depth) {
+    for (int id = 0; id < T_COUNT; ++id)
+        if (ARENA[id].twice_from && depth >= ARENA[id].twice_from && !c->buf[id][1]) CHK(alloc_buf(c, id, 1));
     return 0;
 }
 
 static int build_arena(smk_ctx *c) {
-    const int nb = nbranch(c);
-    CHK(alloc_buf(c, "xin", 255 * 255 * 8));
-    CHK(alloc_buf(c, "p0", 125 * 125 * 64));
-    CHK(alloc_buf(c, "x1", 63 * 63 * 64));
-    CHK(alloc_buf(c, "t1", 63 * 63 * 128));
-    CHK(alloc_buf(c, "t2", 63 * 63 * 128));
-    CHK(alloc_buf(c, "r", 63 * 63 * 256));
-    CHK(alloc_buf(c, "a", 63 * 63 * 256));
-    CHK(alloc_buf(c, "b", 63 * 63 * 256));
-    CHK(alloc_buf(c, "p1", 63 * 63 * 256));
-    // layer2 / layer3 have their OWN intermediates, one layout per buffer (run_backbone): inside the persistent sequence the eight
-    // teams are not synchronised with each other, and a buffer that changes its image pitch between layers lets a team that is ahead
-    // write over the images of a team that is behind (found at B = 9..14: profiles/r03h_b12_race.txt).  Only f16 contexts can run
-    // the sequence kernel; an f32 context launches layer after layer on one stream, where re-using a / b / t1 / t2 / r is safe, so
-    // there the stage-private names are ALIASES of the shared buffers (5.7 M elements per image saved: 1.45 GB at max_batch 64).
-    static const char *STAGE_PRIV[][2] = {{"t1_s", "t1"}, {"t1_2", "t1"}, {"t2_2", "t2"}, {"r_2", "r"}, {"a_2", "a"}, {"b_2", "b"},
-                                          {"t1_3", "t1"}, {"t2_3", "t2"}, {"r_3", "r"}, {"a_3", "a"}, {"b_3", "b"}};
-    static const size_t STAGE_PRIV_ELEMS[] = {63 * 63 * 128, 31 * 31 * 128, 31 * 31 * 128, 31 * 31 * 512, 31 * 31 * 512, 31 * 31 * 512,
-                                              31 * 31 * 256, 31 * 31 * 256, 31 * 31 * 1024, 31 * 31 * 1024, 31 * 31 * 1024};
-    for (size_t i = 0; i < sizeof(STAGE_PRIV) / sizeof(STAGE_PRIV[0]); ++i) {
-        if (c->dtype == DT_F16) CHK(alloc_buf(c, STAGE_PRIV[i][0], STAGE_PRIV_ELEMS[i]));
-        else {
-            if (STAGE_PRIV_ELEMS[i] > c->buf_elems.at(STAGE_PRIV[i][1])) return fail(SMK_E_STATE, "arena alias %s", STAGE_PRIV[i][0]);
-            c->buf[STAGE_PRIV[i][0]] = c->buf.at(STAGE_PRIV[i][1]);
-            c->buf_elems[STAGE_PRIV[i][0]] = STAGE_PRIV_ELEMS[i];
-            c->buf_alias.insert(STAGE_PRIV[i][0]);
-        }
-    }
-    CHK(alloc_buf(c, "p2", 31 * 31 * 512));
-    CHK(alloc_buf(c, "search", 31 * 31 * 256));
-    CHK(alloc_buf(c, "zf", 7 * 7 * 256));
-    CHK(alloc_buf(c, "zk", 5 * 5 * 256 * nb));
-    CHK(alloc_buf(c, "xs", 29 * 29 * 256 * nb));
-    CHK(alloc_buf(c, "corr", 25 * 25 * 256 * nb));
-    CHK(alloc_buf(c, "head0", 25 * 25 * 256 * nb));
-    if (c->variant == SMK_VARIANT_SHARP) {
-        CHK(alloc_buf(c, "rf_d", 15 * 15 * 32));
-        CHK(alloc_buf(c, "rf_h2a", 15 * 15 * 32));
-        CHK(alloc_buf(c, "rf_h2b", 15 * 15 * 32));
-        CHK(alloc_buf(c, "rf_v2a", 15 * 15 * 128));
-        CHK(alloc_buf(c, "rf_s2", 15 * 15 * 32));
-        CHK(alloc_buf(c, "rf_u0", 31 * 31 * 16));
-        CHK(alloc_buf(c, "rf_h1a", 31 * 31 * 16));
-        CHK(alloc_buf(c, "rf_h1b", 31 * 31 * 16));
-        CHK(alloc_buf(c, "rf_v1a", 31 * 31 * 64));
-        CHK(alloc_buf(c, "rf_s1", 31 * 31 * 16));
-        CHK(alloc_buf(c, "rf_u1", 61 * 61 * 8));
-        CHK(alloc_buf(c, "rf_h0a", 61 * 61 * 8));
-        CHK(alloc_buf(c, "rf_h0b", 61 * 61 * 8));
-        CHK(alloc_buf(c, "rf_v0a", 61 * 61 * 16));
-        CHK(alloc_buf(c, "rf_s0", 61 * 61 * 8));
+    uint64_t total = 0;
+    CHK(arena_elems(c->dtype, c->variant, 0, &total));       // (the alias check)
+    for (int id = 0; id < T_COUNT; ++id) {
+        const ArenaRow &t = ARENA[id];
+        if (t.refine && c->variant != SMK_VARIANT_SHARP) continue;
+        if (row_aliased(t, c->dtype)) c->buf[id][0] = c->buf[t.alias][0];      // (a row's alias stands in front of it in the table)
+        else CHK(alloc_buf(c, id, 0));
     }
     HIPCHK(hipMalloc((void **)&c->pos_dev, sizeof(int) * 2 * c->maxB));
     HIPCHK(hipMemset(c->pos_dev, 0, sizeof(int) * 2 * c->maxB));
@@ -715,17 +745,25 @@ static int build_arena(smk_ctx *c) {
     return 0;
 }
 
-static Act act(smk_ctx *c, const char *name, int H, int W, int C) {
-    Act a;
-    // p0 / p1 exist twice while frame steps are pipelined (the tail of frame f reads one copy, the front of f + 1 writes the other)
-    if (c->parity_now && name[0] == 'p' && (name[1] == '0' || name[1] == '1' || name[1] == '2') && !name[2])
-        a.p = c->buf.at(name[1] == '0' ? "p0#1" : (name[1] == '1' ? "p1#1" : "p2#1"));
-    else if (c->parity_now && c->pipe_depth >= 2 && !strcmp(name, "head0")) a.p = c->buf.at("head0#1");   // (depth 2: the mask head of frame f runs beside corr_head of f + 1)
-    else
-    a.p = c->buf.at(name);
-    a.H = H; a.W = W; a.C = C;
-    return a;
+// The view of arena tensor `id` that a launch works on: the row's shape, or (H > 0) a smaller H x W view with the row's channels (the
+// backbone on the 127 x 127 template, the pixel-pair xin, smk_debug_read).  Channels carry the plane factor of a split-operand context;
+// the copy is the one the running step writes.  A view that does not fit its row is an internal error: ACT returns it from the caller.
+static int act(Act &a, smk_ctx *c, int id, int H = 0, int W = 0) {
+    const ArenaRow &t = ARENA[id];
+    // p0 / p1 / p2 follow the parity wherever it is set (the serial entry points read the copy the last tracked frame wrote, whatever
+    // the depth is by then); head0 only while the depth that needs it is on
+    const bool second = c->parity_now && t.twice_from && (t.twice_from == 1 || c->pipe_depth >= t.twice_from);
+    a.p = c->buf[id][second ? 1 : 0];
+    a.H = H > 0 ? H : t.H;
+    a.W = H > 0 ? W : t.W;
+    a.C = t.C * (t.per_branch ? nbranch(c) : 1) * ((c->dtype == DT_F16X3 && !t.refine) ? X3_PLANES : 1);
+    if (!a.p || a.W < 1 || (size_t)a.H * a.W > (size_t)t.H * t.W)
+        return fail(SMK_E_STATE, "internal: view %d x %d of arena tensor %s (%d x %d, copy %d)", a.H, a.W, t.name, t.H, t.W, (int)second);
+    return 0;
 }
+#define ACT(...) ({ Act a_; CHK(act(a_, __VA_ARGS__)); a_; })
+// channel offset of branch g (0 cls, 1 loc, 2 mask) in the per-branch tensors (split operands: a branch's [hi | lo] planes side by side)
+static int branch_off(const smk_ctx *c, int g) { return g * 256 * (c->dtype == DT_F16X3 ? X3_PLANES : 1); }
 
 // ---------------------------------------------------------------------------------------------
 // launch helpers
@@ -904,11 +942,10 @@ static void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, co
 static int seq_flush(smk_ctx *c, StepRec &rec, int B, hipStream_t s) {
     const size_t n = c->seq.rec.size();
     if (!n) return 0;
-    auto buf = [c](const char *name) -> const void * { auto it = c->buf.find(name); return it == c->buf.end() ? nullptr : it->second; };
-    // read behind the list: p2 (Refine) and what smk_debug_read can name
-    std::vector<const void *> read_after;
-    for (const char *name : {"p2", c->p3_buf, "search", "zf", "xs"})
-        if (buf(name)) read_after.push_back(buf(name));
+    // read behind the list: p2 (Refine) and what smk_debug_read can name -- the copies this step writes
+    const void *p2 = ACT(c, T_P2).p;
+    std::vector<const void *> read_after{p2};
+    for (int id : {c->p3_id, (int)T_SEARCH, (int)T_ZF, (int)T_XS}) read_after.push_back(ACT(c, id).p);
     g_seq_last = plan_seq(c->seq.rec, {B, c->seq_grid >> 3, c->seq_xch != nullptr}, nullptr, read_after);
     for (size_t i0 = 0; i0 < n; i0 += SEQ_MAX) {
         SeqArgs a;
@@ -938,7 +975,7 @@ static int seq_flush(smk_ctx *c, StepRec &rec, int B, hipStream_t s) {
         snprintf(idn, sizeof(idn), "seq[%s..%s]", r[0].id.c_str(), r[a.n - 1].id.c_str());
         const double fr = (double)a.n / (double)n;
         ProfScope ps(c, s, idn, "conv_seq", c->seq.flop * fr, c->seq.bytes * fr);
-        ps.ext_bytes(seq_fabric_bytes(a.L, a.n, B, buf("p2")));          // (p2: Refine reads it later)
+        ps.ext_bytes(seq_fabric_bytes(a.L, a.n, B, p2));          // (p2: Refine reads it later)
         if (launch_conv_seq(a, c->seq_grid, s))
             return fail(SMK_E_HIP, "launch of %s failed: %s", idn, hipGetErrorString(hipGetLastError()));
         c->seq_pending = rec.has_seq = true;             // (smk_seq_sync_check: the flag is worth a look once this has drained)
@@ -1128,7 +1165,7 @@ static int run_conv_jobs(smk_ctx *c, const std::vector<ConvJob> &jobs, int B, in
 // Returns 1 when the pair is not eligible (the caller then issues the two convolutions), 0 when it was launched.
 static int run_conv_pair(smk_ctx *c, const char *id3, const Act &in3, const Act &out3, const ConvOpt &o3, const char *id1,
                          const Act &out1, const ConvOpt &o1, int B, hipStream_t s) {
-    if (c->dtype != DT_F16 || !g_tune.pair_launch || c->seq_on || parallel_ok(c) || (c->prof && !c->prof_merge)) return 1;
+    if (c->dtype != DT_F16 || !g_tune.pair_launch || c->seq_on || (c->prof && !c->prof_merge)) return 1;
     // Measured (profiles/r04h_pair_launch_ab.txt, r04i_pair64_ab.txt; whole step, one process per batch, off / on / off / on):
     //   32-row tiles (c3c1_tile):  B = 1 +2 %, B = 4 -1.0 %, B = 10 -5..8 %, B = 32 0, B = 64 +1.2 %
     //   64-row tiles (c3c1s_tile): B = 1 +7 %, B = 10 -10..11 %, B = 32 -5.0 %, B = 64 -5.2 %
@@ -1164,19 +1201,18 @@ static int run_conv_pair(smk_ctx *c, const char *id3, const Act &in3, const Act 
 // phase: PH_FRONT = stem + maxpool + layer1 (p0, p1), PH_BACK = layer2 .. adjust from the kept p1; both = the whole backbone.
 // The pipelined frame step (smk_set_pipeline) runs the two halves as separate graphs.
 enum { PH_FRONT = 1, PH_BACK = 2, PH_ALL = 3 };
-// search_nb / search_nbt > 0 (the search branch's callers): conv_search x search_nb (models/rpn.py:50-54, N-fused) is issued HERE, behind adjust
+// search_nb > 0 (the search branch's callers): conv_search x search_nb (models/rpn.py:50-54, N-fused) is issued HERE, behind adjust
 // and in front of the sequence's flush, so that it becomes the persistent launch's last record (round 6, smk_tune "seq_search"): no kernel
 // boundary, no cold start, the weights behind the team's own L2 -- the register-fed 128 x 256 tiles run at 0.58 us per K tile inside the
 // sequence where the stand-alone launch needs 0.9.  *search_done tells the caller that conv_search has been issued (recorded or launched).
 static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, hipStream_t s, int phase = PH_ALL, int search_nb = 0,
-                        int search_nbt = 0, bool *search_done = nullptr) {
-    // DT_F16X3: the trunk's tensors are stored as [hi | lo] planes -- twice the channels (smk_kernels.h)
-    auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
+                        bool *search_done = nullptr) {
+    // (DT_F16X3: the trunk's tensors are stored as [hi | lo] planes -- act() gives twice the channels, smk_kernels.h)
     const int s0 = (S - 7) / 2 + 1;          // conv1 7x7 s2 p0
     const int s1 = (s0 + 2 - 3) / 2 + 1;     // maxpool 3/2/1
     const int s2 = (s1 - 3) / 2 + 1;         // layer2 3x3 s2 p0
-    Act p0 = act(c, "p0", s0, s0, X(64));
-    Act x1 = act(c, "x1", s1, s1, X(64));
+    Act p0 = ACT(c, T_P0, s0, s0);
+    Act x1 = ACT(c, T_X1, s1, s1);
     auto stem_it = c->conv.find("stem");
     if (stem_it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv stem not packed");
     if (!(phase & PH_FRONT)) {
@@ -1189,7 +1225,7 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
         if (launch_stem_pool(sp_, s)) return fail(SMK_E_HIP, "stem_pool launch failed: %s", hipGetErrorString(hipGetLastError()));
     } else if (c->dtype == DT_F16X3) {
         // split operands: frame -> [hi | lo] x 8 channels, the 7x7 stem as a generic convolution on them, the pool on hi + lo
-        Act xin = act(c, "xin", S, S, X3_PLANES * 8);
+        Act xin = ACT(c, T_XIN, S, S);
         CvtInParams ci{x, xin.p, B, 3, S, S, 8, 0, 1};
         {
             ProfScope ps(c, s, "cvt_in", "cvt_in_x3", 0.0, (double)B * S * S * (3 * 4 + X3_PLANES * 8 * 2));
@@ -1204,7 +1240,7 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
             if (launch_maxpool_x3(pp, s)) return fail(SMK_E_HIP, "maxpool_x3 launch failed");
         }
     } else {
-        Act xin = act(c, "xin", S, (S + 1) / 2, 8);            // pixel-pair layout (see pack_stem)
+        Act xin = ACT(c, T_XIN, S, (S + 1) / 2);            // pixel-pair layout (see pack_stem)
         CvtInParams ci{x, xin.p, B, 3, S, S, 8, 1};
         {
             ProfScope ps(c, s, "cvt_in", "cvt_in", 0.0, (double)B * S * S * (3 * 4 + 8 * esize(c->dtype)));
@@ -1228,16 +1264,15 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
         SeqScope(smk_ctx *c_, bool on) : c(c_) { c->seq_on = on; }
         ~SeqScope() { c->seq_on = false; c->seq.clear(); }
     } seq_scope(c, false);
-    const bool seq_ok = seq_wanted(c, B) && !parallel_ok(c);
+    const bool seq_ok = seq_wanted(c, B);
     bool c1_done = false;                     // the previous block's conv3 launch already computed this block's conv1 (run_conv_pair)
     bool adjust_done = false;
     for (int st = 0; st < 3; ++st) {
         // layer1 stays on the per-launch kernels: short K and 63 tiles of 64 rows per image (two rounds for 32 workgroups)
         // made it 140 us inside the sequence against 96 us as launches (SMK_SEQ_CLK, profiles/r02_seq_ab.txt)
-        if (st == 0 && !(phase & PH_FRONT)) { cur = act(c, "p1", s1, s1, X(256)); continue; }
+        if (st == 0 && !(phase & PH_FRONT)) { cur = ACT(c, T_P1, s1, s1); continue; }
         if (st == 1 && !(phase & PH_BACK)) { c->last_B = B; c->last_S = S; return 0; }
         if (seq_ok && st == g_tune.seq_first_stage) c->seq_on = true;
-        const int planes = STAGE_PLANES[st];
         for (int b = 0; b < STAGE_BLOCKS[st]; ++b) {
             char idb[32];
             snprintf(idb, sizeof(idb), "l%d.%d.", st + 1, b);
@@ -1254,8 +1289,7 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
                     !f1->second.w_frag16 || !f2->second.w_frag16 || !f3->second.w_frag16 || (b == 0 && !fd->second.w_frag16))
                     return fail(SMK_E_STATE, "internal: layer1 block %d not packed for l1_block_kernel", b);
                 const bool last1 = b == STAGE_BLOCKS[0] - 1;
-                const char *on = last1 ? "p1" : ((b & 1) ? "b" : "a");
-                Act out1 = act(c, on, sp, sp, X(256));
+                Act out1 = ACT(c, last1 ? T_P1 : ((b & 1) ? T_B : T_A), sp, sp);
                 L1BlockParams lp;
                 memset(&lp, 0, sizeof(lp));
                 lp.x = cur.p; lp.y = out1.p;
@@ -1283,43 +1317,35 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
                 cur = out1;
                 continue;
             }
-            // one layout per buffer (see build_arena): stage-private names, and layer2.0's pre-stride conv1 output on its own
-            static const char *T1N[3] = {"t1", "t1_2", "t1_3"}, *T2N[3] = {"t2", "t2_2", "t2_3"}, *RN[3] = {"r", "r_2", "r_3"},
-                              *AN[3] = {"a", "a_2", "a_3"}, *BN[3] = {"b", "b_2", "b_3"};
-            Act t1 = act(c, stride == 2 ? "t1_s" : T1N[st], sp, sp, X(planes));
-            Act t2 = act(c, T2N[st], so, so, X(planes));
+            // one layout per buffer (see ARENA): stage-private rows, and layer2.0's pre-stride conv1 output on its own
+            static const int T1N[3] = {T_T1, T_T1_2, T_T1_3}, T2N[3] = {T_T2, T_T2_2, T_T2_3}, RN[3] = {T_R, T_R_2, T_R_3},
+                             AN[3] = {T_A, T_A_2, T_A_3}, BN[3] = {T_B, T_B_2, T_B_3};
+            Act t1 = ACT(c, stride == 2 ? T_T1_S : T1N[st], sp, sp);
+            Act t2 = ACT(c, T2N[st], so, so);
+            if (st == 0) { t1.C /= 2; t2.C /= 2; }       // layer1's 64 planes in rows that are sized for layer2.0's 128 (t1_s aliases t1)
             ConvOpt o1; o1.relu = 1;
             ConvOpt o2; o2.relu = 1; o2.stride = stride; o2.pad = pad2; o2.dil = dil;
             Act res = cur;
-            const bool par = parallel_ok(c);
             const std::string id_ds = id + "ds", id_c1 = id + "c1";
             if (b == 0) {
                 // the shortcut conv only depends on the block input: it shares a launch with conv1
-                Act r = act(c, RN[st], so, so, X(planes * 4));
+                Act r = ACT(c, RN[st], so, so);
                 ConvOpt od;
                 if (st == 0) { od.stride = 1; od.pad = 0; }          // 1x1
                 else if (st == 1) { od.stride = 2; od.pad = 0; }     // 3x3 s2 p0
                 else { od.stride = 1; od.pad = 1; }                  // 3x3 s1 p1
-                if (par) {
-                    hipStream_t sd = c->side[0];
-                    CHK(stream_dep(c, s, sd));
-                    CHK(run_conv(c, id_ds.c_str(), cur, &r, B, od, sd, &rec));
-                    CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s, &rec));
-                } else {
-                    CHK(run_conv_jobs(c, {{id_ds.c_str(), &cur, &r, od}, {id_c1.c_str(), &cur, &t1, o1}}, B, 0, s, &rec));
-                }
+                CHK(run_conv_jobs(c, {{id_ds.c_str(), &cur, &r, od}, {id_c1.c_str(), &cur, &t1, o1}}, B, 0, s, &rec));
                 res = r;
             } else if (!c1_done) {
                 CHK(run_conv(c, id_c1.c_str(), cur, &t1, B, o1, s, &rec));
             }
             c1_done = false;
             CHK(run_conv(c, (id + "c2").c_str(), t1, &t2, B, o2, s, &rec));
-            if (b == 0 && par) CHK(stream_dep(c, c->side[0], s));
             const bool last = b == STAGE_BLOCKS[st] - 1;
-            const char *oname = last ? (st == 0 ? "p1" : st == 1 ? "p2" : AN[2]) : ((b & 1) ? BN[st] : AN[st]);
-            if (last && st == 2 && cur.p == c->buf.at(AN[2])) oname = BN[2];
-            Act out = act(c, oname, so, so, X(planes * 4));
-            if (last && st == 2) c->p3_buf = oname;
+            int oid = last ? (st == 0 ? T_P1 : st == 1 ? T_P2 : AN[2]) : ((b & 1) ? BN[st] : AN[st]);
+            if (last && st == 2 && cur.p == c->buf[AN[2]][0]) oid = BN[2];
+            Act out = ACT(c, oid, so, so);
+            if (last && st == 2) c->p3_id = oid;
             ConvOpt o3; o3.relu = 1; o3.res = &res; o3.res_mode = RES_PRE_RELU;
             // outside the persistent sequence: conv3 and the NEXT 1x1 convolution (the following block's conv1, or adjust behind
             // layer3 on the search branch) as one launch where the pair routine has the shape (layer2 / layer3 identity blocks)
@@ -1328,13 +1354,13 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
                 if (!last) {
                     char idn[32];
                     snprintf(idn, sizeof(idn), "l%d.%d.c1", st + 1, b + 1);
-                    Act t1n = act(c, T1N[st], so, so, X(planes));
+                    Act t1n = ACT(c, T1N[st], so, so);
                     ConvOpt o1n; o1n.relu = 1;
                     paired = run_conv_pair(c, (id + "c3").c_str(), t2, out, o3, idn, t1n, o1n, B, s);
                     if (paired < 0) return paired;
                     if (paired == 0) c1_done = true;
                 } else if (st == 2 && so >= 20) {
-                    Act se = act(c, "search", so, so, X(256));
+                    Act se = ACT(c, T_SEARCH, so, so);
                     ConvOpt oa0;
                     paired = run_conv_pair(c, (id + "c3").c_str(), t2, out, o3, "adjust", se, oa0, B, s);
                     if (paired < 0) return paired;
@@ -1349,16 +1375,16 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
     // adjust: 1x1 1024->256 + BN, no ReLU; template (15 < 20): centre crop [4:-4] (custom.py:21-24)
     ConvOpt oa;
     if (sp < 20) {
-        Act zf = act(c, "zf", sp - 8, sp - 8, X(256));
+        Act zf = ACT(c, T_ZF, sp - 8, sp - 8);
         oa.win = true; oa.Hl = oa.Wl = sp - 8; oa.org_y = oa.org_x = 4;
         CHK(run_conv(c, "adjust", cur, &zf, B, oa, s, &rec));
     } else if (!adjust_done) {
-        Act se = act(c, "search", sp, sp, X(256));
+        Act se = ACT(c, T_SEARCH, sp, sp);
         CHK(run_conv(c, "adjust", cur, &se, B, oa, s, &rec));
     }
     if (c->seq_on && search_nb > 0 && sp >= 20 && g_tune.seq_search && c->seq.rec.size() < (size_t)SEQ_MAX) {
-        Act se = act(c, "search", sp, sp, X(256));
-        Act xs = act(c, "xs", sp - 2, sp - 2, X(256 * search_nbt));
+        Act se = ACT(c, T_SEARCH, sp, sp);
+        Act xs = ACT(c, T_XS, sp - 2, sp - 2);
         ConvOpt o; o.relu = 1; o.n_override = 256 * search_nb;
         CHK(run_conv(c, "conv_search", se, &xs, B, o, s, &rec));         // (not eligible for the sequence: flushed + launched, still done)
         if (search_done) *search_done = true;
@@ -1369,29 +1395,32 @@ static int run_backbone(smk_ctx *c, StepRec &rec, const float *x, int B, int S, 
 }
 
 static int seq_template(smk_ctx *c, StepRec &rec, const float *z, int B, hipStream_t s) {
-    auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
     CHK(run_backbone(c, rec, z, B, 127, s));
-    const int nb = nbranch(c);
-    Act zf = act(c, "zf", 7, 7, X(256));
-    Act zk = act(c, "zk", 5, 5, X(256 * nb));
+    Act zf = ACT(c, T_ZF);
+    Act zk = ACT(c, T_ZK);
     ConvOpt o; o.relu = 1;                       // conv_kernel: 3x3 p0 + BN + ReLU (rpn.py:45-49), all branches fused
     CHK(run_conv(c, "conv_kernel", zf, &zk, B, o, s));
     return 0;
 }
 
-// defer_mask_join: the 63x63 mask head (HBM-write bound, nothing on the device reads it) is forked
-// to a side stream and only joined by the caller at the end of the frame step, so that it runs
-// beside the small decode / Refine launches instead of in front of them
+// the mask branch's head.3 (1x1, 256 -> 63 x 63 logits, NCHW f32) on its slice of head0 -- a plain fp16 pack on the branch's hi plane in
+// a split-operand context: the operands of seq_track's launch, of the form handed to the Refine chain launch and of step_tail's
+static int mask_head_args(smk_ctx *c, float *mask, Act &h0, ConvOpt &om) {
+    CHK(act(h0, c, T_HEAD0));
+    om.nchw_out = mask;
+    om.cin_off = branch_off(c, 2);
+    return 0;
+}
+
 static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags, float *cls, float *loc, float *mask,
-                     hipStream_t s, bool defer_mask_join = false, int phase = PH_ALL) {
-    auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
+                     hipStream_t s, int phase = PH_ALL) {
     const bool x3 = c->dtype == DT_F16X3;
     const int nbt = nbranch(c);                                   // branches laid out in the buffers
     const int nb = (flags & SMK_TRACK_MASK) ? nbt : 2;            // branches computed
     bool search_done = false;
-    CHK(run_backbone(c, rec, x, B, 255, s, phase, nb, nbt, &search_done));
-    Act se = act(c, "search", 31, 31, X(256));
-    Act xs = act(c, "xs", 29, 29, X(256 * nbt));
+    CHK(run_backbone(c, rec, x, B, 255, s, phase, nb, &search_done));
+    Act se = ACT(c, T_SEARCH);
+    Act xs = ACT(c, T_XS);
     ConvOpt o; o.relu = 1; o.n_override = 256 * nb;               // conv_search x nb as one N-fused GEMM
     if (!search_done) CHK(run_conv(c, "conv_search", se, &xs, B, o, s));
     if (rec.gate_late) {
@@ -1401,21 +1430,20 @@ static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags,
         if (launch_pipe_gate(c->pipe_cnt, c->seq_err, c->seq_err_hdev, s, 0, nullptr, c->pipe_cnt + 8)) return fail(SMK_E_HIP, "pipe_gate launch failed");
         rec.has_seq = true;
     }
-    Act corr = act(c, "corr", 25, 25, X(256 * nbt));
-    Act h0 = act(c, "head0", 25, 25, X(256 * nbt));
-    const bool par = parallel_ok(c);
+    Act zk = ACT(c, T_ZK);
+    Act corr = ACT(c, T_CORR);
+    Act h0 = ACT(c, T_HEAD0);
     const bool want_mask = (flags & SMK_TRACK_MASK) && !(flags & SMK_TRACK_NO_MASK_HEAD);
-    hipStream_t s_loc = par ? c->side[0] : s, s_cls = (par && want_mask) ? c->side[1] : s;
     // fp16: correlation + head.0 + cls / loc head.3 as ONE launch (corr_head.hip); the mask branch's head.3 follows as before
     bool fused_heads = false;
-    if (c->dtype == DT_F16 && g_tune.corr_head && !par) {
+    if (c->dtype == DT_F16 && g_tune.corr_head) {
         auto ih = c->conv.find("head0"), ic = c->conv.find("cls3"), il = c->conv.find("loc3");
         if (ih != c->conv.end() && ic != c->conv.end() && il != c->conv.end() && ih->second.w_frag && ic->second.w_frag && il->second.w_frag &&
             ih->second.Kpad == 256 && ic->second.Kpad == 256 && il->second.Kpad == 256 && ih->second.group_rows == 256 &&
             ic->second.N == 10 && il->second.N == 20) {
             CorrHeadParams hp;
             memset(&hp, 0, sizeof(hp));
-            hp.xs = (const _Float16 *)xs.p; hp.zk = (const _Float16 *)c->buf.at("zk"); hp.corr = (_Float16 *)corr.p; hp.h0 = (_Float16 *)h0.p;
+            hp.xs = (const _Float16 *)xs.p; hp.zk = (const _Float16 *)zk.p; hp.corr = (_Float16 *)corr.p; hp.h0 = (_Float16 *)h0.p;
             hp.w0_frag = ih->second.w_frag; hp.b0 = ih->second.bias; hp.w0_bytes = (unsigned)((size_t)ih->second.rows * ih->second.Kpad * 2);
             hp.w3_frag[0] = ic->second.w_frag; hp.b3[0] = ic->second.bias; hp.out3[0] = cls; hp.n3[0] = 10;
             hp.w3_frag[1] = il->second.w_frag; hp.b3[1] = il->second.bias; hp.out3[1] = loc; hp.n3[1] = 20;
@@ -1430,7 +1458,7 @@ static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags,
         }
     }
     if (!fused_heads) {
-    XcorrParams xp{xs.p, c->buf.at("zk"), corr.p, B, 29, 29, 5, 5, 25, 25, 256 * nb, 256 * nbt};
+    XcorrParams xp{xs.p, zk.p, corr.p, B, 29, 29, 5, 5, 25, 25, 256 * nb, 256 * nbt};
     {
         // algorithmic bytes per branch-item: read 256*(29*29 + 5*5), write 256*25*25 elements
         const double xb = (double)B * nb * 256.0 * (29 * 29 + 25 + 625) * esize(c->dtype);
@@ -1440,37 +1468,28 @@ static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags,
     }
     ConvOpt oh; oh.relu = 1; oh.groups = nb;                      // head.0 1x1 + BN + ReLU per branch
     CHK(run_conv(c, "head0", corr, &h0, B, oh, s));
-    // the three head.3 convs are independent: cls / loc / mask side by side
-    if (par) { CHK(stream_dep(c, s, s_loc)); if (s_cls != s) CHK(stream_dep(c, s, s_cls)); }
-    ConvOpt oc; oc.nchw_out = cls; oc.cin_off = 0;
-    ConvOpt ol; ol.nchw_out = loc; ol.cin_off = x3 ? X3_PLANES * 256 : 256;      // (x3: a branch's [hi | lo] planes side by side)
-    if (par) {
-        CHK(run_conv(c, "cls3", h0, nullptr, B, oc, s_cls));
-        CHK(run_conv(c, "loc3", h0, nullptr, B, ol, s_loc));
-    } else {
-        CHK(run_conv_jobs(c, {{"cls3", &h0, nullptr, oc}, {"loc3", &h0, nullptr, ol}}, B, 1, s));
-    }
+    // the cls / loc head.3 convs are independent: one launch
+    ConvOpt oc; oc.nchw_out = cls; oc.cin_off = branch_off(c, 0);
+    ConvOpt ol; ol.nchw_out = loc; ol.cin_off = branch_off(c, 1);
+    CHK(run_conv_jobs(c, {{"cls3", &h0, nullptr, oc}, {"loc3", &h0, nullptr, ol}}, B, 1, s));
     }
     if (want_mask) {
-        ConvOpt om; om.nchw_out = mask; om.cin_off = x3 ? 2 * X3_PLANES * 256 : 512;      // (x3: plain fp16 pack on the hi plane of the mask branch)
-        if (rec.defer_mask && !par) {
+        Act hm;
+        ConvOpt om;
+        CHK(mask_head_args(c, mask, hm, om));
+        if (rec.defer_mask) {
             // handed to seq_refine: it runs inside the chain launch, beside the (B-workgroup) Refine chain
             auto it = c->conv.find("mask3");
             if (it == c->conv.end()) return fail(SMK_E_STATE, "internal: conv mask3 not packed");
-            CHK(conv_params(conv_env(c), it->second, h0, nullptr, B, om, rec.deferred_mask.p));
+            CHK(conv_params(conv_env(c), it->second, hm, nullptr, B, om, rec.deferred_mask.p));
             const ConvParams &mp = rec.deferred_mask.p;
             rec.deferred_mask.flop = 2.0 * mp.M * (double)mp.N * mp.kh * mp.kw * mp.Ci;
             rec.deferred_mask.bytes = (double)mp.M * mp.Ci * esize(c->dtype) + (double)mp.M * mp.N * 4 + (double)mp.N * mp.Ci * esize(c->dtype);
             rec.deferred_mask.have = true;
-        } else if (defer_mask_join && !par && !c->prof && g_tune.mask_overlap && c->side[0]) {
-            CHK(stream_dep(c, s, c->side[0]));
-            CHK(run_conv(c, "mask3", h0, nullptr, B, om, c->side[0]));
-            rec.mask_join_pending = true;
         } else {
-            CHK(run_conv(c, "mask3", h0, nullptr, B, om, s));
+            CHK(run_conv(c, "mask3", hm, nullptr, B, om, s));
         }
     }
-    if (par) { CHK(stream_dep(c, s_loc, s)); if (s_cls != s) CHK(stream_dep(c, s_cls, s)); }
     c->last_nb = nb;
     return 0;
 }
@@ -1479,41 +1498,25 @@ static int seq_track(smk_ctx *c, StepRec &rec, const float *x, int B, int flags,
 // part: 0 = all of it; 1 = the window convolutions + deconv + v*.2 (what reads the kept features and the position); 2 = the chain launch
 // (what reads only part 1's outputs and, for the mask head, head0).  The split exists for the fp16 chain path only (depth-2 pipelining).
 static bool refine_splittable(const smk_ctx *c, int B) {
-    return kdtype(c->dtype) == DT_F16 && g_tune.chain && !parallel_ok(c) && g_tune.merge && (g_tune.merge == 2 || B <= g_tune.merge_max_batch);
+    return kdtype(c->dtype) == DT_F16 && g_tune.chain && g_tune.merge && (g_tune.merge == 2 || B <= g_tune.merge_max_batch);
 }
 static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s, int part = 0) {
     const int *pos = c->pos_dev;
     // (DT_F16X3: Refine runs in plain fp16 on the hi planes of the kept trunk tensors -- channel stride 2 C, first C channels)
-    auto X = [c](int C) { return c->dtype == DT_F16X3 ? X3_PLANES * C : C; };
-    Act corr = act(c, "corr", 25, 25, X(256 * 3));
-    Act p0 = act(c, "p0", 125, 125, X(64)), p1 = act(c, "p1", 63, 63, X(256)), p2 = act(c, "p2", 31, 31, X(512));
-    // The three window convs v2.0 / v1.0 / v0.0 (the heavy part of Refine) depend only on the
-    // kept backbone features and pos: they run on a side stream beside deconv -> h2 -> ...
+    Act corr = ACT(c, T_CORR);
+    Act p0 = ACT(c, T_P0), p1 = ACT(c, T_P1), p2 = ACT(c, T_P2);
+    // The three window convs v2.0 / v1.0 / v0.0 (the heavy part of Refine) depend only on the kept backbone features and pos
     ConvOpt r3; r3.pad = 1; r3.relu = 1;
     ConvOpt w2 = r3; w2.win = true; w2.Hl = w2.Wl = 15; w2.pos = pos; w2.pos_mul = 1; w2.pos_add = -4;   // pad 4 (:135)
     ConvOpt w1 = r3; w1.win = true; w1.Hl = w1.Wl = 31; w1.pos = pos; w1.pos_mul = 2; w1.pos_add = -8;   // pad 8 (:134)
     ConvOpt w0 = r3; w0.win = true; w0.Hl = w0.Wl = 61; w0.pos = pos; w0.pos_mul = 4; w0.pos_add = -16;  // pad 16 (:133)
-    const bool par = parallel_ok(c);
-    hipEvent_t ev_v2 = nullptr, ev_v1 = nullptr, ev_v0 = nullptr;
-    if (par) {
-        hipStream_t sd = c->side[0];
-        CHK(stream_dep(c, s, sd));
-        Act v2a_ = act(c, "rf_v2a", 15, 15, 128), v1a_ = act(c, "rf_v1a", 31, 31, 64), v0a_ = act(c, "rf_v0a", 61, 61, 16);
-        CHK(run_conv(c, "v2.0", p2, &v2a_, B, w2, sd));
-        ev_v2 = c->ev_pool[c->ev_next++ % c->ev_pool.size()];
-        HIPCHK(hipEventRecord(ev_v2, sd));
-        CHK(run_conv(c, "v1.0", p1, &v1a_, B, w1, sd));
-        ev_v1 = c->ev_pool[c->ev_next++ % c->ev_pool.size()];
-        HIPCHK(hipEventRecord(ev_v1, sd));
-        CHK(run_conv(c, "v0.0", p0, &v0a_, B, w0, sd));
-        ev_v0 = c->ev_pool[c->ev_next++ % c->ev_pool.size()];
-        HIPCHK(hipEventRecord(ev_v0, sd));
-    }
     // deconv(corr_feature[:, :, y, x]) -> [15,15,32]            (:145,:149)
-    Act d1 = act(c, "rf_d", 1, 1, 15 * 15 * 32);
-    ConvOpt od; od.win = true; od.Hl = od.Wl = 1; od.pos = pos; od.pos_mul = 1; od.cin_off = c->dtype == DT_F16X3 ? 2 * X3_PLANES * 256 : 512;
-    Act v2a = act(c, "rf_v2a", 15, 15, 128), v1a = act(c, "rf_v1a", 31, 31, 64), v0a = act(c, "rf_v0a", 61, 61, 16);
-    const bool merged = !par && (!c->prof || c->prof_merge) && g_tune.merge && (g_tune.merge == 2 || B <= g_tune.merge_max_batch);
+    Act d = ACT(c, T_RF_D);
+    Act d1 = d;                                   // ... which the deconv GEMM writes as one pixel of 15 * 15 * 32 channels (pack_deconv)
+    d1.H = d1.W = 1; d1.C = d.H * d.W * d.C;
+    ConvOpt od; od.win = true; od.Hl = od.Wl = 1; od.pos = pos; od.pos_mul = 1; od.cin_off = branch_off(c, 2);
+    Act v2a = ACT(c, T_RF_V2A), v1a = ACT(c, T_RF_V1A), v0a = ACT(c, T_RF_V0A);
+    const bool merged = (!c->prof || c->prof_merge) && g_tune.merge && (g_tune.merge == 2 || B <= g_tune.merge_max_batch);
     if (merged && part != 2) {
         // the window convs only depend on the kept backbone features and pos: one launch with deconv
         w2.tile_code = 4;     // 64x64 (256-byte K tile): v2.0's long K chain sets the pace
@@ -1524,8 +1527,7 @@ static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s
     } else if (part != 2) {
         CHK(run_conv(c, "deconv", corr, &d1, B, od, s));
     }
-    Act d = act(c, "rf_d", 15, 15, 32);
-    if (kdtype(c->dtype) == DT_F16 && g_tune.chain && !par) {       // (split-operand contexts: Refine is plain fp16 on the hi planes -- same launches)
+    if (kdtype(c->dtype) == DT_F16 && g_tune.chain) {       // (split-operand contexts: Refine is plain fp16 on the hi planes -- same launches)
         // fp16: v*.2 in one merged launch (they only depend on v*.0), then the nine sequential convolutions
         // h2 -> post0 -> h1 -> post1 -> h0 -> post2 as ONE launch with the activations in LDS (refine_chain.hip)
         if (!merged && part != 2) {
@@ -1533,7 +1535,7 @@ static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s
             CHK(run_conv(c, "v1.0", p1, &v1a, B, w1, s));
             CHK(run_conv(c, "v0.0", p0, &v0a, B, w0, s));
         }
-        Act V2 = act(c, "rf_s2", 15, 15, 32), V1 = act(c, "rf_s1", 31, 31, 16), V0 = act(c, "rf_s0", 61, 61, 8);
+        Act V2 = ACT(c, T_RF_S2), V1 = ACT(c, T_RF_S1), V0 = ACT(c, T_RF_S0);
         ConvOpt r3l = r3;
         r3l.tile_code = g_tune.rf_tile2;          // (A/B knob: workgroup tile of the merged v*.2 launch; 0 = the lead's own choice, 64x64)
         ConvOpt r3w = r3;
@@ -1609,36 +1611,33 @@ static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s
         return 0;
     }
     // stage 2 @15x15                                             (:150)
-    Act h2a = act(c, "rf_h2a", 15, 15, 32), h2b = act(c, "rf_h2b", 15, 15, 32);
+    Act h2a = ACT(c, T_RF_H2A), h2b = ACT(c, T_RF_H2B);
     CHK(run_conv(c, "h2.0", d, &h2a, B, r3, s));
     CHK(run_conv(c, "h2.2", h2a, &h2b, B, r3, s));
-    Act s2 = act(c, "rf_s2", 15, 15, 32);
-    if (par) CHK(hipStreamWaitEvent(s, ev_v2, 0) == hipSuccess ? 0 : fail(SMK_E_HIP, "wait ev_v2"));
-    else if (!merged) CHK(run_conv(c, "v2.0", p2, &v2a, B, w2, s));
+    Act s2 = ACT(c, T_RF_S2);
+    if (!merged) CHK(run_conv(c, "v2.0", p2, &v2a, B, w2, s));
     ConvOpt a2 = r3; a2.res = &h2b; a2.res_mode = RES_POST_RELU;
     CHK(run_conv(c, "v2.2", v2a, &s2, B, a2, s));
-    Act u0 = act(c, "rf_u0", 31, 31, 16);
+    Act u0 = ACT(c, T_RF_U0);
     ConvOpt pu0; pu0.pad = 1; pu0.ups = true; pu0.Hl = pu0.Wl = 31;
     CHK(run_conv(c, "post0", s2, &u0, B, pu0, s));
     // stage 1 @31x31                                             (:151)
-    Act h1a = act(c, "rf_h1a", 31, 31, 16), h1b = act(c, "rf_h1b", 31, 31, 16);
+    Act h1a = ACT(c, T_RF_H1A), h1b = ACT(c, T_RF_H1B);
     CHK(run_conv(c, "h1.0", u0, &h1a, B, r3, s));
     CHK(run_conv(c, "h1.2", h1a, &h1b, B, r3, s));
-    Act s1 = act(c, "rf_s1", 31, 31, 16);
-    if (par) CHK(hipStreamWaitEvent(s, ev_v1, 0) == hipSuccess ? 0 : fail(SMK_E_HIP, "wait ev_v1"));
-    else if (!merged) CHK(run_conv(c, "v1.0", p1, &v1a, B, w1, s));
+    Act s1 = ACT(c, T_RF_S1);
+    if (!merged) CHK(run_conv(c, "v1.0", p1, &v1a, B, w1, s));
     ConvOpt a1 = r3; a1.res = &h1b; a1.res_mode = RES_POST_RELU;
     CHK(run_conv(c, "v1.2", v1a, &s1, B, a1, s));
-    Act u1 = act(c, "rf_u1", 61, 61, 8);
+    Act u1 = ACT(c, T_RF_U1);
     ConvOpt pu1; pu1.pad = 1; pu1.ups = true; pu1.Hl = pu1.Wl = 61;
     CHK(run_conv(c, "post1", s1, &u1, B, pu1, s));
     // stage 0 @61x61                                             (:152)
-    Act h0a = act(c, "rf_h0a", 61, 61, 8), h0b = act(c, "rf_h0b", 61, 61, 8);
+    Act h0a = ACT(c, T_RF_H0A), h0b = ACT(c, T_RF_H0B);
     CHK(run_conv(c, "h0.0", u1, &h0a, B, r3, s));
     CHK(run_conv(c, "h0.2", h0a, &h0b, B, r3, s));
-    Act s0 = act(c, "rf_s0", 61, 61, 8);
-    if (par) CHK(hipStreamWaitEvent(s, ev_v0, 0) == hipSuccess ? 0 : fail(SMK_E_HIP, "wait ev_v0"));
-    else if (!merged) CHK(run_conv(c, "v0.0", p0, &v0a, B, w0, s));
+    Act s0 = ACT(c, T_RF_S0);
+    if (!merged) CHK(run_conv(c, "v0.0", p0, &v0a, B, w0, s));
     ConvOpt a0 = r3; a0.res = &h0b; a0.res_mode = RES_POST_RELU;
     CHK(run_conv(c, "v0.2", v0a, &s0, B, a0, s));
     ConvOpt pu2; pu2.pad = 1; pu2.ups = true; pu2.Hl = pu2.Wl = 127; pu2.nchw_out = out;
@@ -1802,12 +1801,7 @@ int smk_create(smk_ctx **out, int device, int dtype, int variant, int max_batch)
     if (!zero_page()) return fail(SMK_E_HIP, "could not allocate the zero page");   // before any capture
     c->seq_grid = seq_grid_for(prop.multiProcessorCount);
     xcorr_prepare();
-    for (int i = 0; i < 2; ++i) HIPCHK(hipStreamCreateWithFlags(&c->side[i], hipStreamNonBlocking));
-    c->ev_pool.resize(64);
-    for (auto &e : c->ev_pool) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     {
-        const char *cc = getenv("SMK_CONCURRENCY");
-        c->concurrency = !(cc && !strcmp(cc, "0")) && g_concurrency_default != 0;
         double w[625], h[25];
         for (int i = 0; i < 25; ++i) h[i] = 0.5 - 0.5 * std::cos(2.0 * M_PI * i / 24.0);   // np.hanning(25)
         for (int y = 0; y < 25; ++y)
@@ -1825,8 +1819,10 @@ int smk_destroy(smk_ctx *c) {
     if (c->pipe_stream) hipStreamSynchronize(c->pipe_stream);   // a tail may still read the arena
     for (auto &kv : c->graphs) hipGraphExecDestroy(kv.second);
     if (c->cap_stream) hipStreamDestroy(c->cap_stream);
-    for (auto &kv : c->buf)
-        if (!c->buf_alias.count(kv.first)) hipFree(kv.second);
+    for (int id = 0; id < T_COUNT; ++id) {
+        if (c->buf[id][0] && !row_aliased(ARENA[id], c->dtype)) hipFree(c->buf[id][0]);
+        if (c->buf[id][1]) hipFree(c->buf[id][1]);
+    }
     for (auto &kv : c->conv) { hipFree(kv.second.w); hipFree(kv.second.w_halo); hipFree(kv.second.w_frag); hipFree(kv.second.w_frag16); hipFree(kv.second.w_frag_halo); hipFree(kv.second.bias); hipFree(kv.second.oscale); }
     if (c->pos_dev) hipFree(c->pos_dev);
     if (c->dec_scratch) hipFree(c->dec_scratch);
@@ -1840,9 +1836,7 @@ int smk_destroy(smk_ctx *c) {
     if (c->seq_clk2) hipFree(c->seq_clk2);
     if (c->window_dev) hipFree(c->window_dev);
     if (c->ring_cursor) hipFree(c->ring_cursor);
-    for (auto &e : c->ev_pool) hipEventDestroy(e);
     for (auto &e : c->prof_pool) hipEventDestroy(e);
-    for (int i = 0; i < 2; ++i) if (c->side[i]) hipStreamDestroy(c->side[i]);
     for (auto &e : c->pipe_ev) hipEventDestroy(e);
     if (c->pipe_stream) hipStreamDestroy(c->pipe_stream);
     if (c->pipe_cnt) hipFree(c->pipe_cnt);
@@ -2115,7 +2109,6 @@ static const Knob KNOBS[] = {
     {"xcd_mode", &g_tune.xcd_mode, "*", KNOB_RAW, nullptr},
     {"force_tile", &g_tune.force_tile, "0..5", KNOB_RAW, nullptr},
     {"min_blocks_x16", &g_tune.min_blocks_x16, "*", KNOB_RAW, nullptr},
-    {"concurrency", &g_concurrency_default, "*", KNOB_RAW, nullptr},
     {"stages", &g_tune.stages, "0|2..4", KNOB_RAW, nullptr},
     {"kt", &g_tune.kt, "0|128|256", KNOB_RAW, nullptr},
     {"prio", &g_tune.prio, "-1..3", KNOB_RAW, nullptr},
@@ -2138,7 +2131,6 @@ static const Knob KNOBS[] = {
     {"l1_fused", &g_tune.l1_fused, "*", KNOB_BOOL, nullptr},
     {"buf_lds", &g_tune.buf_lds, "*", KNOB_BOOL, nullptr},
     {"a_stage", &g_tune.a_stage, "*", KNOB_BOOL, nullptr},
-    {"mask_overlap", &g_tune.mask_overlap, "*", KNOB_BOOL, nullptr},
     {"wreg", &g_tune.wreg, "0..7", KNOB_RAW, nullptr},
     {"wreg_policy", &g_tune.wreg_policy, "0|1", KNOB_RAW, nullptr},
     {"wreg_stages", &g_tune.wreg_stages, "0|3..8", KNOB_RAW, "0|3|4"},
@@ -2344,13 +2336,13 @@ static StepRec step_rec(const smk_ctx *c, const float *refine_out) {
 // the part of a frame step that feeds the NEXT frame (its crop depends on the decoded box only, tools/test.py:240-250,302-308):
 // layer2 .. decode; `phase` = PH_ALL with the front end in front of it (serial step) or PH_BACK behind the front end of a pipelined step
 static int step_track_decode(smk_ctx *c, StepRec &rec, const float *x, int B, int flags, const double *target_wh, float *cls, float *loc,
-                             float *mask, double *box_out, float *refine_out, hipStream_t st, bool defer_mask_join, int phase) {
+                             float *mask, double *box_out, float *refine_out, hipStream_t st, int phase) {
     // sharp fp16 with Refine: the mask head rides in the Refine chain launch (see chain_mask_kernel)
     rec.defer_mask = refine_out && mask && (flags & SMK_TRACK_MASK) && !(flags & SMK_TRACK_NO_MASK_HEAD) &&
-                     kdtype(c->dtype) == DT_F16 && g_tune.chain && g_tune.chain_mask && !parallel_ok(c) &&
+                     kdtype(c->dtype) == DT_F16 && g_tune.chain && g_tune.chain_mask &&
                      (B <= 16 ||   // measured (profiles/r02_chain_mask_ab.txt): B=8 -6.6 %, B=1 -2 %, B=64 +1 % (64 chain workgroups)
                       rec.two);    // depth-2 pipelining: the tail's first part launches it (step_tail)
-    CHK(seq_track(c, rec, x, B, flags, cls, loc, mask, st, defer_mask_join, phase));
+    CHK(seq_track(c, rec, x, B, flags, cls, loc, mask, st, phase));
     return seq_decode(c, rec, cls, loc, B, target_wh, c->pos_dev, box_out, st);
 }
 
@@ -2359,8 +2351,9 @@ static int step_track_decode(smk_ctx *c, StepRec &rec, const float *x, int B, in
 static int step_tail(smk_ctx *c, StepRec &rec, int B, float *mask, double *box_out, float *refine_out, hipStream_t st, int part = 0) {
     auto mask3 = [&]() {                         // the handed-over mask head as its own launch
         rec.deferred_mask.have = false;
-        Act h0 = act(c, "head0", 25, 25, 256 * nbranch(c));
-        ConvOpt om; om.nchw_out = mask; om.cin_off = 512;
+        Act h0;
+        ConvOpt om;
+        CHK(mask_head_args(c, mask, h0, om));
         return run_conv(c, "mask3", h0, nullptr, B, om, st);
     };
     // depth-2 pipelining: the 63x63 mask head FIRST (it needs head0 only) -- as its own launch beside the next frame's front end; inside
@@ -2370,7 +2363,6 @@ static int step_tail(smk_ctx *c, StepRec &rec, int B, float *mask, double *box_o
     if (refine_out) CHK(seq_refine(c, rec, B, refine_out, st, part));
     if (part == 1) return 0;
     if (rec.deferred_mask.have) CHK(mask3());    // the chain launch did not take it (timing aid on, ...)
-    if (rec.mask_join_pending) CHK(stream_dep(c, c->side[0], st));
     if (c->ring_rows > 0 && refine_out && c->ring_ref && !rec.ring_ref_folded) {      // (the box row was written by the decode launch)
         RingParams rg{box_out, refine_out, nullptr, (_Float16 *)c->ring_ref, c->ring_cursor,
                       (unsigned *)(c->ring_cursor + 1), c->ring_rows, B, 127 * 127};
@@ -2398,7 +2390,7 @@ static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, 
     const bool graphs = c->graph_mode;
     // where the main gate sits: in front of layer2 when that is the persistent sequence (it must own every CU), else in front of the
     // heads -- the first launches that write what the tail reads (smk_tune pipe_late = 0 keeps it in front of layer2 for the A/B)
-    const bool late = g_tune.pipe_late && !(seq_wanted(c, B) && !parallel_ok(c));
+    const bool late = g_tune.pipe_late && !seq_wanted(c, B);
     // depth 2 (the persistent sequence's batches, fp16 chain path, graph replay): the tail in TWO parts.  Part 1 (the mask head, the
     // window convolutions, deconv, v*.2: everything that reads head0, the kept features and the position) runs beside the next frame's
     // front end as before; part 2 (the Refine chain: one low-occupancy launch that only reads part 1's outputs) waits for the
@@ -2418,7 +2410,7 @@ static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, 
         rec.mark_fold = true;               // the decode launch's last writer is the main part's completion mark
         rec.two = two;
         rec.seq_exit = two;                 // the "chip is free for the previous frame's second tail part" semaphore: raised by the persistent launch's last leaving team
-        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, false, PH_BACK));
+        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, PH_BACK));
         if (two && !rec.seq_exit_done && launch_pipe_done(c->pipe_cnt + 7, st)) return fail(SMK_E_HIP, "pipe_done launch failed");   // (no sequence launch took the mark)
         return 0;
     };
@@ -2508,11 +2500,10 @@ int smk_step(smk_ctx *c, const float *x, int B, int flags, const double *target_
     HIPCHK(hipSetDevice(c->device));
     CHK(seq_health(c));
     hipStream_t s = (hipStream_t)stream;
-    // pipelined: only a step with a Refine tail has something to overlap; the profiler times launches one by one; the fork / join
-    // concurrency knob and a persistent sequence that includes layer1 (measurement knobs) keep the serial step; so does split-K
-    // (ONE scratch + arrival-counter set per context: layer1 of frame f + 1 and the Refine convolutions of frame f would share it)
-    if (c->pipe_depth > 0 && refine_out && !c->prof && !parallel_ok(c) && g_tune.seq_first_stage >= 1 && !g_tune.mask_overlap &&
-        !g_tune.ksplit) {
+    // pipelined: only a step with a Refine tail has something to overlap; the profiler times launches one by one; a persistent
+    // sequence that includes layer1 (a measurement knob) keeps the serial step; so does split-K (ONE scratch + arrival-counter
+    // set per context: layer1 of frame f + 1 and the Refine convolutions of frame f would share it)
+    if (c->pipe_depth > 0 && refine_out && !c->prof && g_tune.seq_first_stage >= 1 && !g_tune.ksplit) {
         int rc = step_pipelined(c, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, s);
         if (rc) return rc;
         c->track_B = B;
@@ -2525,7 +2516,7 @@ int smk_step(smk_ctx *c, const float *x, int B, int flags, const double *target_
     GraphKey key{3, B, flags, {x, target_wh, cls, loc, mask, box_out, refine_out, (const void *)pk, (const void *)wi}};
     StepRec rec = step_rec(c, refine_out);
     int rc = run_maybe_graph(c, key, s, rec, [&](hipStream_t st) {
-        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, true, PH_ALL));
+        CHK(step_track_decode(c, rec, x, B, flags, target_wh, cls, loc, mask, box_out, refine_out, st, PH_ALL));
         return step_tail(c, rec, B, mask, box_out, refine_out, st);
     });
     if (rc) return rc;
@@ -2554,12 +2545,7 @@ int smk_set_pipeline(smk_ctx *c, int depth) {
         }
     }
     if (depth > 0) {
-        if (!c->buf.count("p0#1")) {
-            CHK(alloc_buf(c, "p0#1", c->buf_elems.at("p0")));
-            CHK(alloc_buf(c, "p1#1", c->buf_elems.at("p1")));
-            CHK(alloc_buf(c, "p2#1", c->buf_elems.at("p2")));
-        }
-        if (depth >= 2 && !c->buf.count("head0#1")) CHK(alloc_buf(c, "head0#1", c->buf_elems.at("head0")));
+        CHK(alloc_copies(c, depth));
         // (the box rows' own cursor of depth 2 starts where the shared one stands)
         if (c->ring_cursor) HIPCHK(hipMemcpy(c->ring_cursor + 2, c->ring_cursor, sizeof(int), hipMemcpyDeviceToDevice));
         if (!c->pipe_stream) {
@@ -2639,12 +2625,12 @@ int smk_debug_read(smk_ctx *c, const char *name, float *dst, int *C, int *H, int
     const int nbt = nbranch(c);
     const int S = c->last_S ? c->last_S : 255;
     const int s0 = (S - 7) / 2 + 1, s1 = (s0 + 2 - 3) / 2 + 1, s2 = (s1 - 3) / 2 + 1;
-    struct E { const char *n, *b; int h, w, cs, cn; };
+    struct E { const char *n; int id, h, w, cn; };           // public name, arena tensor, the view, logical channels
     const E tab[] = {
-        {"p0", "p0", s0, s0, 64, 64}, {"p1", "p1", s1, s1, 256, 256}, {"p2", "p2", s2, s2, 512, 512},
-        {"p3", c->p3_buf, s2, s2, 1024, 1024}, {"search", "search", 31, 31, 256, 256}, {"zf", "zf", 7, 7, 256, 256},
-        {"zk", "zk", 5, 5, 256 * nbt, 256 * nbt}, {"xs", "xs", 29, 29, 256 * nbt, 256 * nbt},
-        {"corr", "corr", 25, 25, 256 * nbt, 256 * nbt}, {"head0", "head0", 25, 25, 256 * nbt, 256 * nbt},
+        {"p0", T_P0, s0, s0, 64}, {"p1", T_P1, s1, s1, 256}, {"p2", T_P2, s2, s2, 512},
+        {"p3", c->p3_id, s2, s2, 1024}, {"search", T_SEARCH, 31, 31, 256}, {"zf", T_ZF, 7, 7, 256},
+        {"zk", T_ZK, 5, 5, 256 * nbt}, {"xs", T_XS, 29, 29, 256 * nbt},
+        {"corr", T_CORR, 25, 25, 256 * nbt}, {"head0", T_HEAD0, 25, 25, 256 * nbt},
     };
     for (auto &e : tab)
         if (!strcmp(e.n, name)) {
@@ -2655,18 +2641,19 @@ int smk_debug_read(smk_ctx *c, const char *name, float *dst, int *C, int *H, int
             if (c->last_B < 1) return fail(SMK_E_STATE, "smk_debug_read: nothing has run yet");
             CHK(pipe_join(c, (hipStream_t)stream, true));
             c->parity_now = c->last_parity;            // p0 / p1: the copy the last tracked frame wrote
+            const Act a = ACT(c, e.id, e.h, e.w);      // (a.C: the stored channels -- both planes of a split tensor)
             if (c->dtype == DT_F16X3) {
                 // split tensors: value = hi + lo.  Whole-tensor planes, except corr / head0 (per-branch planes: 256 g + cc -> 512 g + cc)
                 const bool per_branch = !strcmp(e.n, "corr") || !strcmp(e.n, "head0");
                 const int ng = per_branch ? e.cn / 256 : 1, cg = e.cn / ng;
                 for (int g = 0; g < ng; ++g) {
-                    CvtOutParams p{act(c, e.b, e.h, e.w, X3_PLANES * e.cs).p, dst, c->last_B, cg, e.h, e.w, X3_PLANES * e.cs, g * X3_PLANES * 256, per_branch ? 256 : e.cs};
+                    CvtOutParams p{a.p, dst, c->last_B, cg, e.h, e.w, a.C, g * X3_PLANES * 256, per_branch ? 256 : e.cn};
                     if (ng > 1) return fail(SMK_E_ARG, "smk_debug_read: %s of a split-operand context is read per branch: not implemented", e.n);
                     if (launch_cvt_out_x3(p, stream)) return fail(SMK_E_HIP, "cvt_out launch failed");
                 }
                 return 0;
             }
-            CvtOutParams p{act(c, e.b, e.h, e.w, e.cs).p, dst, c->last_B, e.cn, e.h, e.w, e.cs, 0};
+            CvtOutParams p{a.p, dst, c->last_B, e.cn, e.h, e.w, a.C, 0};
             if (launch_cvt_out(p, c->dtype, stream)) return fail(SMK_E_HIP, "cvt_out launch failed");
             return 0;
         }
@@ -3542,6 +3529,15 @@ int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *syn
         a_stage[i] = rec[i].L.a_stage;
     }
     return 0;
+}
+
+// What build_arena (pipe_depth 0) and smk_set_pipeline allocate for a context of this kind, from the ARENA table: elements per image, one plane
+int smk_host_arena_elems(int dtype, int variant, int pipe_depth, uint64_t *elems_per_image) {
+    if (!elems_per_image) return fail(SMK_E_ARG, "smk_host_arena_elems: null argument");
+    if (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_F16X3) return fail(SMK_E_ARG, "smk_host_arena_elems: bad dtype %d", dtype);
+    if (variant < SMK_VARIANT_RPN || variant > SMK_VARIANT_SHARP) return fail(SMK_E_ARG, "smk_host_arena_elems: bad variant %d", variant);
+    if (pipe_depth < 0 || pipe_depth > 2) return fail(SMK_E_ARG, "smk_host_arena_elems: depth %d", pipe_depth);
+    return arena_elems(dtype, variant, pipe_depth, elems_per_image);
 }
 
 }  // extern "C"

@@ -199,8 +199,6 @@ struct Tuning {
                                // the batched loads (21.5 us); rocprofv3, profiles/r03_dw_xcorr_variants.txt
     int buf_lds = 1;           // LDS-DMA through buffer resources instead of flat global addresses (measured
                                // faster: l3.0.ds 94 -> 76 us at B=8, profiles/r01_v5_ab_buf_lds.txt)
-    int mask_overlap = 0;      // smk_step: mask head on a side stream beside decode + Refine (measured slower:
-                               // a cross-stream graph edge makes hipGraphLaunch cost ~1 ms of host time)
     int chain_mask = 1;        // fused frame step, fp16: the mask head runs inside the Refine chain launch (chain_mask_kernel)
     int nchw_tn_major = 1;     // large NCHW f32 outputs (the 63x63 mask logits): tn-major tile order (see conv_params)
     int merge = 1;             // share one launch between independent convolutions (ds+c1, cls3+loc3, Refine windows): 0 never, 1 up to

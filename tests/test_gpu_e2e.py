@@ -240,7 +240,7 @@ def test_device_decode_matches_host_decode():
 
 @pytest.mark.parametrize("dtype", ["f32", "f16"])
 def test_fused_step_equals_separate_calls(dtype):
-    """track_step (track -> device decode -> refine, one graph, fork/join concurrency) gives the
+    """track_step (track -> device decode -> refine, one graph) gives the
     same tensors as track_mask + host decode + track_refine."""
     g = load_golden("sharp_damped_b2")
     z = torch.from_numpy(g["z_u8"].astype(np.float32)).cuda()
@@ -259,6 +259,48 @@ def test_fused_step_equals_separate_calls(dtype):
     assert torch.equal(out["refine"], ref)
     if dtype == "f32":
         assert rel_err(out["refine"].cpu().numpy(), g["refine"]) <= 1e-4
+
+
+_FALLBACK_CHILD = """
+import json, sys
+import numpy as np, torch
+sys.path.insert(0, %(tests)r)
+from helpers import load_golden
+from siammask_amd import synth
+from siammask_amd.custom import build
+g = load_golden("sharp_damped_b2")
+z = torch.from_numpy(g["z_u8"].astype(np.float32)).cuda()
+x = torch.from_numpy(g["x_u8"].astype(np.float32)).cuda()
+twh = torch.tensor([[60.0, 80.0]] * 2, dtype=torch.float64).cuda()
+res = {}
+for dtype in ("f16x3", "f16"):
+    m = build("sharp", dtype=dtype, graph=False)
+    m.load_state_dict(synth.torch_state_dict("sharp", "synthetic_damped"))
+    m = m.eval().cuda()
+    m.template(z)
+    mask = m.track_mask(x)[2].clone()
+    out = m.track_step(x, twh)
+    torch.cuda.synchronize()
+    res[dtype] = [bool(torch.equal(out["mask"], mask)), float((out["mask"] - mask).abs().max()), float(mask.abs().max())]
+print("RESULT " + json.dumps(res))
+"""
+
+
+def test_mask_head_fallback_launch_with_split_operands():
+    """The mask head that the Refine chain launch declines (here: eager run with the chain's layer clocks on, SMK_CHAIN_CLK=1, which is read
+    once per process -- hence the child) is launched by the step's tail on its own.  That launch takes head0 and the mask branch's slice
+    from the same helper as track_mask's: the same bits, also where head0 holds [hi | lo] planes (f16x3)."""
+    import subprocess
+    import sys
+    env = dict(os.environ, SMK_GRAPH="0", SMK_CHAIN_CLK="1")
+    r = subprocess.run([sys.executable, "-c", _FALLBACK_CHILD % {"tests": os.path.join(REPO, "tests")}], capture_output=True, text=True,
+                       cwd=REPO, env=env, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "refine_chain layers (us)" in r.stderr          # the chain ran with its clocks: it did not take the mask head
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1][7:])
+    print(res)
+    assert res["f16x3"][0], res
+    assert res["f16"][0], res
 
 
 def test_packed_weight_cache(tmp_path):

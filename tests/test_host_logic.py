@@ -206,7 +206,7 @@ def test_tuning_knobs_read_back():
     table = src[src.index("static const Knob KNOBS[] = {"):]
     table = table[:table.index("};")]
     names = re.findall(r'\{"(\w+)", &\w+(?:\.\w+)?, "', table)            # (read-only diagnostics have no accepted values)
-    assert len(names) == 58 and "npw" in names and "seq_fused_last" not in names
+    assert len(names) == 56 and "npw" in names and "seq_fused_last" not in names
     code = ("import json; from siammask_amd import _lib\n"
             "for k in %r: _lib.tune(**{k: _lib.tune_get(k)})\n"
             "_lib.tune(seq_spoll=5, seq_kstag_mask=15)\n"
@@ -227,17 +227,55 @@ def test_tuning_knobs_read_back():
         _lib.tune(rf_wreg=old)
 
 
-@pytest.mark.parametrize("name", ["pipe_join", "pipe_sig", "pipe_eager", "pipe_two_form", "pipe_prio"])
+@pytest.mark.parametrize("name", ["pipe_join", "pipe_sig", "pipe_eager", "pipe_two_form", "pipe_prio", "concurrency", "mask_overlap"])
 def test_settled_pipeline_knobs_are_gone(name):
     """the measured and dropped forms of the pipelined step (cross-queue event join, event / hipStreamWaitValue32 start of the tail,
     eager parts, depth-2 forms 0 / 2, a side-stream priority; profiles/r05a_*, r05e_*, r05f_*, r05j_*, r05o_*, r06z_*) left the library
-    with their knobs: no kind of build sets or reads them any more"""
+    with their knobs: no kind of build sets or reads them any more.  So did the two modes that captured graphs with parallel branches:
+    fork / join between independent launches and the mask head on a side stream (both measured slower, HISTORY.md round 1, profiles/r06q_*)"""
     from siammask_amd import _lib
     for value in (0, 1, 2):
         with pytest.raises(RuntimeError):
             _lib.tune(**{name: value})
     with pytest.raises(RuntimeError):
         _lib.tune_get(name)
+
+
+# elements per image, one plane, of a context's activation arena at pipeline depth 0 (the sum of the allocations of smk_create)
+ARENA_ELEMS = {"sharp": {"f16": 15263800, "f32": 9589432, "f16x3": 9589432},
+               "base": {"f16": 14904584, "f32": 9230216, "f16x3": 9230216},
+               "rpn": {"f16": 14362888, "f32": 8688520, "f16x3": 8688520}}
+
+
+@pytest.mark.parametrize("variant", ["sharp", "base", "rpn"])
+@pytest.mark.parametrize("dtype", ["f16", "f32", "f16x3"])
+def test_arena_sizes(variant, dtype):
+    """the engine's table of arena tensors sums to what the allocations summed to before there was a table; only f16 contexts (the
+    persistent sequence's) hold the stage-private buffers of layer2 / layer3, the others alias them; pipelined steps add second
+    copies of p0 / p1 / p2 (depth 1) and of head0 (depth 2)"""
+    from siammask_amd import _lib
+
+    def elems(depth):
+        n = ctypes.c_uint64(0)
+        _lib.check(_lib.lib().smk_host_arena_elems(_lib.DTYPE[dtype], _lib.VARIANT[variant], depth, ctypes.byref(n)))
+        return n.value
+
+    base = ARENA_ELEMS[variant][dtype]
+    assert elems(0) == base
+    assert elems(1) == base + 125 * 125 * 64 + 63 * 63 * 256 + 31 * 31 * 512 == base + 2508096
+    assert elems(2) == elems(1) + 25 * 25 * 256 * (2 if variant == "rpn" else 3)
+    n = ctypes.c_uint64(0)
+    for bad in ((3, 2, 0), (1, 3, 0), (1, 2, 3), (1, 2, -1)):
+        assert _lib.lib().smk_host_arena_elems(*bad, ctypes.byref(n)) != 0
+
+
+def test_arena_tensors_are_stated_once():
+    """every launch takes its view of an arena tensor from the engine's one table (act / ACT with a table id): no tensor is looked up by
+    name, and none restates a shape beside a name"""
+    src = open(os.path.join(REPO, "siammask_amd", "csrc", "engine.cpp")).read()
+    assert "static const ArenaRow ARENA[T_COUNT] = {" in src
+    assert not re.findall(r'\b(?:act|ACT)\([^\n;]*"', src)             # a call of act / ACT with a string literal among its arguments
+    assert "buf.at(" not in src and "buf.find(" not in src
 
 
 def _plan(B, cin, hw, cout, k, stride=1, pad=0, dil=1, res=False, win=None, dtype="f16"):
