@@ -141,6 +141,25 @@ int smk_op_dw_xcorr(int dtype, const float *x_dev, const float *k_dev, int B, in
 int smk_op_maxpool3x3s2(int dtype, const float *x_dev, int B, int C, int H, int W,
                         float *y_dev, void *stream);
 
+/* The fused front end of the fp16 path, ONE kernel on caller tensors (unit parity, tests/test_gpu_front.py).  f32 NCHW device
+ * tensors at the boundary, host weights, fp16 arithmetic; the weights take the context's own route into the kernels' fragment
+ * order.  The NHWC fp16 output buffers are filled with 0xFF bytes (fp16 NaN) before the launch, so that a pixel the kernel does
+ * not write reads back as NaN, and lie between two 4 KB guard bands of a fixed byte: a band that changed (a tile wrote outside
+ * its image) is SMK_E_STATE naming the buffer.  Bad arguments are SMK_E_ARG before a device is touched.  Both synchronise the
+ * stream (test helpers).
+ * smk_op_stem_pool: stem_pool_kernel -- x [B,3,S,S] -> p0 = relu(conv 7x7 stride 2 pad 0 (x, w) + b) [B,64,s0,s0] and
+ *   x1 = maxpool 3x3 stride 2 pad 1 (p0) [B,64,s1,s1], s0 = (S - 7) / 2 + 1, s1 = (s0 - 1) / 2 + 1; 7 <= S <= 8192.
+ *   w_host [64,3,7,7], b_host [64].
+ * smk_op_l1_block: l1_block_kernel -- one layer1 Bottleneck on x [B,Cin,S,S], Cin = 64 (block 0: projection shortcut wd [256,64,1,1],
+ *   bd [256], both required) or 256 (identity shortcut: wd, bd must be NULL); 1 <= S <= 4096.
+ *   y = relu(conv1x1(relu(conv3x3 pad 1 (relu(conv1x1(x, w1) + b1), w2) + b2), w3) + b3 + shortcut) [B,256,S,S];
+ *   w1 [64,Cin,1,1], w2 [64,64,3,3], w3 [256,64,1,1], b1 [64], b2 [64], b3 [256] (host, all required). */
+int smk_op_stem_pool(const float *x_dev, const float *w_host, const float *b_host, int S, int B, float *p0_dev,
+                     float *x1_dev, void *stream);
+int smk_op_l1_block(const float *x_dev, const float *w1_host, const float *b1_host, const float *w2_host,
+                    const float *b2_host, const float *w3_host, const float *b3_host, const float *wd_host,
+                    const float *bd_host, int Cin, int S, int B, float *y_dev, void *stream);
+
 /* measurement aid: time `iters` back-to-back launches of the MFMA conv kernel for geometry g
  * (random f16/f32 operands allocated internally, NHWC epilogue unless algo low byte is 2) with
  * HIP events on `stream`; *usec_out = average microseconds per launch.  algo as above. */

@@ -610,6 +610,27 @@ static int pack_deconv(smk_ctx *c) {
 // features.conv1 (7x7 s2 p0, 3 -> 64) on the pixel-pair input layout [H][ceil(W/2)][2 px x 4 ch]:
 // a 7 x 4 convolution over pixel pairs (vertical stride 2, horizontal stride 1 pair), K = 7*4*8 = 224
 // instead of 7*7*8 = 392 with the channel-padded layout; the 8th pixel and the 4th channel have zero weights
+static void stem_pair_rows(std::vector<float> &rows, std::vector<float> &bias, int Kpad, const float *w, const double *scale,
+                           const double *shift) {
+    for (int n = 0; n < 64; ++n) {
+        for (int ky = 0; ky < 7; ++ky)
+            for (int kx = 0; kx < 7; ++kx)
+                for (int ci = 0; ci < 3; ++ci) {
+                    const double v = (double)w[(((size_t)n * 3 + ci) * 7 + ky) * 7 + kx] * scale[n];
+                    rows[(size_t)n * Kpad + (size_t)(ky * 4 + kx / 2) * 8 + (kx & 1) * 4 + ci] = (float)v;
+                }
+        bias[n] = (float)shift[n];
+    }
+}
+
+// the stem's pack (without its weights): geometry of the pixel-pair matrix
+static PackedConv stem_pack_geom() {
+    PackedConv pc;
+    pc.Ci = 8; pc.k = 7; pc.kw = 4; pc.K = 7 * 4 * 8; pc.Kpad = rup(pc.K, KPAD_ALIGN); pc.alg_k = 3 * 7 * 7;
+    pc.groups = 1; pc.N = 64; pc.group_rows = pc.rows = rup(64, NPAD_ALIGN);
+    return pc;
+}
+
 static int pack_stem(smk_ctx *c) {
     const std::string f = "features.features.";
     const HostTensor *w = find_w(c, f + "conv1.weight");
@@ -618,19 +639,9 @@ static int pack_stem(smk_ctx *c) {
         return fail(SMK_E_WEIGHT, "weight %sconv1.weight has wrong shape", f.c_str());
     std::vector<double> scale, shift;
     CHK(fold(c, bnpart(f + "conv1", f + "bn1"), 64, scale, shift));
-    PackedConv pc;
-    pc.Ci = 8; pc.k = 7; pc.kw = 4; pc.K = 7 * 4 * 8; pc.Kpad = rup(pc.K, KPAD_ALIGN); pc.alg_k = 3 * 7 * 7;
-    pc.groups = 1; pc.N = 64; pc.group_rows = pc.rows = rup(64, NPAD_ALIGN);
+    PackedConv pc = stem_pack_geom();
     std::vector<float> rows((size_t)pc.rows * pc.Kpad, 0.f), bias(pc.rows, 0.f);
-    for (int n = 0; n < 64; ++n) {
-        for (int ky = 0; ky < 7; ++ky)
-            for (int kx = 0; kx < 7; ++kx)
-                for (int ci = 0; ci < 3; ++ci) {
-                    const double v = (double)w->data[(((size_t)n * 3 + ci) * 7 + ky) * 7 + kx] * scale[n];
-                    rows[(size_t)n * pc.Kpad + (size_t)(ky * 4 + kx / 2) * 8 + (kx & 1) * 4 + ci] = (float)v;
-                }
-        bias[n] = (float)shift[n];
-    }
+    stem_pair_rows(rows, bias, pc.Kpad, w->data.data(), scale.data(), shift.data());
     CHK(upload_packed(pc, rows, bias, kdtype(c->dtype)));
     c->conv["stem"] = pc;
     return 0;
@@ -3064,6 +3075,125 @@ int smk_op_maxpool3x3s2(int dtype, const float *x_dev, int B, int C, int H, int 
     CvtOutParams co{y, y_dev, B, C, Ho, Wo, C, 0};
     if (launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
     HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+// ---- the fused front end on caller tensors: stem_pool_kernel, l1_block_kernel -----------------------------------------
+// An output buffer of these two entries: NHWC fp16, every byte 0xFF before the launch (fp16 NaN: a pixel the kernel does not
+// write surfaces as NaN in the result) between two guard bands of a fixed byte.  A band that changed means that a tile wrote
+// outside its image -- inside this allocation; a write further out is not seen.
+constexpr size_t OP_GUARD = 4096;
+constexpr int OP_GUARD_BYTE = 0xA5;
+struct GuardedBuf {
+    unsigned char *base = nullptr;
+    size_t bytes = 0;
+    void *p() const { return base + OP_GUARD; }
+    int alloc(TmpBufs &tmp, size_t n, hipStream_t s) {
+        HIPCHK(hipMalloc((void **)&base, n + 2 * OP_GUARD));
+        tmp.v.push_back(base);
+        bytes = n;
+        HIPCHK(hipMemsetAsync(base, OP_GUARD_BYTE, OP_GUARD, s));
+        HIPCHK(hipMemsetAsync(base + OP_GUARD, 0xFF, n, s));
+        HIPCHK(hipMemsetAsync(base + OP_GUARD + n, OP_GUARD_BYTE, OP_GUARD, s));
+        return 0;
+    }
+    // after the stream has been synchronised: both bands intact?
+    int check(const char *entry, const char *name) const {
+        std::vector<unsigned char> h(2 * OP_GUARD);
+        HIPCHK(hipMemcpy(h.data(), base, OP_GUARD, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h.data() + OP_GUARD, base + OP_GUARD + bytes, OP_GUARD, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < 2 * OP_GUARD; ++i)
+            if (h[i] != OP_GUARD_BYTE)
+                return fail(SMK_E_STATE, "%s: the kernel wrote outside the %s buffer (guard band %s it, byte %d)", entry, name,
+                            i < OP_GUARD ? "before" : "after", (int)(i % OP_GUARD));
+        return 0;
+    }
+};
+
+// one convolution's weights for a per-op entry: pack_host -> upload_packed (fp16), the device copies owned by tmp
+static int op_pack(TmpBufs &tmp, PackedConv &pc, int Cin, int Cout, int k, const float *w, const float *b) {
+    smk_conv_geom g;
+    memset(&g, 0, sizeof(g));
+    g.B = 1; g.Cin = Cin; g.H = g.W = k; g.Cout = Cout; g.k = k; g.stride = 1; g.dil = 1;
+    Act in; ConvOpt o; int Ho, Wo;
+    CHK(fill_geom(&g, pc, in, o, Ho, Wo));
+    std::vector<float> rows, bias;
+    pack_host(&g, pc, w, b, rows, bias);
+    const int rc = upload_packed(pc, rows, bias, DT_F16);
+    for (void *q : {pc.w, (void *)pc.bias, pc.w_frag, pc.w_frag16})
+        if (q) tmp.v.push_back(q);
+    return rc;
+}
+
+int smk_op_stem_pool(const float *x_dev, const float *w_host, const float *b_host, int S, int B, float *p0_dev, float *x1_dev,
+                     void *stream) {
+    if (!x_dev || !w_host || !b_host || !p0_dev || !x1_dev) return fail(SMK_E_ARG, "smk_op_stem_pool: null argument");
+    if (S < 7 || S > 8192) return fail(SMK_E_ARG, "smk_op_stem_pool: S = %d (7 .. 8192)", S);
+    if (B < 1 || B > 1024) return fail(SMK_E_ARG, "smk_op_stem_pool: B = %d (1 .. 1024)", B);
+    hipStream_t s = (hipStream_t)stream;
+    const int s0 = (S - 7) / 2 + 1, s1 = (s0 - 1) / 2 + 1;
+    // the context's pack: pixel-pair rows -> upload_packed -> the fragment-order copy the kernel reads
+    PackedConv pc = stem_pack_geom();
+    std::vector<float> rows((size_t)pc.rows * pc.Kpad, 0.f), bias(pc.rows, 0.f);
+    const std::vector<double> one(64, 1.0), shift(b_host, b_host + 64);
+    stem_pair_rows(rows, bias, pc.Kpad, w_host, one.data(), shift.data());
+    TmpBufs tmp;
+    const int rc = upload_packed(pc, rows, bias, DT_F16);
+    for (void *q : {pc.w, (void *)pc.bias, pc.w_frag, pc.w_frag16})
+        if (q) tmp.v.push_back(q);
+    CHK(rc);
+    if (!pc.w_frag) return fail(SMK_E_STATE, "smk_op_stem_pool: internal: the stem has no fragment-order pack");
+    GuardedBuf p0, x1;
+    CHK(p0.alloc(tmp, (size_t)B * s0 * s0 * 64 * 2, s));
+    CHK(x1.alloc(tmp, (size_t)B * s1 * s1 * 64 * 2, s));
+    StemPoolParams sp{x_dev, pc.w_frag, pc.bias, p0.p(), x1.p(), B, S, s0, s1, pc.Kpad, 0};
+    if (launch_stem_pool(sp, s)) return fail(SMK_E_HIP, "stem_pool launch failed: %s", hipGetErrorString(hipGetLastError()));
+    CvtOutParams c0{p0.p(), p0_dev, B, 64, s0, s0, 64, 0}, c1{x1.p(), x1_dev, B, 64, s1, s1, 64, 0};
+    if (launch_cvt_out(c0, DT_F16, s) || launch_cvt_out(c1, DT_F16, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(p0.check("smk_op_stem_pool", "p0"));
+    CHK(x1.check("smk_op_stem_pool", "x1"));
+    return 0;
+}
+
+int smk_op_l1_block(const float *x_dev, const float *w1_host, const float *b1_host, const float *w2_host, const float *b2_host,
+                    const float *w3_host, const float *b3_host, const float *wd_host, const float *bd_host, int Cin, int S, int B,
+                    float *y_dev, void *stream) {
+    if (!x_dev || !w1_host || !b1_host || !w2_host || !b2_host || !w3_host || !b3_host || !y_dev)
+        return fail(SMK_E_ARG, "smk_op_l1_block: null argument");
+    if (Cin != 64 && Cin != 256) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = %d (64: block 0 with its projection, 256)", Cin);
+    if (Cin == 64 && (!wd_host || !bd_host)) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = 64 needs the projection shortcut wd, bd");
+    if (Cin == 256 && (wd_host || bd_host)) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = 256 has an identity shortcut: wd, bd must be null");
+    if (S < 1 || S > 4096) return fail(SMK_E_ARG, "smk_op_l1_block: S = %d (1 .. 4096)", S);
+    if (B < 1 || B > 1024) return fail(SMK_E_ARG, "smk_op_l1_block: B = %d (1 .. 1024)", B);
+    hipStream_t s = (hipStream_t)stream;
+    TmpBufs tmp;
+    PackedConv p1, p2, p3, pd;
+    CHK(op_pack(tmp, p1, Cin, 64, 1, w1_host, b1_host));
+    CHK(op_pack(tmp, p2, 64, 64, 3, w2_host, b2_host));
+    CHK(op_pack(tmp, p3, 64, 256, 1, w3_host, b3_host));
+    if (Cin == 64) CHK(op_pack(tmp, pd, 64, 256, 1, wd_host, bd_host));
+    if (!p1.w_frag16 || !p2.w_frag16 || !p3.w_frag16 || (Cin == 64 && !pd.w_frag16))
+        return fail(SMK_E_STATE, "smk_op_l1_block: internal: a layer has no 16x16x32 fragment-order pack");
+    void *x;
+    CHK(tmp.alloc(&x, (size_t)B * S * S * Cin * 2));
+    CvtInParams ci{x_dev, x, B, Cin, S, S, Cin, 0};
+    if (launch_cvt_in(ci, DT_F16, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
+    GuardedBuf y;
+    CHK(y.alloc(tmp, (size_t)B * S * S * 256 * 2, s));
+    L1BlockParams lp;
+    memset(&lp, 0, sizeof(lp));
+    lp.x = x; lp.y = y.p();
+    lp.w1 = p1.w_frag16; lp.w2 = p2.w_frag16; lp.w3 = p3.w_frag16;
+    lp.b1 = p1.bias; lp.b2 = p2.bias; lp.b3 = p3.bias;
+    lp.K1pad = p1.Kpad; lp.K2pad = p2.Kpad; lp.K3pad = p3.Kpad;
+    if (Cin == 64) { lp.wd = pd.w_frag16; lp.bd = pd.bias; lp.Kdpad = pd.Kpad; }
+    lp.B = B; lp.S = S; lp.Cin = Cin;
+    if (launch_l1_block(lp, s)) return fail(SMK_E_HIP, "l1_block launch failed: %s", hipGetErrorString(hipGetLastError()));
+    CvtOutParams co{y.p(), y_dev, B, 256, S, S, 256, 0};
+    if (launch_cvt_out(co, DT_F16, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
+    HIPCHK(hipStreamSynchronize(s));
+    CHK(y.check("smk_op_l1_block", "y"));
     return 0;
 }
 

@@ -3,6 +3,8 @@
 conv2d    -> the implicit-GEMM MFMA kernel every convolution of the path uses
 dw_xcorr  -> models/rpn.py:32-38 conv2d_dw_group
 maxpool   -> nn.MaxPool2d(3, 2, 1) (experiments/siammask_sharp/resnet.py:158)
+stem_pool -> the fp16 stem as one launch (stem_pool_kernel): conv1 7x7/2 + ReLU -> p0 -> maxpool -> x1
+l1_block  -> one layer1 Bottleneck as one launch (l1_block_kernel, fp16)
 All take / return float32 NCHW tensors; ``dtype`` selects the device arithmetic type."""
 import ctypes
 
@@ -179,6 +181,49 @@ def maxpool3x3s2(x, dtype="f32"):
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().smk_op_maxpool3x3s2(_lib.DTYPE[dtype], x.data_ptr(), B, C, H, W, y.data_ptr(),
                                                   _lib.current_stream_ptr()))
+    return y
+
+
+def _host_f32(a):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+
+def stem_pool(x, w, b):
+    """smk_op_stem_pool: x [B,3,S,S] float32 CUDA tensor, w [64,3,7,7], b [64] -> (p0 [B,64,s0,s0], x1 [B,64,s1,s1]), fp16
+    arithmetic.  A pixel the kernel leaves unwritten comes back as NaN; a write outside an output buffer raises."""
+    _chk_cuda(x)
+    x = x.contiguous().float()
+    B, C, S, S2 = x.shape
+    w, b = _host_f32(w), _host_f32(b)
+    if C != 3 or S != S2 or w.shape != (64, 3, 7, 7) or b.shape != (64,):
+        raise ValueError("stem_pool: x [B,3,S,S], w [64,3,7,7], b [64]")
+    s0 = (S - 7) // 2 + 1
+    s1 = (s0 - 1) // 2 + 1
+    p0 = torch.empty((B, 64, max(s0, 0), max(s0, 0)), dtype=torch.float32, device=x.device)
+    x1 = torch.empty((B, 64, max(s1, 0), max(s1, 0)), dtype=torch.float32, device=x.device)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().smk_op_stem_pool(x.data_ptr(), vp(w), vp(b), S, B, p0.data_ptr(), x1.data_ptr(),
+                                               _lib.current_stream_ptr()))
+    return p0, x1
+
+
+def l1_block(x, w1, b1, w2, b2, w3, b3, wd=None, bd=None):
+    """smk_op_l1_block: one layer1 Bottleneck on x [B,Cin,S,S] (float32 CUDA tensor), Cin = 64 (wd [256,64,1,1], bd [256]
+    required: the projection shortcut) or 256 (identity shortcut) -> y [B,256,S,S], fp16 arithmetic.  A pixel the kernel
+    leaves unwritten comes back as NaN; a write outside the output buffer raises."""
+    _chk_cuda(x)
+    x = x.contiguous().float()
+    B, Cin, S, S2 = x.shape
+    hs = [None if a is None else _host_f32(a) for a in (w1, b1, w2, b2, w3, b3, wd, bd)]
+    want = [(64, Cin, 1, 1), (64,), (64, 64, 3, 3), (64,), (256, 64, 1, 1), (256,), (256, 64, 1, 1), (256,)]
+    if S != S2 or any(a is not None and a.shape != s for a, s in zip(hs, want)):
+        raise ValueError("l1_block: x [B,Cin,S,S], w1 [64,Cin,1,1], w2 [64,64,3,3], w3 / wd [256,64,1,1]")
+    y = torch.empty((B, 256, S, S), dtype=torch.float32, device=x.device)
+    vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().smk_op_l1_block(x.data_ptr(), *[vp(a) for a in hs], Cin, S, B, y.data_ptr(),
+                                              _lib.current_stream_ptr()))
     return y
 
 
