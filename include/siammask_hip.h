@@ -340,6 +340,53 @@ int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_
                       int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
                       uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
                       uint8_t *labels_out_dev, void *stream);
+/* ABI 1.10: the two entries above with an object's START frame (tools/test.py:493,503-504: at f == start_frame the object's row
+ * of pred_masks is the init mask itself).  Bit o of given_mask: prob_o = init_labels_dev[y][x] == object_ids[o] ? 1.0f : 0.0f
+ * instead of the warped probability, whatever alive_mask says for o.  init_labels_dev: uint8 [H][W]; required when given_mask != 0
+ * (bits at or above n_obj are refused).  With given_mask == 0 the call IS the entry above (which passes 0 / NULL). */
+int smk_vos_score_ex(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                     const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                     float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, uint32_t given_mask,
+                     const uint8_t *init_labels_dev, void *stream);
+int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                         uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                         uint8_t *labels_out_dev, uint32_t given_mask, const uint8_t *init_labels_dev, void *stream);
+
+/* ---- starting a stream on the device (tools/test.py:146-152 siamese_init, :481-504 track_vos; ABI 1.10, additive) ------------
+ * What lies between "an annotation / a rectangle" and "the stream is planned for its next frame", as launches on one stream with no
+ * host read-back, for SOME of the B streams of a state block while the others keep their records.  No context; every entry is
+ * asynchronous on `stream` and refuses bad arguments (SMK_E_ARG) before anything is enqueued; host arrays travel as kernel arguments.
+ * W, H in 1..32768; B and n_obj in 1..32.
+ * smk_label_rects <- cv2.boundingRect(labels == id) (:494) for n_obj ids in one pass over labels_dev (uint8 [H][W]):
+ *   rects_out_dev int32 [n_obj][4] = (x, y, w, h) = min x, min y, max x - min x + 1, max y - min y + 1 over the pixels whose byte
+ *   equals object_ids[o]; (0, 0, 0, 0) for an id that does not occur.  Duplicate ids each get their rectangle; bytes that match no
+ *   id are skipped.  Fully defined by the call (initialised on `stream`), exact (integer min / max).
+ * smk_frame_sums: per-channel integer sums of n uint8 frames [H][W][3], frame_stride_bytes apart -> sums_out_dev uint64 [n][3]
+ *   (zeroed on `stream` by the call; exact).  np.mean(im, axis=(0, 1)) (:146) is sum / (H * W) in float64, bit for bit.
+ * smk_trk_start <- siamese_init (:146-152) + the plan of the next frame, one lane per stream, for the streams b with bit b of
+ *   start_mask set (bits at or above B are refused); the records of the others are not written.  Exactly one of rects_dev (device
+ *   int32 [B][4] as smk_label_rects writes them: target_pos = (x + w / 2, y + h / 2), target_sz = (w, h), :494-497) and pos_host /
+ *   sz_host (host f64 [B][2] each) is given.  sums_dev: uint64 rows of 3 as smk_frame_sums writes them, stream b reads row
+ *   b * sums_stride (0: one frame shared by the streams).  Per started stream: the record as smk_trk_set would leave it (im_w,
+ *   im_h, avg_bgr = the truncated mean, derived fields zeroed), then smk_trk_plan's fields and target_wh[b];
+ *   win_out_dev int32 [B][3] <- the exemplar's integer window (xmin, ymin, s_z) with s_z = round(sqrt(wc_z * hc_z)) half to even
+ *   (:147-152, :70-76); result_out_dev f64 [B][8] <- started (1), the float64 mean colour (3), target_pos (2), target_sz (2).
+ *   A stream whose size is not positive in both directions (its object is absent from the init label map; the reference would fail in
+ *   cv2.resize) starts nothing: record, window and target_wh untouched, its result row is zeros (started = 0).
+ * smk_crop_exemplar_dev: smk_crop_resize_dev for the exemplar -- window from win_dev, mean colour from the record, into row b of
+ *   z_all_dev f32 [B][3][model_sz][model_sz] -- for the streams of start_mask whose result row says started; the rows of all other
+ *   streams stay as they were.  smk_template on the whole buffer then gives every unchanged row the template it had, bit for bit. */
+int smk_label_rects(const uint8_t *labels_dev, int W, int H, const uint8_t *object_ids, int n_obj, int32_t *rects_out_dev,
+                    void *stream);
+int smk_frame_sums(const uint8_t *frames_dev, int64_t frame_stride_bytes, int n, int H, int W, uint64_t *sums_out_dev,
+                   void *stream);
+int smk_trk_start(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                  const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride, int im_w, int im_h,
+                  int32_t *win_out_dev, double *result_out_dev, void *stream);
+int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev,
+                          const int32_t *win_dev, const double *result_dev, uint32_t start_mask, int B, int model_sz,
+                          float *z_all_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,8 @@ SYMBOLS = (
     "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels", "smk_mask_rbox_workspace", "smk_mask_rbox",
     "smk_trk_state_bytes", "smk_trk_set", "smk_trk_plan", "smk_trk_advance", "smk_crop_resize_dev", "smk_paste_mask_dev",
     "smk_vos_score", "smk_vos_score_dev", "smk_host_trk_plan", "smk_host_trk_advance",
+    "smk_vos_score_ex", "smk_vos_score_dev_ex", "smk_label_rects", "smk_frame_sums", "smk_trk_start", "smk_crop_exemplar_dev",
+    "smk_host_trk_start",
 )
 
 
@@ -144,6 +146,14 @@ def lib():
     cf, u32 = ctypes.c_float, ctypes.c_uint32
     L.smk_vos_score.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, vp, u32, vp, ci, cf, vp, vp, vp]
     L.smk_vos_score_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, vp, vp, u32, vp, ci, cf, vp, vp, vp]
+    L.smk_vos_score_ex.argtypes = L.smk_vos_score.argtypes[:-1] + [u32, vp, vp]
+    L.smk_vos_score_dev_ex.argtypes = L.smk_vos_score_dev.argtypes[:-1] + [u32, vp, vp]
+    i64 = ctypes.c_int64
+    L.smk_label_rects.argtypes = [vp, ci, ci, vp, ci, vp, vp]
+    L.smk_frame_sums.argtypes = [vp, i64, ci, ci, ci, vp, vp]
+    L.smk_trk_start.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, ci, ci, vp, vp, vp]
+    L.smk_host_trk_start.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, ci, ci, vp, vp]
+    L.smk_crop_exemplar_dev.argtypes = [vp, i64, ci, ci, vp, vp, vp, u32, ci, ci, fp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

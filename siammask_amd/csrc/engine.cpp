@@ -1782,7 +1782,7 @@ static int seq_grid_for(int ncu) {
 // ---------------------------------------------------------------------------------------------
 extern "C" {
 
-int smk_version(void) { return (1 << 16) | 9; }   // 1.9: smk_vos_score / smk_vos_score_dev (1.8: tracker state on the device, smk_trk_* / smk_*_dev; 1.7: smk_mask_rbox; 1.6: SMK_DTYPE_F16X3)
+int smk_version(void) { return (1 << 16) | 10; }   // 1.10: stream start on the device, smk_label_rects / smk_frame_sums / smk_trk_start / smk_crop_exemplar_dev / smk_vos_score*_ex (1.9: smk_vos_score / smk_vos_score_dev; 1.8: tracker state on the device, smk_trk_* / smk_*_dev; 1.7: smk_mask_rbox; 1.6: SMK_DTYPE_F16X3)
 //   // 1.2: smk_decode / smk_step take float64 target_wh and write a float64 box; 1.3: smk_op_conv_seq,
                                                   // sequence failures reported at the next entry point
 
@@ -3429,13 +3429,31 @@ static int vos_fill(const char *who, VosParams &p, const float *src, int mask_si
     return 0;
 }
 
+// given_mask / init_labels_dev of the _ex entries: bits at or above n_obj are refused, and so is a mask without the label map
+static int vos_given(const char *who, VosParams &p, int n_obj, uint32_t given_mask, const uint8_t *init_labels_dev) {
+    if (n_obj < 32 && (given_mask >> n_obj)) return fail(SMK_E_ARG, "%s: given_mask %#x has bits at or above %d objects", who, given_mask, n_obj);
+    if (given_mask && !init_labels_dev) return fail(SMK_E_ARG, "%s: given_mask without init_labels_dev", who);
+    p.given = given_mask;
+    p.init_labels = given_mask ? init_labels_dev : nullptr;
+    return 0;
+}
+
 int smk_vos_score(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
                   const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
                   float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, void *stream) {
+    return smk_vos_score_ex(logits_dev, mask_size, inv_map, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
+                            seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
+}
+
+int smk_vos_score_ex(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                     const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                     float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, uint32_t given_mask,
+                     const uint8_t *init_labels_dev, void *stream) {
     if (!inv_map) return fail(SMK_E_ARG, "smk_vos_score: null argument");
     VosParams p;
     CHK(vos_fill("smk_vos_score", p, logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
                  seg_thr, counts_out_dev, labels_out_dev));
+    CHK(vos_given("smk_vos_score_ex", p, n_obj, given_mask, init_labels_dev));
     for (int i = 0; i < n_obj; ++i)
         for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
     if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
@@ -3446,15 +3464,128 @@ int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_
                       int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
                       uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
                       uint8_t *labels_out_dev, void *stream) {
+    return smk_vos_score_dev_ex(logits_dev, head_dev, score_size, mask_size, state_dev, slot, n_obj, W, H, border, gt_dev,
+                                object_ids, alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
+}
+
+int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                         uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                         uint8_t *labels_out_dev, uint32_t given_mask, const uint8_t *init_labels_dev, void *stream) {
     if (!state_dev) return fail(SMK_E_ARG, "smk_vos_score_dev: null argument");
     if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_score_dev: slot %d (0 or 1)", slot);
     if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_score_dev: score_size %d", score_size);
     VosParams p;
     CHK(vos_fill("smk_vos_score_dev", p, head_dev ? head_dev : logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids,
                  alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev));
+    CHK(vos_given("smk_vos_score_dev_ex", p, n_obj, given_mask, init_labels_dev));
     p.head_S = head_dev ? score_size : 0; p.slot = slot;
     p.st = (const smk_trk_stream *)state_dev;
     if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
+    return 0;
+}
+
+// ---- stream start on the device (tools/test.py:146-152,494-497; tracker_init.hip / tracker_state.h) -----------------------
+int smk_label_rects(const uint8_t *labels_dev, int W, int H, const uint8_t *object_ids, int n_obj, int32_t *rects_out_dev,
+                    void *stream) {
+    if (!labels_dev || !object_ids || !rects_out_dev) return fail(SMK_E_ARG, "smk_label_rects: null argument");
+    if (n_obj < 1 || n_obj > RECT_MAX_OBJ) return fail(SMK_E_ARG, "smk_label_rects: %d objects (1..%d)", n_obj, RECT_MAX_OBJ);
+    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_label_rects: bad geometry (%d x %d, 1..32768)", W, H);
+    if ((uintptr_t)rects_out_dev % 4) return fail(SMK_E_ARG, "smk_label_rects: rects_out_dev must be 4-byte aligned");
+    LabelRectsParams p;
+    memset(&p, 0, sizeof(p));
+    p.labels = labels_dev; p.rects = rects_out_dev; p.W = W; p.H = H; p.n_obj = n_obj;
+    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
+    if (launch_label_rects(p, stream)) return fail(SMK_E_HIP, "label_rects launch failed");
+    return 0;
+}
+
+int smk_frame_sums(const uint8_t *frames_dev, int64_t frame_stride_bytes, int n, int H, int W, uint64_t *sums_out_dev,
+                   void *stream) {
+    if (!frames_dev || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums: null argument");
+    if (n < 1 || n > 65535 || frame_stride_bytes < 0) return fail(SMK_E_ARG, "smk_frame_sums: %d frames (1..65535), stride %lld", n, (long long)frame_stride_bytes);
+    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_frame_sums: bad geometry (%d x %d, 1..32768)", W, H);
+    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums: sums_out_dev must be 8-byte aligned");
+    FrameSumsParams p;
+    p.frames = frames_dev; p.stride = (long)frame_stride_bytes; p.sums = (unsigned long long *)sums_out_dev;
+    p.bytes = (long)H * W * 3; p.n = n;
+    if (launch_frame_sums(p, stream)) return fail(SMK_E_HIP, "frame_sums launch failed");
+    return 0;
+}
+
+// the checks and the kernarg smk_trk_start and smk_host_trk_start share
+static int trk_start_fill(const char *who, TrkStartArgs &a, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
+                          const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
+                          int64_t sums_stride, int im_w, int im_h, int32_t *win_out, double *result_out) {
+    if (!state || !sums || !win_out || !result_out) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
+    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, start_mask, B);
+    if ((rects != nullptr) == (pos_host != nullptr || sz_host != nullptr) || ((pos_host != nullptr) != (sz_host != nullptr)))
+        return fail(SMK_E_ARG, "%s: exactly one of the device rectangles and the host position / size pair is given", who);
+    if (im_w < 1 || im_h < 1 || im_w > 32768 || im_h > 32768) return fail(SMK_E_ARG, "%s: bad geometry (%d x %d, 1..32768)", who, im_w, im_h);
+    if (sums_stride < 0) return fail(SMK_E_ARG, "%s: sums_stride %lld", who, (long long)sums_stride);
+    if ((uintptr_t)state % 8 || (uintptr_t)sums % 8 || (uintptr_t)result_out % 8 || (uintptr_t)win_out % 4 || (uintptr_t)rects % 4)
+        return fail(SMK_E_ARG, "%s: misaligned argument", who);
+    CHK(trk_cfg_check(who, cfg));
+    memset(&a, 0, sizeof(a));
+    a.cfg = *cfg; a.rects = rects; a.sums = (const unsigned long long *)sums; a.sums_stride = (long)sums_stride;
+    a.win = win_out; a.res = result_out; a.mask = start_mask; a.B = B; a.im_w = im_w; a.im_h = im_h;
+    if (pos_host)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < 2; ++k) {
+                a.pos[b][k] = pos_host[2 * b + k];
+                a.sz[b][k] = sz_host[2 * b + k];
+            }
+    return 0;
+}
+
+int smk_trk_start(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                  const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride, int im_w, int im_h,
+                  int32_t *win_out_dev, double *result_out_dev, void *stream) {
+    TrkStartArgs a;
+    CHK(trk_start_fill("smk_trk_start", a, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride, im_w,
+                       im_h, win_out_dev, result_out_dev));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_start(st, (double *)(st + B), a, stream)) return fail(SMK_E_HIP, "trk_start launch failed");
+    return 0;
+}
+
+int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
+                       const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,
+                       double *result_out) {
+    TrkStartArgs a;
+    CHK(trk_start_fill("smk_host_trk_start", a, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_w, im_h, win_out,
+                       result_out));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) {
+        if (!((start_mask >> b) & 1)) continue;
+        double px, py, w, h;
+        if (rects) {
+            const int32_t *r = rects + 4 * b;
+            w = (double)r[2]; h = (double)r[3];
+            px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
+        } else {
+            px = a.pos[b][0]; py = a.pos[b][1]; w = a.sz[b][0]; h = a.sz[b][1];
+        }
+        trk_start(st[b], *cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, im_w, im_h, win_out + 3 * b,
+                  result_out + TRK_START_ROW * b, twh + 2 * b);
+    }
+    return 0;
+}
+
+int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev,
+                          const int32_t *win_dev, const double *result_dev, uint32_t start_mask, int B, int model_sz,
+                          float *z_all_dev, void *stream) {
+    if (!frames_dev || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: null argument");
+    if (H < 1 || W < 1 || H > 32768 || W > 32768 || model_sz < 1 || model_sz > 65535 || B < 1 || B > TRK_SET_MAX_B || frame_stride_bytes < 0)
+        return fail(SMK_E_ARG, "smk_crop_exemplar_dev: bad geometry");
+    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: start_mask %#x has bits at or above %d streams", start_mask, B);
+    CropExemplarParams p;
+    p.frames = frames_dev; p.frame_stride = (long)frame_stride_bytes; p.out = z_all_dev;
+    p.H = H; p.W = W; p.model_sz = model_sz;
+    p.st = (const smk_trk_stream *)state_dev; p.win = win_dev; p.res = result_dev; p.mask = start_mask;
+    if (launch_crop_exemplar_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev launch failed");
     return 0;
 }
 

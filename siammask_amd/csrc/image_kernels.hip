@@ -102,6 +102,33 @@ __global__ __launch_bounds__(256) void crop_resize_dev_kernel(const CropDevParam
     crop_pixel(p, b, dx, dy, s->xmin, s->ymin, sz, a0, a1, a2);
 }
 
+// the exemplar crop of a stream start (smk_crop_exemplar_dev): window from smk_trk_start's win array, mean colour from the record
+// it wrote, row b of z_all.  Only the streams of `mask` that did start: the workgroups of the others leave at once and their rows
+// stay as they were.
+__global__ __launch_bounds__(256) void crop_exemplar_dev_kernel(const CropExemplarParams p) {
+    const int b = blockIdx.z;
+    if (!((p.mask >> b) & 1) || p.res[TRK_START_ROW * b] == 0.0) return;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+    if (dx >= p.model_sz) return;
+    const smk_trk_stream *s = p.st + b;
+    const int *win = p.win + 3 * b;
+    const int sz = win[2], a0 = s->avg_bgr[0], a1 = s->avg_bgr[1], a2 = s->avg_bgr[2];
+    if (sz < 1 || sz > 32768) {                           // (as crop_resize_dev_kernel: outside smk_crop_resize's range)
+        const size_t plane = (size_t)p.model_sz * p.model_sz;
+        float *out = p.out + (size_t)b * 3 * plane + (size_t)dy * p.model_sz + dx;
+        out[0] = (float)a0; out[plane] = (float)a1; out[2 * plane] = (float)a2;
+        return;
+    }
+    crop_pixel(p, b, dx, dy, win[0], win[1], sz, a0, a1, a2);
+}
+
+int launch_crop_exemplar_dev(const CropExemplarParams &p, int B, void *stream) {
+    if (B < 1 || B > TRK_SET_MAX_B) return -1;
+    dim3 grid((p.model_sz + 255) / 256, p.model_sz, B);
+    hipLaunchKernelGGL(crop_exemplar_dev_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_crop_resize_dev(const CropDevParams &p, int B, void *stream) {
     if (B < 1 || B > 65535) return -1;
     dim3 grid((p.model_sz + 255) / 256, p.model_sz, B);
@@ -213,7 +240,10 @@ __global__ __launch_bounds__(256) void paste_labels_kernel(const PasteParams p, 
 // A workgroup covers 256 pixels of VOS_ROWS consecutive rows (fewer workgroups -> fewer global atomics on the O*K*2 counters).
 constexpr int VOS_ROWS = 4;
 
-template <bool DEV>
+// GIVEN (smk_vos_score*_ex with a non-zero given_mask): bit o of p.given replaces prob_o by the init mask itself,
+// init_labels == id[o] ? 1 : 0 -- the reference puts it into pred_masks at an object's start frame (tools/test.py:493,503-504).
+// A compile-time switch: without it the kernel is the one it was.
+template <bool DEV, bool GIVEN>
 __global__ __launch_bounds__(256) void vos_score_kernel(const VosParams p) {
     __shared__ int cnt[VOS_MAX_OBJ * VOS_MAX_THR * 2];
     __shared__ int sid[VOS_MAX_OBJ];
@@ -232,7 +262,12 @@ __global__ __launch_bounds__(256) void vos_score_kernel(const VosParams p) {
         if (in_x) {
             for (int o = 0; o < O; ++o) {
                 float v = -1.f;
-                if ((p.alive >> o) & 1) {
+                bool given = false;
+                if constexpr (GIVEN) {
+                    given = (p.given >> o) & 1;
+                    if (given) v = p.init_labels[(size_t)y * p.W + x] == sid[o] ? 1.f : 0.f;
+                }
+                if (!given && ((p.alive >> o) & 1)) {
                     if constexpr (DEV) {
                         const smk_trk_stream *s = p.st + o;
                         const float *lg = p.logits + (size_t)o * p.ms * p.ms;
@@ -300,8 +335,14 @@ int launch_vos_score(const VosParams &p, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     if (hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * p.n_obj * p.n_thr, s) != hipSuccess) return -4;
     dim3 grid((p.W + 255) / 256, (p.H + VOS_ROWS - 1) / VOS_ROWS, 1);
-    if (p.st) hipLaunchKernelGGL(vos_score_kernel<true>, grid, dim3(256), 0, s, p);
-    else      hipLaunchKernelGGL(vos_score_kernel<false>, grid, dim3(256), 0, s, p);
+    if (p.given && !p.init_labels) return -1;
+    if (p.given) {
+        if (p.st) hipLaunchKernelGGL((vos_score_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((vos_score_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (p.st) hipLaunchKernelGGL((vos_score_kernel<true, false>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((vos_score_kernel<false, false>), grid, dim3(256), 0, s, p);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -124,7 +124,53 @@ SMK_TRK_HD void trk_advance(smk_trk_stream &s, const smk_trk_cfg &c, const doubl
     s.target_sz[0] = cs0; s.target_sz[1] = cs1;
 }
 
-// ---- launchers (tracker_state.hip, image_kernels.hip) ----------------------------------------------------------------
+// tools/test.py:146-152 siamese_init (as restated by tracker.py DeviceTracker.init + preproc.subwindow_box, :70-76) for one
+// stream, followed by the plan of its next frame.  (px, py) / (w, h): the target's centre and size; sums: the integer channel
+// sums of its init frame (np.mean(im, axis=(0, 1)) == sum / (H * W) in float64: the sums are exact integers below 2^53).
+// win [3] <- the exemplar's integer window (xmin, ymin, s_z); res [TRK_START_ROW] <- started, the float64 mean colour (3),
+// target_pos (2), target_sz (2).  A target without a positive width and height (the object is absent from the init label map)
+// starts nothing: the record, win and twh are untouched and res is (0, 0, ...).  -> started
+constexpr int TRK_START_ROW = 8;
+SMK_TRK_HD int trk_start(smk_trk_stream &s, const smk_trk_cfg &c, double px, double py, double w, double h,
+                         const unsigned long long *sums, int im_w, int im_h, int *win, double *res, double *twh) {
+    if (!(w > 0.0) || !(h > 0.0)) {
+        for (int k = 0; k < TRK_START_ROW; ++k) res[k] = 0.0;
+        return 0;
+    }
+    const double n_px = t_mul((double)im_h, (double)im_w);
+    const double avg0 = t_div((double)sums[0], n_px), avg1 = t_div((double)sums[1], n_px), avg2 = t_div((double)sums[2], n_px);
+    // the exemplar (:147-152)
+    const double ctx = t_mul(c.context_amount, t_add(w, h));
+    const double wc_z = t_add(w, ctx), hc_z = t_add(h, ctx);
+    const double s_z = t_rint(t_sqrt(t_mul(wc_z, hc_z)));
+    const double cc = t_div(t_add(s_z, 1.0), 2.0);                        // subwindow_box: (original_sz + 1) / 2
+    win[0] = t_int(t_rint(t_sub(px, cc)));
+    win[1] = t_int(t_rint(t_sub(py, cc)));
+    win[2] = t_int(s_z);
+    res[0] = 1.0; res[1] = avg0; res[2] = avg1; res[3] = avg2;
+    res[4] = px; res[5] = py; res[6] = w; res[7] = h;
+    // the record as smk_trk_set leaves it (in place: no private copy), then the plan of the next frame
+    s.target_pos[0] = px; s.target_pos[1] = py;
+    s.target_sz[0] = w; s.target_sz[1] = h;
+    s.scale_x = 0.0; s.s_x = 0.0;
+    for (int k = 0; k < 4; ++k) s.crop_box[k] = 0.0;
+    for (int k = 0; k < 6; ++k) { s.inv_map[0][k] = 0.0; s.inv_map[1][k] = 0.0; }
+    s.im_w = im_w; s.im_h = im_h;
+    s.xmin = 0; s.ymin = 0; s.sz = 0;
+    s.best_id = 0;
+    s.delta_yx[0][0] = 0; s.delta_yx[0][1] = 0; s.delta_yx[1][0] = 0; s.delta_yx[1][1] = 0;
+    s.avg_bgr[0] = (unsigned char)t_int(avg0);                            // the numpy assignment truncates (:92-99)
+    s.avg_bgr[1] = (unsigned char)t_int(avg1);
+    s.avg_bgr[2] = (unsigned char)t_int(avg2);
+    s.avg_bgr[3] = 0;
+    s.reserved = 0;
+    trk_plan(s, c, twh);
+    return 1;
+}
+// centre of a cv2.boundingRect row (x, y, w, h) as tools/test.py:494-497 takes it: x + w / 2, y + h / 2
+SMK_TRK_HD double t_rect_centre(int x, int w) { return t_add((double)x, t_div((double)w, 2.0)); }
+
+// ---- launchers (tracker_state.hip, image_kernels.hip, tracker_init.hip) ----------------------------------------------
 constexpr int TRK_SET_MAX_B = 32;
 struct TrkSetArgs {                 // smk_trk_set: the host's values travel in the kernarg
     double pos[TRK_SET_MAX_B][2], sz[TRK_SET_MAX_B][2];
@@ -166,8 +212,53 @@ struct VosParams {
     double thr[VOS_MAX_THR];
     unsigned char ids[VOS_MAX_OBJ];
     double inv_map[VOS_MAX_OBJ][6];
+    // smk_vos_score*_ex (appended: the fields above keep their kernarg offsets).  bit o of `given`: prob_o is the init mask itself,
+    // init_labels[y][x] == ids[o] ? 1 : 0 (tools/test.py:493,503-504), whatever `alive` says; 0 selects the kernel without it
+    const unsigned char *init_labels;
+    unsigned given;
 };
 int launch_vos_score(const VosParams &p, void *stream);
+
+// ---- stream start on the device (tracker_init.hip; the exemplar crop is image_kernels.hip's, beside crop_pixel) ----------
+constexpr int RECT_MAX_OBJ = 32, RECT_ROWS = 4;
+struct LabelRectsParams {
+    const unsigned char *labels;    // [H][W]
+    int *rects;                     // [O][4]: accumulators during the pass, (x, y, w, h) behind the finishing launch
+    int W, H, n_obj;
+    unsigned char ids[RECT_MAX_OBJ];
+};
+int launch_label_rects(const LabelRectsParams &p, void *stream);
+struct FrameSumsParams {
+    const unsigned char *frames;    // n frames [H][W][3], `stride` bytes apart
+    long stride;
+    unsigned long long *sums;       // [n][3]
+    long bytes;                     // H * W * 3
+    int n;
+};
+int launch_frame_sums(const FrameSumsParams &p, void *stream);
+struct TrkStartArgs {               // smk_trk_start: host values travel in the kernarg
+    double pos[TRK_SET_MAX_B][2], sz[TRK_SET_MAX_B][2];
+    smk_trk_cfg cfg;
+    const int *rects;               // device [B][4] (x, y, w, h), or nullptr: pos / sz above
+    const unsigned long long *sums; // device rows of 3; stream b reads row b * sums_stride
+    long sums_stride;
+    int *win;                       // device [B][3]
+    double *res;                    // device [B][TRK_START_ROW]
+    unsigned mask;
+    int B, im_w, im_h;
+};
+int launch_trk_start(smk_trk_stream *st, double *twh, const TrkStartArgs &a, void *stream);
+struct CropExemplarParams {         // (the members crop_pixel reads are named as CropDevParams names them)
+    const unsigned char *frames;
+    long frame_stride;
+    float *out;                     // z_all [B][3][model_sz][model_sz]
+    int H, W, model_sz;
+    const smk_trk_stream *st;
+    const int *win;                 // [B][3] of smk_trk_start
+    const double *res;              // [B][TRK_START_ROW]: row b starts with the `started` flag
+    unsigned mask;
+};
+int launch_crop_exemplar_dev(const CropExemplarParams &p, int B, void *stream);
 
 }  // namespace smk
 #endif

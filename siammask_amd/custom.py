@@ -302,21 +302,36 @@ class Custom(nn.Module):
         once()
 
     # -- the reference surface ------------------------------------------------------------------
-    def template(self, template):
-        """custom.py:173-174 -- caches the template features (and conv_kernel(zf)) on device."""
+    def template(self, template, sync=True):
+        """custom.py:173-174 -- caches the template features (and conv_kernel(zf)) on device.
+        The images are staged into the model's persistent buffer (template_input()); passing that buffer itself skips the copy.
+        sync=False: enqueue only -- no smk_seq_sync_check (a stream synchronisation for batches that run the persistent
+        sequence) behind the call: the counterpart of track_step(stage=False).  A sequence failure then surfaces at the next
+        entry point, where the free-running tracker handles it (tracker.DeviceTracker._fr_rewind replays this call)."""
         B = template.shape[0]
         self._ensure(template, B, grow=True)
         with torch.cuda.device(self._ctx_device):
-            z = self._stage_in("z", template, spec.TEMPLATE_SIZE)
-            if not self._graph:
-                z = z.clone()        # kept for a re-run (the staged buffer of graph mode is ours already)
+            if template.dim() != 4 or tuple(template.shape[1:]) != (3, spec.TEMPLATE_SIZE, spec.TEMPLATE_SIZE):
+                raise ValueError("expected a [B,3,%d,%d] tensor, got %s" % (spec.TEMPLATE_SIZE, spec.TEMPLATE_SIZE, tuple(template.shape)))
+            # one persistent buffer with or without graph mode: a stable pointer for the captured graph, the input kept for a
+            # re-run, and the rows a stream start overwrites (DeviceTracker.start)
+            z = self._buf("z", tuple(template.shape), template.device)
+            if template is not z:
+                z.copy_(template)
 
             def run():
                 _lib.check(_lib.lib().smk_template(self._ctx, z.data_ptr(), B, _lib.current_stream_ptr()))
             self._replay = {"template": run}
-            self._guarded("template", run)
+            if sync:
+                self._guarded("template", run)
+            else:
+                run()
         self.zf = ("device-resident", B)
         self._tracked = 0
+
+    def template_input(self):
+        """the persistent float32 CUDA buffer [B,3,127,127] the last template() was computed from (None before the first)"""
+        return self._io.get("z")
 
     def _track(self, search, flags, want_mask):
         if self.zf is None:

@@ -264,6 +264,48 @@ def vos_score_dev(logits, state, slot, im_wh, gt, object_ids, thrs, alive=None, 
     return (counts, labels) if labels is not None else counts
 
 
+def label_rects(labels, ids, out=None):
+    """cv2.boundingRect(labels == id) (tools/test.py:494) for up to 32 ids in one pass over a label map on the device.
+    labels: uint8 CUDA [H,W]; ids: O integers in 0..255 (duplicates allowed; they need not occur).
+    -> int32 CUDA [O,4] = (x, y, w, h); (0, 0, 0, 0) for an id that does not occur.  out: a contiguous int32 CUDA [O,4]."""
+    _need_cuda(labels, "labels")
+    if labels.dtype != torch.uint8 or labels.dim() != 2 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous uint8 CUDA tensor [H,W]")
+    ids = np.asarray(ids)
+    if ids.ndim != 1 or not 1 <= ids.size <= 32 or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+        raise ValueError("ids must be 1..32 integers in 0..255")
+    O = int(ids.size)
+    ids = np.ascontiguousarray(ids.astype(np.uint8))
+    H, W = int(labels.shape[0]), int(labels.shape[1])
+    if out is None:
+        out = torch.empty((O, 4), dtype=torch.int32, device=labels.device)
+    elif out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (O, 4):
+        raise ValueError("out must be a contiguous int32 CUDA tensor [%d,4]" % O)
+    with torch.cuda.device(labels.device):
+        _lib.check(_lib.lib().smk_label_rects(labels.data_ptr(), W, H, ids.ctypes.data, O, out.data_ptr(),
+                                              _lib.current_stream_ptr()))
+    return out
+
+
+def frame_sums(frames, out=None):
+    """Per-channel integer sums of uint8 frames on the device: frames uint8 CUDA [H,W,3] or [n,H,W,3] -> int64 CUDA [n,3]
+    (the view of the uint64 sums; exact).  sum / (H * W) in float64 is np.mean(im, axis=(0, 1)) (tools/test.py:146) bit for bit.
+    out: a contiguous int64 CUDA [n,3] to write into."""
+    _need_cuda(frames, "frames")
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or frames.shape[-1] != 3:
+        raise ValueError("frames must be uint8 [H,W,3] or [n,H,W,3]")
+    frames = frames.contiguous()
+    n = int(frames.shape[0]) if frames.dim() == 4 else 1
+    H, W = int(frames.shape[-3]), int(frames.shape[-2])
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.int64, device=frames.device)
+    elif out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n, 3):
+        raise ValueError("out must be a contiguous int64 CUDA tensor [%d,3]" % n)
+    with torch.cuda.device(frames.device):
+        _lib.check(_lib.lib().smk_frame_sums(frames.data_ptr(), H * W * 3, n, H, W, out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
 _rbox_ws = {}      # (device, stream, B, W, H) -> scratch of smk_mask_rbox (sized for the worst case of ceil(W/2)*H runs per mask)
 
 

@@ -19,6 +19,13 @@ csrc/tracker_state.hip) -- any number of frames is enqueued without a host synch
     res = tr.run(frames, gt=gt_u8_cuda, vos={'object_ids': ids, 'thrs': vos.THRS})   # B objects on a shared frame, scored
     res['vos_counts'], res['labels']                               # against gt on the device (tools/test.py:421-456, 521-523)
 track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
+
+Streams that start on their own frames (siamese_init per stream on the device, enqueue-only; csrc/tracker_init.hip):
+    tr.reserve(B, H, W)                                            # an all-idle tracker, nothing from the host
+    tr.start(frame, [5], labels=labels_u8_cuda, object_ids=[9])    # stream 5 <- cv2.boundingRect(labels == 9) (tools/test.py:493-498)
+    tr.start(frame, [2], pos=[(cx, cy)], sz=[(w, h)])              # the VOT re-init (:354-363); the other streams keep running
+    res = tr.run(frames, gt=gt, vos={'object_ids': ids, 'thrs': vos.THRS, 'start': {...}, 'end': {...}})   # track_vos (:481-504)
+    res['alive'], res['events']                                    # bool [T,B]; what every start event did
 """
 import ctypes
 
@@ -34,6 +41,7 @@ STREAM_DTYPE = np.dtype([
     ("inv_map", "<f8", (2, 6)), ("im_w", "<i4"), ("im_h", "<i4"), ("xmin", "<i4"), ("ymin", "<i4"), ("sz", "<i4"),
     ("best_id", "<i4"), ("delta_yx", "<i4", (2, 2)), ("avg_bgr", "u1", (4,)), ("reserved", "<i4")])
 RESULT_ROW = 16        # float64 per stream and frame (smk_trk_advance)
+START_ROW = 8          # float64 per stream and start event (smk_trk_start): started, mean colour (3), target_pos, target_sz
 _ROWS_PER_BLOCK = 128
 
 
@@ -64,8 +72,10 @@ class TrackerConfig(object):
 
 
 def _mean_colour(frame):
-    """np.mean(im, axis=(0, 1)) (tools/test.py:146) on the device, in float64"""
-    return frame.to(torch.float64).mean(dim=(0, 1)).cpu().numpy()
+    """np.mean(im, axis=(0, 1)) (tools/test.py:146): the channel sums on the device in float64 (exact integers), the division on
+    the host -- sum / N, np.mean's bits.  torch's device mean (and its division by a host scalar) multiplies by the rounded
+    reciprocal of N, which is one ulp off for some sums; smk_trk_start divides as np.mean does, and both must agree."""
+    return frame.to(torch.float64).sum(dim=(0, 1)).cpu().numpy() / np.float64(int(frame.shape[0]) * int(frame.shape[1]))
 
 
 class DeviceTracker(object):
@@ -107,6 +117,127 @@ class DeviceTracker(object):
         self._fr_setup(frame.device, B, H, W)
         self._fr_upload()
         return self.state
+
+    def reserve(self, B, H, W, device="cuda"):
+        """An all-idle tracker of B streams on H x W frames, nothing read from or by the host: every record is harmless (centre
+        of the frame, 10 x 10, planned), the template input is zeros, one template(sync=False).  start() then hands streams to
+        targets while the others keep running.  Enqueue-only."""
+        B, H, W = int(B), int(H), int(W)
+        if not 1 <= B <= 32:
+            raise ValueError("reserve(): 1..32 streams, got %d" % B)
+        if H < 1 or W < 1:
+            raise ValueError("reserve(): bad frame size %d x %d" % (H, W))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("siammask_amd.tracker runs on the MI355X only: device must be a CUDA(HIP) device")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        p = self.p
+        with torch.cuda.device(device):
+            z = torch.zeros((B, 3, p.exemplar_size, p.exemplar_size), dtype=torch.float32, device=device)
+            self.model.template(z, sync=False)
+        if self.pipeline and self.refine:
+            self.model.set_pipeline(True)
+        self.state = {"im_h": H, "im_w": W, "avg_chans": [np.zeros(3) for _ in range(B)],
+                      "target_pos": np.tile(np.array([W / 2, H / 2], dtype=np.float64), (B, 1)),
+                      "target_sz": np.full((B, 2), 10.0), "score": np.zeros(B), "mask": None}
+        self._fr_setup(device, B, H, W)
+        self._fr_upload()
+        return self.state
+
+    def _start_spec(self, frame, streams, pos, sz, labels, object_ids):
+        """the checked request of one start() (before anything is launched) -> (stream list, bit mask, host pos / sz or None,
+        ids per STREAM for smk_label_rects or None)"""
+        fr, st = self._fr, self.state
+        if st is None or fr is None:
+            raise RuntimeError("DeviceTracker.start(): reserve() or init() first")
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        if B > 32:
+            raise ValueError("start() takes trackers of up to 32 streams, this one has %d" % B)
+        z = self.model.template_input()
+        if fr.get("z_all") is None or "z_snap" not in fr or z is not fr["z_all"] or self.model.zf is None:
+            raise RuntimeError("DeviceTracker.start(): the model's template is not the one this tracker was reserved / initialised with")
+        if not isinstance(frame, torch.Tensor) or not frame.is_cuda:
+            raise RuntimeError("siammask_amd.tracker runs on the MI355X only: frame must be a CUDA(HIP) tensor")
+        if frame.dtype != torch.uint8 or tuple(frame.shape) not in ((H, W, 3), (B, H, W, 3)):
+            raise ValueError("frame must be uint8 [%d,%d,3] or [%d,%d,%d,3], got %s %s" % (H, W, B, H, W, frame.dtype, tuple(frame.shape)))
+        streams = [int(b) for b in np.asarray(streams).reshape(-1)]
+        if not streams or len(set(streams)) != len(streams) or min(streams) < 0 or max(streams) >= B:
+            raise ValueError("streams must be distinct indices in 0..%d" % (B - 1))
+        n = len(streams)
+        by_host, by_labels = pos is not None or sz is not None, labels is not None or object_ids is not None
+        if by_host == by_labels or (by_host and (pos is None or sz is None)) or (by_labels and (labels is None or object_ids is None)):
+            raise ValueError("start(): either pos= and sz=, or labels= and object_ids=")
+        bits = sum(1 << b for b in streams)
+        if by_host:
+            hp = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
+            hs = np.asarray(sz, dtype=np.float64).reshape(-1, 2)
+            if hp.shape != (n, 2) or hs.shape != (n, 2):
+                raise ValueError("pos and sz must be [%d,2], one row per stream of `streams`" % n)
+            pos_all, sz_all = np.zeros((B, 2)), np.zeros((B, 2))
+            pos_all[streams], sz_all[streams] = hp, hs
+            return streams, bits, pos_all, sz_all, None
+        if (not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.uint8 or
+                tuple(labels.shape) != (H, W)):
+            raise ValueError("labels must be a uint8 CUDA tensor [%d,%d]" % (H, W))
+        ids = np.asarray(object_ids).reshape(-1)
+        if ids.shape != (n,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+            raise ValueError("object_ids must be %d integers in 0..255, one per stream of `streams`" % n)
+        ids_all = np.full(B, int(ids[0]), dtype=np.uint8)             # (a row per STREAM; the others repeat an asked id)
+        ids_all[streams] = ids
+        return streams, bits, None, None, ids_all
+
+    def start(self, frame, streams, pos=None, sz=None, labels=None, object_ids=None):
+        """siamese_init (tools/test.py:132-170) for SOME streams while the others keep running, enqueue-only: nothing is read
+        by the host.  streams: the stream indices that start on ``frame`` (uint8 CUDA [H,W,3] or [B,H,W,3]).  Their targets are
+        either host values pos / sz ([n,2] each, a row per entry of ``streams``: the VOT re-init, a service's new target), or
+        labels (uint8 CUDA [H,W]) and object_ids (n ids): the bounding rectangle of labels == id, taken on the device
+        (tools/test.py:493-497).  An object that is absent from the labels starts nothing (collect() says so).
+        Launches: [join + paste-back of a deferred frame] -> frame sums -> [label rectangles] -> start + plan -> exemplar crop
+        into the template input -> template(sync=False) on the whole batch: the rows that did not change reproduce their
+        template bit for bit.  May be called between enqueue() calls.  -> the chunk index of the event (the index the next
+        enqueued frame gets); collect() returns the events of the chunk."""
+        streams, bits, hpos, hsz, ids_all = self._start_spec(frame, streams, pos, sz, labels, object_ids)
+        fr, st = self._fr, self.state
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        frame = frame.contiguous()
+        if labels is not None:
+            labels = labels.contiguous()
+        L, model = _lib.lib(), self.model
+        try:
+            with torch.cuda.device(fr["device"]):
+                sp = _lib.current_stream_ptr()
+                if fr["synced"] is None or st["target_pos"] is not fr["synced"][0] or st["target_sz"] is not fr["synced"][1]:
+                    self._fr_upload()                                 # a track() in between: the host is ahead
+                if fr["pending"] == 0 and not fr["events"]:           # chunk start (as in enqueue())
+                    fr["snap"].copy_(fr["dev"])
+                    fr["start"] = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}
+                if not fr["z_snapped"]:                               # the chunk's first start: z_all has not changed since its start
+                    fr["z_snap"].copy_(fr["z_all"])
+                    fr["z_snapped"] = True
+                if fr["deferred"] is not None:                        # smk_template joins the pipeline: paste what is outstanding first
+                    model.pipeline_join()
+                    job, fr["deferred"] = fr["deferred"], None
+                    self._fr_paste(job, sp)
+                per_stream = frame.dim() == 4
+                _lib.check(L.smk_frame_sums(frame.data_ptr(), H * W * 3, B if per_stream else 1, H, W, fr["sums"].data_ptr(), sp))
+                if ids_all is not None:
+                    _lib.check(L.smk_label_rects(labels.data_ptr(), W, H, ids_all.ctypes.data, B, fr["rects"].data_ptr(), sp))
+                res = torch.empty((B, START_ROW), dtype=torch.float64, device=fr["device"])
+                _lib.check(L.smk_trk_start(
+                    fr["dev"].data_ptr(), B, ctypes.byref(fr["cfg"]), bits, fr["rects"].data_ptr() if ids_all is not None else None,
+                    hpos.ctypes.data if hpos is not None else None, hsz.ctypes.data if hsz is not None else None,
+                    fr["sums"].data_ptr(), 1 if per_stream else 0, W, H, fr["win"].data_ptr(), res.data_ptr(), sp))
+                _lib.check(L.smk_crop_exemplar_dev(frame.data_ptr(), H * W * 3 if per_stream else 0, H, W, fr["dev"].data_ptr(),
+                                                   fr["win"].data_ptr(), res.data_ptr(), bits, B, self.p.exemplar_size,
+                                                   fr["z_all"].data_ptr(), sp))
+                model.template(fr["z_all"], sync=False)
+                fr["events"].append({"t": fr["pending"], "streams": streams, "res": res})
+        except _lib.SmkError as e:
+            if e.code == _lib.E_SEQ:
+                self._fr_rewind()
+            raise
+        return fr["pending"]
 
     # -- siamese_track (tools/test.py:173-311) ---------------------------------------------------
     def track(self, frame, want_mask=True, keep_crop=False, want_polygon=False):
@@ -180,6 +311,16 @@ class DeviceTracker(object):
         fr["cfg"] = _lib.TrkCfg(float(p.context_amount), float(p.lr), int(p.exemplar_size), int(p.instance_size),
                                 int(p.total_stride), int(p.base_size), int(p.score_size), int(self.mask_size))
         assert STREAM_DTYPE.itemsize * B + 16 * B == n, "STREAM_DTYPE does not match smk_trk_stream"
+        # stream starts (start()): z_all is the model's persistent template input -- a start overwrites rows of it and replays the
+        # template; allocated here, touched by start() only
+        fr["z_all"] = self.model.template_input()
+        fr["events"], fr["z_snapped"] = [], False
+        if B <= 32 and fr["z_all"] is not None and fr["z_all"].shape[0] == B:
+            with torch.cuda.device(device):
+                fr["z_snap"] = torch.empty_like(fr["z_all"])
+                fr["win"] = torch.zeros((B, 3), dtype=torch.int32, device=device)
+                fr["rects"] = torch.zeros((B, 4), dtype=torch.int32, device=device)
+                fr["sums"] = torch.zeros((B, 3), dtype=torch.int64, device=device)
 
     def _fr_upload(self):
         """the host's state -> the device block (values as kernel arguments), then the plan of the next frame"""
@@ -212,9 +353,10 @@ class DeviceTracker(object):
             raise ValueError("gt must be a uint8 CUDA tensor [%d,%d]" % (H, W))
         if B > 32:
             raise ValueError("VOS scoring takes up to 32 objects, the tracker has %d" % B)
-        unknown = set(vos) - {"object_ids", "thrs", "alive"}
+        unknown = set(vos) - {"object_ids", "thrs", "alive", "given", "init"}
         if unknown or "object_ids" not in vos or "thrs" not in vos:
-            raise ValueError("vos = {'object_ids': B ids, 'thrs': 1..8 thresholds[, 'alive': B booleans]}")
+            raise ValueError("vos = {'object_ids': B ids, 'thrs': 1..8 thresholds[, 'alive': B booleans][, 'given': B booleans, "
+                             "'init': uint8 CUDA labels]}")
         ids = np.asarray(vos["object_ids"])
         if ids.shape != (B,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
             raise ValueError("vos['object_ids'] must be %d integers in 0..255" % B)
@@ -233,7 +375,17 @@ class DeviceTracker(object):
         if labels_out is not None and (labels_out.dtype != torch.uint8 or not labels_out.is_cuda or
                                        not labels_out.is_contiguous() or tuple(labels_out.shape) != (H, W)):
             raise ValueError("labels_out must be a contiguous uint8 CUDA tensor [%d,%d]" % (H, W))
-        return gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits
+        given, init = vos.get("given"), vos.get("init")
+        gbits = 0
+        if given is not None:                                         # an object's start frame: its probability is the init mask
+            given = np.asarray(given)
+            if given.shape != (B,):
+                raise ValueError("vos['given'] must be %d booleans" % B)
+            gbits = sum(1 << b for b in range(B) if given[b])
+        if gbits and (not isinstance(init, torch.Tensor) or not init.is_cuda or init.dtype != torch.uint8 or
+                      tuple(init.shape) != (H, W)):
+            raise ValueError("vos['given'] comes with vos['init'], a uint8 CUDA tensor [%d,%d]" % (H, W))
+        return gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits, init.contiguous() if gbits else None
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
@@ -268,7 +420,7 @@ class DeviceTracker(object):
                 sp = _lib.current_stream_ptr()
                 if fr["synced"] is None or st["target_pos"] is not fr["synced"][0] or st["target_sz"] is not fr["synced"][1]:
                     self._fr_upload()                                 # a track() in between: the host is ahead
-                if fr["pending"] == 0:                                # chunk start: what a reported sequence failure rewinds to
+                if fr["pending"] == 0 and not fr["events"]:           # chunk start: what a reported sequence failure rewinds to
                     fr["snap"].copy_(fr["dev"])
                     fr["start"] = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in st.items()}
                 t = fr["pending"]
@@ -281,7 +433,7 @@ class DeviceTracker(object):
                     fr["rbox"][blk] = torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=fr["device"])
                 score = None
                 if spec is not None:
-                    K = int(spec[2].size)
+                    K = int(spec[2].size)                             # spec: gt, ids, thrs, alive bits, given bits, init labels
                     if i == 0 and blk == len(fr["vos"]):              # count rows per block, like fr["rows"]
                         fr["vos"].append(torch.empty((_ROWS_PER_BLOCK, B, 8, 2), dtype=torch.int32, device=fr["device"]))
                     labels = labels_out if labels_out is not None else torch.empty((H, W), dtype=torch.uint8, device=fr["device"])
@@ -332,12 +484,15 @@ class DeviceTracker(object):
         if rbox is not None:                                          # same stream, behind the paste-back (:285-303)
             preproc.mask_rboxes(mask, out=rbox)
         if score is not None:                                         # the same slot of the same state block, same stream
-            gt, ids, thrs, bits, row, labels = score
-            _lib.check(_lib.lib().smk_vos_score_dev(
-                logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
-                int(head.shape[-1]) if head is not None else 0, self.mask_size, fr["dev"].data_ptr(), slot, fr["B"], fr["W"],
-                fr["H"], -1.0, gt.data_ptr(), ids.ctypes.data, bits, thrs.ctypes.data, int(thrs.size), float(p.seg_thr),
-                row.data_ptr(), labels.data_ptr(), sp))
+            gt, ids, thrs, bits, gbits, init, row, labels = score
+            args = (logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
+                    int(head.shape[-1]) if head is not None else 0, self.mask_size, fr["dev"].data_ptr(), slot, fr["B"], fr["W"],
+                    fr["H"], -1.0, gt.data_ptr(), ids.ctypes.data, bits, thrs.ctypes.data, int(thrs.size), float(p.seg_thr),
+                    row.data_ptr(), labels.data_ptr())
+            if gbits:                                                 # an object's start frame (tools/test.py:493,503-504)
+                _lib.check(_lib.lib().smk_vos_score_dev_ex(*(args + (gbits, init.data_ptr(), sp))))
+            else:
+                _lib.check(_lib.lib().smk_vos_score_dev(*(args + (sp,))))
 
     def _fr_rewind(self):
         """a persistent-sequence failure was reported (SMK_E_SEQ): every frame of the pending chunk is invalid and so is the
@@ -349,7 +504,10 @@ class DeviceTracker(object):
             fr["dev"].copy_(fr["snap"])
             self.state = fr["start"]
             fr["synced"] = (self.state["target_pos"], self.state["target_sz"])
+            if fr["z_snapped"]:                                       # the chunk held a stream start: the template input as it was
+                fr["z_all"].copy_(fr["z_snap"])
         fr["start"] = None
+        fr["events"], fr["z_snapped"] = [], False
         fr["pending"], fr["deferred"], fr["masks"], fr["poly"] = 0, None, [], []
         fr["labels"], fr["vos_k"] = [], None
         fr.pop("whole", None)
@@ -373,8 +531,11 @@ class DeviceTracker(object):
         T, B = fr["pending"], fr["B"]
         whole = fr.pop("whole", None)                                 # run() (or its caller) gave one [T,B,H,W] mask tensor
         whole_labels = fr.pop("whole_labels", None)
-        if T == 0:
+        events = fr["events"]
+        if T == 0 and not events:
             return None
+        if T == 0:
+            return self._collect_events_only()
         try:
             with torch.cuda.device(fr["device"]):
                 sp = _lib.current_stream_ptr()
@@ -396,7 +557,13 @@ class DeviceTracker(object):
                     n_row = rows.shape[2]
                     vc = vc.reshape(T, B * 16)[:, :B * K * 2].reshape(T, B, K * 2)      # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
-                host = rows.cpu().numpy()                             # the one synchronisation
+                if events:                                            # the start events' result rows ride along
+                    shape = tuple(rows.shape)
+                    flat = torch.cat([rows.reshape(-1)] + [e["res"].reshape(-1) for e in events]).cpu().numpy()
+                    host = flat[:rows.numel()].reshape(shape)         # the one synchronisation
+                    ev_rows = flat[rows.numel():].reshape(len(events), B, START_ROW)
+                else:
+                    host = rows.cpu().numpy()                         # the one synchronisation
         except _lib.SmkError as e:
             if e.code == _lib.E_SEQ:
                 self._fr_rewind()
@@ -439,9 +606,50 @@ class DeviceTracker(object):
                   crop_box=[[float(v[0]), float(v[1]), int(v[2]), int(v[3])] for v in res["crop_box"][-1]], x_crop=None)
         if fr["poly"][-1]:
             st["polygon"], st["polygon_found"] = res["polygon"][-1].copy(), res["polygon_found"][-1].copy()
+        if events:
+            res["events"] = self._apply_events(events, ev_rows, T)
         fr["synced"] = (st["target_pos"], st["target_sz"])            # the device holds exactly these values
         fr["pending"], fr["masks"], fr["poly"], fr["start"] = 0, [], [], None
         fr["labels"], fr["vos_k"] = [], None
+        fr["events"], fr["z_snapped"] = [], False
+        return res
+
+    def _apply_events(self, events, ev_rows, T):
+        """the start events of a collected chunk -> [{'t', 'streams', 'started', 'avg_chans', 'target_pos', 'target_sz'}]; tr.state
+        takes the mean colour of every stream that started, and the position / size of one no frame of the chunk followed"""
+        st = self.state
+        st["avg_chans"] = list(st["avg_chans"])
+        out = []
+        for e, rows in zip(events, ev_rows):
+            r = rows[e["streams"]]
+            started = r[:, 0] != 0
+            out.append({"t": e["t"], "streams": list(e["streams"]), "started": started, "avg_chans": r[:, 1:4].copy(),
+                        "target_pos": r[:, 4:6].copy(), "target_sz": r[:, 6:8].copy()})
+            for i, b in enumerate(e["streams"]):
+                if not started[i]:
+                    continue
+                st["avg_chans"][b] = r[i, 1:4].copy()
+                if e["t"] == T:
+                    st["target_pos"][b], st["target_sz"][b] = r[i, 4:6], r[i, 6:8]
+        return out
+
+    def _collect_events_only(self):
+        """collect() of a chunk that holds start events and no frame: ONE synchronisation -> {'events': [...]}"""
+        fr, st = self._fr, self.state
+        events, B = fr["events"], fr["B"]
+        try:
+            with torch.cuda.device(fr["device"]):
+                _lib.check(_lib.lib().smk_seq_sync_check(self.model._ctx, _lib.current_stream_ptr(), None))
+                ev_rows = torch.cat([e["res"].reshape(-1) for e in events]).cpu().numpy().reshape(len(events), B, START_ROW)
+        except _lib.SmkError as e:
+            if e.code == _lib.E_SEQ:
+                self._fr_rewind()
+            raise
+        st["target_pos"], st["target_sz"] = st["target_pos"].copy(), st["target_sz"].copy()
+        res = {"events": self._apply_events(events, ev_rows, 0)}
+        fr["synced"] = (st["target_pos"], st["target_sz"])
+        fr["start"] = None
+        fr["events"], fr["z_snapped"] = [], False
         return res
 
     def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None):
@@ -449,7 +657,8 @@ class DeviceTracker(object):
         mask_out: uint8 CUDA [T,B,H,W] to receive the masks.
         gt (uint8 CUDA [T,im_h,im_w]) and vos (as for enqueue(); 'alive' may be [T,B]): every frame is scored against its
         annotation -> res['vos_counts'] int64 [T,B,K,2] (siammask_amd.vos.mean_iou takes it) and res['labels'] uint8 CUDA
-        [T,im_h,im_w]."""
+        [T,im_h,im_w].  vos with 'start' / 'end' (object id -> frame, as the dataset's dictionaries) [and 'init']: the objects
+        start and end on their own frames of the WHOLE video ``frames`` (see _run_lifetimes)."""
         fr = self._fr
         if self.state is None or fr is None:
             raise RuntimeError("DeviceTracker.run(): init() first")
@@ -459,6 +668,8 @@ class DeviceTracker(object):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T = int(frames.shape[0])
         labels, alive = None, None
+        if isinstance(vos, dict) and ("start" in vos or "end" in vos or "init" in vos):
+            return self._run_lifetimes(frames, want_mask, want_polygon, mask_out, gt, vos)
         if gt is not None or vos is not None:                         # checked for the whole run before the first launch
             if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T or not isinstance(vos, dict):
                 raise ValueError("VOS scoring: frames [T,H,W,3] shared by the objects, gt uint8 CUDA [T,H,W] and a vos spec")
@@ -487,6 +698,78 @@ class DeviceTracker(object):
         if labels is not None:
             fr["whole_labels"] = labels
         return self.collect()
+
+    def _run_lifetimes(self, frames, want_mask, want_polygon, mask_out, gt, vos):
+        """run() with vos['start'] / vos['end']: the loop of track_vos (tools/test.py:481-504) for the B objects of one video.
+        frames are ALL T frames, indexed as the dataset's dictionaries index them; object j = vos['object_ids'][j] runs on
+        stream j.  On frame f == start it is started from vos['init'] (uint8 CUDA [H,W], or [T,H,W] indexed by the frame;
+        default gt) BEHIND the frame's step, its mask row is init == id and the scoring takes that row as given (:493,503-504);
+        on start < f <= end it is tracked and alive; otherwise idle: mask zeros, not alive.  -> collect()'s dict plus
+        'alive' bool [T,B] (tracked frames); the scalar rows (target_pos, score, ...) of a stream on a frame where it is not
+        alive are unspecified, and so is everything of a stream whose object was absent from its init labels
+        (res['events'] says which started)."""
+        fr = self._fr
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        T = int(frames.shape[0])
+        if "start" not in vos or "end" not in vos:
+            raise ValueError("vos['start'] and vos['end'] come together")
+        if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T:
+            raise ValueError("VOS scoring: frames [T,H,W,3] shared by the objects, gt uint8 CUDA [T,H,W] and a vos spec")
+        if "alive" in vos or "given" in vos:
+            raise ValueError("with vos['start'] / vos['end'] the lifetimes decide 'alive' and 'given'")
+        base = {k: vos[k] for k in vos if k not in ("start", "end", "init")}
+        ids = np.asarray(base.get("object_ids", ()))
+        if ids.shape != (B,) or ids.dtype.kind not in "iu":
+            raise ValueError("vos['object_ids'] must be %d integers in 0..255" % B)
+        first, last = np.zeros(B, dtype=np.int64), np.zeros(B, dtype=np.int64)
+        for j, i in enumerate(ids):
+            for d, out in ((vos["start"], first), (vos["end"], last)):
+                if str(int(i)) in d:
+                    out[j] = int(d[str(int(i))])
+                elif int(i) in d:
+                    out[j] = int(d[int(i)])
+                else:
+                    raise ValueError("object id %d is missing from vos['start'] / vos['end']" % int(i))
+            if not 0 <= first[j] < T:
+                raise ValueError("object id %d starts on frame %d, the video has %d" % (int(i), first[j], T))
+        init = vos.get("init", gt)
+        if (not isinstance(init, torch.Tensor) or not init.is_cuda or init.dtype != torch.uint8 or
+                tuple(init.shape) not in ((H, W), (T, H, W))):
+            raise ValueError("vos['init'] must be a uint8 CUDA tensor [%d,%d] or [%d,%d,%d]" % (H, W, T, H, W))
+        f_idx = np.arange(T)[:, None]
+        given = f_idx == first[None]
+        alive = (f_idx > first[None]) & (f_idx <= last[None])
+        init_at = (lambda f: init[f]) if init.dim() == 3 else (lambda f: init)
+        specs = [dict(base, alive=alive[f], given=given[f], init=init_at(f)) for f in range(T)]
+        for f in range(T):                                            # everything is checked before the first launch
+            self._vos_spec(3, want_mask, gt[f], specs[f])
+            if given[f].any():
+                self._start_spec(frames[f], np.nonzero(given[f])[0], None, None, init_at(f), ids[given[f]])
+        if fr["pending"] or fr["events"]:
+            raise ValueError("run() with lifetimes starts its own chunk: collect() first")
+        shape = (T, B, H, W)
+        if mask_out is None:
+            masks = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+        elif mask_out.dtype != torch.uint8 or not mask_out.is_cuda or not mask_out.is_contiguous() or tuple(mask_out.shape) != shape:
+            raise ValueError("mask_out must be a contiguous uint8 CUDA tensor %s" % (shape,))
+        else:
+            masks = mask_out
+        labels = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
+        for f in range(T):
+            self.enqueue(frames[f], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[f], gt=gt[f], vos=specs[f],
+                         labels_out=labels[f])
+            if given[f].any():                                        # behind the step: the stream's first tracked frame is f + 1
+                self.start(frames[f], np.nonzero(given[f])[0], labels=init_at(f), object_ids=ids[given[f]])
+        fr["whole"], fr["whole_labels"] = masks, labels
+        res = self.collect()
+        # the mask rows the tracker did not produce: the init mask at a start frame, zeros while idle
+        for f, j in np.argwhere(given):
+            res["mask"][f, j] = (init_at(f) == int(ids[j])).to(torch.uint8)
+        idle = ~(given | alive)
+        if idle.any():
+            res["mask"][torch.from_numpy(idle).to(res["mask"].device)] = 0
+        res["alive"] = alive
+        return res
 
     @staticmethod
     def _vos_at(vos, alive, t):
