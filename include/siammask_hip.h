@@ -388,6 +388,35 @@ int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes,
                           const int32_t *win_dev, const double *result_dev, uint32_t start_mask, int B, int model_sz,
                           float *z_all_dev, void *stream);
 
+/* ---- VOT overlap of the tracked polygon with the annotation (tools/test.py:344-354 vot_overlap; ABI 1.11, additive) ---------
+ * What track_vot asks of the reference's utils/pyvotkit after every tracked frame -- region.c compute_polygon_overlap of two
+ * 4-vertex polygons inside the bounds (left 0, top 0, right im_w, bottom im_h), non-legacy rasterisation -- for B pairs in
+ * one launch, one workgroup per pair, the returned float32 bit for bit: vertices narrowed float64 -> float32, bounds floored /
+ * ceiled and cut to the image, vertices moved to the joint window and rounded half away from zero, one node per non-horizontal
+ * edge whose closed row range holds the row, at (int)((double)x_i + (double)(row - y_i) / r * k), nodes sorted, pairs filled
+ * inclusively with a pair of equal neighbours advancing by one, ends clamped to the window.  Pixels are counted as SET MASK
+ * PIXELS (a pixel two fills of one polygon share counts once); no mask is stored.  Every early return of the reference is
+ * kept and reported: counts[3] = 0 rasterised; 1 / 2 area ratio a1 / a2 resp. a2 / a1 below 1e-10 (negative ratios included,
+ * NaN ratios not); 3 window narrower or lower than 1; 4 bounds_overlap == 0 -- the overlap is then 0 and the counts are 0.
+ * overlap_dev f32 [B] <- inter / (only1 + only2 + inter); NaN (0 / 0) where neither polygon sets a pixel, which the caller
+ * treats as "not lost", as Python's `if b_overlap:` does.  counts_dev (may be NULL) int32 [B][4] <- pixels of the annotation
+ * only, of the prediction only, of both, and the path.  The annotation is the reference's FIRST polygon, the prediction its
+ * second, as at :354; corners are used in the order given.
+ * The prediction of pair b:
+ *   pred_dev rows of pred_stride 8: its corners x0 y0 .. x3 y3;
+ *   pred_dev rows of pred_stride 12 (what smk_mask_rbox writes): the corners, unless the row's `found` (column 9) is not
+ *     positive and adv_rows_dev is given -- then the box of an empty mask (:298-303): centre / size BEFORE the clip (columns
+ *     8..11 of row b of adv_rows_dev, f64 [B][16] as smk_trk_advance writes them), corners (x, y) (x + w, y) (x + w, y + h)
+ *     (x, y + h) with x = cx - w / 2, y = cy - h / 2 in float64;
+ *   pred_dev NULL (a variant without a mask branch, :340,350-353): the same box of the CLIPPED state, columns 0..3 of the
+ *     advance row; adv_rows_dev is then required.
+ * gt_dev f64 [B][8].  im_w, im_h in 1..4096, B in 1..65535; coordinates whose magnitude does not fit an int32 take the value
+ * the reference's own conversion gives on x86 (INT32_MIN).  No context; asynchronous on `stream`, no host synchronisation, no
+ * workspace; bad arguments give SMK_E_ARG before anything is enqueued.  smk_version() keeps reporting 1.10: the presence of
+ * this symbol is the probe for the block. */
+int smk_vot_overlap(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev, int B, int im_w,
+                    int im_h, float *overlap_dev, int32_t *counts_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,7 @@ SYMBOLS = (
     "smk_trk_state_bytes", "smk_trk_set", "smk_trk_plan", "smk_trk_advance", "smk_crop_resize_dev", "smk_paste_mask_dev",
     "smk_vos_score", "smk_vos_score_dev", "smk_host_trk_plan", "smk_host_trk_advance",
     "smk_vos_score_ex", "smk_vos_score_dev_ex", "smk_label_rects", "smk_frame_sums", "smk_trk_start", "smk_crop_exemplar_dev",
-    "smk_host_trk_start",
+    "smk_host_trk_start", "smk_vot_overlap", "smk_host_vot_overlap",
 )
 
 
@@ -154,6 +154,8 @@ def lib():
     L.smk_trk_start.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, ci, ci, vp, vp, vp]
     L.smk_host_trk_start.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, ci, ci, vp, vp]
     L.smk_crop_exemplar_dev.argtypes = [vp, i64, ci, ci, vp, vp, vp, u32, ci, ci, fp, vp]
+    L.smk_vot_overlap.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, vp, vp]
+    L.smk_host_vot_overlap.argtypes = [vp, vp, ci, ci, ci, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

@@ -27,6 +27,7 @@
 #include "conv_plan.h"
 #include "smk_kernels.h"
 #include "tracker_state.h"
+#include "vot_overlap.h"
 
 using namespace smk;
 
@@ -3586,6 +3587,35 @@ int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes,
     p.H = H; p.W = W; p.model_sz = model_sz;
     p.st = (const smk_trk_stream *)state_dev; p.win = win_dev; p.res = result_dev; p.mask = start_mask;
     if (launch_crop_exemplar_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev launch failed");
+    return 0;
+}
+
+// ---- VOT overlap (tools/test.py:354 vot_overlap; vot_overlap.hip / vot_overlap.h) ------------------------------------------
+int smk_vot_overlap(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev, int B, int im_w,
+                    int im_h, float *overlap_dev, int32_t *counts_dev, void *stream) {
+    if (!gt_dev || !overlap_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap: null argument");
+    if (pred_dev && pred_stride != 8 && pred_stride != 12)
+        return fail(SMK_E_ARG, "smk_vot_overlap: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
+    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap: %d pairs (1..65535)", B);
+    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
+    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)overlap_dev % 4 ||
+        (uintptr_t)counts_dev % 4)
+        return fail(SMK_E_ARG, "smk_vot_overlap: misaligned argument");
+    VotParams p;
+    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
+    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = im_w; p.im_h = im_h;
+    if (launch_vot_overlap(p, stream)) return fail(SMK_E_HIP, "vot_overlap launch failed");
+    return 0;
+}
+
+int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, int im_h, float *overlap, int32_t *counts) {
+    if (!pred || !gt || !overlap) return fail(SMK_E_ARG, "smk_host_vot_overlap: null argument");
+    if (n < 1) return fail(SMK_E_ARG, "smk_host_vot_overlap: %d pairs", n);
+    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_host_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
+    for (int i = 0; i < n; ++i)                                        // the annotation is the reference's first polygon (:354)
+        overlap[i] = vot_overlap_serial(gt + 8 * (size_t)i, pred + 8 * (size_t)i, im_w, im_h, counts ? counts + 4 * (size_t)i : nullptr);
     return 0;
 }
 

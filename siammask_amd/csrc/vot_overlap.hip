@@ -1,0 +1,59 @@
+// vot_overlap.hip -- the VOT overlap (tools/test.py:354 vot_overlap) of B (prediction, annotation) polygon pairs on the device
+// (gfx950), so that the supervised loop of track_vot needs no polygon on the host.  One workgroup per pair:
+// every lane derives the joint window (a few dozen float operations, the same in every lane), the lanes then take the rows of
+// the window in a strided loop -- a row is two sorted 4-node lists turned into closed intervals, all in registers
+// (vot_overlap.h) -- and the three exact int32 sums are reduced by shuffles per wave and through LDS across the waves.  No mask
+// is written anywhere; the result leaves in plain vector stores by one lane.
+#include <hip/hip_runtime.h>
+#include "vot_overlap.h"
+
+namespace smk {
+
+constexpr int VOT_THREADS = 256, VOT_WAVES = VOT_THREADS / 64;
+
+__global__ __launch_bounds__(VOT_THREADS) void vot_overlap_kernel(const VotParams p) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= p.B) return;                                             // (uniform per workgroup)
+    __shared__ int part[VOT_WAVES][3];
+    double c[8];
+    vot_pred_corners(p.pred, p.pred_stride, p.adv, b, c);
+    const VotPoly p2 = vot_poly(c);                                   // the prediction is the reference's second polygon
+    const VotPoly p1 = vot_poly(p.gt + 8 * (size_t)b);
+    const VotWindow w = vot_window(p1, p2, p.im_w, p.im_h);
+    int cnt[3] = {0, 0, 0};
+    if (w.path == VOT_PATH_RASTER) {                                  // (uniform: every lane computed the same window)
+        const VotPoly q1 = vot_place(p1, w.ox, w.oy), q2 = vot_place(p2, w.ox, w.oy);
+        for (int Y = tid; Y < w.height; Y += VOT_THREADS) vot_row_counts(q1, q2, Y, w.width, cnt);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt[0] += __shfl_down(cnt[0], off, 64);
+        cnt[1] += __shfl_down(cnt[1], off, 64);
+        cnt[2] += __shfl_down(cnt[2], off, 64);
+    }
+    if ((tid & 63) == 0) {
+        part[tid >> 6][0] = cnt[0];
+        part[tid >> 6][1] = cnt[1];
+        part[tid >> 6][2] = cnt[2];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n1 = 0, n2 = 0, inter = 0;
+#pragma unroll
+        for (int k = 0; k < VOT_WAVES; ++k) { n1 += part[k][0]; n2 += part[k][1]; inter += part[k][2]; }
+        int32_t out[4];
+        p.overlap[b] = vot_result(n1, n2, inter, w.path, out);
+        if (p.counts) {
+            int32_t *dst = p.counts + 4 * (size_t)b;
+            dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
+        }
+    }
+}
+
+int launch_vot_overlap(const VotParams &p, void *stream) {
+    if (p.B < 1 || p.B > 65535) return -1;
+    hipLaunchKernelGGL(vot_overlap_kernel, dim3(p.B), dim3(VOT_THREADS), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+}  // namespace smk

@@ -338,3 +338,43 @@ def mask_rboxes(mask, min_area=100.0, out=None):
             raise ValueError("mask_rboxes: out must be a contiguous float64 CUDA tensor of %d elements" % (B * 12))
         _lib.check(L.smk_mask_rbox(m.data_ptr(), B, W, H, float(min_area), ws.data_ptr(), need, out.data_ptr(), stream))
     return out
+
+
+def vot_overlap(pred, gt, im_wh, adv_rows=None, out=None, counts=None):
+    """vot_overlap(gt_polygon, pred_polygon, (im_w, im_h)) of tools/test.py:354 for B pairs on the device, bit for bit
+    (include/siammask_hip.h: smk_vot_overlap).  pred: float64 CUDA [B,8] / [B,4,2] corners, or the [B,12] rows of mask_rboxes
+    (with adv_rows, float64 CUDA [B,16] rows of the tracker's advance, a row whose mask was empty takes the box of the state
+    before the clip), or None: the box of the clipped state of adv_rows (a variant without a mask branch).  gt: float64 CUDA
+    [B,8] / [B,4,2].  im_wh: (im_w, im_h), each 1..4096.
+    -> float32 CUDA [B] (NaN where neither polygon sets a pixel); out: a contiguous float32 CUDA [B] to write into; counts: a
+    contiguous int32 CUDA [B,4] that receives (annotation only, prediction only, both, path).  Enqueue-only."""
+    _need_cuda(gt, "gt")
+    if gt.dtype != torch.float64 or gt.dim() not in (2, 3) or gt[0].numel() != 8 or not gt.is_contiguous():
+        raise ValueError("gt must be a contiguous float64 CUDA tensor [B,8] or [B,4,2]")
+    B = int(gt.shape[0])
+    stride = 0
+    if pred is not None:
+        _need_cuda(pred, "pred")
+        if pred.dtype != torch.float64 or pred.dim() not in (2, 3) or pred.shape[0] != B or not pred.is_contiguous() or \
+                pred[0].numel() not in (8, 12):
+            raise ValueError("pred must be a contiguous float64 CUDA tensor [%d,8], [%d,4,2] or [%d,12]" % (B, B, B))
+        stride = int(pred[0].numel())
+    elif adv_rows is None:
+        raise ValueError("vot_overlap: pred, or adv_rows for the box of the state")
+    if adv_rows is not None:
+        _need_cuda(adv_rows, "adv_rows")
+        if adv_rows.dtype != torch.float64 or tuple(adv_rows.shape) != (B, 16) or not adv_rows.is_contiguous():
+            raise ValueError("adv_rows must be a contiguous float64 CUDA tensor [%d,16]" % B)
+    if out is None:
+        out = torch.empty(B, dtype=torch.float32, device=gt.device)
+    elif out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (B,):
+        raise ValueError("out must be a contiguous float32 CUDA tensor [%d]" % B)
+    if counts is not None and (counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or
+                               tuple(counts.shape) != (B, 4)):
+        raise ValueError("counts must be a contiguous int32 CUDA tensor [%d,4]" % B)
+    with torch.cuda.device(gt.device):
+        _lib.check(_lib.lib().smk_vot_overlap(
+            pred.data_ptr() if pred is not None else None, stride, adv_rows.data_ptr() if adv_rows is not None else None,
+            gt.data_ptr(), B, int(im_wh[0]), int(im_wh[1]), out.data_ptr(), counts.data_ptr() if counts is not None else None,
+            _lib.current_stream_ptr()))
+    return out

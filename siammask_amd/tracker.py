@@ -26,6 +26,14 @@ Streams that start on their own frames (siamese_init per stream on the device, e
     tr.start(frame, [2], pos=[(cx, cy)], sz=[(w, h)])              # the VOT re-init (:354-363); the other streams keep running
     res = tr.run(frames, gt=gt, vos={'object_ids': ids, 'thrs': vos.THRS, 'start': {...}, 'end': {...}})   # track_vos (:481-504)
     res['alive'], res['events']                                    # bool [T,B]; what every start event did
+
+The VOT supervised loop (track_vot, :318-365) for B videos in lock-step, still enqueue-only: the overlap of every tracked polygon
+with its annotation is computed on the device (csrc/vot_overlap.hip), the host learns of a loss through a read-back that lags
+skip - 1 frames behind the queue head and re-initialises the stream with start(pos=, sz=) (siammask_amd/vot.py: the decisions):
+    tr.reserve(B, H, W)
+    res = tr.run(frames, want_polygon=True, vot={'gt': gt_f64[T,B,8], 'skip': 5, 'length': None})
+    res['vot_code'], res['overlap'], res['lost_times']             # int8 [T,B] (1 init, 2 lost, 0 skipped, -1 tracked), f32 [T,B], [B]
+    vot.region_lines(res, b)                                       # the lines of <video>_001.txt (:403-406)
 """
 import ctypes
 
@@ -387,7 +395,7 @@ class DeviceTracker(object):
             raise ValueError("vos['given'] comes with vos['init'], a uint8 CUDA tensor [%d,%d]" % (H, W))
         return gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits, init.contiguous() if gbits else None
 
-    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None):
+    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _vot=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -459,8 +467,11 @@ class DeviceTracker(object):
                 mask = None
                 if want_mask:
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=fr["device"])
+                    vot_job = None
+                    if _vot is not None:                              # run(vot=): + this frame's advance rows
+                        vot_job = dict(_vot, adv=fr["rows"][blk][i])
                     job = (out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
-                           fr["rbox"][blk][i] if want_polygon else None, score)
+                           fr["rbox"][blk][i] if want_polygon else None, score, vot_job)
                     if depth:
                         fr["deferred"] = job                          # pasted behind the NEXT step (or by collect())
                     else:
@@ -475,7 +486,7 @@ class DeviceTracker(object):
         return t
 
     def _fr_paste(self, job, sp):
-        logits, head, slot, mask, rbox, score = job
+        logits, head, slot, mask, rbox, score, vot_job = job
         fr, p = self._fr, self.p
         _lib.check(_lib.lib().smk_paste_mask_dev(
             logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
@@ -493,6 +504,19 @@ class DeviceTracker(object):
                 _lib.check(_lib.lib().smk_vos_score_dev_ex(*(args + (gbits, init.data_ptr(), sp))))
             else:
                 _lib.check(_lib.lib().smk_vos_score_dev(*(args + (sp,))))
+        if vot_job is not None:                                       # behind the rotated box, same stream (tools/test.py:344-354)
+            preproc.vot_overlap(rbox, vot_job["gt"], (fr["W"], fr["H"]), adv_rows=vot_job["adv"], out=vot_job["out"])
+            vot_job["host"].copy_(vot_job["out"], non_blocking=True)  # the lagging read-back: [B] floats into pinned memory
+            vot_job["event"].record(torch.cuda.current_stream())
+            vot_job["recorded"][0] = True
+
+    def _fr_flush(self, sp):
+        """paste (and score) the frame whose paste-back is still deferred, if there is one"""
+        fr = self._fr
+        if fr["deferred"] is not None:
+            self.model.pipeline_join()
+            job, fr["deferred"] = fr["deferred"], None
+            self._fr_paste(job, sp)
 
     def _fr_rewind(self):
         """a persistent-sequence failure was reported (SMK_E_SEQ): every frame of the pending chunk is invalid and so is the
@@ -652,13 +676,15 @@ class DeviceTracker(object):
         fr["events"], fr["z_snapped"] = [], False
         return res
 
-    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None):
+    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, vot=None):
         """enqueue every frame of ``frames`` (uint8 CUDA [T,H,W,3], or [T,B,H,W,3] for per-stream frames), then collect().
         mask_out: uint8 CUDA [T,B,H,W] to receive the masks.
         gt (uint8 CUDA [T,im_h,im_w]) and vos (as for enqueue(); 'alive' may be [T,B]): every frame is scored against its
         annotation -> res['vos_counts'] int64 [T,B,K,2] (siammask_amd.vos.mean_iou takes it) and res['labels'] uint8 CUDA
         [T,im_h,im_w].  vos with 'start' / 'end' (object id -> frame, as the dataset's dictionaries) [and 'init']: the objects
-        start and end on their own frames of the WHOLE video ``frames`` (see _run_lifetimes)."""
+        start and end on their own frames of the WHOLE video ``frames`` (see _run_lifetimes).
+        vot ({'gt': float64 [T,B,8][, 'skip': 5][, 'length': [B]]}, with want_polygon): the supervised loop of track_vot for B
+        videos in lock-step, frames [T,B,H,W,3] (see _run_vot)."""
         fr = self._fr
         if self.state is None or fr is None:
             raise RuntimeError("DeviceTracker.run(): init() first")
@@ -668,6 +694,10 @@ class DeviceTracker(object):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T = int(frames.shape[0])
         labels, alive = None, None
+        if vot is not None:
+            if gt is not None or vos is not None:
+                raise ValueError("run(): vot= (polygon annotations, the supervised loop) or gt= / vos= (label maps), not both")
+            return self._run_vot(frames, want_mask, want_polygon, mask_out, vot)
         if isinstance(vos, dict) and ("start" in vos or "end" in vos or "init" in vos):
             return self._run_lifetimes(frames, want_mask, want_polygon, mask_out, gt, vos)
         if gt is not None or vos is not None:                         # checked for the whole run before the first launch
@@ -769,6 +799,93 @@ class DeviceTracker(object):
         if idle.any():
             res["mask"][torch.from_numpy(idle).to(res["mask"].device)] = 0
         res["alive"] = alive
+        return res
+
+    def _run_vot(self, frames, want_mask, want_polygon, mask_out, spec):
+        """run() with vot=: the loop of track_vot (tools/test.py:318-365) for B videos in lock-step -- after every tracked frame
+        the polygon is compared with the annotation (smk_vot_overlap behind the frame's rotated box), an overlap of exactly 0
+        is a loss, the stream skips `skip` frames and is re-initialised from the annotation's axis-aligned box
+        (vot.axis_aligned_bbox) with start(pos=, sz=).  The queue is never drained: a loss on frame f takes effect on frame
+        f + skip, so before frame g is enqueued the host waits only for the [B] overlaps of frame g - skip (an asynchronous copy
+        into pinned memory followed by an event), `skip` - 1 frames behind the queue head; the decisions are vot.Schedule's.
+        frames: ALL T frames, uint8 CUDA [T,B,H,W,3] (or [T,H,W,3]: one video shared by the streams); spec['gt']: host float64
+        [T,B,8] ([T,8] for B = 1), uploaded once; spec['length'] [B]: a video's frame count -- the stream is idle behind it.
+        Stream b starts on frame 0 from gt[0, b]: reserve() suffices, no init().  A stream inside a skip window keeps stepping
+        in lock-step; what it reports there is ignored and the re-initialisation overwrites its state.
+        -> collect()'s dict (with 'events': every start) plus vot_code int8 [T,B] (1 init, 2 lost, 0 skipped or idle, -1
+        tracked: the region is polygon[t, b]), overlap float32 [T,B] (the kernel's value on tracked and lost frames, NaN kept,
+        0 elsewhere), lost_times [B], vot_length [B]; vot.region_lines(res, b) writes the result file.  The scalar rows, masks
+        and polygons of a stream on a frame whose code is not -1 / 2 are unspecified."""
+        from . import vot as votmod
+        fr = self._fr
+        B, H, W = fr["B"], fr["H"], fr["W"]
+        T = int(frames.shape[0])
+        if not isinstance(spec, dict) or "gt" not in spec or set(spec) - {"gt", "skip", "length"}:
+            raise ValueError("vot = {'gt': float64 [T,B,8][, 'skip': frames skipped after a loss (5)][, 'length': B frame counts]}")
+        if not want_polygon or not want_mask or self.model.variant == "rpn":
+            raise ValueError("run(vot=) compares the polygon of the mask: want_mask, want_polygon and a variant with a mask branch")
+        if T < 1 or frames.dtype != torch.uint8 or tuple(frames.shape[1:]) not in ((B, H, W, 3), (H, W, 3)):
+            raise ValueError("frames must be uint8 [T,%d,%d,%d,3] (or [T,%d,%d,3] shared by the streams)" % (B, H, W, H, W))
+        gt = np.asarray(spec["gt"], dtype=np.float64)
+        if gt.shape == (T, 8) and B == 1:
+            gt = gt[:, None]
+        if gt.shape != (T, B, 8) or not np.isfinite(gt).all():
+            raise ValueError("vot['gt'] must be %d x %d x 8 finite values (4-corner regions)" % (T, B))
+        skip = spec.get("skip", 5)
+        if int(skip) != skip or skip < 1:
+            raise ValueError("vot['skip'] must be an integer >= 1")
+        sched = votmod.Schedule(T, B, skip=int(skip), length=spec.get("length"))       # (checks length)
+        skip = sched.skip
+
+        def boxes(g, streams):                                        # [n,4] cx cy w h; only start frames need them
+            return np.array([votmod.axis_aligned_bbox(gt[g, b]) for b in streams], dtype=np.float64).reshape(-1, 4)
+        box0 = boxes(0, range(B))
+        self._start_spec(frames[0], list(range(B)), box0[:, 0:2], box0[:, 2:4], None, None)
+        if fr["pending"] or fr["events"]:
+            raise ValueError("run(vot=) starts its own chunk: collect() first")
+        shape = (T, B, H, W)
+        if mask_out is None:
+            masks = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+        elif mask_out.dtype != torch.uint8 or not mask_out.is_cuda or not mask_out.is_contiguous() or tuple(mask_out.shape) != shape:
+            raise ValueError("mask_out must be a contiguous uint8 CUDA tensor %s" % (shape,))
+        else:
+            masks = mask_out
+        ring_n = skip + 1                                             # row f is consumed before frame f + skip + 1 writes it again
+        with torch.cuda.device(fr["device"]):
+            gt_dev = torch.from_numpy(np.ascontiguousarray(gt)).to(fr["device"])
+            ov_dev = torch.zeros((T, B), dtype=torch.float32, device=fr["device"])
+            ring = torch.zeros((ring_n, B), dtype=torch.float32).pin_memory()
+            jobs = [None] * T
+
+            def report_next():
+                f = sched.reported
+                job = jobs[f]
+                if job is None:                                       # no stream was tracked on f: nothing was computed
+                    sched.report(np.zeros(B, dtype=np.float32))
+                    return
+                if not job["recorded"][0]:                            # its paste-back is still deferred (skip 1, pipelined)
+                    self._fr_flush(_lib.current_stream_ptr())
+                job["event"].synchronize()
+                sched.report(job["host"].numpy().copy())
+                jobs[f] = None
+
+            for g in range(T):
+                while sched.reported <= g - skip:
+                    report_next()
+                starts = sched.starts(g)
+                if sched.may_track(g).any():
+                    jobs[g] = {"gt": gt_dev[g], "out": ov_dev[g], "host": ring[g % ring_n], "event": torch.cuda.Event(),
+                               "recorded": [False]}
+                self.enqueue(frames[g], want_mask=True, want_polygon=True, mask_out=masks[g], _vot=jobs[g])
+                if starts:                                            # behind the step: the stream's first tracked frame is g + 1
+                    box = boxes(g, starts)
+                    self.start(frames[g], starts, pos=box[:, 0:2], sz=box[:, 2:4])
+            fr["whole"] = masks
+            res = self.collect()
+            while sched.reported < T:                                 # the queue's tail: everything is complete behind collect()
+                report_next()
+        res["vot_code"], res["overlap"], res["lost_times"] = sched.code, sched.overlap, sched.lost_times
+        res["vot_length"] = sched.length.copy()
         return res
 
     @staticmethod
