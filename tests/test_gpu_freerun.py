@@ -126,7 +126,7 @@ def test_run_equals_the_track_loop_sharp_fp32_and_the_restatement_is_the_track_l
     _same_state(tr2, tr)
     # the device block holds the state as well: read it with one copy
     from siammask_amd.tracker import state_records
-    rec, _ = state_records(tr2._fr["dev"].cpu().numpy(), B)
+    rec, _ = state_records(tr2._fr.dev.cpu().numpy(), B)
     assert np.array_equal(R.bits(rec["target_pos"]), R.bits(tr.state["target_pos"]))
     assert np.array_equal(R.bits(rec["target_sz"]), R.bits(tr.state["target_sz"]))
 
@@ -264,7 +264,7 @@ def test_sequence_failure_rewinds_the_chunk_and_raises():
     tr = _tracker(m, HP, False, frames, B)
     tr.run(frames[1:3])                                               # (the chunk under test does not start at init)
     start = {k: np.array(tr.state[k]).copy() for k in ("target_pos", "target_sz", "score", "best_id", "delta_yx")}
-    dev_start = tr._fr["dev"].cpu().numpy().copy()
+    dev_start = tr._fr.dev.cpu().numpy().copy()
     res, err = None, None
     try:
         tr.enqueue(frames[3])
@@ -279,14 +279,14 @@ def test_sequence_failure_rewinds_the_chunk_and_raises():
     for k, v in start.items():
         now = np.array(tr.state[k])
         assert now.dtype == v.dtype and np.array_equal(now.view(np.uint64), v.view(np.uint64)), k      # (8-byte items: the bits)
-    assert np.array_equal(tr._fr["dev"].cpu().numpy(), dev_start)
+    assert np.array_equal(tr._fr.dev.cpu().numpy(), dev_start)
     assert tr.collect() is None                                       # the chunk's pending results were discarded
     assert _seq_grid(m) == 0
     again = tr.run(frames[3:7])
     assert np.isfinite(again["target_pos"]).all() and np.isfinite(again["target_sz"]).all() and np.isfinite(again["score"]).all()
     assert ((again["best_id"] >= 0) & (again["best_id"] < 3125)).all()
     assert again["mask"].shape == (4, B, 240, 320)
-    rec, _ = state_records(tr._fr["dev"].cpu().numpy(), B)
+    rec, _ = state_records(tr._fr.dev.cpu().numpy(), B)
     assert np.array_equal(R.bits(rec["target_pos"]), R.bits(tr.state["target_pos"]))
 
 

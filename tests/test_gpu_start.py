@@ -196,7 +196,7 @@ def test_reserve_and_start_equal_init():
     _same_state(a, b)
     assert np.array_equal(R.bits(np.stack(a.state["avg_chans"])), R.bits(np.stack(b.state["avg_chans"])))
     assert (a.state["im_w"], a.state["im_h"]) == (b.state["im_w"], b.state["im_h"])
-    assert torch.equal(a._fr["dev"], b._fr["dev"])
+    assert torch.equal(a._fr.dev, b._fr.dev)
 
 
 # ---- 6. late start and restart ---------------------------------------------------------------------------------------------------
@@ -298,7 +298,7 @@ def test_lifetime_loop_equals_the_restatement_of_track_vos():
     stack = np.full((B, T, 240, 320), -1.0, dtype=np.float32)
     for f in range(T):
         t = tr2.enqueue(frames[f])
-        prob = preproc.paste_masks_dev(m._io["refine1" if t & 1 else "refine"], tr2._fr["dev"], t & 1, (320, 240), seg_thr=HP["seg_thr"],
+        prob = preproc.paste_masks_dev(m._io["refine1" if t & 1 else "refine"], tr2._fr.dev, t & 1, (320, 240), seg_thr=HP["seg_thr"],
                                        want_prob=True)[1].cpu().numpy()
         for j in range(B):
             if first[j] < f <= last[j]:
@@ -346,7 +346,7 @@ def test_lifetime_loop_equals_the_restatement_of_track_vos():
     for ex in (False, True):
         cnt = torch.full((B, 4, 2), -1, dtype=torch.int32, device="cuda")
         lb = torch.full((240, 320), 255, dtype=torch.uint8, device="cuda")
-        args = (m._io["refine"].data_ptr(), None, 0, 127, tr2._fr["dev"].data_ptr(), 0, B, 320, 240, -1.0, gt[4].data_ptr(),
+        args = (m._io["refine"].data_ptr(), None, 0, 127, tr2._fr.dev.data_ptr(), 0, B, 320, 240, -1.0, gt[4].data_ptr(),
                 idb.ctypes.data, 0b101, thr.ctypes.data, 4, 0.35, cnt.data_ptr(), lb.data_ptr())
         _lib.check(L.smk_vos_score_dev_ex(*(args + (0, None, _lib.current_stream_ptr()))) if ex else
                    L.smk_vos_score_dev(*(args + (_lib.current_stream_ptr(),))))
@@ -372,17 +372,63 @@ def test_rewind_restores_the_template_input():
     want_tr.enqueue(frames[3])
     want = want_tr.collect()
     tr = _init(m, False, frames[0], pos, sz)
-    z_before, dev_before = tr._fr["z_all"].clone(), tr._fr["dev"].clone()
+    z_before, dev_before = tr._fr.z_all.clone(), tr._fr.dev.clone()
     chunk(tr)
-    assert not torch.equal(tr._fr["z_all"][5], z_before[5])
+    assert not torch.equal(tr._fr.z_all[5], z_before[5])
     tr._fr_rewind()
-    assert torch.equal(tr._fr["z_all"], z_before) and torch.equal(tr._fr["dev"], dev_before)
-    assert tr._fr["pending"] == 0 and not tr._fr["events"] and tr.collect() is None
+    assert torch.equal(tr._fr.z_all, z_before) and torch.equal(tr._fr.dev, dev_before)
+    assert tr._fr.chunk.pending == 0 and not tr._fr.chunk.events and tr.collect() is None
     chunk(tr)
     tr.enqueue(frames[3])
     got = tr.collect()
     _same(got, want, "the chunk re-run behind a rewind")
     assert got["events"][0]["started"].all()
+
+
+def test_rewind_of_a_chunk_that_holds_everything():
+    """a pipelined chunk with scored frames (two thresholds), a deferred paste-back and a stream start is rewound; the tracker
+    then runs a whole video with lifetimes exactly as a fresh tracker does"""
+    B, T = 8, 4
+    m = _model("sharp", "f16", B, "pipe")
+    frames = _frames(T - 1)
+    ids = list(range(1, B + 1))
+    rects = [(8 + 36 * j, 20 + 22 * j, 31 + 2 * j, 41 - 2 * j) for j in range(B)]
+    gt = torch.from_numpy(np.stack([_label_map([(x + 3 * t, y + t, w, h) for x, y, w, h in rects], ids) for t in range(T)])).cuda()
+    two = {"object_ids": ids, "thrs": [0.3, 0.5]}
+    spec = {"object_ids": ids, "thrs": vos.THRS, "start": {i: i % 2 for i in ids}, "end": {i: T - 1 - (i % 3 == 0) for i in ids}}
+
+    def reserved():
+        tr = DeviceTracker(m, HP, pipeline=True)
+        tr.reserve(B, 240, 320)
+        return tr
+
+    tr = reserved()
+    z_before, dev_before = tr._fr.z_all.clone(), tr._fr.dev.clone()
+    tr.enqueue(frames[0], gt=gt[0], vos=two)
+    tr.enqueue(frames[1], gt=gt[1], vos=two)
+    assert tr._fr.chunk.deferred is not None                            # pipelined: the second frame is not pasted yet
+    assert tr.start(frames[1], [5], labels=gt[1], object_ids=[6]) == 2
+    tr.enqueue(frames[2], gt=gt[2], vos=two)                            # (and a paste-back is outstanding when the rewind comes)
+    c = tr._fr.chunk
+    assert c.pending == 3 and len(c.events) == 1 and c.vos_k == 2 and len(c.labels) == 3 and c.z_snapped and c.start is not None
+    assert c.deferred is not None
+    assert not torch.equal(tr._fr.z_all[5], z_before[5]) and not torch.equal(tr._fr.dev, dev_before)
+    tr._fr_rewind()
+    assert torch.equal(tr._fr.dev, dev_before) and torch.equal(tr._fr.z_all, z_before)
+    c = tr._fr.chunk
+    assert c.pending == 0 and not c.events and c.deferred is None and not c.masks and not c.poly and not c.labels
+    assert c.vos_k is None and not c.z_snapped and c.start is None and tr.collect() is None
+    got = tr.run(frames, gt=gt, vos=spec)
+    want = reserved().run(frames, gt=gt, vos=spec)
+    assert set(got) == set(want)
+    _same(got, want, "lifetimes behind a rewind")
+    assert np.array_equal(R.bits(got["crop_box"]), R.bits(want["crop_box"]))
+    assert torch.equal(got["labels"], want["labels"]) and np.array_equal(got["vos_counts"], want["vos_counts"])
+    assert got["vos_counts"].shape == (T, B, len(vos.THRS), 2) and got["vos_counts"].any()
+    assert np.array_equal(got["alive"], want["alive"]) and got["alive"].any() and len(got["events"]) == len(want["events"]) == 2
+    for a, b in zip(got["events"], want["events"]):
+        assert (a["t"], a["streams"]) == (b["t"], b["streams"]) and np.array_equal(a["started"], b["started"]) and a["started"].all()
+        assert all(np.array_equal(R.bits(a[k]), R.bits(b[k])) for k in ("avg_chans", "target_pos", "target_sz"))
 
 
 # ---- 9. errors ----------------------------------------------------------------------------------------------------------------------
@@ -401,8 +447,8 @@ def test_errors_are_raised_before_any_launch():
     tr = DeviceTracker(m, HP)
     tr.reserve(B, 240, 320)
     torch.cuda.synchronize()
-    before = tr._fr["dev"].clone()
-    z_before = tr._fr["z_all"].clone()
+    before = tr._fr.dev.clone()
+    z_before = tr._fr.z_all.clone()
     ok = {"object_ids": [1, 2], "thrs": vos.THRS, "start": {1: 0, 2: 1}, "end": {1: 2, 2: 2}}
     for bad in ({k: v for k, v in ok.items() if k != "end"}, {k: v for k, v in ok.items() if k != "start"},
                 dict(ok, start={1: 0}), dict(ok, end={1: 2, 3: 2}), dict(ok, start={1: 0, 2: 7}), dict(ok, alive=[True, True]),
@@ -419,5 +465,5 @@ def test_errors_are_raised_before_any_launch():
             tr.start(frames[0], streams, pos=[[1, 2]] * len(streams), sz=[[3, 4]] * len(streams))
     with pytest.raises(ValueError):
         tr.start(frames[0][:100], [0], pos=[[1, 2]], sz=[[3, 4]])
-    assert tr._fr["pending"] == 0 and not tr._fr["events"] and tr.collect() is None
-    assert torch.equal(tr._fr["dev"], before) and torch.equal(tr._fr["z_all"], z_before)
+    assert tr._fr.chunk.pending == 0 and not tr._fr.chunk.events and tr.collect() is None
+    assert torch.equal(tr._fr.dev, before) and torch.equal(tr._fr.z_all, z_before)

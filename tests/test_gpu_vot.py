@@ -219,7 +219,7 @@ def test_run_vot_errors_are_raised_before_any_launch():
         m.set_pipeline(False)
     tr.reserve(B, 240, 320)
     torch.cuda.synchronize()
-    before = tr._fr["dev"].clone()
+    before = tr._fr.dev.clone()
     gt = np.tile(np.array(_rect(150, 120, 60, 40)), (4, B, 1))
     bad_gt = gt.copy()
     bad_gt[2, 1, 3] = np.nan
@@ -231,5 +231,5 @@ def test_run_vot_errors_are_raised_before_any_launch():
         kw.setdefault("want_polygon", True)
         with pytest.raises(ValueError):
             tr.run(kw.pop("frames", frames), **kw)
-    assert tr._fr["pending"] == 0 and not tr._fr["events"] and tr.collect() is None
-    assert torch.equal(tr._fr["dev"], before)
+    assert tr._fr.chunk.pending == 0 and not tr._fr.chunk.events and tr.collect() is None
+    assert torch.equal(tr._fr.dev, before)

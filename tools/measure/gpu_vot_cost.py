@@ -109,9 +109,9 @@ def main():
             stamp = [0.0]
             collect = tr.collect
 
-            def stamped():
+            def stamped(*a, **kw):
                 stamp[0] = time.perf_counter()
-                return collect()
+                return collect(*a, **kw)
             tr.collect = stamped
             waited[0] = 0.0
             torch.cuda.synchronize()
