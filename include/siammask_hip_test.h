@@ -40,6 +40,9 @@ extern "C" {
  *   "chain" 0|1 (fp16: Refine's nine sequential convolutions as one launch,
  *   refine_chain_kernel; default 1)   "ksplit" 0|1|2|4 (split-K across workgroups with a last-arrival reduction:
  *   off (default; measured a net loss at B=8) | auto for long-K few-tile launches | forced factor).
+ *   "chain_mask" 0|1|2 (fp16 frame step: the 63x63 mask head in a launch of its own | inside the Refine chain launch, chain_mask_kernel
+ *   (default) | the same with the mask head on the generic 128x128 implicit-GEMM tiles, there and in its own launch, instead of the
+ *   stationary-pixel tile of mask_head_tile.inc; bit-identical logits).
  *   "a_stage" 0|1 (conv_wreg_kernel / conv_seq_kernel producers: activation rows by LDS-DMA with the swizzle on the source
  *   address | global -> VGPR in ascending lane order, swizzle applied by ds_write_b128; same LDS image, bit-identical results).
  *   "seq_fuse" 0..3 (conv_seq_kernel: a Bottleneck's conv3 + the 1x1 convolution that reads it -- the next block's conv1, adjust -- as
@@ -100,7 +103,9 @@ typedef struct smk_conv_geom {
  *                2 = MFMA kernel, NCHW-f32 epilogue; 3 = naive kernel, NCHW-f32 epilogue;
  *                4 = conv3x3_halo_kernel (tile code 1 = 128 rows, else 64); 5 = conv_wreg_kernel (tile code 1..8 =
  *                64x256 64x128 64x64 128x256 128x128 128x64 96x256 32x64; ring-depth bits: 0 the library's choice, 1 eight k-steps ahead on every shape (measurement builds; else = 2), 2 / 3 = a three- / four-deep ring); 6 = conv_pp_kernel
- *                (256 x 256 tiles, fp16 only, conv_pp.hip);
+ *                (256 x 256 tiles, fp16 only, conv_pp.hip); 7 = mask_head_kernel (mask_head_tile.inc: the 63x63 mask head on stationary
+ *                pixels, NCHW-f32 output straight from the accumulators; fp16, k = 1, Cin = 256, Cout <= 4096, no ReLU / residual -- bit-equal
+ *                to algo 2 with 128x128 tiles);
  *       second byte: bits 0-3 tile override 0 auto, 1 128x128, 2 128x64, 3 64x128, 4 64x64, 5 256x128;
  *                    bits 4-5 K tile 0 auto, 1 = 128 B, 2 = 256 B; bits 6-7 LDS ring depth
  *                    0 auto, 1..3 = 2..4 stages.

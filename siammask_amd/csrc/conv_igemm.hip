@@ -1015,21 +1015,28 @@ int launch_conv_halo(const ConvParams &p, int dtype, int bm, void *stream) {
 // refine_chain_kernel occupies B of the 256 CUs for ~44 us (one workgroup per stream, custom.py:150-153 is a dependent
 // chain); the mask head (256 -> 3969 1x1 convolution, custom.py:185, 79 MB of fp32 logits at B = 8) is bound by its
 // stores and by nothing on the Refine path -- it only needs head.0's output.  As two launches they cost ~44 + ~40 us
-// back to back.  Here workgroups [0, B) run the chain (all 1024 threads) and the others run TWO 128x128 mask-head
-// tiles each (threads 0-511 / 512-1023, an LDS half each: the same two-workgroups-per-CU overlap the stand-alone
-// launch has; both halves execute the same number of barriers).  Cross-stream forks in the captured graph were the
+// back to back.  Here workgroups [0, B) run the chain (all 1024 threads) and the others run the mask head: one tile of
+// mask_head_tile.inc each (128 stationary pixels x a range of channel blocks, all sixteen waves) -- or, on the generic
+// path (smk_tune chain_mask = 2, shapes the tile does not cover), TWO 128x128 implicit-GEMM tiles each (threads 0-511 /
+// 512-1023, an LDS half each; both halves execute the same number of barriers).  Cross-stream forks in the captured graph were the
 // measured alternative: hipGraphLaunch then costs ~1 ms of host time per replay.
 // ---------------------------------------------------------------------------------------------
 }  // namespace smk
 namespace smk {
 #include "refine_chain_body.inc"
+#include "mask_head_tile.inc"
 constexpr int CM_CONV_LDS = IgemmLds<2, 2, 1, 128, 2>::v;
 constexpr int CM_LDS = CMax<RC_LDS, 2 * CM_CONV_LDS>::v;
+static_assert(MH_LDS <= CM_LDS, "the stationary-pixel mask-head tile fits the fused launch's LDS");
 
-__global__ __launch_bounds__(1024) void chain_mask_kernel(const RefineChainParams rp, const ConvBatch cb) {
+// mh_nsplit > 0: the mask half runs mask_head_tile (one tile per workgroup, mh_nsplit channel ranges per pixel tile) instead of
+// two generic 128x128 tile bodies
+__global__ __launch_bounds__(1024) void chain_mask_kernel(const RefineChainParams rp, const ConvBatch cb, const int mh_nsplit) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[CM_LDS];
     if ((int)blockIdx.x < rp.B) {
         refine_chain_body<false>(rp, (int)blockIdx.x, smem);
+    } else if (mh_nsplit > 0) {
+        mask_head_tile(cb.p[0], (int)blockIdx.x - rp.B, mh_nsplit, smem);
     } else {
         const int half = threadIdx.x >> 9;
         const int bx = 2 * ((int)blockIdx.x - rp.B) + half;
@@ -1051,11 +1058,79 @@ __global__ __launch_bounds__(1024) void chain_mask_kernel(const RefineChainParam
     }
 }
 
-// cb: ONE f16 problem with the NCHW f32 epilogue (the mask head), 128x128 tiles
-int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, void *stream) {
+// ---- the stationary-pixel mask head (mask_head_tile.inc) as a launch of its own (depth-2 pipelining, B > 16) ----
+__global__ __launch_bounds__(1024) void mask_head_kernel(const ConvParams p, const int nsplit) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[MH_LDS];
+    set_wave_prio(p.wave_prio);
+    mask_head_tile(p, (int)blockIdx.x, nsplit, smem);
+}
+
+// what mask_head_tile computes: a 1x1 stride-1 convolution of ALL pixels of a 256-channel slice (fp16, fragment-order pack) into
+// NCHW f32, + bias, nothing else in the epilogue; every byte offset the tile forms stays below its out-of-range offset
+bool mask_head_eligible(const ConvParams &p, int dtype) {
+    return dtype == DT_F16 && p.out_mode == OUT_NCHW_F32 && p.wgt_frag != nullptr && p.kh == 1 && p.kw == 1 && p.stride == 1 &&
+           p.stride_x == 1 && p.pad == 0 && !p.ups && !p.pos && p.org_y == 0 && p.org_x == 0 && p.Hl == p.Hs && p.Wl == p.Ws &&
+           p.Ho == p.Hs && p.Wo == p.Ws && p.groups <= 1 && p.Ci == MH_K && p.K == MH_K && p.Kpad == MH_K && !p.relu &&
+           !p.oscale && !p.x3_in && p.res_mode == RES_NONE && p.N >= 1 && p.N <= MH_NMAX && (p.Cs % 8) == 0 && (p.cin_off % 8) == 0 &&
+           p.cin_off + MH_K <= p.Cs && p.M == p.B * p.Ho * p.Wo && p.in_bytes > 0 && p.in_bytes < 0x7fff0000u &&
+           p.in_bytes >= (unsigned long long)p.M * p.Cs * 2 && p.w_bytes < 0x7fff0000u &&
+           p.w_bytes >= (unsigned long long)((p.N + 31) / 32) * 32 * MH_K * 2 && (unsigned long long)p.M * p.N * 4 < 0x7fff0000ull;
+}
+
+// Channel ranges per pixel tile.  One round of the chip (`cus` workgroups at most) while the pixel tiles allow it, every range at
+// least eight blocks long (a wave pair per block): B = 8 -> 40 pixel tiles x 6 ranges of 20 / 21 blocks = 240 workgroups (+ the
+// chain's 8 = 248).  More pixel tiles than that: the split of 2..8 ranges that wastes least of the launch's last round.
+int mask_head_nsplit(const ConvParams &p, int cus) {
+    const int ptiles = (p.M + MH_PX - 1) / MH_PX, nblk = (p.N + 31) / 32;
+    int cap = nblk / 8;
+    if (cap < 1) cap = 1;
+    if (ptiles * 2 <= cus) {
+        const int ns = cus / ptiles;
+        return ns < cap ? ns : cap;
+    }
+    int best = 1;
+    double best_eff = 0.0;
+    for (int ns = 2; ns <= 8 && ns <= cap; ++ns) {
+        const long wgs = (long)ptiles * ns, rounds = (wgs + cus - 1) / cus;
+        const double eff = (double)wgs / (double)(rounds * cus);
+        if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
+    }
+    return best;
+}
+
+// Streaming (nt) or plain stores.  One dword per lane, the tile's stores are faster plain -- alone on the chip 22.7 us plain
+// against 43.1 us nt at B = 8, 233 against 311 us at B = 64 (the generic tiles: 36 / 278 us either way) -- but in a frame step of
+// up to 16 streams the logits leave beside the next frame's front end, and 79 MB of plain stores through the L2s cost that more
+// than the head gains: B = 8 pipelined step 0.530-0.532 ms nt, 0.534-0.536 plain (generic tiles 0.545-0.553); B = 64, where the
+// launch has the chip to itself, 3.07 ms nt, 2.975 plain (generic 3.000).  profiles/mask_head_wat_ab.txt
+static int mask_head_nt(const ConvParams &p) { return (p.nt_store && p.M <= 16 * 625) ? 1 : 0; }
+
+int launch_mask_head(const ConvParams &p0, void *stream) {
+    if (!mask_head_eligible(p0, DT_F16)) return 1;
+    ConvParams p = p0;
+    p.nt_store = mask_head_nt(p);
+    const int nsplit = mask_head_nsplit(p, 256);
+    const int ptiles = (p.M + MH_PX - 1) / MH_PX;
+    hipLaunchKernelGGL(mask_head_kernel, dim3(ptiles * nsplit), dim3(1024), 0, (hipStream_t)stream, p, nsplit);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// cb: ONE f16 problem with the NCHW f32 epilogue (the mask head): mask_head_tile where the caller asks for it (stationary != 0) and
+// the tile covers the problem, else 128x128 tiles
+int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, int stationary, void *stream) {
     if (rp.v2_cs != 32 || rp.v1_cs != 16 || rp.v0_cs != 8 || cb.n != 1) return -1;
     ConvParams &p = cb.p[0];
     if (p.out_mode != OUT_NCHW_F32 || p.groups > 1) return -1;
+    if (stationary && mask_head_eligible(p, DT_F16)) {
+        const int nsplit = mask_head_nsplit(p, 256 - rp.B > 64 ? 256 - rp.B : 64);
+        const int ptiles = (p.M + MH_PX - 1) / MH_PX;
+        cb.start[0] = 0;
+        for (int i = 1; i <= CONV_BATCH_MAX; ++i) cb.start[i] = ptiles * nsplit;
+        p.ksplit = 1;
+        p.nt_store = mask_head_nt(p);
+        hipLaunchKernelGGL(chain_mask_kernel, dim3(rp.B + ptiles * nsplit), dim3(1024), 0, (hipStream_t)stream, rp, cb, nsplit);
+        return hipGetLastError() == hipSuccess ? 0 : -4;
+    }
     const int tiles = ((p.M + 127) / 128) * ((p.Nst + 127) / 128);
     // The two 128x128 tile bodies of a workgroup (threads 0-511 / 512-1023) share workgroup-wide barriers: both halves must
     // run the same number of them, i.e. both must HAVE a tile (same K, ksplit 1).  An odd tile count would leave the last
@@ -1065,7 +1140,7 @@ int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, void *stream) 
     cb.start[0] = 0;
     for (int i = 1; i <= CONV_BATCH_MAX; ++i) cb.start[i] = tiles;
     p.ksplit = 1;
-    hipLaunchKernelGGL(chain_mask_kernel, dim3(rp.B + (tiles + 1) / 2), dim3(1024), 0, (hipStream_t)stream, rp, cb);
+    hipLaunchKernelGGL(chain_mask_kernel, dim3(rp.B + (tiles + 1) / 2), dim3(1024), 0, (hipStream_t)stream, rp, cb, 0);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

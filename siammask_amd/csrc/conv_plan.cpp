@@ -454,6 +454,9 @@ ConvPlan plan_conv(const ConvParams &p, const ConvOpt &o, const PackedConv &pc, 
     ConvPlan pl;
     pl.tile = tile_from_code(o.tile_code, p, kd);
     if (o.algo_naive) { pl.kind = CK_NAIVE; return pl; }
+    // the 63x63 mask head as its own launch (depth-2 pipelining, B > 16) in fp16 contexts: the stationary-pixel tile (smk_tune "chain_mask" = 2,
+    // fp32 and split-operand contexts: the generic tiles)
+    if (dtype == DT_F16 && g_tune.chain_mask != 2 && !o.tile_code && !o.halo && !o.wreg && mask_head_eligible(p, kd)) { pl.kind = CK_MHEAD; return pl; }
     // halo_choice's own answer is also an input of the rules below, whether or not the halo kernel then takes the geometry
     int bm = halo_choice(pc, p, o, kd);
     if (bm && !o.halo && conv_ksplit(p, kd, pl.tile) > 1) bm = 0;       // under-filled: split-K on the generic kernel wins
@@ -491,6 +494,7 @@ std::string plan_kernel_name(const ConvPlan &pl, int dtype, int out_mode, int me
     switch (pl.kind) {
     case CK_NAIVE: return "conv_naive";
     case CK_PP: return "conv_pp<f16,256x256>";
+    case CK_MHEAD: return "mask_head<f16,128px,nchw>";
     case CK_HALO: snprintf(kn, sizeof(kn), "conv3x3_halo<%s,%dx128>", dt, pl.halo_bm); break;
     case CK_WREG: snprintf(kn, sizeof(kn), "conv_wreg<%s,%dx%d,s%d%s>", dt, WREG_TILE[pl.wreg][0], WREG_TILE[pl.wreg][1], pl.stages, mg); break;
     default:

@@ -63,7 +63,7 @@ inline const char *dtname(int dt) { return dt == smk::DT_F16 ? "f16" : "f32"; }
 
 #pragma GCC visibility push(hidden)   // (nothing here is part of the library's ABI)
 
-enum ConvKernel { CK_NAIVE, CK_IGEMM, CK_HALO, CK_WREG, CK_PP };
+enum ConvKernel { CK_NAIVE, CK_IGEMM, CK_HALO, CK_WREG, CK_PP, CK_MHEAD };   // CK_MHEAD: mask_head_kernel (mask_head_tile.inc)
 struct ConvPlan {
     int kind = CK_IGEMM;
     smk::TileChoice tile{};   // CK_IGEMM

@@ -1083,6 +1083,7 @@ static int launch_plan(const ConvPlan &pl, ConvBatch &cb, const void *w_halo, in
         break;
     }
     case CK_NAIVE: rc = launch_conv_naive(cb.p[0], dtype, s); break;
+    case CK_MHEAD: rc = launch_mask_head(cb.p[0], s); break;
     default: rc = launch_conv_mfma_batch(cb, dtype, pl.tile, s);
     }
     if (rc == 1) return fail(SMK_E_STATE, "internal: %s is not eligible for the kernel planned for it", what);
@@ -1597,7 +1598,8 @@ static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s
             cb.p[0] = rec.deferred_mask.p;
             ProfScope ps(c, s, "refine_chain+mask3", "chain_mask", flop + rec.deferred_mask.flop, cbytes + rec.deferred_mask.bytes);
             if (rec.tail_fold) rp.tail_sem = c->pipe_cnt;      // pipelined step: this launch ends the tail, its last workgroup is the "done" mark
-            const int rc = launch_chain_mask(rp, cb, s);
+            // fp16 contexts: the mask half on the stationary-pixel tile (mask_head_tile.inc); split-operand contexts and smk_tune chain_mask = 2 keep the generic tiles
+            const int rc = launch_chain_mask(rp, cb, c->dtype == DT_F16 && g_tune.chain_mask != 2, s);
             rp.tail_sem = nullptr;
             if (rc == 0) {
                 rec.deferred_mask.have = false;
@@ -2131,7 +2133,7 @@ static const Knob KNOBS[] = {
     {"rf_tile2", &g_tune.rf_tile2, "0..5", KNOB_RAW, nullptr},
     {"nchw_tn_major", &g_tune.nchw_tn_major, "*", KNOB_BOOL, nullptr},
     {"chain", &g_tune.chain, "*", KNOB_BOOL, nullptr},
-    {"chain_mask", &g_tune.chain_mask, "*", KNOB_BOOL, nullptr},
+    {"chain_mask", &g_tune.chain_mask, "0..2", KNOB_RAW, nullptr},
     {"corr_head", &g_tune.corr_head, "*", KNOB_BOOL, nullptr},
     {"pair_launch", &g_tune.pair_launch, "0..3", KNOB_RAW, nullptr},
     {"halo", &g_tune.halo, "0|1|64|128", KNOB_RAW, nullptr},
@@ -2749,6 +2751,7 @@ static int plan_from_algo(int algo, const ConvParams &p, int dtype, ConvPlan &pl
         if (pl.wreg < 1 || pl.wreg > 8) return -1;
         return conv_wreg_eligible(p, dtype) ? 0 : 1;
     case 6: pl.kind = CK_PP; return conv_pp_eligible(p, dtype) ? 0 : 1;
+    case 7: pl.kind = CK_MHEAD; return mask_head_eligible(p, dtype) ? 0 : 1;
     default: pl.kind = CK_IGEMM; pl.tile = tile_from_code(code, p, dtype); return 0;
     }
 }
@@ -2802,7 +2805,7 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
         o.pos = pos_dev;
     }
     const int mode = algo & 0xff;
-    const bool nchw = (mode == 2 || mode == 3);
+    const bool nchw = (mode == 2 || mode == 3 || mode == 7);
     if (mode == 4) {                                   // halo kernel (3x3 stride 1): its chunk-major pack (f16: + the fragment-order copy)
         CHK(upload_halo_pack(pc, rows, dtype));
         if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);
@@ -2835,7 +2838,9 @@ int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x
     if (prc < 0) return fail(SMK_E_ARG, "smk_op_conv2d_ex: wreg tile code 1..8");
     if (prc)
         return fail(SMK_E_ARG, "smk_op_conv2d_ex: %s", pl.kind == CK_HALO ? "geometry is not eligible for the halo kernel"
-                    : (pl.kind == CK_WREG ? "geometry / dtype is not eligible for conv_wreg_kernel" : "geometry / dtype is not eligible for conv_pp_kernel"));
+                    : (pl.kind == CK_WREG ? "geometry / dtype is not eligible for conv_wreg_kernel"
+                       : (pl.kind == CK_MHEAD ? "geometry / dtype is not eligible for mask_head_kernel (fp16, 1x1, Cin = 256, Cout <= 4096, no ReLU)"
+                          : "geometry / dtype is not eligible for conv_pp_kernel")));
     ConvBatch cb;
     cb.n = 1;
     cb.p[0] = p;
@@ -3659,11 +3664,12 @@ int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, in
         o.pos = pos_dev;
     }
     const int mode = algo & 0xff;
-    if (mode == 5) pc.w_frag = pc.w;                    // timing only: the fragment order is irrelevant
+    if (mode == 5 || mode == 7) pc.w_frag = pc.w;       // timing only: the fragment order is irrelevant
     Act out, res;
     out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8);
     float *nchw = nullptr;
-    if (mode == 2) {
+    const bool nchw_mode = mode == 2 || mode == 7;
+    if (nchw_mode) {
         CHK(tmp.alloc((void **)&nchw, (size_t)g->B * g->Cout * Ho * Wo * 4));
         o.nchw_out = nchw;
     } else {
@@ -3679,12 +3685,12 @@ int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, in
     HIPCHK(hipGetDevice(&env.device));
     CHK(op_ks_scratch(env));
     ConvParams p;
-    CHK(conv_params(env, pc, in, mode == 2 ? nullptr : &out, g->B, o, p));
+    CHK(conv_params(env, pc, in, nchw_mode ? nullptr : &out, g->B, o, p));
     ConvPlan pl;
     const int prc = plan_from_algo(mode == 1 || mode == 3 ? algo & ~0xff : algo, p, dtype, pl);     // (no naive kernel here: 1 / 3 time the MFMA one)
     if (prc < 0) return fail(SMK_E_ARG, "smk_bench_conv: wreg tile code 1..8");
     if (prc && pl.kind == CK_HALO) return fail(SMK_E_HIP, "conv launch failed or geometry not eligible");
-    if (prc) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for %s", pl.kind == CK_WREG ? "conv_wreg_kernel" : "conv_pp_kernel");
+    if (prc) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for %s", pl.kind == CK_WREG ? "conv_wreg_kernel" : (pl.kind == CK_MHEAD ? "mask_head_kernel" : "conv_pp_kernel"));
     auto launch = [&]() {
         ConvBatch cb;                                    // (a launcher writes its grid layout into the batch)
         cb.n = 1;

@@ -199,7 +199,9 @@ struct Tuning {
                                // the batched loads (21.5 us); rocprofv3, profiles/r03_dw_xcorr_variants.txt
     int buf_lds = 1;           // LDS-DMA through buffer resources instead of flat global addresses (measured
                                // faster: l3.0.ds 94 -> 76 us at B=8, profiles/r01_v5_ab_buf_lds.txt)
-    int chain_mask = 1;        // fused frame step, fp16: the mask head runs inside the Refine chain launch (chain_mask_kernel)
+    int chain_mask = 1;        // fused frame step, fp16: the mask head runs inside the Refine chain launch (chain_mask_kernel); 2 = the same with the mask
+                               // head on the generic 128x128 implicit-GEMM tiles, there and in its stand-alone launch, instead of the stationary-pixel
+                               // tile of mask_head_tile.inc (A/B and parity arm: the logits are bit-identical)
     int nchw_tn_major = 1;     // large NCHW f32 outputs (the 63x63 mask logits): tn-major tile order (see conv_params)
     int merge = 1;             // share one launch between independent convolutions (ds+c1, cls3+loc3, Refine windows): 0 never, 1 up to
                                // merge_max_batch streams (beyond it every member fills the chip by itself), 2 always
@@ -464,8 +466,15 @@ struct RefineChainParams {
     unsigned *tail_sem;
 };
 int launch_refine_chain(const RefineChainParams &p, void *stream);
-// the chain and ONE NCHW f32 convolution (the mask head, 128x128 tiles) as one horizontally fused launch
-int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, void *stream);
+// the chain and ONE NCHW f32 convolution (the mask head) as one horizontally fused launch; stationary != 0: the mask half on
+// mask_head_tile where it covers the problem, else on 128x128 implicit-GEMM tiles
+int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, int stationary, void *stream);
+// the mask head on stationary pixels (mask_head_tile.inc: C^T = W x A^T, stores straight from the accumulators): 1x1, 256 -> N <= 4096,
+// fp16 with a fragment-order pack, NCHW f32 + bias; launch_mask_head returns 1 when the problem is not eligible.  mask_head_nsplit:
+// channel ranges per 128-pixel tile for a chip share of `cus` workgroups (host code; the CPU tests pin it)
+bool mask_head_eligible(const ConvParams &p, int dtype);
+int mask_head_nsplit(const ConvParams &p, int cus);
+int launch_mask_head(const ConvParams &p, void *stream);
 int launch_xcorr(const XcorrParams &p, int dtype, void *stream);
 // DT_F16X3 (x3_kernels.hip): x [B][H][W][2 Cx], k [B][kh][kw][2 Cx] in whole-tensor planes [hi | lo] (stride Cx = p.Cs), C = channels computed; out
 // [B][Ho][Wo][2 Cx] PER-BRANCH planes: channel c = 256 g + cc lives at 512 g + 256 plane + cc (head.0 is a grouped convolution)

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 
-ALGO = {"mfma": 0, "naive": 1, "mfma_nchw": 2, "naive_nchw": 3, "halo": 4, "wreg": 5, "pp": 6}
+ALGO = {"mfma": 0, "naive": 1, "mfma_nchw": 2, "naive_nchw": 3, "halo": 4, "wreg": 5, "pp": 6, "mask_head": 7}
 WREG_TILE = {(64, 256): 1, (64, 128): 2, (64, 64): 3, (128, 256): 4, (128, 128): 5, (128, 64): 6, (96, 256): 7, (32, 64): 8}
 TILE = {None: 0, "auto": 0, (128, 128): 1, (128, 64): 2, (64, 128): 3, (64, 64): 4, (256, 128): 5}
 
@@ -36,8 +36,9 @@ def wreg_code(tile, stages=0):
 
 def conv2d(x, w, b=None, stride=1, pad=0, dil=1, relu=False, res=None, res_mode=1, dtype="f32",
            algo="mfma", tile=None, win=None, ups=None, pos=None, pos_mul=0, pos_add=0, org=(0, 0),
-           cin_off=0, cin_len=0, kt=0, stages=0):
-    _chk_cuda(x, res)
+           cin_off=0, cin_len=0, kt=0, stages=0, out=None):
+    """out: optional contiguous float32 CUDA tensor [B, Cout, Ho, Wo] the result is written into (e.g. a view between guard rows)"""
+    _chk_cuda(x, res, out)
     x = x.contiguous().float()
     B, Cin, H, W = x.shape
     w = np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
@@ -60,7 +61,9 @@ def conv2d(x, w, b=None, stride=1, pad=0, dil=1, relu=False, res=None, res_mode=
         Hl, Wl = ups
     Ho = (Hl + 2 * pad - dil * (g.k - 1) - 1) // stride + 1
     Wo = (Wl + 2 * pad - dil * (g.k - 1) - 1) // stride + 1
-    y = torch.empty((B, g.Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    y = out if out is not None else torch.empty((B, g.Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    if tuple(y.shape) != (B, g.Cout, Ho, Wo) or y.dtype != torch.float32 or not y.is_contiguous():
+        raise ValueError("out must be a contiguous float32 tensor of shape %s" % ((B, g.Cout, Ho, Wo),))
     p = None if pos is None else np.ascontiguousarray(pos, dtype=np.int32)
     r = None if res is None else res.contiguous().float()
     code = ALGO[algo] | ((wreg_code(tile, stages) if algo == "wreg" else tile_code(tile, kt, stages)) << 8)
