@@ -417,6 +417,55 @@ int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes,
 int smk_vot_overlap(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev, int B, int im_w,
                     int im_h, float *overlap_dev, int32_t *counts_dev, void *stream);
 
+/* ---- streams with their own frame sizes in one batch (additive; smk_version() keeps reporting 1.10, the presence of these
+ * symbols is the probe) -------------------------------------------------------------------------------------------------
+ * The B streams of a state block may follow B different videos: smk_trk_stream holds im_w, im_h per stream, the plan, the advance
+ * and the network never see a frame size.  These entries are the image-side ones with the size taken per stream.  A frame of
+ * stream b is an smk_image_ref: data (device, uint8 BGR, no alignment required), row_bytes >= 3 * w between rows (a view into a
+ * wider buffer is fine), w and h in 1..32768.  The refs are HOST arrays that travel as kernel arguments, as the values of
+ * smk_trk_set and smk_trk_start do: no device table, no copy, no synchronisation, nothing of the caller's host memory is read
+ * after the call returns.  B (n) in 1..32.  No context; every entry is asynchronous on `stream` and refuses bad arguments
+ * (SMK_E_ARG: null pointers, B outside 1..32, w / h out of range, row_bytes < 3 * w, start_mask bits at or above B, a canvas
+ * smaller than a size the host gave) before anything is enqueued.
+ * smk_crop_resize_dev_v: smk_crop_resize_dev with images_host[b] as the frame of stream b -- window and mean colour from the record,
+ *   the in-image test and the addressing from the ref.  Row b of out_dev holds, bit for bit, what smk_crop_resize_dev writes for
+ *   that frame at its own size.
+ * smk_crop_exemplar_dev_v: smk_crop_exemplar_dev likewise; only the refs of the streams of start_mask are read (and checked), the
+ *   rows of all other streams stay as they were.
+ * smk_frame_sums_v: uint64 channel sums [n][3] of n frames of different sizes and pitches in one launch (zeroed on `stream` by the
+ *   call; exact at every size).
+ * smk_trk_start_v: smk_trk_start with im_wh_host (int32 [B][2] = w, h; rows of the streams of start_mask are read and checked) in
+ *   place of one im_w, im_h: a started stream's record gets its own size, everything else as smk_trk_start.
+ * smk_paste_mask_dev_v: smk_paste_mask_dev onto a canvas uint8 [B][canvas_h][canvas_w].  The mask of stream b fills
+ *   [0:im_h_b][0:im_w_b] of its plane with im_w_b, im_h_b read from its record -- the bytes smk_paste_mask_dev writes for that
+ *   stream at its own size -- and every other byte of the plane is written 0 by the same launch: the canvas is fully defined by
+ *   the call.  Both input forms of smk_paste_mask_dev.  A record larger than the canvas is an invalid state: the kernel clamps
+ *   (nothing is written outside the canvas); im_wh_host (int32 [B][2], may be NULL), the sizes as the host knows them, lets the
+ *   entry refuse it.  canvas_w >= 1, canvas_h in 1..65535.
+ * smk_vot_overlap_dev: smk_vot_overlap with the bounds of pair b taken from record b of state_dev (B <= 65535 records): the float32
+ *   and the four counts of smk_vot_overlap at that pair's im_w, im_h (a record outside 1..4096, an invalid state, is clamped into
+ *   that range).
+ * smk_mask_rbox runs on the canvas unchanged: a zero border right of and below a mask adds no run and moves no coordinate. */
+typedef struct smk_image_ref {
+    const uint8_t *data;           /* device: pixel (0, 0), BGR                */
+    int64_t row_bytes;             /* >= 3 * w                                 */
+    int32_t w, h;
+} smk_image_ref;
+
+int smk_crop_resize_dev_v(const smk_image_ref *images_host, const void *state_dev, int B, int model_sz, float *out_dev,
+                          void *stream);
+int smk_crop_exemplar_dev_v(const smk_image_ref *images_host, const void *state_dev, const int32_t *win_dev,
+                            const double *result_dev, uint32_t start_mask, int B, int model_sz, float *z_all_dev, void *stream);
+int smk_frame_sums_v(const smk_image_ref *images_host, int n, uint64_t *sums_out_dev, void *stream);
+int smk_trk_start_v(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                    const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride,
+                    const int32_t *im_wh_host, int32_t *win_out_dev, double *result_out_dev, void *stream);
+int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, float seg_thr, float border,
+                         uint8_t *canvas_out_dev, void *stream);
+int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
+                        const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

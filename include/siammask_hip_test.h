@@ -208,6 +208,10 @@ int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const doubl
 int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
                        const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,
                        double *result_out);
+/* smk_trk_start_v on HOST memory: im_wh int32 [B][2] = (w, h) per stream in place of one im_w, im_h */
+int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
+                         const double *sz, const uint64_t *sums, int64_t sums_stride, const int32_t *im_wh, int32_t *win_out,
+                         double *result_out);
 /* Host only: smk_vot_overlap's arithmetic on HOST memory -- the very inline functions the kernel compiles
  * (csrc/vot_overlap.h), rows looped by one thread.  pred, gt: f64 [n][8] corners; overlap f32 [n]; counts int32 [n][4] (may be
  * NULL) as for smk_vot_overlap. */

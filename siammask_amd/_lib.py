@@ -34,6 +34,8 @@ SYMBOLS = (
     "smk_vos_score", "smk_vos_score_dev", "smk_host_trk_plan", "smk_host_trk_advance",
     "smk_vos_score_ex", "smk_vos_score_dev_ex", "smk_label_rects", "smk_frame_sums", "smk_trk_start", "smk_crop_exemplar_dev",
     "smk_host_trk_start", "smk_vot_overlap", "smk_host_vot_overlap",
+    "smk_crop_resize_dev_v", "smk_crop_exemplar_dev_v", "smk_frame_sums_v", "smk_trk_start_v", "smk_host_trk_start_v",
+    "smk_paste_mask_dev_v", "smk_vot_overlap_dev",
 )
 
 
@@ -54,6 +56,11 @@ class TrkCfg(ctypes.Structure):
     """smk_trk_cfg: the tracker's configuration for the scalar kernels (utils/tracker_config.py + hp)"""
     _fields_ = [("context_amount", ctypes.c_double), ("lr", ctypes.c_double)] + [(n, ctypes.c_int) for n in (
         "exemplar_size", "instance_size", "total_stride", "base_size", "score_size", "mask_size")]
+
+
+class ImageRef(ctypes.Structure):
+    """smk_image_ref: the frame of one stream (device pointer, bytes between rows, width, height)"""
+    _fields_ = [("data", ctypes.c_void_p), ("row_bytes", ctypes.c_int64), ("w", ctypes.c_int32), ("h", ctypes.c_int32)]
 
 
 class SmkError(RuntimeError):
@@ -156,6 +163,13 @@ def lib():
     L.smk_crop_exemplar_dev.argtypes = [vp, i64, ci, ci, vp, vp, vp, u32, ci, ci, fp, vp]
     L.smk_vot_overlap.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, vp, vp]
     L.smk_host_vot_overlap.argtypes = [vp, vp, ci, ci, ci, vp, vp]
+    L.smk_crop_resize_dev_v.argtypes = [vp, vp, ci, ci, fp, vp]
+    L.smk_crop_exemplar_dev_v.argtypes = [vp, vp, vp, vp, u32, ci, ci, fp, vp]
+    L.smk_frame_sums_v.argtypes = [vp, ci, vp, vp]
+    L.smk_trk_start_v.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    L.smk_host_trk_start_v.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.smk_paste_mask_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, vp, cf, cf, vp, vp]
+    L.smk_vot_overlap_dev.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

@@ -3556,27 +3556,31 @@ int smk_trk_start(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start
     return 0;
 }
 
+// trk_start on host memory for the streams of the mask; im_wh != nullptr: stream b on a frame of im_wh[2 b], im_wh[2 b + 1]
+static void trk_start_host(const TrkStartArgs &a, smk_trk_stream *st, const smk_trk_cfg &cfg, const int32_t *im_wh) {
+    double *twh = (double *)(st + a.B);
+    for (int b = 0; b < a.B; ++b) {
+        if (!((a.mask >> b) & 1)) continue;
+        double px, py, w, h;
+        if (a.rects) {
+            const int32_t *r = a.rects + 4 * b;
+            w = (double)r[2]; h = (double)r[3];
+            px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
+        } else {
+            px = a.pos[b][0]; py = a.pos[b][1]; w = a.sz[b][0]; h = a.sz[b][1];
+        }
+        trk_start(st[b], cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, im_wh ? im_wh[2 * b] : a.im_w,
+                  im_wh ? im_wh[2 * b + 1] : a.im_h, a.win + 3 * b, a.res + TRK_START_ROW * b, twh + 2 * b);
+    }
+}
+
 int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
                        const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,
                        double *result_out) {
     TrkStartArgs a;
     CHK(trk_start_fill("smk_host_trk_start", a, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_w, im_h, win_out,
                        result_out));
-    smk_trk_stream *st = (smk_trk_stream *)state;
-    double *twh = (double *)(st + B);
-    for (int b = 0; b < B; ++b) {
-        if (!((start_mask >> b) & 1)) continue;
-        double px, py, w, h;
-        if (rects) {
-            const int32_t *r = rects + 4 * b;
-            w = (double)r[2]; h = (double)r[3];
-            px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
-        } else {
-            px = a.pos[b][0]; py = a.pos[b][1]; w = a.sz[b][0]; h = a.sz[b][1];
-        }
-        trk_start(st[b], *cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, im_w, im_h, win_out + 3 * b,
-                  result_out + TRK_START_ROW * b, twh + 2 * b);
-    }
+    trk_start_host(a, (smk_trk_stream *)state, *cfg, nullptr);
     return 0;
 }
 
@@ -3621,6 +3625,138 @@ int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, 
         return fail(SMK_E_ARG, "smk_host_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
     for (int i = 0; i < n; ++i)                                        // the annotation is the reference's first polygon (:354)
         overlap[i] = vot_overlap_serial(gt + 8 * (size_t)i, pred + 8 * (size_t)i, im_w, im_h, counts ? counts + 4 * (size_t)i : nullptr);
+    return 0;
+}
+
+// ---- streams with their own frame sizes (image_kernels.hip, tracker_init.hip, vot_overlap.hip) ---------------------------------
+// the refs of the streams of `mask`, checked and copied into the kernarg; -> the largest h among them through max_h (may be null)
+static int image_refs_fill(const char *who, smk_image_ref *dst, const smk_image_ref *src, int B, uint32_t mask, int *max_h) {
+    if (!src) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
+    if (B < 32 && (mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, mask, B);
+    memset(dst, 0, sizeof(smk_image_ref) * TRK_SET_MAX_B);
+    int mh = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!((mask >> b) & 1)) continue;
+        const smk_image_ref &r = src[b];
+        if (!r.data) return fail(SMK_E_ARG, "%s: image %d has no data", who, b);
+        if (r.w < 1 || r.h < 1 || r.w > 32768 || r.h > 32768) return fail(SMK_E_ARG, "%s: image %d is %d x %d (1..32768)", who, b, r.w, r.h);
+        if (r.row_bytes < 3 * (int64_t)r.w) return fail(SMK_E_ARG, "%s: image %d: row_bytes %lld < 3 * %d", who, b, (long long)r.row_bytes, r.w);
+        dst[b] = r;
+        mh = r.h > mh ? r.h : mh;
+    }
+    if (max_h) *max_h = mh;
+    return 0;
+}
+static uint32_t all_streams(int B) { return B >= 32 ? 0xffffffffu : (B < 1 ? 0u : (1u << B) - 1u); }
+
+int smk_crop_resize_dev_v(const smk_image_ref *images_host, const void *state_dev, int B, int model_sz, float *out_dev, void *stream) {
+    if (!images_host || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: null argument");
+    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: model_sz %d", model_sz);
+    CropVParams p;
+    CHK(image_refs_fill("smk_crop_resize_dev_v", p.im, images_host, B, all_streams(B), nullptr));
+    p.out = out_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
+    p.win = nullptr; p.res = nullptr; p.mask = 0;
+    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev_v launch failed");
+    return 0;
+}
+
+int smk_crop_exemplar_dev_v(const smk_image_ref *images_host, const void *state_dev, const int32_t *win_dev,
+                            const double *result_dev, uint32_t start_mask, int B, int model_sz, float *z_all_dev, void *stream) {
+    if (!images_host || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: null argument");
+    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: model_sz %d", model_sz);
+    CropVParams p;
+    CHK(image_refs_fill("smk_crop_exemplar_dev_v", p.im, images_host, B, start_mask, nullptr));
+    p.out = z_all_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
+    p.win = win_dev; p.res = result_dev; p.mask = start_mask;
+    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev_v launch failed");
+    return 0;
+}
+
+int smk_frame_sums_v(const smk_image_ref *images_host, int n, uint64_t *sums_out_dev, void *stream) {
+    if (!images_host || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums_v: null argument");
+    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums_v: sums_out_dev must be 8-byte aligned");
+    FrameSumsVParams p;
+    CHK(image_refs_fill("smk_frame_sums_v", p.im, images_host, n, all_streams(n), &p.max_h));
+    p.sums = (unsigned long long *)sums_out_dev; p.n = n;
+    if (launch_frame_sums_v(p, stream)) return fail(SMK_E_HIP, "frame_sums_v launch failed");
+    return 0;
+}
+
+// the checks and the kernarg smk_trk_start_v and smk_host_trk_start_v share: trk_start_fill's, with a size per stream of the mask
+static int trk_start_fill_v(const char *who, TrkStartVArgs &v, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
+                            const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
+                            int64_t sums_stride, const int32_t *im_wh, int32_t *win_out, double *result_out) {
+    if (!im_wh) return fail(SMK_E_ARG, "%s: null argument", who);
+    CHK(trk_start_fill(who, v.a, state, B, cfg, start_mask, rects, pos_host, sz_host, sums, sums_stride, 1, 1, win_out, result_out));
+    memset(v.im_wh, 0, sizeof(v.im_wh));
+    for (int b = 0; b < B; ++b) {
+        if (!((start_mask >> b) & 1)) continue;
+        const int w = im_wh[2 * b], h = im_wh[2 * b + 1];
+        if (w < 1 || h < 1 || w > 32768 || h > 32768) return fail(SMK_E_ARG, "%s: bad geometry of stream %d (%d x %d, 1..32768)", who, b, w, h);
+        v.im_wh[b][0] = w; v.im_wh[b][1] = h;
+    }
+    v.a.im_w = 0; v.a.im_h = 0;
+    return 0;
+}
+
+int smk_trk_start_v(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                    const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride,
+                    const int32_t *im_wh_host, int32_t *win_out_dev, double *result_out_dev, void *stream) {
+    TrkStartVArgs v;
+    CHK(trk_start_fill_v("smk_trk_start_v", v, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride,
+                         im_wh_host, win_out_dev, result_out_dev));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_start_v(st, (double *)(st + B), v, stream)) return fail(SMK_E_HIP, "trk_start_v launch failed");
+    return 0;
+}
+
+int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
+                         const double *sz, const uint64_t *sums, int64_t sums_stride, const int32_t *im_wh, int32_t *win_out,
+                         double *result_out) {
+    TrkStartVArgs v;
+    CHK(trk_start_fill_v("smk_host_trk_start_v", v, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_wh, win_out,
+                         result_out));
+    trk_start_host(v.a, (smk_trk_stream *)state, *cfg, &v.im_wh[0][0]);
+    return 0;
+}
+
+int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, float seg_thr, float border,
+                         uint8_t *canvas_out_dev, void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev || !canvas_out_dev) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: null argument");
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: %d streams (1..%d)", B, TRK_SET_MAX_B);
+    if (canvas_w < 1 || canvas_h < 1 || canvas_h > 65535 || mask_size < 1 || (head_dev && (score_size < 1 || score_size > 1024)))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev_v: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: slot %d (0 or 1)", slot);
+    if (im_wh_host)
+        for (int b = 0; b < B; ++b)
+            if (im_wh_host[2 * b] > canvas_w || im_wh_host[2 * b + 1] > canvas_h)
+                return fail(SMK_E_ARG, "smk_paste_mask_dev_v: stream %d is %d x %d, the canvas %d x %d", b, im_wh_host[2 * b],
+                            im_wh_host[2 * b + 1], canvas_w, canvas_h);
+    PasteDevParams p;
+    p.logits = head_dev ? head_dev : logits_dev;
+    p.mask_out = canvas_out_dev; p.prob_out = nullptr;
+    p.ms = mask_size; p.W = canvas_w; p.H = canvas_h; p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.seg_thr = seg_thr; p.border = border;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_paste_mask_dev_v(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev_v launch failed");
+    return 0;
+}
+
+int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
+                        const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
+    if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");
+    if (pred_dev && pred_stride != 8 && pred_stride != 12)
+        return fail(SMK_E_ARG, "smk_vot_overlap_dev: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
+    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap_dev: %d pairs (1..65535)", B);
+    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)state_dev % 8 ||
+        (uintptr_t)overlap_dev % 4 || (uintptr_t)counts_dev % 4)
+        return fail(SMK_E_ARG, "smk_vot_overlap_dev: misaligned argument");
+    VotParams p;
+    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
+    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = 0; p.im_h = 0;
+    if (launch_vot_overlap_dev(p, state_dev, stream)) return fail(SMK_E_HIP, "vot_overlap_dev launch failed");
     return 0;
 }
 

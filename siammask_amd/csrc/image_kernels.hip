@@ -33,18 +33,40 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int ssize, double scale) {
     return c;
 }
 
-// one output pixel (dx, dy) of stream b; P = CropParams (window and mean colour in the kernarg) or CropDevParams (read from the
-// tracker's state block): the same per-pixel code for both, the resize branch is uniform per stream either way
+// where the frame of stream b lies and how a pixel of it is addressed, per parameter type.  Packed: frames [H][W][3] of one size,
+// frame_stride bytes apart (CropParams, CropDevParams, CropExemplarParams).  Pitched: stream b's own smk_image_ref (CropVParams).
+struct CropSrcPacked {
+    const unsigned char *im;
+    int H, W;
+    __device__ __forceinline__ const unsigned char *at(int y, int x) const { return im + ((size_t)y * W + x) * 3; }
+};
+struct CropSrcPitched {
+    const unsigned char *im;
+    long row_bytes;
+    int H, W;
+    __device__ __forceinline__ const unsigned char *at(int y, int x) const { return im + (size_t)y * row_bytes + (size_t)x * 3; }
+};
+template <class P>
+__device__ __forceinline__ CropSrcPacked crop_src(const P &p, int b) {
+    return {p.frames + (size_t)b * p.frame_stride, p.H, p.W};
+}
+__device__ __forceinline__ CropSrcPitched crop_src(const CropVParams &p, int b) {
+    return {p.im[b].data, (long)p.im[b].row_bytes, p.im[b].h, p.im[b].w};
+}
+
+// one output pixel (dx, dy) of stream b; P = CropParams (window and mean colour in the kernarg), CropDevParams (read from the
+// tracker's state block) or CropVParams (the same with a frame of its own size per stream): the same per-pixel code for all, the
+// resize branch is uniform per stream either way
 template <class P>
 __device__ __forceinline__ void crop_pixel(const P &p, int b, int dx, int dy, int xmin, int ymin, int sz, int avg0, int avg1,
                                            int avg2) {
-    const unsigned char *im = p.frames + (size_t)b * p.frame_stride;
-    const int H = p.H, W = p.W;
+    const auto src = crop_src(p, b);
+    const int H = src.H, W = src.W;
     // patch pixel (py, px) -> frame pixel or the mean colour (tools/test.py:89-100)
     auto px3 = [&](int py, int px, int (&v)[3]) {
         const int y = ymin + py, x = xmin + px;
         if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
-            const unsigned char *q = im + ((size_t)y * W + x) * 3;
+            const unsigned char *q = src.at(y, x);
             v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
         } else {
             v[0] = avg0; v[1] = avg1; v[2] = avg2;
@@ -120,6 +142,44 @@ __global__ __launch_bounds__(256) void crop_exemplar_dev_kernel(const CropExempl
         return;
     }
     crop_pixel(p, b, dx, dy, win[0], win[1], sz, a0, a1, a2);
+}
+
+// ---- streams with their own frame sizes (smk_crop_resize_dev_v / smk_crop_exemplar_dev_v): the two kernels above with the frame of
+// stream b taken from its smk_image_ref in the kernarg -- the in-image test uses that frame's w and h, the address its row_bytes
+__device__ __forceinline__ void crop_fill(const CropVParams &p, int b, int dx, int dy, int a0, int a1, int a2) {
+    const size_t plane = (size_t)p.model_sz * p.model_sz;
+    float *out = p.out + (size_t)b * 3 * plane + (size_t)dy * p.model_sz + dx;
+    out[0] = (float)a0; out[plane] = (float)a1; out[2 * plane] = (float)a2;
+}
+
+__global__ __launch_bounds__(256) void crop_resize_dev_v_kernel(const CropVParams p) {
+    const int b = blockIdx.z;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+    if (dx >= p.model_sz) return;
+    const smk_trk_stream *s = p.st + b;
+    const int sz = s->sz, a0 = s->avg_bgr[0], a1 = s->avg_bgr[1], a2 = s->avg_bgr[2];
+    if (sz < 1 || sz > 32768) return crop_fill(p, b, dx, dy, a0, a1, a2);        // (an invalid state, as crop_resize_dev_kernel)
+    crop_pixel(p, b, dx, dy, s->xmin, s->ymin, sz, a0, a1, a2);
+}
+
+__global__ __launch_bounds__(256) void crop_exemplar_dev_v_kernel(const CropVParams p) {
+    const int b = blockIdx.z;
+    if (!((p.mask >> b) & 1) || p.res[TRK_START_ROW * b] == 0.0) return;
+    const int dx = blockIdx.x * blockDim.x + threadIdx.x, dy = blockIdx.y;
+    if (dx >= p.model_sz) return;
+    const smk_trk_stream *s = p.st + b;
+    const int *win = p.win + 3 * b;
+    const int sz = win[2], a0 = s->avg_bgr[0], a1 = s->avg_bgr[1], a2 = s->avg_bgr[2];
+    if (sz < 1 || sz > 32768) return crop_fill(p, b, dx, dy, a0, a1, a2);
+    crop_pixel(p, b, dx, dy, win[0], win[1], sz, a0, a1, a2);
+}
+
+int launch_crop_v(const CropVParams &p, int B, void *stream) {
+    if (B < 1 || B > TRK_SET_MAX_B) return -1;
+    dim3 grid((p.model_sz + 255) / 256, p.model_sz, B);
+    if (p.win) hipLaunchKernelGGL(crop_exemplar_dev_v_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else       hipLaunchKernelGGL(crop_resize_dev_v_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 int launch_crop_exemplar_dev(const CropExemplarParams &p, int B, void *stream) {
@@ -206,6 +266,35 @@ __global__ __launch_bounds__(256) void paste_mask_dev_kernel(const PasteDevParam
     const size_t o = ((size_t)b * p.H + y) * p.W + x;
     if (p.prob_out) p.prob_out[o] = v;
     if (p.mask_out) p.mask_out[o] = v > p.seg_thr ? 1 : 0;
+}
+
+// smk_paste_mask_dev_v: p.W x p.H is a CANVAS [B][H][W]; the mask of stream b fills [0:im_h][0:im_w] of its plane with im_w / im_h of
+// its record (clamped to the canvas: a larger one is an invalid state) and every other byte of the plane is written 0 here
+__global__ __launch_bounds__(256) void paste_mask_dev_v_kernel(const PasteDevParams p) {
+    const int b = blockIdx.z;
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= p.W) return;
+    const smk_trk_stream *s = p.st + b;
+    const int w = min(s->im_w, p.W), h = min(s->im_h, p.H);
+    unsigned char m = 0;
+    if (x < w && y < h) {
+        const float *lg = p.logits + (size_t)b * p.ms * p.ms;
+        int ls = 1;
+        if (p.head_S) {
+            ls = p.head_S * p.head_S;
+            const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1), dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+            lg = p.logits + (size_t)b * p.ms * p.ms * ls + dy * p.head_S + dx;
+        }
+        m = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y) > p.seg_thr ? 1 : 0;
+    }
+    p.mask_out[((size_t)b * p.H + y) * p.W + x] = m;
+}
+
+int launch_paste_mask_dev_v(const PasteDevParams &p, int B, void *stream) {
+    if (B < 1 || B > TRK_SET_MAX_B || !p.mask_out) return -1;
+    dim3 grid((p.W + 255) / 256, p.H, B);
+    hipLaunchKernelGGL(paste_mask_dev_v_kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 int launch_paste_mask_dev(const PasteDevParams &p, int B, void *stream) {

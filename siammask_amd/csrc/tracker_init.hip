@@ -164,6 +164,80 @@ int launch_frame_sums(const FrameSumsParams &p, void *stream) {
 }
 
 // ------------------------------------------------------------------------------------------
+// frame_sums_v: the same sums for n frames of DIFFERENT sizes and row pitches (one smk_image_ref each, in the kernarg) in one
+// launch.  A pitched frame is not one run of bytes, so the unit is the row: blockIdx.y = frame, a WAVE takes a row (the rows of
+// a frame are dealt round-robin to the waves of its workgroups), the channel phase restarts with every row.  Per row: the up
+// to 15 bytes in front of the first 16-byte aligned address and behind the last one are read one per lane (lanes 0..15 / 16..31),
+// the aligned body as uint4, one chunk per lane and turn, summed and rotated as above.  The 32-bit counters are folded into the
+// lane's 64-bit sums after every row -- a row of 32768 pixels gives a lane at most 97 chunks of 6 * 255 -- so nothing can wrap
+// at any size.  Reduction and output as frame_sums_kernel: shuffles, LDS, one 64-bit atomic add per workgroup and channel.
+constexpr int SUMS_V_ROWS_PER_WAVE = 8, SUMS_V_MAX_BLOCKS = 1024;
+
+__global__ __launch_bounds__(256) void frame_sums_v_kernel(const FrameSumsVParams p) {
+    __shared__ unsigned long long part[4][3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const smk_image_ref &im = p.im[blockIdx.y];
+    const int h = im.h;
+    const long row_len = 3L * im.w;
+    unsigned long long s0 = 0, s1 = 0, s2 = 0;
+    for (int y = blockIdx.x * 4 + wave; y < h; y += gridDim.x * 4) {
+        const unsigned char *f = im.data + (size_t)y * im.row_bytes;
+        const long head = min((long)((16 - ((size_t)f & 15)) & 15), row_len);
+        const long n_chunk = (row_len - head) / 16;
+        const long tail0 = head + 16 * n_chunk;
+        unsigned c0 = 0, c1 = 0, c2 = 0;
+        const uint4 *body = (const uint4 *)(f + head);
+        for (long i = lane; i < n_chunk; i += 64) {
+            const uint4 v = body[i];
+            unsigned t0 = 0, t1 = 0, t2 = 0;
+            sums_add_word(v.x, t0, t1, t2);
+            sums_add_word(v.y, t1, t2, t0);
+            sums_add_word(v.z, t2, t0, t1);
+            sums_add_word(v.w, t0, t1, t2);
+            const int ph = (int)((head + 16 * i) % 3);                    // channel of position 0 (a row starts at channel 0)
+            c0 += ph == 0 ? t0 : (ph == 1 ? t2 : t1);
+            c1 += ph == 0 ? t1 : (ph == 1 ? t0 : t2);
+            c2 += ph == 0 ? t2 : (ph == 1 ? t1 : t0);
+        }
+        if (lane < 32) {
+            const long i = lane < 16 ? (long)lane : tail0 + (lane - 16);
+            const bool on = lane < 16 ? (long)lane < head : i < row_len;
+            if (on) {
+                const unsigned v = f[i];
+                const int ch = (int)(i % 3);
+                c0 += ch == 0 ? v : 0u;
+                c1 += ch == 1 ? v : 0u;
+                c2 += ch == 2 ? v : 0u;
+            }
+        }
+        s0 += c0; s1 += c1; s2 += c2;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        s0 += __shfl_down(s0, d);
+        s1 += __shfl_down(s1, d);
+        s2 += __shfl_down(s2, d);
+    }
+    if (lane == 0) { part[wave][0] = s0; part[wave][1] = s1; part[wave][2] = s2; }
+    __syncthreads();
+    if (tid < 3) {
+        const unsigned long long v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+        if (v) atomicAdd(p.sums + 3 * (size_t)blockIdx.y + tid, v);
+    }
+}
+
+int launch_frame_sums_v(const FrameSumsVParams &p, void *stream) {
+    if (!p.sums || p.n < 1 || p.n > TRK_SET_MAX_B || p.max_h < 1) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(p.sums, 0, sizeof(unsigned long long) * 3 * p.n, s) != hipSuccess) return -4;
+    const int per_block = 4 * SUMS_V_ROWS_PER_WAVE;
+    int blocks = (p.max_h + per_block - 1) / per_block;
+    blocks = blocks > SUMS_V_MAX_BLOCKS ? SUMS_V_MAX_BLOCKS : blocks;
+    hipLaunchKernelGGL(frame_sums_v_kernel, dim3((unsigned)blocks, p.n, 1), dim3(256), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ------------------------------------------------------------------------------------------
 // trk_start: one lane per stream; the streams outside `mask` are not touched
 __global__ __launch_bounds__(64) void trk_start_kernel(smk_trk_stream *st, double *twh, const TrkStartArgs a) {
     const int b = threadIdx.x;
@@ -185,9 +259,38 @@ __global__ __launch_bounds__(64) void trk_start_kernel(smk_trk_stream *st, doubl
     }
 }
 
+// smk_trk_start_v: the same lane with the size of stream b's own frame.  (A kernel of its own and not a shared body: with one,
+// the compiler schedules trk_start_kernel differently, and the existing kernels keep their instructions.)
+__global__ __launch_bounds__(64) void trk_start_v_kernel(smk_trk_stream *st, double *twh, const TrkStartVArgs v) {
+    const int b = threadIdx.x;
+    const TrkStartArgs &a = v.a;
+    if (b >= a.B || !((a.mask >> b) & 1)) return;
+    double px, py, w, h;
+    if (a.rects) {
+        const int *r = a.rects + 4 * b;
+        w = (double)r[2]; h = (double)r[3];
+        px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
+    } else {
+        px = a.pos[b][0]; py = a.pos[b][1];
+        w = a.sz[b][0]; h = a.sz[b][1];
+    }
+    double wh[2];
+    if (trk_start(st[b], a.cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, v.im_wh[b][0], v.im_wh[b][1], a.win + 3 * b,
+                  a.res + TRK_START_ROW * b, wh)) {
+        twh[2 * b] = wh[0];
+        twh[2 * b + 1] = wh[1];
+    }
+}
+
 int launch_trk_start(smk_trk_stream *st, double *twh, const TrkStartArgs &a, void *stream) {
     if (a.B < 1 || a.B > TRK_SET_MAX_B || !st || !twh || !a.sums || !a.win || !a.res) return -1;
     hipLaunchKernelGGL(trk_start_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st, twh, a);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_trk_start_v(smk_trk_stream *st, double *twh, const TrkStartVArgs &v, void *stream) {
+    if (v.a.B < 1 || v.a.B > TRK_SET_MAX_B || !st || !twh || !v.a.sums || !v.a.win || !v.a.res) return -1;
+    hipLaunchKernelGGL(trk_start_v_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, st, twh, v);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

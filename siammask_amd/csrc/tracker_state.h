@@ -260,5 +260,30 @@ struct CropExemplarParams {         // (the members crop_pixel reads are named a
 };
 int launch_crop_exemplar_dev(const CropExemplarParams &p, int B, void *stream);
 
+// ---- streams with their own frame sizes (the smk_*_v entries): one smk_image_ref per stream, host values in the kernarg --------
+struct CropVParams {                // smk_crop_resize_dev_v (win == nullptr) and smk_crop_exemplar_dev_v
+    smk_image_ref im[TRK_SET_MAX_B];
+    float *out;
+    int model_sz;
+    const smk_trk_stream *st;
+    const int *win;                 // exemplar: [B][3] of smk_trk_start_v, res [B][TRK_START_ROW], the streams of mask
+    const double *res;
+    unsigned mask;
+};
+int launch_crop_v(const CropVParams &p, int B, void *stream);
+// the canvas form of launch_paste_mask_dev: p.W x p.H is the canvas, each stream's size comes from its record; prob_out unused
+int launch_paste_mask_dev_v(const PasteDevParams &p, int B, void *stream);
+struct FrameSumsVParams {
+    smk_image_ref im[TRK_SET_MAX_B];
+    unsigned long long *sums;       // [n][3]
+    int n, max_h;
+};
+int launch_frame_sums_v(const FrameSumsVParams &p, void *stream);
+struct TrkStartVArgs {              // smk_trk_start_v: a.im_w / a.im_h unused, stream b starts on a frame of im_wh[b]
+    TrkStartArgs a;
+    int im_wh[TRK_SET_MAX_B][2];
+};
+int launch_trk_start_v(smk_trk_stream *st, double *twh, const TrkStartVArgs &a, void *stream);
+
 }  // namespace smk
 #endif

@@ -226,6 +226,8 @@ struct VotParams {
     int pred_stride, B, im_w, im_h;
 };
 int launch_vot_overlap(const VotParams &p, void *stream);
+// the same with the bounds of pair b read from record b (smk_trk_stream) of the tracker's state block; p.im_w / p.im_h unused
+int launch_vot_overlap_dev(const VotParams &p, const void *state, void *stream);
 
 // the predicted polygon of pair b as the tracker reports it: see smk_vot_overlap in include/siammask_hip.h
 SMK_VOT_HD void vot_pred_corners(const double *pred, int pred_stride, const double *adv, int b, double *c) {

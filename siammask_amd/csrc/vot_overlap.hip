@@ -6,6 +6,7 @@
 // is written anywhere; the result leaves in plain vector stores by one lane.
 #include <hip/hip_runtime.h>
 #include "vot_overlap.h"
+#include "../../include/siammask_hip.h"
 
 namespace smk {
 
@@ -50,9 +51,59 @@ __global__ __launch_bounds__(VOT_THREADS) void vot_overlap_kernel(const VotParam
     }
 }
 
+// smk_vot_overlap_dev: the bounds of pair b are im_w, im_h of record b of the tracker's state block.  A record outside
+// 1..VOT_MAX_DIM (an invalid state) is clamped into it, so that the joint window stays an exact int32 count.  (The kernel above
+// with two loads in front, written out: as a shared body the compiler schedules vot_overlap_kernel differently, and the existing
+// kernels keep their instructions.)
+__global__ __launch_bounds__(VOT_THREADS) void vot_overlap_dev_kernel(const VotParams p, const smk_trk_stream *st) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (b >= p.B) return;
+    const int im_w = min(max(st[b].im_w, 1), VOT_MAX_DIM), im_h = min(max(st[b].im_h, 1), VOT_MAX_DIM);
+    __shared__ int part[VOT_WAVES][3];
+    double c[8];
+    vot_pred_corners(p.pred, p.pred_stride, p.adv, b, c);
+    const VotPoly p2 = vot_poly(c);                                   // the prediction is the reference's second polygon
+    const VotPoly p1 = vot_poly(p.gt + 8 * (size_t)b);
+    const VotWindow w = vot_window(p1, p2, im_w, im_h);
+    int cnt[3] = {0, 0, 0};
+    if (w.path == VOT_PATH_RASTER) {                                  // (uniform: every lane computed the same window)
+        const VotPoly q1 = vot_place(p1, w.ox, w.oy), q2 = vot_place(p2, w.ox, w.oy);
+        for (int Y = tid; Y < w.height; Y += VOT_THREADS) vot_row_counts(q1, q2, Y, w.width, cnt);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        cnt[0] += __shfl_down(cnt[0], off, 64);
+        cnt[1] += __shfl_down(cnt[1], off, 64);
+        cnt[2] += __shfl_down(cnt[2], off, 64);
+    }
+    if ((tid & 63) == 0) {
+        part[tid >> 6][0] = cnt[0];
+        part[tid >> 6][1] = cnt[1];
+        part[tid >> 6][2] = cnt[2];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n1 = 0, n2 = 0, inter = 0;
+#pragma unroll
+        for (int k = 0; k < VOT_WAVES; ++k) { n1 += part[k][0]; n2 += part[k][1]; inter += part[k][2]; }
+        int32_t out[4];
+        p.overlap[b] = vot_result(n1, n2, inter, w.path, out);
+        if (p.counts) {
+            int32_t *dst = p.counts + 4 * (size_t)b;
+            dst[0] = out[0]; dst[1] = out[1]; dst[2] = out[2]; dst[3] = out[3];
+        }
+    }
+}
+
 int launch_vot_overlap(const VotParams &p, void *stream) {
     if (p.B < 1 || p.B > 65535) return -1;
     hipLaunchKernelGGL(vot_overlap_kernel, dim3(p.B), dim3(VOT_THREADS), 0, (hipStream_t)stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_vot_overlap_dev(const VotParams &p, const void *state, void *stream) {
+    if (p.B < 1 || p.B > 65535 || !state) return -1;
+    hipLaunchKernelGGL(vot_overlap_dev_kernel, dim3(p.B), dim3(VOT_THREADS), 0, (hipStream_t)stream, p, (const smk_trk_stream *)state);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -340,7 +340,81 @@ def mask_rboxes(mask, min_area=100.0, out=None):
     return out
 
 
-def vot_overlap(pred, gt, im_wh, adv_rows=None, out=None, counts=None):
+def image_refs(frames):
+    """smk_image_ref array of a list of uint8 CUDA tensors [h,w,3] (packed pixels, rows at any pitch >= 3 w; no copy)"""
+    refs = (_lib.ImageRef * len(frames))()
+    for r, f in zip(refs, frames):
+        _need_cuda(f, "frames")
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.stride(2) != 1 or f.stride(1) != 3:
+            raise ValueError("frames must be uint8 [h,w,3] with packed pixels")
+        r.data, r.row_bytes, r.w, r.h = f.data_ptr(), max(int(f.stride(0)), 3 * int(f.shape[1])), int(f.shape[1]), int(f.shape[0])
+    return refs
+
+
+def crop_batch_dev_v(frames, state, model_sz, out=None):
+    """crop_batch_dev for streams with their own frame sizes: frames is a list of B uint8 CUDA tensors [h_b,w_b,3]"""
+    B = len(frames)
+    refs = image_refs(frames)
+    _need_cuda(state, "state")
+    if out is None:
+        out = torch.empty((B, 3, model_sz, model_sz), dtype=torch.float32, device=state.device)
+    with torch.cuda.device(state.device):
+        _lib.check(_lib.lib().smk_crop_resize_dev_v(refs, state.data_ptr(), B, int(model_sz), out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
+def frame_sums_v(frames, out=None):
+    """frame_sums for a list of n <= 32 frames of different sizes and pitches, one launch -> int64 CUDA [n,3]"""
+    n = len(frames)
+    refs = image_refs(frames)
+    if out is None:
+        out = torch.empty((n, 3), dtype=torch.int64, device=frames[0].device)
+    elif out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (n, 3):
+        raise ValueError("out must be a contiguous int64 CUDA tensor [%d,3]" % n)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().smk_frame_sums_v(refs, n, out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
+def paste_masks_dev_v(logits, state, slot, canvas_wh, seg_thr=0.35, padding=-1.0, head=None, mask_size=None, out=None, sizes=None):
+    """paste_masks_dev onto a canvas uint8 [B,canvas_h,canvas_w]: stream b's mask fills [:im_h_b, :im_w_b] (sizes from its record),
+    everything else of the canvas is written 0.  sizes: the streams' (w, h) [B,2] as the host knows them (checked against the canvas)"""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B, S = src.shape[0], 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    W, H = int(canvas_wh[0]), int(canvas_wh[1])
+    mask = out if out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=src.device)
+    if mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or tuple(mask.shape) != (B, H, W):
+        raise ValueError("out must be a contiguous uint8 CUDA tensor [%d,%d,%d]" % (B, H, W))
+    wh = np.ascontiguousarray(sizes, dtype=np.int32).reshape(B, 2) if sizes is not None else None
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().smk_paste_mask_dev_v(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, W, H, wh.ctypes.data if wh is not None else None, float(seg_thr), float(padding),
+            mask.data_ptr(), _lib.current_stream_ptr()))
+    return mask
+
+
+def vot_overlap_dev(pred, gt, state, adv_rows=None, out=None, counts=None):
+    """vot_overlap with the bounds of pair b taken on the device from record b of the tracker's state block (streams with
+    their own frame sizes; include/siammask_hip.h: smk_vot_overlap_dev)"""
+    _need_cuda(state, "state")
+    return vot_overlap(pred, gt, None, adv_rows=adv_rows, out=out, counts=counts, _state=state)
+
+
+def vot_overlap(pred, gt, im_wh, adv_rows=None, out=None, counts=None, _state=None):
     """vot_overlap(gt_polygon, pred_polygon, (im_w, im_h)) of tools/test.py:354 for B pairs on the device, bit for bit
     (include/siammask_hip.h: smk_vot_overlap).  pred: float64 CUDA [B,8] / [B,4,2] corners, or the [B,12] rows of mask_rboxes
     (with adv_rows, float64 CUDA [B,16] rows of the tracker's advance, a row whose mask was empty takes the box of the state
@@ -373,8 +447,11 @@ def vot_overlap(pred, gt, im_wh, adv_rows=None, out=None, counts=None):
                                tuple(counts.shape) != (B, 4)):
         raise ValueError("counts must be a contiguous int32 CUDA tensor [%d,4]" % B)
     with torch.cuda.device(gt.device):
-        _lib.check(_lib.lib().smk_vot_overlap(
-            pred.data_ptr() if pred is not None else None, stride, adv_rows.data_ptr() if adv_rows is not None else None,
-            gt.data_ptr(), B, int(im_wh[0]), int(im_wh[1]), out.data_ptr(), counts.data_ptr() if counts is not None else None,
-            _lib.current_stream_ptr()))
+        shared = (pred.data_ptr() if pred is not None else None, stride, adv_rows.data_ptr() if adv_rows is not None else None,
+                  gt.data_ptr())
+        tail = (out.data_ptr(), counts.data_ptr() if counts is not None else None, _lib.current_stream_ptr())
+        if _state is not None:
+            _lib.check(_lib.lib().smk_vot_overlap_dev(*(shared + (_state.data_ptr(), B) + tail)))
+        else:
+            _lib.check(_lib.lib().smk_vot_overlap(*(shared + (B, int(im_wh[0]), int(im_wh[1])) + tail)))
     return out

@@ -27,6 +27,14 @@ Streams that start on their own frames (siamese_init per stream on the device, e
     res = tr.run(frames, gt=gt, vos={'object_ids': ids, 'thrs': vos.THRS, 'start': {...}, 'end': {...}})   # track_vos (:481-504)
     res['alive'], res['events']                                    # bool [T,B]; what every start event did
 
+Streams with their own frame sizes (B different videos in one free-running batch; the smk_*_v entries):
+    tr.reserve(B, H, W)                                            # (H, W): the canvas, the largest frame any slot will see
+    tr.start([f0, f1], [0, 1], pos=..., sz=...)                    # a LIST: one uint8 CUDA [h,w,3] per started stream (h <= H, w <= W;
+    res = tr.run([v0, v1], want_polygon=True)                      #   pitched rows allowed); B videos [T,h_b,w_b,3]
+    res['mask'], res['sizes']                                      # uint8 CUDA [T,B,H,W], zero outside each stream's image; (w, h) [T,B,2]
+tr.state['im_w'] / ['im_h'] are then per-stream arrays; a slot may be started again on a video of another size.  Free-running only:
+track(), gt= / vos= / labels_out= (the objects of VOS share one frame) raise ValueError in this mode.
+
 The VOT supervised loop (track_vot, :318-365) for B videos in lock-step, still enqueue-only: the overlap of every tracked polygon
 with its annotation is computed on the device (csrc/vot_overlap.hip), the host learns of a loss through a read-back that lags
 skip - 1 frames behind the queue head and re-initialises the stream with start(pos=, sz=) (siammask_amd/vot.py: the decisions):
@@ -101,7 +109,8 @@ def _box_corners(pos, sz):
 
 # one frame's paste-back: Refine logits or the mask head, the state slot, the mask to write, its rbox rows or None, a _Score or
 # None, and a hook called behind them as after(rbox rows, advance rows) (run(vot=) enqueues its overlap there)
-_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv")
+# sizes: None, or (mixed sizes) the int32 [B,2] (w, h) of the streams' frames when the frame was enqueued: mask is then the canvas
+_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes")
 # a checked VOS request as the C entry takes it (_vos_spec); enqueue() adds the frame's count row and label map
 _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels")
 _Event = collections.namedtuple("_Event", "t streams res")            # one start(): chunk index, streams, device rows [B,START_ROW]
@@ -109,12 +118,13 @@ _Event = collections.namedtuple("_Event", "t streams res")            # one star
 
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
-    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "events", "z_snapped", "start")
+    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "events", "z_snapped", "start", "sizes")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
+        self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
 
 
 class _Queue(object):
@@ -143,6 +153,20 @@ class _Launching(object):
         self.guard.__exit__(kind, e, tb)
         if isinstance(e, _lib.SmkError) and e.code == _lib.E_SEQ:
             self.tr._fr_rewind()
+
+
+class _Videos(object):
+    """run() with a list: B videos uint8 CUDA [T,h_b,w_b,3] of one length; videos[t] is the list of their frames t"""
+
+    def __init__(self, videos, B):
+        ok = len(videos) == B and all(isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.uint8 and v.dim() == 4
+                                      for v in videos)
+        if not ok or len(set(int(v.shape[0]) for v in videos)) != 1 or int(videos[0].shape[0]) < 1:
+            raise ValueError("frames must be a list of %d uint8 CUDA tensors [T,h,w,3] with one T >= 1" % B)
+        self.videos, self.shape, self.device = list(videos), (int(videos[0].shape[0]),), videos[0].device
+
+    def __getitem__(self, t):
+        return [v[t] for v in self.videos]
 
 
 def _apply_events(st, events, ev_rows, T):
@@ -282,14 +306,21 @@ class DeviceTracker(object):
             raise ValueError("start() takes trackers of up to 32 streams, this one has %d" % B)
         if not q.can_start or self.model.template_input() is not q.z_all or self.model.zf is None:
             raise RuntimeError("DeviceTracker.start(): the model's template is not the one this tracker was reserved / initialised with")
-        self._check_frame(frame)
         streams = [int(b) for b in np.asarray(streams).reshape(-1)]
         if not streams or len(set(streams)) != len(streams) or min(streams) < 0 or max(streams) >= B:
             raise ValueError("streams must be distinct indices in 0..%d" % (B - 1))
         n = len(streams)
+        if isinstance(frame, (list, tuple)):                          # a frame of its own size per started stream
+            if labels is not None or object_ids is not None:
+                raise ValueError("start(): a list of frames takes pos= and sz=; labels= / object_ids= share one frame")
+            self._frame_list(frame, n, "start(): one frame per entry of `streams`")
+        else:
+            self._check_frame(frame)
         by_host, by_labels = pos is not None or sz is not None, labels is not None or object_ids is not None
         if by_host == by_labels or (by_host and (pos is None or sz is None)) or (by_labels and (labels is None or object_ids is None)):
             raise ValueError("start(): either pos= and sz=, or labels= and object_ids=")
+        if by_labels and self._mixed():
+            raise ValueError("start(): labels= / object_ids= share one frame; these streams have their own sizes (pos= and sz=)")
         bits = sum(1 << b for b in streams)
         if by_host:
             hp = np.asarray(pos, dtype=np.float64).reshape(-1, 2)
@@ -321,6 +352,8 @@ class DeviceTracker(object):
         streams, bits, hpos, hsz, ids_all = self._start_spec(frame, streams, pos, sz, labels, object_ids)
         q = self._fr
         c, B, H, W = q.chunk, q.B, q.H, q.W
+        if isinstance(frame, (list, tuple)):
+            return self._start_mixed(list(frame), streams, bits, hpos, hsz)
         frame = frame.contiguous()
         if labels is not None:
             labels = labels.contiguous()
@@ -343,6 +376,86 @@ class DeviceTracker(object):
             _lib.check(L.smk_crop_exemplar_dev(frame.data_ptr(), H * W * 3 if per_stream else 0, H, W, q.dev.data_ptr(),
                                                q.win.data_ptr(), res.data_ptr(), bits, B, self.p.exemplar_size, q.z_all.data_ptr(), sp))
             self.model.template(q.z_all, sync=False)
+            if self._mixed():                                         # the slots now follow a frame of the canvas size
+                self._set_sizes(streams, [(W, H)] * len(streams), hsz)
+            c.events.append(_Event(c.pending, streams, res))
+            return c.pending
+
+    # -- streams with their own frame sizes (the smk_*_v entries) ----------------------------------
+    def _mixed(self):
+        """the streams have their own frame sizes: tr.state['im_w'] / ['im_h'] are per-stream arrays"""
+        return self.state is not None and isinstance(self.state["im_w"], np.ndarray)
+
+    def _sizes(self):
+        """int32 [B,2]: (w, h) of every slot's current frame"""
+        st = self.state
+        return np.ascontiguousarray(np.stack([st["im_w"], st["im_h"]], axis=1).astype(np.int32))
+
+    def _set_sizes(self, streams, wh, hsz=None):
+        """slots `streams` now follow frames of wh [(w, h)]; the first call turns the mode on.  hsz: the targets' host sizes [B,2] --
+        a stream without a positive one starts nothing (smk_trk_start) and keeps its record, so it keeps its size here"""
+        st, q = self.state, self._fr
+        if not self._mixed():
+            st["im_w"], st["im_h"] = np.full(q.B, q.W, dtype=np.int64), np.full(q.B, q.H, dtype=np.int64)
+        for b, (w, h) in zip(streams, wh):
+            if hsz is None or (hsz[b, 0] > 0 and hsz[b, 1] > 0):
+                st["im_w"][b], st["im_h"][b] = w, h
+
+    def _frame_list(self, frames, n, what, sizes=None):
+        """frames is a list of n uint8 CUDA tensors [h,w,3] on the tracker's device, h <= H and w <= W of the canvas, pixels packed
+        and rows at any pitch >= 3 w (a view into a wider buffer: no copy is made) [, of exactly ``sizes`` [(w, h)]] -> [(w, h)]"""
+        q = self._fr
+        if not isinstance(frames, (list, tuple)) or len(frames) != n:
+            raise ValueError("%s: a list of %d frames" % (what, n))
+        wh = []
+        for i, f in enumerate(frames):
+            if not isinstance(f, torch.Tensor) or not f.is_cuda:
+                raise RuntimeError("siammask_amd.tracker runs on the MI355X only: frame must be a CUDA(HIP) tensor")
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3 or f.device != q.device:
+                raise ValueError("%s: frame %d must be uint8 [h,w,3] on %s, got %s %s" % (what, i, q.device, f.dtype, tuple(f.shape)))
+            h, w = int(f.shape[0]), int(f.shape[1])
+            if not (1 <= h <= q.H and 1 <= w <= q.W):
+                raise ValueError("%s: frame %d is %d x %d, the canvas reserved is %d x %d" % (what, i, h, w, q.H, q.W))
+            if f.stride(2) != 1 or f.stride(1) != 3 or (h > 1 and f.stride(0) < 3 * w):
+                raise ValueError("%s: frame %d: pixels must be packed BGR, rows at a pitch >= 3 * w" % (what, i))
+            if sizes is not None and (w, h) != (int(sizes[i][0]), int(sizes[i][1])):
+                raise ValueError("%s: frame %d is %d x %d (h x w), slot %d follows a %d x %d video: start() the slot on the new one"
+                                 % (what, i, h, w, i, int(sizes[i][1]), int(sizes[i][0])))
+            wh.append((w, h))
+        return wh
+
+    def _image_refs(self, frames, streams):
+        """smk_image_ref [B] for the C entries: slot streams[i] <- frames[i]; the other slots repeat the first one (the entries that
+        take a start mask do not look at them, smk_frame_sums_v sums a valid frame for nothing)"""
+        refs = (_lib.ImageRef * self._fr.B)()
+        for b in range(self._fr.B):
+            f = frames[streams.index(b)] if b in streams else frames[0]
+            r = refs[b]
+            r.data, r.row_bytes, r.w, r.h = f.data_ptr(), max(int(f.stride(0)), 3 * int(f.shape[1])), int(f.shape[1]), int(f.shape[0])
+        return refs
+
+    def _start_mixed(self, frames, streams, bits, hpos, hsz):
+        """start() with a frame of its own size per started stream: the launches of start() through the _v entries"""
+        q, L = self._fr, _lib.lib()
+        c, B = q.chunk, q.B
+        wh = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
+        refs = self._image_refs(frames, streams)
+        im_wh = np.zeros((B, 2), dtype=np.int32)
+        im_wh[streams] = wh
+        with q.launch as sp:
+            self._fr_begin()
+            if not c.z_snapped:
+                q.z_snap.copy_(q.z_all)
+                c.z_snapped = True
+            self._fr_flush(sp)                                        # (a deferred frame is pasted at the size its slot still has)
+            _lib.check(L.smk_frame_sums_v(refs, B, q.sums.data_ptr(), sp))
+            res = torch.empty((B, START_ROW), dtype=torch.float64, device=q.device)
+            _lib.check(L.smk_trk_start_v(q.dev.data_ptr(), B, ctypes.byref(q.cfg), bits, None, hpos.ctypes.data, hsz.ctypes.data,
+                                         q.sums.data_ptr(), 1, im_wh.ctypes.data, q.win.data_ptr(), res.data_ptr(), sp))
+            _lib.check(L.smk_crop_exemplar_dev_v(refs, q.dev.data_ptr(), q.win.data_ptr(), res.data_ptr(), bits, B,
+                                                 self.p.exemplar_size, q.z_all.data_ptr(), sp))
+            self.model.template(q.z_all, sync=False)
+            self._set_sizes(streams, wh, hsz)
             c.events.append(_Event(c.pending, streams, res))
             return c.pending
 
@@ -351,6 +464,8 @@ class DeviceTracker(object):
         """want_polygon: also the rotated rectangle the reference returns as state['ploygon'] (variants with a mask branch, and
         want_mask): st['polygon'] float64 [B,4,2], st['polygon_found'] bool [B]; the only extra device -> host traffic is
         [B,12] float64.  Without it the returned state has exactly the keys and values it always had."""
+        if self._mixed():
+            raise ValueError("track(): streams with their own frame sizes are free-running only (enqueue / run)")
         p, st = self.p, self.state
         st.pop("polygon", None)                                       # (of an earlier step that asked for it)
         st.pop("polygon_found", None)
@@ -435,6 +550,8 @@ class DeviceTracker(object):
     def _fr_upload(self):
         """the host's state -> the device block (values as kernel arguments), then the plan of the next frame"""
         q, st, L = self._fr, self.state, _lib.lib()
+        if self._mixed():
+            raise RuntimeError("the host's state cannot be uploaded for streams with their own frame sizes: start() them")
         pos = np.ascontiguousarray(st["target_pos"], dtype=np.float64)
         sz = np.ascontiguousarray(st["target_sz"], dtype=np.float64)
         # numpy assignment of the float mean into a uint8 image truncates (tools/test.py:92-99), as in preproc.crop_batch
@@ -526,7 +643,8 @@ class DeviceTracker(object):
         return _Score(gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits,
                       init.contiguous() if gbits else None, None, None)
 
-    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None):
+    def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
+                _unsized=False):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -534,23 +652,35 @@ class DeviceTracker(object):
         booleans]}): the B streams are the objects of one shared frame; behind the frame's paste-back the intersection / union
         counts of tools/test.py:421-456 and the fused label map (:521-523, at the tracker's seg_thr; labels_out: uint8 CUDA
         [im_h,im_w] to receive it) are computed on the device and come back from collect().
-        _after (private, tracker_loops.run_vot): the hook of the frame's _Job.
+        _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
+        stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
         q = self._fr
         if self.state is None or q is None:
             raise RuntimeError("DeviceTracker.enqueue(): init() first")
-        self._check_frame(frame)
         c, B, H, W = q.chunk, q.B, q.H, q.W
+        mixed = self._mixed() or isinstance(frame, (list, tuple))
+        if mixed:                                                     # B frames of the slots' current sizes, refused before any launch
+            if gt is not None or vos is not None or labels_out is not None:
+                raise ValueError("gt= / vos= / labels_out=: the objects of VOS share one frame; these streams have their own sizes")
+            if isinstance(frame, torch.Tensor) and frame.dim() in (3, 4):         # (the canvas-sized forms: a view per stream)
+                frame = list(frame.unbind(0)) if frame.dim() == 4 else [frame] * B
+            sizes = self._sizes() if self._mixed() else np.tile(np.array([W, H], dtype=np.int32), (B, 1))
+            self._frame_list(frame, B, "enqueue(): one frame per stream", None if _unsized else sizes)
+        else:
+            self._check_frame(frame)
         want_mask = want_mask and self.model.variant != "rpn"
         want_polygon = want_polygon and want_mask
         self._mask_out(mask_out, want_mask=want_mask)
         if c.pending and (c.vos_k is not None) != (vos is not None or gt is not None):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
-        score = self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
-        frame = frame.contiguous()
+        score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
+        frame = list(frame) if mixed else frame.contiguous()
         L, model = _lib.lib(), self.model
         with q.launch as sp:
             self._fr_begin()
+            if mixed and not self._mixed():
+                self._set_sizes([], [])
             t, slot = c.pending, c.pending & 1
             blk, i = divmod(t, _ROWS_PER_BLOCK)
             if i == 0 and blk == len(q.rows):
@@ -566,8 +696,12 @@ class DeviceTracker(object):
                 c.vos_k = int(score.thrs.size)
                 c.labels.append(labels)
             dev_ptr = q.dev.data_ptr()
-            _lib.check(L.smk_crop_resize_dev(frame.data_ptr(), H * W * 3 if frame.dim() == 4 else 0, H, W, dev_ptr, B,
-                                             self.p.instance_size, q.x.data_ptr(), sp))
+            if mixed:
+                _lib.check(L.smk_crop_resize_dev_v(self._image_refs(frame, list(range(B))), dev_ptr, B, self.p.instance_size,
+                                                   q.x.data_ptr(), sp))
+            else:
+                _lib.check(L.smk_crop_resize_dev(frame.data_ptr(), H * W * 3 if frame.dim() == 4 else 0, H, W, dev_ptr, B,
+                                                 self.p.instance_size, q.x.data_ptr(), sp))
             refine = self.refine and want_mask
             out = model.track_step(q.x, q.twh, refine=refine, mask_head=not self.refine, stage=False, out_set=slot if refine else 0)
             _lib.check(L.smk_trk_advance(dev_ptr, B, ctypes.byref(q.cfg), out["box"].data_ptr(), slot,
@@ -580,12 +714,14 @@ class DeviceTracker(object):
             if want_mask:
                 mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
-                           q.rbox[blk][i] if want_polygon else None, score, _after, q.rows[blk][i] if _after is not None else None)
+                           q.rbox[blk][i] if want_polygon else None, score, _after, q.rows[blk][i] if _after is not None else None,
+                           sizes if mixed else None)
                 if depth:
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
                     self._fr_paste(job, sp)
             c.masks.append(mask)
+            c.sizes.append(sizes if mixed else None)
             c.poly.append(bool(want_polygon))
             c.pending = t + 1
             return t
@@ -596,7 +732,10 @@ class DeviceTracker(object):
         logits, head, mask, s = job.logits, job.head, job.mask, job.score
         shared = (logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
                   int(head.shape[-1]) if head is not None else 0, self.mask_size, q.dev.data_ptr(), job.slot, q.B, q.W, q.H)
-        _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
+        if job.sizes is not None:                                     # the canvas: each stream at the size of its record, 0 elsewhere
+            _lib.check(L.smk_paste_mask_dev_v(*(shared + (job.sizes.ctypes.data, float(p.seg_thr), -1.0, mask.data_ptr(), sp))))
+        else:
+            _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
         if job.rbox is not None:                                      # same stream, behind the paste-back (:285-303)
             preproc.mask_rboxes(mask, out=job.rbox)
         if s is not None:                                             # the same slot of the same state block, same stream
@@ -683,6 +822,9 @@ class DeviceTracker(object):
             if K is not None:
                 res["labels"] = _labels if _labels is not None and _labels.shape[0] == T else torch.stack(c.labels)
             new["mask"] = masks[-1]
+            if any(z is not None for z in c.sizes):                   # [T,B,2] (w, h): the mask of (t, b) is mask[t, b, :h, :w]
+                res["sizes"] = np.stack([z if z is not None else np.tile(np.array([q.W, q.H], dtype=np.int32), (B, 1))
+                                         for z in c.sizes]).astype(np.int64)
         st.clear()
         st.update(new)
         q.synced = (st["target_pos"], st["target_sz"])                # the device holds exactly these values
@@ -702,9 +844,14 @@ class DeviceTracker(object):
         q = self._fr
         if self.state is None or q is None:
             raise RuntimeError("DeviceTracker.run(): init() first")
-        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        if isinstance(frames, (list, tuple)):                         # B videos of their own sizes, [T,h_b,w_b,3] each
+            if gt is not None or vos is not None:
+                raise ValueError("gt= / vos=: the objects of VOS share one frame; these streams have their own sizes")
+            frames = _Videos(frames, q.B)
+            self._frame_list(frames[0], q.B, "run(): one video per stream", self._sizes() if self._mixed() and vot is None else None)
+        elif not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise RuntimeError("siammask_amd.tracker runs on the MI355X only: frames must be a CUDA(HIP) tensor")
-        if frames.dim() not in (4, 5):
+        elif frames.dim() not in (4, 5):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T, labels, alive = int(frames.shape[0]), None, None
         if vot is not None:

@@ -78,7 +78,8 @@ def run_vot(tr, frames, want_mask, want_polygon, mask_out, spec):
     (vot.axis_aligned_bbox) with start(pos=, sz=).  The queue is never drained: a loss on frame f takes effect on frame
     f + skip, so before frame g is enqueued the host waits only for the [B] overlaps of frame g - skip (an asynchronous copy
     into pinned memory followed by an event), `skip` - 1 frames behind the queue head; the decisions are vot.Schedule's.
-    frames: ALL T frames, uint8 CUDA [T,B,H,W,3] (or [T,H,W,3]: one video shared by the streams); spec['gt']: host float64
+    frames: ALL T frames, uint8 CUDA [T,B,H,W,3] (or [T,H,W,3]: one video shared by the streams; or B videos of their own sizes,
+    as run() takes them: the overlap is then smk_vot_overlap_dev's, inside each stream's own bounds); spec['gt']: host float64
     [T,B,8] ([T,8] for B = 1), uploaded once; spec['length'] [B]: a video's frame count -- the stream is idle behind it.
     Stream b starts on frame 0 from gt[0, b]: reserve() suffices, no init().  A stream inside a skip window keeps stepping
     in lock-step; what it reports there is ignored and the re-initialisation overwrites its state.
@@ -91,7 +92,8 @@ def run_vot(tr, frames, want_mask, want_polygon, mask_out, spec):
         raise ValueError("vot = {'gt': float64 [T,B,8][, 'skip': frames skipped after a loss (5)][, 'length': B frame counts]}")
     if not want_polygon or not want_mask or tr.model.variant == "rpn":
         raise ValueError("run(vot=) compares the polygon of the mask: want_mask, want_polygon and a variant with a mask branch")
-    if T < 1 or not _u8_cuda(frames, (T, B, H, W, 3), (T, H, W, 3)):
+    mixed = not isinstance(frames, torch.Tensor)                      # B videos of their own sizes (tracker._Videos, checked)
+    if not mixed and (T < 1 or not _u8_cuda(frames, (T, B, H, W, 3), (T, H, W, 3))):
         raise ValueError("frames must be uint8 [T,%d,%d,%d,3] (or [T,%d,%d,3] shared by the streams)" % (B, H, W, H, W))
     gt = np.asarray(spec["gt"], dtype=np.float64)
     if gt.shape == (T, 8) and B == 1:
@@ -124,7 +126,10 @@ def run_vot(tr, frames, want_mask, want_polygon, mask_out, spec):
             gt_g, out, (host, event) = gt_dev[g], ov_dev[g], done[g]
 
             def after(rbox, adv):
-                preproc.vot_overlap(rbox, gt_g, (W, H), adv_rows=adv, out=out)
+                if mixed:                                             # the bounds of pair b: im_w, im_h of its record
+                    preproc.vot_overlap_dev(rbox, gt_g, tr._fr.dev, adv_rows=adv, out=out)
+                else:
+                    preproc.vot_overlap(rbox, gt_g, (W, H), adv_rows=adv, out=out)
                 host.copy_(out, non_blocking=True)                    # the lagging read-back: [B] floats into pinned memory
                 event.record(torch.cuda.current_stream())
             return after
@@ -147,11 +152,11 @@ def run_vot(tr, frames, want_mask, want_polygon, mask_out, spec):
             if sched.may_track(g).any():
                 done[g] = (ring[g % ring_n], torch.cuda.Event())
             tr.enqueue(frames[g], want_mask=True, want_polygon=True, mask_out=masks[g],
-                       _after=overlap_behind(g) if done[g] is not None else None)
+                       _after=overlap_behind(g) if done[g] is not None else None, _unsized=mixed and g == 0)
             head = g
             if starts:                                                # behind the step: the stream's first tracked frame is g + 1
                 box = boxes(g, starts)
-                tr.start(frames[g], starts, pos=box[:, 0:2], sz=box[:, 2:4])
+                tr.start([frames[g][b] for b in starts] if mixed else frames[g], starts, pos=box[:, 0:2], sz=box[:, 2:4])
         res = tr.collect(_masks=masks)
         while sched.reported < T:                                     # the queue's tail: everything is complete behind collect()
             report_next()
