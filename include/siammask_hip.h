@@ -466,6 +466,28 @@ int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int sco
 int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
                         const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream);
 
+/* ---- per-stream tracker hyper-parameters (additive; smk_version() keeps reporting 1.10, the presence of these symbols is the
+ * probe) -----------------------------------------------------------------------------------------------------------------
+ * The three hp a sweep varies (tools/tune_vot.py:225-228: penalty_k, window_influence, lr) per STREAM instead of per context, so
+ * that the B streams of one batch can be B points of a grid -- or B kinds of target with their own motion prior.
+ * The table is a caller-owned DEVICE array of float64, SMK_HP_STRIDE columns per stream: penalty_k, window_influence, lr, and a
+ * fourth column that is reserved and must be 0 (torch: a float64 CUDA tensor [B,4]).  Caller-owned for the reason the tracker's
+ * state block is: the library allocates nothing per tracker, and the caller can rewrite it with launches of its own.
+ * smk_set_stream_hp: from now on smk_decode / smk_step of this context take penalty_k and window_influence of stream b from row b
+ *   of hp_dev (rows 0 .. batch - 1) instead of the values of smk_set_decode_params; NULL: back to the context's values.  The
+ *   POINTER is remembered, nothing is copied: the caller keeps the table alive until it is cleared or replaced.  Setting or
+ *   clearing joins an outstanding pipelined tail and keeps every captured graph: the graphs are keyed on the table's address in
+ *   place of the two values, so those captured without a table are replayed again once it is cleared.  The table's CONTENTS may
+ *   be rewritten by the caller in stream order between steps (a copy or a kernel on the stream the steps are given): the kernel
+ *   reads the row when it runs, no re-capture.  Everything but the source of the two values is the arithmetic of smk_decode.
+ *   SMK_E_ARG: a null ctx; a non-null hp_dev that the HIP runtime does not report as device memory.
+ * smk_trk_advance_hp: smk_trk_advance with lr of stream b = hp_dev[b * SMK_HP_STRIDE + 2]; cfg->lr is ignored.  (No context:
+ *   the table is an argument, as the state block is.) */
+#define SMK_HP_STRIDE 4
+int smk_set_stream_hp(smk_ctx *ctx, const double *hp_dev);
+int smk_trk_advance_hp(void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev, int slot,
+                       double *result_row_dev, int plan_next, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,9 @@ int smk_host_arena_elems(int dtype, int variant, int pipe_depth, uint64_t *elems
 int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg);
 int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const double *box, int slot, double *result_row,
                          int plan_next);
+/* smk_trk_advance_hp on HOST memory (hp [B][SMK_HP_STRIDE] host too): stream b advances with lr = hp[b * SMK_HP_STRIDE + 2] */
+int smk_host_trk_advance_hp(void *state, int B, const smk_trk_cfg *cfg, const double *hp, const double *box, int slot,
+                            double *result_row, int plan_next);
 /* smk_trk_start on HOST memory (state, rects, sums, win_out, result_out all host; same checks, same inline function) */
 int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
                        const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,

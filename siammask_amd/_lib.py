@@ -22,6 +22,7 @@ DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "f16": 1, "fp16": 1, "float16": 1, "
          "f16x3": 2}       # split-operand fp16 (SMK_DTYPE_F16X3): fp32-grade cls / loc / box on the fp16 matrix pipe
 VARIANT = {"rpn": 0, "base": 1, "sharp": 2}
 TRACK_BOX, TRACK_MASK, TRACK_NO_MASK_HEAD = 0, 1, 2
+HP_STRIDE = 4     # SMK_HP_STRIDE: columns of a per-stream hp table (penalty_k, window_influence, lr, reserved 0)
 
 # every symbol include/siammask_hip.h declares
 SYMBOLS = (
@@ -36,6 +37,7 @@ SYMBOLS = (
     "smk_host_trk_start", "smk_vot_overlap", "smk_host_vot_overlap",
     "smk_crop_resize_dev_v", "smk_crop_exemplar_dev_v", "smk_frame_sums_v", "smk_trk_start_v", "smk_host_trk_start_v",
     "smk_paste_mask_dev_v", "smk_vot_overlap_dev",
+    "smk_set_stream_hp", "smk_trk_advance_hp", "smk_host_trk_advance_hp",
 )
 
 
@@ -170,6 +172,9 @@ def lib():
     L.smk_host_trk_start_v.argtypes = [vp, ci, cp, u32, vp, vp, vp, vp, i64, vp, vp, vp]
     L.smk_paste_mask_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, vp, cf, cf, vp, vp]
     L.smk_vot_overlap_dev.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
+    L.smk_set_stream_hp.argtypes = [vp, vp]
+    L.smk_trk_advance_hp.argtypes = [vp, ci, cp, vp, vp, ci, vp, ci, vp]
+    L.smk_host_trk_advance_hp.argtypes = [vp, ci, cp, vp, vp, ci, vp, ci]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

@@ -358,6 +358,7 @@ struct smk_ctx {
     int anchor_stride = 8;
     double *window_dev = nullptr;        // [25*25] outer(hanning(25), hanning(25))
     double penalty_k = 0.04, window_influence = 0.4;   // config_davis.json hp
+    const double *stream_hp = nullptr;   // smk_set_stream_hp: the caller's device table [B][SMK_HP_STRIDE], or nullptr: the two values above
 
     // per-launch profiling (smk_profile): HIP events around every kernel, eager mode only
     bool prof = false;
@@ -2287,6 +2288,14 @@ static void fill_decode_params(smk_ctx *c, const float *cls, const float *loc, i
     p.B = B; p.A = 5; p.S = 25; p.stride = c->anchor_stride;
     for (int i = 0; i < 5; ++i) { p.anchor_w[i] = c->anchor_w[i]; p.anchor_h[i] = c->anchor_h[i]; }
     p.penalty_k = c->penalty_k; p.window_influence = c->window_influence;
+    p.hp = c->stream_hp;
+}
+
+// what a step's graph key holds for the hp its decode launch was captured with: the bit patterns of the context's two values, or --
+// with a per-stream table -- the table's address and all-ones (no finite window_influence): the launch reads the table when it runs
+static void hp_graph_key(const smk_ctx *c, int64_t &pk, int64_t &wi) {
+    memcpy(&pk, &c->penalty_k, 8); memcpy(&wi, &c->window_influence, 8);
+    if (c->stream_hp) { pk = (int64_t)(intptr_t)c->stream_hp; wi = -1; }
 }
 
 static int seq_decode(smk_ctx *c, const StepRec &rec, const float *cls, const float *loc, int B, const double *target_wh, int *pos_out,
@@ -2325,6 +2334,24 @@ int smk_set_decode_params(smk_ctx *c, const float *anchor_wh, int n_anchor, int 
     for (auto &kv : c->graphs) hipGraphExecDestroy(kv.second);   // hp are baked into captured launches
     c->graphs.clear();
     c->graph_used.clear();
+    return 0;
+}
+
+int smk_set_stream_hp(smk_ctx *c, const double *hp_dev) {
+    if (!c) return fail(SMK_E_ARG, "ctx is NULL");
+    HIPCHK(hipSetDevice(c->device));
+    if (hp_dev) {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof(at));
+        if (hipPointerGetAttributes(&at, hp_dev) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(SMK_E_ARG, "smk_set_stream_hp: %p is not device memory", (const void *)hp_dev);
+        }
+        if (at.type != hipMemoryTypeDevice || (uintptr_t)hp_dev % 8)
+            return fail(SMK_E_ARG, "smk_set_stream_hp: %p is not (8-byte aligned) device memory", (const void *)hp_dev);
+    }
+    CHK(pipe_quiesce(c));                // (a tail in flight belongs to a step of the previous setting; the graphs stay)
+    c->stream_hp = hp_dev;
     return 0;
 }
 
@@ -2399,7 +2426,7 @@ static int step_pipelined_enqueue(smk_ctx *c, const float *x, int B, int flags, 
     const int par = c->pipe_parity;
     c->parity_now = par;
     int64_t pk, wi;
-    memcpy(&pk, &c->penalty_k, 8); memcpy(&wi, &c->window_influence, 8);
+    hp_graph_key(c, pk, wi);
     const std::vector<const void *> io{x, target_wh, cls, loc, mask, box_out, refine_out, (const void *)pk, (const void *)wi};
     const bool graphs = c->graph_mode;
     // where the main gate sits: in front of layer2 when that is the persistent sequence (it must own every CU), else in front of the
@@ -2526,7 +2553,7 @@ int smk_step(smk_ctx *c, const float *x, int B, int flags, const double *target_
     CHK(pipe_join(c, s, true));
     c->parity_now = c->last_parity = 0;
     int64_t pk, wi;
-    memcpy(&pk, &c->penalty_k, 8); memcpy(&wi, &c->window_influence, 8);
+    hp_graph_key(c, pk, wi);
     GraphKey key{3, B, flags, {x, target_wh, cls, loc, mask, box_out, refine_out, (const void *)pk, (const void *)wi}};
     StepRec rec = step_rec(c, refine_out);
     int rc = run_maybe_graph(c, key, s, rec, [&](hipStream_t st) {
@@ -3358,6 +3385,20 @@ int smk_trk_advance(void *state_dev, int B, const smk_trk_cfg *cfg, const double
     return 0;
 }
 
+int smk_trk_advance_hp(void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev, int slot,
+                       double *result_row_dev, int plan_next, void *stream) {
+    if (!state_dev || !box_dev || !hp_dev) return fail(SMK_E_ARG, "smk_trk_advance_hp: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_trk_advance_hp: batch %d", B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_trk_advance_hp: slot %d (0 or 1)", slot);
+    if ((uintptr_t)state_dev % 8 || (uintptr_t)hp_dev % 8)
+        return fail(SMK_E_ARG, "smk_trk_advance_hp: the state block and the hp table must be 8-byte aligned");
+    CHK(trk_cfg_check("smk_trk_advance_hp", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_step(st, (double *)(st + B), B, *cfg, box_dev, slot, result_row_dev, plan_next ? 3 : 1, stream, hp_dev))
+        return fail(SMK_E_HIP, "trk_step launch failed");
+    return 0;
+}
+
 int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg) {
     if (!state) return fail(SMK_E_ARG, "smk_host_trk_plan: null argument");
     if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_plan: batch %d", B);
@@ -3377,7 +3418,22 @@ int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const doubl
     smk_trk_stream *st = (smk_trk_stream *)state;
     double *twh = (double *)(st + B);
     for (int b = 0; b < B; ++b) {
-        trk_advance(st[b], *cfg, box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
+        trk_advance(st[b], *cfg, cfg->lr, box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
+        if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
+    }
+    return 0;
+}
+
+int smk_host_trk_advance_hp(void *state, int B, const smk_trk_cfg *cfg, const double *hp, const double *box, int slot,
+                            double *result_row, int plan_next) {
+    if (!state || !box || !hp) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: batch %d", B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: slot %d (0 or 1)", slot);
+    CHK(trk_cfg_check("smk_host_trk_advance_hp", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) {
+        trk_advance(st[b], *cfg, hp[SMK_HP_STRIDE * b + 2], box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
         if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
     }
     return 0;

@@ -459,7 +459,10 @@ constexpr int DEC_THREADS = 640;                 // >= S*S = 625 candidates of o
 __device__ __forceinline__ float exp_f32_cr(float x) { return (float)exp((double)x); }
 
 // one candidate per thread: `have` = this thread owns candidate rem of anchor shape a; c0, c1 = the two class logits,
-// l0..l3 = the four box regressions of that candidate (float32, as the network returned them)
+// l0..l3 = the four box regressions of that candidate (float32, as the network returned them).  PER_STREAM: penalty_k and
+// window_influence are the stream's own (p.hp, smk_set_stream_hp) -- two plain loads, uniform over the workgroup, made once in
+// front of the candidate's chain; every operation behind them is the same
+template <bool PER_STREAM>
 __device__ __forceinline__ void decode_tail(const DecodeParams &p, const int a, const int b, const int rem, const bool have,
                                             const float c0, const float c1, const float l0, const float l1, const float l2,
                                             const float l3) {
@@ -469,7 +472,9 @@ __device__ __forceinline__ void decode_tail(const DecodeParams &p, const int a, 
     const double tpad = __dmul_rn(__dadd_rn(tw, th), 0.5);
     const double tsz = __dsqrt_rn(__dmul_rn(__dadd_rn(tw, tpad), __dadd_rn(th, tpad)));
     const double tratio = __ddiv_rn(tw, th);
-    const double one_minus_wi = 1.0 - p.window_influence;
+    const double penalty_k = PER_STREAM ? p.hp[4 * b] : p.penalty_k;
+    const double window_influence = PER_STREAM ? p.hp[4 * b + 1] : p.window_influence;
+    const double one_minus_wi = 1.0 - window_influence;
     const int ori = -(p.S / 2) * p.stride;
     double best = -1e300;
     int best_i = 0x7fffffff;
@@ -493,9 +498,9 @@ __device__ __forceinline__ void decode_tail(const DecodeParams &p, const int a, 
         s_c = fmax(s_c, __ddiv_rn(1.0, s_c));
         double r_c = __ddiv_rn(tratio, (double)ratio);
         r_c = fmax(r_c, __ddiv_rn(1.0, r_c));
-        const double penalty = exp(__dmul_rn(-__dsub_rn(__dmul_rn(r_c, s_c), 1.0), p.penalty_k));
+        const double penalty = exp(__dmul_rn(-__dsub_rn(__dmul_rn(r_c, s_c), 1.0), penalty_k));
         const double pscore = __dmul_rn(penalty, (double)score);
-        best = __dadd_rn(__dmul_rn(pscore, one_minus_wi), __dmul_rn(p.window[rem], p.window_influence));
+        best = __dadd_rn(__dmul_rn(pscore, one_minus_wi), __dmul_rn(p.window[rem], window_influence));
         if (!(best == best)) best = -1e300;          // NaN candidates never win (np.argmax would pick the first NaN;
                                                      // the tool's exp overflow case is not a tracked state worth keeping)
         best_i = a * SS + rem;
@@ -593,6 +598,7 @@ __device__ __forceinline__ void decode_tail(const DecodeParams &p, const int a, 
 }
 
 
+template <bool PER_STREAM>
 __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(const DecodeParams p) {
     const int a = blockIdx.x, b = blockIdx.y, SS = p.S * p.S;
     const float *cls = p.cls + (size_t)b * 2 * p.A * SS;
@@ -605,7 +611,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(const DecodeParams 
         l0 = loc[(0 * p.A + a) * SS + rem]; l1 = loc[(1 * p.A + a) * SS + rem];
         l2 = loc[(2 * p.A + a) * SS + rem]; l3 = loc[(3 * p.A + a) * SS + rem];
     }
-    decode_tail(p, a, b, rem, have, c0, c1, l0, l1, l2, l3);
+    decode_tail<PER_STREAM>(p, a, b, rem, have, c0, c1, l0, l1, l2, l3);
 }
 
 // ---- result ring (smk_set_result_ring): what a tracker keeps per stream and frame for the end-of-batch gather --------------
@@ -720,7 +726,8 @@ int launch_ring_commit(const RingParams &p, void *stream) {
 
 int launch_decode(const DecodeParams &p, void *stream) {
     if (p.A > 8 || p.B < 1 || p.S * p.S > DEC_THREADS || !p.part_val || !p.part_idx || !p.part_box || !p.arrived) return -1;
-    hipLaunchKernelGGL(decode_kernel, dim3(p.A, p.B), dim3(DEC_THREADS), 0, (hipStream_t)stream, p);
+    if (p.hp) hipLaunchKernelGGL(decode_kernel<true>, dim3(p.A, p.B), dim3(DEC_THREADS), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(decode_kernel<false>, dim3(p.A, p.B), dim3(DEC_THREADS), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

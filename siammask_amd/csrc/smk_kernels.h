@@ -380,6 +380,9 @@ struct DecodeParams {
     int *ring_also;          // a second cursor advanced together with ring_cursor (the engine keeps a box-row cursor and a frames-committed cursor), or nullptr
     // pipelined frame step: the last stream's writer adds one to *mark (the semaphore the tail's gate waits on); mark_arrived counts streams
     unsigned *mark, *mark_arrived;
+    // per-stream hp (smk_set_stream_hp; appended: the fields above keep their kernarg offsets): [B][SMK_HP_STRIDE] f64, stream b takes
+    // penalty_k / window_influence from hp[4 b + {0, 1}] instead of the two values above; nullptr selects the kernel without it
+    const double *hp;
 };
 
 // result ring (misc_kernels.hip ring_commit_kernel): row (cursor % rows) <- this frame's box + fp16 Refine logits; cursor advances

@@ -72,11 +72,12 @@ SMK_TRK_HD void trk_plan(smk_trk_stream &s, const smk_trk_cfg &c, double *twh) {
 }
 
 // tracker.py:136-144,159-162 (tools/test.py:240-254,302-305) + preproc_back_box (:275-279), preproc.crop_back_map (:263-268),
-// preproc.invert_affine (cv::invertAffineTransform); box = cx cy w h score penalty pscore best_id of smk_step
-SMK_TRK_HD void trk_advance(smk_trk_stream &s, const smk_trk_cfg &c, const double *box, int slot, double *row) {
+// preproc.invert_affine (cv::invertAffineTransform); box = cx cy w h score penalty pscore best_id of smk_step; hp_lr: the hp 'lr'
+// of this stream (:241) -- c.lr for smk_trk_advance, the stream's row of the hp table for smk_trk_advance_hp (c.lr is not read here)
+SMK_TRK_HD void trk_advance(smk_trk_stream &s, const smk_trk_cfg &c, double hp_lr, const double *box, int slot, double *row) {
     const double pred0 = t_div(box[0], s.scale_x), pred1 = t_div(box[1], s.scale_x);
     const double pred2 = t_div(box[2], s.scale_x), pred3 = t_div(box[3], s.scale_x);
-    const double lr = t_mul(t_mul(box[5], box[4]), c.lr);
+    const double lr = t_mul(t_mul(box[5], box[4]), hp_lr);
     const double keep = t_sub(1.0, lr);
     const double pos0 = t_add(pred0, s.target_pos[0]), pos1 = t_add(pred1, s.target_pos[1]);
     const double sz0 = t_add(t_mul(s.target_sz[0], keep), t_mul(pred2, lr));
@@ -178,9 +179,10 @@ struct TrkSetArgs {                 // smk_trk_set: the host's values travel in 
     int im_w, im_h, n;
 };
 int launch_trk_set(smk_trk_stream *st, const TrkSetArgs &a, void *stream);
-// flags: bit 0 advance (box, slot, row), bit 1 plan
+// flags: bit 0 advance (box, slot, row), bit 1 plan; hp != nullptr (smk_trk_advance_hp): [B][SMK_HP_STRIDE] f64 on the device, stream
+// b advances with lr = hp[4 b + 2]
 int launch_trk_step(smk_trk_stream *st, double *twh, int B, const smk_trk_cfg &cfg, const double *box, int slot,
-                    double *row, int flags, void *stream);
+                    double *row, int flags, void *stream, const double *hp = nullptr);
 struct CropDevParams {
     const unsigned char *frames;
     long frame_stride;

@@ -20,12 +20,14 @@ __global__ __launch_bounds__(64) void trk_set_kernel(smk_trk_stream *st, const T
     st[b] = s;
 }
 
+// PER_STREAM (smk_trk_advance_hp): the lane's hp 'lr' comes from its row of the hp table instead of cfg.lr
+template <bool PER_STREAM>
 __global__ __launch_bounds__(64) void trk_step_kernel(smk_trk_stream *st, double *twh, int B, const smk_trk_cfg cfg,
-                                                      const double *box, int slot, double *row, int flags) {
+                                                      const double *box, int slot, double *row, int flags, const double *hp) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     smk_trk_stream &s = st[b];            // (in place: a private copy indexed by `slot` would live in scratch)
-    if (flags & 1) trk_advance(s, cfg, box + 8 * b, slot, row ? row + 16 * b : nullptr);
+    if (flags & 1) trk_advance(s, cfg, PER_STREAM ? hp[SMK_HP_STRIDE * b + 2] : cfg.lr, box + 8 * b, slot, row ? row + 16 * b : nullptr);
     double wh[2];
     if (flags & 2) {
         trk_plan(s, cfg, wh);
@@ -41,10 +43,11 @@ int launch_trk_set(smk_trk_stream *st, const TrkSetArgs &a, void *stream) {
 }
 
 int launch_trk_step(smk_trk_stream *st, double *twh, int B, const smk_trk_cfg &cfg, const double *box, int slot,
-                    double *row, int flags, void *stream) {
+                    double *row, int flags, void *stream, const double *hp) {
     if (B < 1) return -1;
-    hipLaunchKernelGGL(trk_step_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, st, twh, B, cfg, box, slot, row,
-                       flags);
+    const dim3 grid((B + 63) / 64), block(64);
+    if (hp) hipLaunchKernelGGL(trk_step_kernel<true>, grid, block, 0, (hipStream_t)stream, st, twh, B, cfg, box, slot, row, flags, hp);
+    else hipLaunchKernelGGL(trk_step_kernel<false>, grid, block, 0, (hipStream_t)stream, st, twh, B, cfg, box, slot, row, flags, hp);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

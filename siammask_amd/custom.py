@@ -108,6 +108,7 @@ class Custom(nn.Module):
         self._tracked = 0
         self._hp = None
         self._hp_dirty = True
+        self._stream_hp = None  # the per-stream hp table the context reads (set_stream_hp), kept alive here
         self.zf = None          # reference attribute (custom.py:174); opaque handle here
         self._replay = {}       # what a failed persistent-sequence launch needs to be re-run (see _guarded)
         self.seq_recovered = 0  # frames re-run on the per-layer kernels after a reported sequence failure
@@ -237,6 +238,7 @@ class Custom(nn.Module):
         self._ring = None
         self._replay = {}
         self._pipeline = False
+        self._stream_hp = None
 
     def __del__(self):
         try:
@@ -309,6 +311,9 @@ class Custom(nn.Module):
         sequence) behind the call: the counterpart of track_step(stage=False).  A sequence failure then surfaces at the next
         entry point, where the free-running tracker handles it (tracker.DeviceTracker._fr_rewind replays this call)."""
         B = template.shape[0]
+        if getattr(self, "_stream_hp", None) is not None and B > self._stream_hp.shape[0]:
+            raise ValueError("template(): batch %d, but the per-stream hp table set has %d rows (set_stream_hp(None) first)"
+                             % (B, self._stream_hp.shape[0]))
         self._ensure(template, B, grow=True)
         with torch.cuda.device(self._ctx_device):
             if template.dim() != 4 or tuple(template.shape[1:]) != (3, spec.TEMPLATE_SIZE, spec.TEMPLATE_SIZE):
@@ -390,6 +395,32 @@ class Custom(nn.Module):
         self._anchor_wh = np.asarray(wh, dtype=np.float32)
         self._hp_dirty = True
 
+    def set_stream_hp(self, table):
+        """Per-stream hp (smk_set_stream_hp): ``table`` is a contiguous float64 CUDA tensor [B,4] on the context's device -- penalty_k,
+        window_influence, lr, 0 per stream; decode() and track_step() then take stream b's penalty_k / window_influence from row
+        b instead of set_tracker_hp()'s values (the 'lr' column is smk_trk_advance_hp's, see tracker.DeviceTracker.set_hp).
+        None: back to the uniform values.  The tensor is kept alive here and read when a step RUNS: rewrite it in stream order
+        (table.copy_(...)) and the next step sees the new rows; no captured graph is dropped either way."""
+        if self._ctx is None:
+            raise RuntimeError("set_stream_hp(): run template() first")
+        if table is not None:
+            if (not isinstance(table, torch.Tensor) or not table.is_cuda or table.dtype != torch.float64 or table.dim() != 2 or
+                    table.shape[1] != _lib.HP_STRIDE or table.shape[0] < 1 or not table.is_contiguous()):
+                raise ValueError("set_stream_hp() takes a contiguous float64 CUDA tensor [B,%d] or None" % _lib.HP_STRIDE)
+            need = self.zf[1] if self.zf else self._max_batch
+            if table.shape[0] < need:
+                raise ValueError("the hp table has %d rows, the batch is %d" % (table.shape[0], need))
+            if table.device.index != self._ctx_device:
+                raise ValueError("the hp table is on %s, the model's context on cuda:%d" % (table.device, self._ctx_device))
+        with torch.cuda.device(self._ctx_device):
+            _lib.check(_lib.lib().smk_set_stream_hp(self._ctx, table.data_ptr() if table is not None else None))
+        self._stream_hp = table
+        self._fast = {}                      # (the next track_step checks the table's rows against its batch again)
+
+    def _hp_rows_cover(self, B):
+        if self._stream_hp is not None and self._stream_hp.shape[0] < B:
+            raise ValueError("batch %d, but the per-stream hp table has %d rows" % (B, self._stream_hp.shape[0]))
+
     def _push_hp(self):
         if getattr(self, "_hp", None) is None:
             self.set_tracker_hp()
@@ -408,6 +439,7 @@ class Custom(nn.Module):
         if cls.dtype != torch.float32 or loc.dtype != torch.float32:
             raise ValueError("decode() takes the float32 cls/loc the network returns")
         self._ensure(cls, B)
+        self._hp_rows_cover(B)
         self._push_hp()
         dev = cls.device
         with torch.cuda.device(self._ctx_device):
@@ -449,6 +481,7 @@ class Custom(nn.Module):
                     del self._replay["track"]
                 return out
         self._ensure(search, B)
+        self._hp_rows_cover(B)
         self._push_hp()
         flags = _lib.TRACK_BOX if self.variant == "rpn" else _lib.TRACK_MASK
         want_mask = self.variant != "rpn" and mask_head

@@ -242,10 +242,80 @@ class DeviceTracker(object):
         model.set_tracker_hp(self.p.penalty_k, self.p.window_influence)
         self.state = None
         self._fr = None               # free-running mode: a _Queue (device state, persistent buffers) and its pending _Chunk
+        # per-stream hp (set_hp): the float64 CUDA table [B,4] the kernels read and the host's copy of it; None: uniform (self.p)
+        self._hp_table = self._hp_host = None
+        self._drop_hp()               # (a table an earlier tracker left on the model is not this tracker's)
+
+    # -- per-stream hyper-parameters (smk_set_stream_hp / smk_trk_advance_hp) ---------------------
+    HP_KEYS = ("penalty_k", "window_influence", "lr")
+
+    def _drop_hp(self):
+        """back to uniform hp on both sides (init() / reserve() start without a table)"""
+        if getattr(self.model, "_stream_hp", None) is not None:
+            self.model.set_stream_hp(None)
+        self._hp_table = self._hp_host = None
+
+    def _hp_rows(self, hp):
+        """the checked request of set_hp() -> float64 [B,4] (penalty_k, window_influence, lr, 0)"""
+        B, keys = self._fr.B, self.HP_KEYS
+        rows = np.zeros((B, _lib.HP_STRIDE), dtype=np.float64)
+        rows[:, :3] = [float(getattr(self.p, k)) for k in keys]
+        if isinstance(hp, dict):
+            cols = hp
+        elif isinstance(hp, (list, tuple)) and all(isinstance(d, dict) for d in hp):
+            if len(hp) != B:
+                raise ValueError("set_hp(): %d dicts for %d streams" % (len(hp), B))
+            if set().union(*[set(d) for d in hp]) - set(keys):
+                raise ValueError("set_hp(): the keys are among %s" % (keys,))
+            cols = {k: [d.get(k, getattr(self.p, k)) for d in hp] for k in keys}
+        else:
+            raise ValueError("set_hp() takes a list of B dicts, a dict of length-B arrays, or None")
+        if set(cols) - set(keys):
+            raise ValueError("set_hp(): the keys are among %s" % (keys,))
+        for k, v in cols.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.shape != (B,):
+                raise ValueError("set_hp(): %r must hold %d values, one per stream" % (k, B))
+            rows[:, keys.index(k)] = v
+        if not np.isfinite(rows).all():
+            raise ValueError("set_hp(): the values must be finite")
+        return rows
+
+    def set_hp(self, hp):
+        """Give every stream its own penalty_k / window_influence / lr.  hp: a list of B dicts, or a dict of length-B arrays (keys
+        among HP_KEYS; a missing key takes the tracker's uniform value), or None: back to the uniform values.  After reserve() /
+        init() and only while no chunk is open (RuntimeError otherwise); non-finite values, unknown keys and a wrong length are
+        ValueErrors -- all before anything is launched.  One copy on the current stream into the [B,4] table the decode and the
+        advance kernels read; setting new values later rewrites the same table: no captured graph is dropped, nothing is
+        re-captured.  track(), enqueue() and run() then agree bit for bit, and stream b of a batch equals stream b of a uniform
+        batch at row b's values.  run() with VOS lifetimes refuses a table (the objects of one video share one configuration)."""
+        q = self._fr
+        if self.state is None or q is None:
+            raise RuntimeError("DeviceTracker.set_hp(): reserve() or init() first")
+        if self._chunk_open():
+            raise RuntimeError("DeviceTracker.set_hp(): a chunk is open -- collect() first")
+        if hp is None:
+            self._drop_hp()
+            return
+        rows = self._hp_rows(hp)
+        with torch.cuda.device(q.device):
+            if self._hp_table is None:
+                self._hp_table = torch.empty((q.B, _lib.HP_STRIDE), dtype=torch.float64, device=q.device)
+            self._hp_table.copy_(torch.from_numpy(rows))              # in stream order: behind the steps enqueued so far
+            if getattr(self.model, "_stream_hp", None) is not self._hp_table:
+                self.model.set_stream_hp(self._hp_table)
+        self._hp_host = rows
+
+    def get_hp(self):
+        """what set_hp() holds: None, or {'penalty_k': [B], 'window_influence': [B], 'lr': [B]} (copies; set_hp() takes it back)"""
+        if self._hp_host is None:
+            return None
+        return {k: self._hp_host[:, i].copy() for i, k in enumerate(self.HP_KEYS)}
 
     # -- siamese_init (tools/test.py:132-170) ---------------------------------------------------
     def init(self, frame, target_pos, target_sz):
         p = self.p
+        self._drop_hp()
         pos = np.asarray(target_pos, dtype=np.float64).reshape(-1, 2)
         sz = np.asarray(target_sz, dtype=np.float64).reshape(-1, 2)
         B = pos.shape[0]
@@ -283,6 +353,7 @@ class DeviceTracker(object):
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         p = self.p
+        self._drop_hp()
         with torch.cuda.device(device):
             z = torch.zeros((B, 3, p.exemplar_size, p.exemplar_size), dtype=torch.float32, device=device)
             self.model.template(z, sync=False)
@@ -466,6 +537,8 @@ class DeviceTracker(object):
         [B,12] float64.  Without it the returned state has exactly the keys and values it always had."""
         if self._mixed():
             raise ValueError("track(): streams with their own frame sizes are free-running only (enqueue / run)")
+        if getattr(self.model, "_stream_hp", None) is not self._hp_table:
+            raise RuntimeError("DeviceTracker.track(): the model's per-stream hp table is not this tracker's (set_hp() again)")
         p, st = self.p, self.state
         st.pop("polygon", None)                                       # (of an earlier step that asked for it)
         st.pop("polygon_found", None)
@@ -494,7 +567,7 @@ class DeviceTracker(object):
         new_pos, new_sz = pos.copy(), sz.copy()
         for b in range(B):
             pred = box[b, :4] / scale_x[b]                            # pred_in_crop (:240)
-            lr = box[b, 5] * box[b, 4] * p.lr                         # penalty * score * lr (:241)
+            lr = box[b, 5] * box[b, 4] * (p.lr if self._hp_host is None else self._hp_host[b, 2])      # penalty * score * lr (:241)
             new_pos[b] = [pred[0] + pos[b, 0], pred[1] + pos[b, 1]]
             new_sz[b] = [sz[b, 0] * (1 - lr) + pred[2] * lr, sz[b, 1] * (1 - lr) + pred[3] * lr]
         masks = None
@@ -669,6 +742,8 @@ class DeviceTracker(object):
             self._frame_list(frame, B, "enqueue(): one frame per stream", None if _unsized else sizes)
         else:
             self._check_frame(frame)
+        if getattr(self.model, "_stream_hp", None) is not self._hp_table:
+            raise RuntimeError("DeviceTracker.enqueue(): the model's per-stream hp table is not this tracker's (set_hp() again)")
         want_mask = want_mask and self.model.variant != "rpn"
         want_polygon = want_polygon and want_mask
         self._mask_out(mask_out, want_mask=want_mask)
@@ -704,8 +779,12 @@ class DeviceTracker(object):
                                                  self.p.instance_size, q.x.data_ptr(), sp))
             refine = self.refine and want_mask
             out = model.track_step(q.x, q.twh, refine=refine, mask_head=not self.refine, stage=False, out_set=slot if refine else 0)
-            _lib.check(L.smk_trk_advance(dev_ptr, B, ctypes.byref(q.cfg), out["box"].data_ptr(), slot,
-                                         q.rows[blk].data_ptr() + i * B * RESULT_ROW * 8, 1, sp))
+            row_ptr = q.rows[blk].data_ptr() + i * B * RESULT_ROW * 8
+            if self._hp_table is not None:                            # the stream's own lr (set_hp)
+                _lib.check(L.smk_trk_advance_hp(dev_ptr, B, ctypes.byref(q.cfg), self._hp_table.data_ptr(), out["box"].data_ptr(),
+                                                slot, row_ptr, 1, sp))
+            else:
+                _lib.check(L.smk_trk_advance(dev_ptr, B, ctypes.byref(q.cfg), out["box"].data_ptr(), slot, row_ptr, 1, sp))
             depth = int(getattr(model, "_pipeline", 0) or 0) if self.refine else 0     # (the model's, whoever set it)
             # pipelined: the Refine logits of the previous frame are complete behind this step's decode (smk_set_pipeline, depth
             # 1); a step without Refine has no gate, and depth 2 completes them one step later -- join explicitly

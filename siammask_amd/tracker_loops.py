@@ -18,6 +18,8 @@ def run_lifetimes(tr, frames, want_mask, want_polygon, mask_out, gt, vos):
     alive are unspecified, and so is everything of a stream whose object was absent from its init labels
     (res['events'] says which started)."""
     T, B, H, W = int(frames.shape[0]), tr._fr.B, tr._fr.H, tr._fr.W
+    if tr.get_hp() is not None:
+        raise ValueError("run() with lifetimes: the objects of one video share one configuration -- set_hp(None) first")
     if "start" not in vos or "end" not in vos:
         raise ValueError("vos['start'] and vos['end'] come together")
     if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T:
