@@ -314,7 +314,7 @@ def q16(a):
 class QuantOracle(Oracle):
     """The reference op sequence with the rounding points of the fp16 kernels:
       * BatchNorm folded into the conv in float64, folded weights rounded to fp16, folded
-        bias kept in fp32 (engine.cpp: fold/pack_rows/upload_packed);
+        bias kept in fp32 (engine.cpp fold, weight_pack.cpp pack_rows / upload_packed);
       * every activation that the kernels STORE (NHWC, fp16) is rounded to fp16 after the fused
         epilogue (bias, residual, ReLU); accumulation is exact here (fp32 on the device);
       * tensors handed back to the caller (cls, loc, mask, refine logits) are fp32: not rounded.

@@ -2,7 +2,7 @@
 // becomes persistent sequence launches (internal to libsiammask_hip.so).
 // Host code only and no HIP runtime call (the CU count and the grid are arguments): every launch path of the engine, its per-op
 // entry points and smk_host_plan_conv plan through plan_conv, and seq_flush, smk_op_conv_seq and smk_host_plan_seq through
-// plan_seq, so the CPU tests pin what the GPU runs.  engine.cpp's launch_plan is the only code that turns a plan into a launch.
+// plan_seq, so the CPU tests pin what the GPU runs.  conv_launch.cpp's launch_plan is the only code that turns a plan into a launch.
 #pragma once
 #include <string>
 #include <vector>

@@ -1,6 +1,19 @@
-// engine.cpp -- host side of libsiammask_hip.so: context, BN folding + weight packing,
-// activation arena, the launch sequences for template / track / refine, hipGraph capture,
-// and the extern "C" ABI declared in include/siammask_hip.h (product) and include/siammask_hip_test.h (tests, measurement).
+// engine.cpp -- the context (struct smk_ctx, private to this file) and everything that uses one: BN folding and the layer list
+// of the weight packer, the activation arena, the launch sequences for template / track / refine, hipGraph capture, the
+// pipelined frame step, the result ring, decode, the packed-weight cache, profiling, and their extern "C" entry points.
+//
+// The host side of libsiammask_hip.so by file (the ABI is include/siammask_hip.h, product, and include/siammask_hip_test.h,
+// tests and measurement):
+//   engine.cpp         every entry point that takes a context; smk_version, smk_last_error; smk_host_arena_elems beside the ARENA
+//                      table; fail and the thread-local error string; seq_grid_for, seq_print_clk, g_seq_last, zero_page
+//   engine_internal.h  what the files below share with this one: fail / CHK / HIPCHK, rup, esize, the context-free helpers
+//   weight_pack.cpp    host packing and upload of one convolution (pack_rows, upload_*, the split-operand and stem packs)
+//   conv_launch.cpp    ConvEnv, conv_params, conv_work, launch_plan
+//   conv_plan.cpp      which kernel and tile a convolution gets, the marks on a sequence list (conv_plan.h; no HIP call)
+//   tune.cpp           smk_tune / smk_tune_get and the KNOBS table
+//   op_api.cpp         smk_op_*, smk_bench_conv, smk_host_conv2d_ex, smk_host_plan_conv, smk_host_plan_seq
+//   stream_api.cpp     the stateless product entries: crop / paste / labels, smk_mask_rbox, smk_trk_*, smk_host_trk_*,
+//                      smk_vos_score*, stream start, smk_vot_overlap*, the *_v entries
 //
 // The network topology restated here (layer names, geometry) follows
 //   experiments/siammask_sharp/resnet.py:59-103,151-227   modified ResNet-50
@@ -24,19 +37,17 @@
 
 #include "../../include/siammask_hip.h"
 #include "../../include/siammask_hip_test.h"
-#include "conv_plan.h"
-#include "smk_kernels.h"
-#include "tracker_state.h"
-#include "vot_overlap.h"
+#include "engine_internal.h"
 
 using namespace smk;
 
 // ---------------------------------------------------------------------------------------------
-// errors
+// errors: the one string smk_last_error reads (engine_internal.h declares fail for every translation unit)
 // ---------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 
-static int fail(int code, const char *fmt, ...) {
+namespace smk {
+int fail(int code, const char *fmt, ...) {
     char buf[1024];
     va_list ap;
     va_start(ap, fmt);
@@ -46,25 +57,8 @@ static int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(SMK_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
-                        __FILE__, __LINE__);                                               \
-    } while (0)
-
-#define CHK(expr)                     \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != 0) return rc_;     \
-    } while (0)
-
-static inline int rup(int x, int a) { return (x + a - 1) / a * a; }
-
 // 8 KB of zeros per device: every padded tap / out-of-range row / K tail of the conv kernel's
 // LDS-DMA gather reads from here, which keeps the loads branch-free.
-namespace smk {
 const void *zero_page() {
     static void *pages[64] = {nullptr};
     int dev = 0;
@@ -94,119 +88,7 @@ struct ConvPart {
     std::string bias;   // "<name>.bias" or ""
 };
 
-constexpr size_t KS_PART_FLOATS = 8u << 20;      // 32 MB: e.g. 256 tiles x 4 parts x 64x128
-constexpr int KS_CNT = 8192;
 constexpr size_t DEC_SCRATCH_PER_STREAM = 8 * 8 + 64 * 8 + 8 * 4 + 4;     // decode_kernel's cross-workgroup scratch
-
-static size_t esize(int dtype) { return dtype == DT_F32 ? 4 : 2; }
-
-// host-side packing of ONE weight tensor [Cout][Cin][k][k] (already scaled) into rows of a
-// [rows][Kpad] matrix with K ordered (ky, kx, cin_padded)
-static void pack_rows(std::vector<float> &dst, int row0, int Kpad, const float *w, const double *scale,
-                      int Cout, int Cin, int k, int Ci) {
-    for (int n = 0; n < Cout; ++n)
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int ky = 0; ky < k; ++ky)
-                for (int kx = 0; kx < k; ++kx) {
-                    const double v = (double)w[(((size_t)n * Cin + ci) * k + ky) * k + kx] * scale[n];
-                    dst[(size_t)(row0 + n) * Kpad + (size_t)(ky * k + kx) * Ci + ci] = (float)v;
-                }
-}
-
-// Which derived copies of a pack exist (the packer makes them, smk_host_plan_conv fakes them from the same rules)
-static bool has_frag_pack(const PackedConv &pc, int dtype) { return dtype == DT_F16 && pc.rows % 32 == 0 && pc.Kpad % 16 == 0; }
-static bool has_frag16_pack(const PackedConv &pc, int dtype) {
-    return has_frag_pack(pc, dtype) && pc.rows <= 256 && pc.Kpad <= 640 && pc.Kpad % 32 == 0 && pc.groups == 1;
-}
-static bool has_halo_pack(const PackedConv &pc, int dtype) { return pc.k == 3 && pc.kw == 0 && pc.Ci % (dtype == DT_F16 ? 64 : 32) == 0; }
-static bool has_frag_halo_pack(const PackedConv &pc, int dtype) { return has_halo_pack(pc, dtype) && has_frag_pack(pc, dtype) && pc.Kpad == 9 * pc.Ci; }
-
-// fragment-order copy of an f16 pack for conv_wreg_kernel: one contiguous KB per (32 rows, 16 k) MFMA operand --
-// [rows/32][Kpad/16][lane 0..63][8 halves] with lane = (n % 32) + 32 * ((k % 16) / 8), element e = k % 8
-static int upload_frag_pack(PackedConv &pc, const std::vector<float> &rows_f32, int dtype) {
-    if (!has_frag_pack(pc, dtype)) return 0;
-    const int KS16 = pc.Kpad / 16;
-    std::vector<_Float16> h((size_t)pc.rows * pc.Kpad);
-    for (int n = 0; n < pc.rows; ++n) {
-        const float *src = rows_f32.data() + (size_t)n * pc.Kpad;
-        const size_t blk = (size_t)(n / 32) * KS16;
-        for (int k = 0; k < pc.Kpad; ++k) {
-            const int lane = (n % 32) + 32 * ((k % 16) / 8);
-            h[((blk + k / 16) * 64 + lane) * 8 + k % 8] = (_Float16)src[k];
-        }
-    }
-    HIPCHK(hipMalloc(&pc.w_frag, h.size() * 2));
-    HIPCHK(hipMemcpy(pc.w_frag, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    if (has_frag16_pack(pc, dtype)) {
-        // [rows/16][Kpad/32][lane 0..63][8 halves] with lane = (n % 16) + 16 * ((k % 32) / 8), element e = k % 8
-        const int KS32 = pc.Kpad / 32;
-        std::vector<_Float16> g((size_t)pc.rows * pc.Kpad);
-        for (int n = 0; n < pc.rows; ++n) {
-            const float *src = rows_f32.data() + (size_t)n * pc.Kpad;
-            const size_t blk = (size_t)(n / 16) * KS32;
-            for (int k = 0; k < pc.Kpad; ++k) {
-                const int lane = (n % 16) + 16 * ((k % 32) / 8);
-                g[((blk + k / 32) * 64 + lane) * 8 + k % 8] = (_Float16)src[k];
-            }
-        }
-        HIPCHK(hipMalloc(&pc.w_frag16, g.size() * 2));
-        HIPCHK(hipMemcpy(pc.w_frag16, g.data(), g.size() * 2, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-
-static int upload_packed(PackedConv &pc, const std::vector<float> &rows_f32, const std::vector<float> &bias,
-                         int dtype, const std::vector<float> *frag_rows = nullptr) {
-    const size_t n = rows_f32.size();
-    HIPCHK(hipMalloc(&pc.w, n * esize(dtype)));
-    if (dtype == DT_F16) {
-        std::vector<_Float16> h(n);
-        for (size_t i = 0; i < n; ++i) h[i] = (_Float16)rows_f32[i];
-        HIPCHK(hipMemcpy(pc.w, h.data(), n * 2, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(hipMemcpy(pc.w, rows_f32.data(), n * 4, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc((void **)&pc.bias, bias.size() * 4));
-    HIPCHK(hipMemcpy(pc.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    return upload_frag_pack(pc, frag_rows ? *frag_rows : rows_f32, dtype);       // derived copy for conv_wreg_kernel (f16 only)
-}
-
-// chunk-major copy of a 3x3 pack: k = (tap*Ci + c)  ->  k' = ((c / CH)*9 + tap)*CH + c % CH
-static int upload_halo_pack(PackedConv &pc, const std::vector<float> &rows_f32, int dtype) {
-    if (!has_halo_pack(pc, dtype)) return 0;
-    const int CH = dtype == DT_F16 ? 64 : 32;
-    std::vector<float> hp(rows_f32.size(), 0.f);
-    for (int n = 0; n < pc.rows; ++n)
-        for (int tap = 0; tap < 9; ++tap)
-            for (int ci = 0; ci < pc.Ci; ++ci)
-                hp[(size_t)n * pc.Kpad + (size_t)((ci / CH) * 9 + tap) * CH + ci % CH] =
-                    rows_f32[(size_t)n * pc.Kpad + (size_t)tap * pc.Ci + ci];
-    const size_t cnt = hp.size();
-    if (has_frag_halo_pack(pc, dtype)) {
-        // the same matrix in fragment order (upload_frag_pack's layout) for the patch-sharing tile of the sequences
-        const int KS16 = pc.Kpad / 16;
-        std::vector<_Float16> h(cnt);
-        for (int n = 0; n < pc.rows; ++n) {
-            const float *src = hp.data() + (size_t)n * pc.Kpad;
-            const size_t blk = (size_t)(n / 32) * KS16;
-            for (int k = 0; k < pc.Kpad; ++k) {
-                const int lane = (n % 32) + 32 * ((k % 16) / 8);
-                h[((blk + k / 16) * 64 + lane) * 8 + k % 8] = (_Float16)src[k];
-            }
-        }
-        HIPCHK(hipMalloc(&pc.w_frag_halo, cnt * 2));
-        HIPCHK(hipMemcpy(pc.w_frag_halo, h.data(), cnt * 2, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMalloc(&pc.w_halo, cnt * esize(dtype)));
-    if (dtype == DT_F16) {
-        std::vector<_Float16> h(cnt);
-        for (size_t i = 0; i < cnt; ++i) h[i] = (_Float16)hp[i];
-        HIPCHK(hipMemcpy(pc.w_halo, h.data(), cnt * 2, hipMemcpyHostToDevice));
-    } else {
-        HIPCHK(hipMemcpy(pc.w_halo, hp.data(), cnt * 4, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------
 // arena: ONE row per activation tensor -- what build_arena sizes, what act() hands to the launches, what smk_debug_read names
@@ -303,7 +185,6 @@ static int arena_elems(int dtype, int variant, int depth, uint64_t *total) {
 // ---------------------------------------------------------------------------------------------
 
 typedef std::tuple<int, int, int, std::vector<const void *>> GraphKey;
-constexpr long MI355X_CUS = 256;     // what host-only planning (smk_host_plan_conv) plans for
 
 struct smk_ctx {
     int device = 0, dtype = DT_F32, variant = SMK_VARIANT_SHARP, maxB = 1;
@@ -466,68 +347,7 @@ static int fold(const smk_ctx *c, const ConvPart &part, int Cout, std::vector<do
     return 0;
 }
 
-// pack `parts` either N-fused (one group, rows concatenated) or as separate groups
-// x3 (DT_F16X3 contexts, the layers of the track path's trunk): per tap the Ci0 = rup(Cin, 8) channels three times -- [w_hi | w_lo | w_hi]
-// with w_hi = fp16(w), w_lo = fp16(w - w_hi) -- against activations stored as [hi | hi | lo] planes
-// Every row is first scaled by a power of two that takes its largest |w| into [2^13, 2^14): w_lo = fp16(s w - w_hi) is then a NORMAL fp16
-// number for every weight within 2^-16 of the row's maximum, i.e. the pair carries 22 bits where the unscaled, BN-folded weights (1e-2 .. 1e-3)
-// leave w_lo in the subnormals (3e-6 .. 3e-5 relative).  oscale[n] = 1 / s_n (exact); the epilogue multiplies the accumulator by it.
-static void split_rows_x3(std::vector<float> &rows, int nrows, int Kpad1, int Kpad3, int taps, int Ci0, std::vector<float> &oscale) {
-    std::vector<float> out((size_t)nrows * Kpad3, 0.f);
-    oscale.assign(nrows, 1.f);
-    for (int n = 0; n < nrows; ++n) {
-        float mx = 0.f;
-        for (int k = 0; k < taps * Ci0; ++k) mx = std::max(mx, std::fabs(rows[(size_t)n * Kpad1 + k]));
-        int e = 0;
-        if (mx > 0.f) {
-            e = 13 - (int)std::floor(std::log2(mx));                 // 2^e mx in [2^13, 2^14)
-            e = std::max(-8, std::min(e, 40));
-        }
-        const float sc = std::ldexp(1.f, e);
-        oscale[n] = std::ldexp(1.f, -e);
-        for (int t = 0; t < taps; ++t)
-            for (int ci = 0; ci < Ci0; ++ci) {
-                const float v = rows[(size_t)n * Kpad1 + (size_t)t * Ci0 + ci] * sc;
-                const float hi = (float)(_Float16)v, lo = (float)(_Float16)(v - hi);
-                float *d = out.data() + (size_t)n * Kpad3 + (size_t)t * 3 * Ci0 + ci;
-                d[0] = hi; d[Ci0] = lo; d[2 * Ci0] = hi;
-            }
-    }
-    rows.swap(out);
-}
-// FUSED order of a split pack for conv_wreg_kernel (wreg_tile.inc x3ct): per tap the 3 CT tiles of 64 weights [w_hi_0 .. | w_lo_0 .. | w_hi_0 ..] become
-// (w_hi_0, w_lo_0, w_hi_1, w_lo_1, .., w_hi_{CT-1}, w_lo_{CT-1}, then w_hi_0 .. w_hi_{CT-1} for the lo plane): the two products of a hi activation tile are neighbours
-// in the weight stream.  Needs Ci0 % 64 == 0.  Sets pc.x3_ct / pc.x3_nreal; returns false (and leaves `out` alone) when the pack cannot be fused.
-static bool fuse_rows_x3(const std::vector<float> &rows, PackedConv &pc, int taps, int Ci0, std::vector<float> &out) {
-    if (Ci0 < 64 || Ci0 % 64) return false;
-    const int CT = Ci0 / 64, Kp = pc.Kpad;
-    out.assign(rows.size(), 0.f);
-    for (int n = 0; n < pc.rows; ++n) {
-        const float *s = rows.data() + (size_t)n * Kp;
-        float *d = out.data() + (size_t)n * Kp;
-        for (int t = 0; t < taps; ++t) {
-            const float *st = s + (size_t)t * 3 * Ci0;
-            float *dt = d + (size_t)t * 3 * Ci0;
-            for (int j = 0; j < CT; ++j) {
-                memcpy(dt + (size_t)(2 * j) * 64, st + (size_t)j * 64, 64 * sizeof(float));                       // w_hi_j   (x hi_j)
-                memcpy(dt + (size_t)(2 * j + 1) * 64, st + (size_t)Ci0 + (size_t)j * 64, 64 * sizeof(float));     // w_lo_j   (x hi_j again)
-                memcpy(dt + (size_t)(2 * CT + j) * 64, st + (size_t)2 * Ci0 + (size_t)j * 64, 64 * sizeof(float)); // w_hi_j   (x lo_j)
-            }
-        }
-    }
-    pc.x3_ct = CT;
-    pc.x3_nreal = 0;
-    for (int w = 0; w < Kp / 64; ++w) {
-        const int r = w % (3 * CT);
-        if (!(r < 2 * CT && (r & 1))) ++pc.x3_nreal;       // (the same cyclic rule the consumers apply, K padding included)
-    }
-    return true;
-}
-static int upload_oscale(PackedConv &pc, const std::vector<float> &oscale) {
-    HIPCHK(hipMalloc((void **)&pc.oscale, oscale.size() * 4));
-    HIPCHK(hipMemcpy(pc.oscale, oscale.data(), oscale.size() * 4, hipMemcpyHostToDevice));
-    return 0;
-}
+// pack `parts` either N-fused (one group, rows concatenated) or as separate groups; x3: as split operands (weight_pack.cpp split_rows_x3)
 static int pack_conv(smk_ctx *c, const std::string &id, const std::vector<ConvPart> &parts, int Cin, int Cout,
                      int k, bool grouped, bool x3 = false) {
     PackedConv pc;
@@ -609,30 +429,7 @@ static int pack_deconv(smk_ctx *c) {
     return 0;
 }
 
-// features.conv1 (7x7 s2 p0, 3 -> 64) on the pixel-pair input layout [H][ceil(W/2)][2 px x 4 ch]:
-// a 7 x 4 convolution over pixel pairs (vertical stride 2, horizontal stride 1 pair), K = 7*4*8 = 224
-// instead of 7*7*8 = 392 with the channel-padded layout; the 8th pixel and the 4th channel have zero weights
-static void stem_pair_rows(std::vector<float> &rows, std::vector<float> &bias, int Kpad, const float *w, const double *scale,
-                           const double *shift) {
-    for (int n = 0; n < 64; ++n) {
-        for (int ky = 0; ky < 7; ++ky)
-            for (int kx = 0; kx < 7; ++kx)
-                for (int ci = 0; ci < 3; ++ci) {
-                    const double v = (double)w[(((size_t)n * 3 + ci) * 7 + ky) * 7 + kx] * scale[n];
-                    rows[(size_t)n * Kpad + (size_t)(ky * 4 + kx / 2) * 8 + (kx & 1) * 4 + ci] = (float)v;
-                }
-        bias[n] = (float)shift[n];
-    }
-}
-
-// the stem's pack (without its weights): geometry of the pixel-pair matrix
-static PackedConv stem_pack_geom() {
-    PackedConv pc;
-    pc.Ci = 8; pc.k = 7; pc.kw = 4; pc.K = 7 * 4 * 8; pc.Kpad = rup(pc.K, KPAD_ALIGN); pc.alg_k = 3 * 7 * 7;
-    pc.groups = 1; pc.N = 64; pc.group_rows = pc.rows = rup(64, NPAD_ALIGN);
-    return pc;
-}
-
+// features.conv1 on the pixel-pair input layout (weight_pack.cpp stem_pair_rows)
 static int pack_stem(smk_ctx *c) {
     const std::string f = "features.features.";
     const HostTensor *w = find_w(c, f + "conv1.weight");
@@ -781,121 +578,18 @@ static int branch_off(const smk_ctx *c, int g) { return g * 256 * (c->dtype == D
 // ---------------------------------------------------------------------------------------------
 // launch helpers
 // ---------------------------------------------------------------------------------------------
-// what conv_params takes from its surroundings: a context's (conv_env) or a context-free entry point's own
-struct ConvEnv {
-    int dtype = DT_F32, device = 0;      // device < 0: host-side walk (CPU tests)
-    float *ks_part = nullptr;            // split-K scratch (KS_PART_FLOATS) and arrival counters (KS_CNT), or none
-    unsigned *ks_cnt = nullptr;
-    int wave_prio = 0;
-};
+// what conv_params (conv_launch.cpp) takes from a context
 static ConvEnv conv_env(const smk_ctx *c) { return {c->dtype, c->device, c->ks_part, c->ks_cnt, c->wave_prio_now}; }
-
-static int conv_params(const ConvEnv &env, const PackedConv &pc, const Act &in, const Act *out, int B,
-                       const ConvOpt &o, ConvParams &p) {
-    memset(&p, 0, sizeof(p));
-    p.in = in.p;
-    p.wgt = pc.w;
-    p.wgt_frag = pc.w_frag;
-    p.wgt_frag_halo = pc.w_frag_halo;
-    p.bias = pc.bias;
-    p.oscale = pc.oscale;
-    p.pos = o.pos;
-    p.B = B;
-    p.Hs = in.H; p.Ws = in.W; p.Cs = in.C;
-    p.cin_off = o.cin_off;
-    p.Ci = pc.Ci;
-    p.x3_ct = pc.x3_ct; p.x3_nreal = pc.x3_nreal;
-    p.x3_in = pc.x3 ? pc.Ci / 3 : 0;      // split tensor in: the operand's [hi | hi | lo] channels of a tap are gathered from the stored [hi | lo] planes
-    p.Hl = (o.win || o.ups) ? o.Hl : in.H;
-    p.Wl = (o.win || o.ups) ? o.Wl : in.W;
-    p.org_y = o.org_y; p.org_x = o.org_x;
-    p.pos_mul = o.pos_mul; p.pos_add = o.pos_add;
-    p.ups = o.ups ? 1 : 0;
-    p.kh = pc.k;
-    p.kw = pc.kw ? pc.kw : pc.k;
-    p.stride = o.stride; p.pad = o.pad; p.dil = o.dil;
-    p.stride_x = o.stride_x ? o.stride_x : o.stride;
-    p.Ho = (p.Hl + 2 * o.pad - o.dil * (p.kh - 1) - 1) / p.stride + 1;
-    p.Wo = (p.Wl + 2 * o.pad - o.dil * (p.kw - 1) - 1) / p.stride_x + 1;
-    p.K = pc.K; p.Kpad = pc.Kpad;
-    p.N = o.n_override ? o.n_override : pc.N;
-    p.M = B * p.Ho * p.Wo;
-    p.relu = o.relu;
-    p.groups = o.groups;
-    if (o.groups > 1) {
-        p.g_cin_off = pc.x3 ? pc.Ci / 3 * X3_PLANES : pc.Ci;      // branches sit side by side in the channel dimension (split tensors: a branch's
-        p.g_wgt_off = pc.group_rows;                               //  two stored planes side by side; pc.Ci is the OPERAND's channel count, 3 per value)
-        p.g_cout_off = pc.group_rows * (pc.x3 ? X3_PLANES : 1);
-    }
-    if (o.nchw_out) {
-        p.out = o.nchw_out;
-        p.out_mode = OUT_NCHW_F32;
-        p.Nst = rup(p.N, 4);
-    } else {
-        if (!out) return fail(SMK_E_ARG, "conv without output");
-        if (out->H != p.Ho || out->W != p.Wo)
-            return fail(SMK_E_ARG, "internal: conv output %dx%d != buffer %dx%d", p.Ho, p.Wo, out->H, out->W);
-        p.out = out->p;
-        p.out_mode = OUT_NHWC;
-        p.Cos = out->C;
-        p.cout_off = o.cout_off;
-        p.Nst = rup(p.N, 8);
-        if (pc.x3) {
-            // split output: whole-tensor planes (stride = half of the buffer's channels), per-branch planes for a grouped launch
-            p.x3_out = o.groups > 1 ? pc.group_rows : out->C / X3_PLANES;
-            if (out->C % X3_PLANES || o.cout_off + (o.groups - 1) * X3_PLANES * pc.group_rows + p.x3_out + p.Nst > out->C)
-                return fail(SMK_E_ARG, "internal: split conv output channels exceed buffer");
-        } else if (o.cout_off + (o.groups - 1) * pc.group_rows + p.Nst > out->C)
-            return fail(SMK_E_ARG, "internal: conv output channels exceed buffer");
-    }
-    p.xcd_mode = g_tune.xcd_mode;
-    // NCHW f32 epilogue: a tile writes 128 consecutive positions of each channel plane (512 B at a 4-byte aligned, not
-    // line aligned, offset), so the first / last line of every segment is completed by the NEIGHBOURING M tile.  tn-major
-    // order runs the M neighbours of one channel block back to back on one XCD: the partial lines meet in that L2
-    // before they are evicted (tm-major: the neighbour comes tilesN tiles later -> read-modify-write at the memory side)
-    // (measured, profiles/r02_tail_ab.txt: B=64 -1.3 % on the step, B=8 / B=1 within noise -> large launches only)
-    if (o.nchw_out && g_tune.nchw_tn_major && p.xcd_mode == 1 && p.M >= 20000 && (double)p.M * p.N * 4 >= 4.0e6) p.xcd_mode = 2;
-    p.prio = g_tune.prio;
-    p.wave_prio = env.wave_prio;
-    {
-        const double ib = (double)B * in.H * in.W * in.C * esize(env.dtype), wb = (double)pc.rows * pc.Kpad * esize(env.dtype);
-        p.buf_lds = (g_tune.buf_lds && ib < 2.0e9 && wb < 2.0e9) ? 1 : 0;
-        p.a_stage = g_tune.a_stage;
-        p.res_nt = g_tune.res_nt;
-        p.in_bytes = (unsigned)(ib < 4.0e9 ? ib : 0);
-        p.w_bytes = (unsigned)(wb < 4.0e9 ? wb : 0);
-    }
-    p.nt_store = (g_tune.nt_store && o.nchw_out && (double)p.M * p.N * 4 >= 4.0e6) ? 1 : 0;
-    p.ci_shift = -1;
-    for (int sh = 0; sh < 16; ++sh)
-        if ((1 << sh) == p.Ci) p.ci_shift = sh;
-    p.kw_magic = 65536 / p.kw + 1;                        // exact for tap < 4096 and kw <= 15
-    p.zero = env.device >= 0 ? zero_page() : nullptr;
-    if (env.device >= 0 && !p.zero) return fail(SMK_E_HIP, "could not allocate the zero page");
-    if (o.res) {
-        p.res = o.res->p;
-        p.res_Cs = o.res->C;
-        p.res_coff = o.res_coff;
-        p.res_mode = o.res_mode;
-        if (pc.x3) p.x3_res = o.res->C / X3_PLANES;
-    }
-    p.ksplit = 1;
-    p.ks_part = env.ks_part;
-    p.ks_cnt = env.ks_cnt;
-    p.ks_part_cap = env.ks_part ? KS_PART_FLOATS : 0;
-    p.ks_cnt_cap = env.ks_cnt ? KS_CNT : 0;
-    return 0;
-}
 
 // ---- persistent per-XCD convolution sequences (conv_seq_kernel) ---------------------------------------------------
 // While c->seq_on, run_conv / run_conv_jobs RECORD eligible convolutions instead of launching them; seq_flush plans the whole
 // recorded list (plan_seq, conv_plan.cpp) and turns it into persistent launches of <= SEQ_MAX layers.  Everything else
 // (non-eligible convolutions, other kernels) flushes first, so program order is preserved.
-static SeqPlanStats g_seq_last;   // marks of the launch issued last (smk_tune_get "seq_fused_last" / "seq_fused3_last" / "seq_yres_last", diagnostics)
+namespace smk {
+SeqPlanStats g_seq_last;   // written by seq_flush and smk_op_conv_seq (op_api.cpp), read by smk_tune_get (tune.cpp): engine_internal.h
 
 // SMK_SEQ_CLK (measurement aid, eager runs only): print what (team 0, slot 0) stamped
-static void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, const unsigned long long *h,
-                          const unsigned long long *h2) {
+void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, const unsigned long long *h, const unsigned long long *h2) {
     fprintf(stderr, "[seq clk] %s total %.2f us\n", idn, (h[2 * a.n] - h[0]) / 100.0);
     for (int i = 0; i < a.n; ++i)
         fprintf(stderr, "[seq clk]   %-10s cfg %d sync %d kstag %d  tiles %.2f us  arrive %.2f us\n", r[i].id.c_str(), a.L[i].cfg,
@@ -951,6 +645,7 @@ static void seq_print_clk(const SeqArgs &a, const SeqRec *r, const char *idn, co
                 us > 0 ? (double)(t[9] - t[8]) / us : 0.0);
     }
 }
+}  // namespace smk
 
 static int seq_flush(smk_ctx *c, StepRec &rec, int B, hipStream_t s) {
     const size_t n = c->seq.rec.size();
@@ -1057,39 +752,6 @@ static bool seq_wanted(const smk_ctx *c, int B) {
     if (B >= g_tune.seq_min_batch && B <= g_tune.seq_max_batch) return true;
     if (B == g_tune.seq_extra_batch) return true;
     return B % 8 == 0 && B <= g_tune.seq_mult_max;
-}
-
-// algorithmic work of one convolution: 2*M*N*K_real flops; bytes = activations read once + weights + output written once
-static void conv_work(const PackedConv &pc, const ConvParams &p, int B, int dtype, double &flop, double &bytes) {
-    const int ng = p.groups > 0 ? p.groups : 1;
-    const double kreal = pc.alg_k ? (double)pc.alg_k : (double)p.kh * p.kw * p.Ci;
-    const size_t es = esize(kdtype(dtype));
-    flop += 2.0 * p.M * (double)p.N * kreal * ng;
-    bytes += (double)B * (p.ups ? p.Hs * p.Ws : (double)p.Hl * p.Wl) * p.Ci * es * ng + (double)p.M * p.N * ng * (p.out_mode == OUT_NCHW_F32 ? 4 : es) +
-             (double)p.N * kreal * es * ng + (p.res ? (double)p.M * p.N * es : 0.0);
-}
-
-// The one place a plan becomes a launch: cb holds the planned problem (CK_PP, CK_HALO, CK_NAIVE: cb.p[0]) or the members of a
-// merged one; w_halo is the chunk-major pack of the halo kernel.  A launcher that turns down the geometry it was planned for is
-// an internal error, not a fallback.
-static int launch_plan(const ConvPlan &pl, ConvBatch &cb, const void *w_halo, int dtype, hipStream_t s, const char *what) {
-    int rc;
-    switch (pl.kind) {
-    case CK_PP: rc = launch_conv_pp(cb.p[0], s); break;
-    case CK_WREG: rc = launch_conv_wreg_batch(cb, WREG_TILE[pl.wreg][0], WREG_TILE[pl.wreg][1], pl.stages, s); break;
-    case CK_HALO: {
-        ConvParams ph = cb.p[0];
-        ph.wgt = w_halo;
-        rc = launch_conv_halo(ph, dtype, pl.halo_bm, s);
-        break;
-    }
-    case CK_NAIVE: rc = launch_conv_naive(cb.p[0], dtype, s); break;
-    case CK_MHEAD: rc = launch_mask_head(cb.p[0], s); break;
-    default: rc = launch_conv_mfma_batch(cb, dtype, pl.tile, s);
-    }
-    if (rc == 1) return fail(SMK_E_STATE, "internal: %s is not eligible for the kernel planned for it", what);
-    if (rc) return fail(SMK_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(hipGetLastError()));
-    return 0;
 }
 
 // rec: the step record of a caller that may be recording a sequence (run_backbone); a flush fills it
@@ -1762,7 +1424,7 @@ static int pipe_join(smk_ctx *c, hipStream_t s, bool clear) {
 // deals consecutive blocks round-robin over the XCDs -- observed, not a HIP guarantee) and that one workgroup of it
 // (139 KB of LDS, 512 threads) is resident per CU: checked once per context with a census launch and the runtime's
 // occupancy answer for THAT kernel; if either fails the per-launch kernels are used instead.  Returns the grid or 0.
-static int seq_grid_for(int ncu) {
+int smk::seq_grid_for(int ncu) {
     if (ncu < 8 || ncu % 8 != 0 || ncu > 1024) return 0;
     std::vector<int> x(ncu, -1);
     const int crc = xcc_census(ncu, x.data());
@@ -2107,125 +1769,6 @@ int smk_refine(smk_ctx *c, const int32_t *pos, int on_device, int B, float *out,
     GraphKey key{2, B, c->parity_now, {out}};
     StepRec rec;
     return run_maybe_graph(c, key, s, rec, [&](hipStream_t st) { return seq_refine(c, rec, B, out, st); });
-}
-
-// ---- smk_tune / smk_tune_get: one table --------------------------------------------------------------------------
-// accept: the values smk_tune takes -- "*" any, else terms "a", "a..b" or ">=a" joined by '|'; nullptr: a read-only diagnostic.
-// conv: what is stored -- KNOB_RAW the value, KNOB_BOOL value != 0, > 0 value & conv.  product: a knob whose other values are
-// measured losers that only a `make MEASURE=1` library carries -- the values a product library takes (its default among them).
-enum { KNOB_RAW = 0, KNOB_BOOL = -1 };
-struct Knob { const char *name; int *slot; const char *accept; int conv; const char *product; };
-#ifdef SMK_MEASURE
-static int g_measure_build = 1;                  // smk_tune_get "measure_build": the K-loop ablation kernels are present
-#else
-static int g_measure_build = 0;
-#endif
-static const Knob KNOBS[] = {
-    {"xcd_mode", &g_tune.xcd_mode, "*", KNOB_RAW, nullptr},
-    {"force_tile", &g_tune.force_tile, "0..5", KNOB_RAW, nullptr},
-    {"min_blocks_x16", &g_tune.min_blocks_x16, "*", KNOB_RAW, nullptr},
-    {"stages", &g_tune.stages, "0|2..4", KNOB_RAW, nullptr},
-    {"kt", &g_tune.kt, "0|128|256", KNOB_RAW, nullptr},
-    {"prio", &g_tune.prio, "-1..3", KNOB_RAW, nullptr},
-    {"nt_store", &g_tune.nt_store, "*", KNOB_BOOL, nullptr},
-    {"merge", &g_tune.merge, "0..2", KNOB_RAW, nullptr},
-    {"merge_max_batch", &g_tune.merge_max_batch, "*", KNOB_RAW, nullptr},
-    {"rf_wreg", &g_tune.rf_wreg, "*", KNOB_RAW, nullptr},           // (+ tile codes 0..8 in bits 4..7 and 8..11: smk_tune)
-    {"rf_tile2", &g_tune.rf_tile2, "0..5", KNOB_RAW, nullptr},
-    {"nchw_tn_major", &g_tune.nchw_tn_major, "*", KNOB_BOOL, nullptr},
-    {"chain", &g_tune.chain, "*", KNOB_BOOL, nullptr},
-    {"chain_mask", &g_tune.chain_mask, "0..2", KNOB_RAW, nullptr},
-    {"corr_head", &g_tune.corr_head, "*", KNOB_BOOL, nullptr},
-    {"pair_launch", &g_tune.pair_launch, "0..3", KNOB_RAW, nullptr},
-    {"halo", &g_tune.halo, "0|1|64|128", KNOB_RAW, nullptr},
-    {"halo_db", &g_tune.halo_db, "*", KNOB_BOOL, nullptr},
-    {"ksplit", &g_tune.ksplit, "0|1|2|4", KNOB_RAW, nullptr},
-    {"xc_ch", &g_tune.xc_ch, "32|64", KNOB_RAW, nullptr},
-    {"xc_full", &g_tune.xc_full, "0..2", KNOB_RAW, nullptr},
-    {"stem_fused", &g_tune.stem_fused, "*", KNOB_BOOL, nullptr},
-    {"l1_fused", &g_tune.l1_fused, "*", KNOB_BOOL, nullptr},
-    {"buf_lds", &g_tune.buf_lds, "*", KNOB_BOOL, nullptr},
-    {"a_stage", &g_tune.a_stage, "*", KNOB_BOOL, nullptr},
-    {"wreg", &g_tune.wreg, "0..7", KNOB_RAW, nullptr},
-    {"wreg_policy", &g_tune.wreg_policy, "0|1", KNOB_RAW, nullptr},
-    {"wreg_stages", &g_tune.wreg_stages, "0|3..8", KNOB_RAW, "0|3|4"},
-    {"wreg96", &g_tune.wreg96, "*", KNOB_BOOL, nullptr},
-    {"wreg32", &g_tune.wreg32, "0..4096", KNOB_RAW, nullptr},
-    {"npw", &g_tune.npw, "2|4", KNOB_RAW, nullptr},
-    {"res_nt", &g_tune.res_nt, "*", KNOB_BOOL, nullptr},
-    {"pp", &g_tune.pp, "0..2", KNOB_RAW, nullptr},
-    {"x3_fused", &g_tune.x3_fused, "*", KNOB_BOOL, nullptr},          // (read when a split-operand context packs its weights)
-    {"ablate", &g_tune.ablate, "*", 127, "0"},
-    {"front_occ1", &g_tune.front_occ1, "*", 3, "0"},
-    {"seq", &g_tune.seq, "*", KNOB_BOOL, nullptr},
-    {"seq_spoll", &g_tune.seq_spoll, "*", KNOB_BOOL, nullptr},
-    {"seq_kstag", &g_tune.seq_kstag, "0..2", KNOB_RAW, nullptr},
-    {"seq_kstag_mask", &g_tune.seq_kstag_mask, "*", 7, nullptr},
-    {"seq_tall", &g_tune.seq_tall, "0..2", KNOB_RAW, nullptr},
-    {"seq_fuse", &g_tune.seq_fuse, "0..3", KNOB_RAW, nullptr},
-    {"seq_fuse3", &g_tune.seq_fuse3, "0..2", KNOB_RAW, "0"},
-    {"seq_pair2d", &g_tune.seq_pair2d, "0..2", KNOB_RAW, "0"},
-    {"seq_deep", &g_tune.seq_deep, "*", KNOB_BOOL, "0"},
-    {"seq_ds128", &g_tune.seq_ds128, "*", KNOB_BOOL, nullptr},
-    {"seq_halo", &g_tune.seq_halo, "*", KNOB_BOOL, nullptr},
-    {"seq_yres", &g_tune.seq_yres, "*", KNOB_BOOL, nullptr},
-    {"seq_search", &g_tune.seq_search, "*", KNOB_BOOL, nullptr},
-    {"seq_first_stage", &g_tune.seq_first_stage, "0..3", KNOB_RAW, "1..3"},
-    {"seq_min_batch", &g_tune.seq_min_batch, ">=1", KNOB_RAW, nullptr},
-    {"seq_max_batch", &g_tune.seq_max_batch, ">=1", KNOB_RAW, nullptr},
-    {"seq_extra_batch", &g_tune.seq_extra_batch, "*", KNOB_RAW, nullptr},
-    {"seq_mult_max", &g_tune.seq_mult_max, ">=0", KNOB_RAW, nullptr},
-    {"main_prio", &g_tune.main_prio, "0..3", KNOB_RAW, nullptr},
-    {"pipe_late", &g_tune.pipe_late, "*", KNOB_BOOL, nullptr},
-    {"seq_fused_last", &g_seq_last.pairs, nullptr, KNOB_RAW, nullptr},     // pairs fused in the sequence launched last
-    {"seq_yres_last", &g_seq_last.resident, nullptr, KNOB_RAW, nullptr},
-    {"seq_fused3_last", &g_seq_last.triples, nullptr, KNOB_RAW, nullptr},
-    {"measure_build", &g_measure_build, nullptr, KNOB_RAW, nullptr},
-};
-
-static bool knob_accepts(const char *spec, int v) {
-    if (!strcmp(spec, "*")) return true;
-    for (const char *t = spec; t; t = strchr(t, '|') ? strchr(t, '|') + 1 : nullptr) {
-        if (t[0] == '>' && t[1] == '=') {
-            if (v >= atoi(t + 2)) return true;
-            continue;
-        }
-        char *e = nullptr;
-        const long lo = strtol(t, &e, 10), hi = (e[0] == '.' && e[1] == '.') ? strtol(e + 2, nullptr, 10) : lo;
-        if (v >= lo && v <= hi) return true;
-    }
-    return false;
-}
-
-static const Knob *find_knob(const char *key) {
-    for (const Knob &k : KNOBS)
-        if (!strcmp(key, k.name)) return &k;
-    return nullptr;
-}
-
-int smk_tune(const char *key, int value) {
-    if (!key) return fail(SMK_E_ARG, "smk_tune: key is NULL");
-    const Knob *k = find_knob(key);
-    if (!k) return fail(SMK_E_ARG, "smk_tune: unknown key %s", key);
-    if (!k->accept) return fail(SMK_E_ARG, "smk_tune: %s is a read-only diagnostic", key);
-    if (!knob_accepts(k->accept, value)) return fail(SMK_E_ARG, "smk_tune: %s takes %s, not %d", key, k->accept, value);
-#ifndef SMK_MEASURE
-    if (k->product && !knob_accepts(k->product, value))
-        return fail(SMK_E_ARG, "smk_tune: %s %d is a measured alternative, only in a library built with `make MEASURE=1` (this one takes %s)",
-                    key, value, k->product);
-#endif
-    if (k->slot == &g_tune.rf_wreg && (((value >> 4) & 15) > 8 || ((value >> 8) & 15) > 8))   // (WREG_TILE has codes 1..8)
-        return fail(SMK_E_ARG, "smk_tune: rf_wreg tile codes (bits 4..7, 8..11) 0..8");
-    *k->slot = k->conv == KNOB_BOOL ? value != 0 : (k->conv > 0 ? value & k->conv : value);
-    return 0;
-}
-
-int smk_tune_get(const char *key, int *value) {
-    if (!key || !value) return fail(SMK_E_ARG, "smk_tune_get: null argument");
-    const Knob *k = find_knob(key);
-    if (!k) return fail(SMK_E_ARG, "smk_tune_get: unknown key %s", key);
-    *value = *k->slot;
-    return 0;
 }
 
 int smk_profile(smk_ctx *c, int enable) {
@@ -2699,1325 +2242,6 @@ int smk_debug_read(smk_ctx *c, const char *name, float *dst, int *C, int *H, int
             return 0;
         }
     return fail(SMK_E_ARG, "smk_debug_read: unknown tensor %s", name);
-}
-
-// ---- per-op entry points -------------------------------------------------------------------
-struct TmpBufs {
-    std::vector<void *> v;
-    ~TmpBufs() { for (void *p : v) hipFree(p); }
-    int alloc(void **p, size_t bytes) {
-        HIPCHK(hipMalloc(p, bytes + 256));
-        HIPCHK(hipMemset(*p, 0, bytes + 256));
-        v.push_back(*p);
-        return 0;
-    }
-};
-
-static int fill_geom(const smk_conv_geom *g, PackedConv &pc, Act &in, ConvOpt &o, int &Ho, int &Wo) {
-    const int cin_len = g->cin_len > 0 ? g->cin_len : g->Cin;
-    pc.Ci = rup(cin_len, 8);
-    pc.k = g->k;
-    pc.K = g->k * g->k * pc.Ci;
-    pc.Kpad = rup(pc.K, KPAD_ALIGN);
-    pc.groups = 1;
-    pc.N = g->Cout;
-    pc.group_rows = pc.rows = rup(g->Cout, NPAD_ALIGN);
-    in.H = g->H; in.W = g->W; in.C = rup(g->Cin, 8);
-    o.stride = g->stride; o.pad = g->pad; o.dil = g->dil; o.relu = g->relu;
-    o.cin_off = g->cin_off;
-    o.win = g->win != 0; o.ups = g->ups != 0;
-    o.Hl = g->Hl; o.Wl = g->Wl; o.org_y = g->org_y; o.org_x = g->org_x;
-    o.pos_mul = g->pos_mul; o.pos_add = g->pos_add;
-    const int Hl = (o.win || o.ups) ? g->Hl : g->H, Wl = (o.win || o.ups) ? g->Wl : g->W;
-    Ho = (Hl + 2 * g->pad - g->dil * (g->k - 1) - 1) / g->stride + 1;
-    Wo = (Wl + 2 * g->pad - g->dil * (g->k - 1) - 1) / g->stride + 1;
-    if (Ho < 1 || Wo < 1) return fail(SMK_E_ARG, "conv geometry gives empty output");
-    if (g->cin_off % 8 != 0) return fail(SMK_E_ARG, "cin_off must be a multiple of 8");
-    if (g->cin_off + cin_len > g->Cin) return fail(SMK_E_ARG, "channel slice out of range");
-    return 0;
-}
-
-static void pack_host(const smk_conv_geom *g, const PackedConv &pc, const float *w, const float *b,
-                      std::vector<float> &rows, std::vector<float> &bias) {
-    const int cin_len = g->cin_len > 0 ? g->cin_len : g->Cin;
-    rows.assign((size_t)pc.rows * pc.Kpad, 0.f);
-    bias.assign(pc.rows, 0.f);
-    std::vector<double> one(g->Cout, 1.0);
-    pack_rows(rows, 0, pc.Kpad, w, one.data(), g->Cout, cin_len, g->k, pc.Ci);
-    if (b) for (int n = 0; n < g->Cout; ++n) bias[n] = b[n];
-}
-
-// split-K scratch of the context-free entry points (per-op tests, smk_bench_conv): one per device, lazily
-static int op_ks_scratch(ConvEnv &env) {
-    static float *part[64] = {nullptr};
-    static unsigned *cnt[64] = {nullptr};
-    const int d = env.device;
-    if (d < 0 || d >= 64) return 0;
-    if (!part[d]) {
-        HIPCHK(hipMalloc((void **)&part[d], KS_PART_FLOATS * sizeof(float)));
-        HIPCHK(hipMalloc((void **)&cnt[d], KS_CNT * sizeof(unsigned)));
-        HIPCHK(hipMemset(cnt[d], 0, KS_CNT * sizeof(unsigned)));
-    }
-    env.ks_part = part[d];
-    env.ks_cnt = cnt[d];
-    return 0;
-}
-
-// The kernel a per-op entry point's algo code forces (siammask_hip_test.h: low byte 0 / 2 conv_igemm_kernel, 1 / 3 the naive
-// kernel, 4 conv3x3_halo_kernel, 5 conv_wreg_kernel, 6 conv_pp_kernel; bits 8..15 the tile code).  Returns 0, -1 for a wreg tile
-// code outside 1..8, 1 when the geometry is not eligible for the kernel.
-static int plan_from_algo(int algo, const ConvParams &p, int dtype, ConvPlan &pl) {
-    const int mode = algo & 0xff, code = (algo >> 8) & 0xff;
-    switch (mode) {
-    case 1: case 3: pl.kind = CK_NAIVE; return 0;
-    case 4:
-        pl.kind = CK_HALO; pl.halo_bm = (code & 15) == 1 ? 128 : 64;
-        return conv_halo_eligible(p, dtype, pl.halo_bm) ? 0 : 1;
-    case 5:
-        pl.kind = CK_WREG; pl.wreg = code & 15; pl.stages = wreg_stages_from_code(code);
-        if (pl.wreg < 1 || pl.wreg > 8) return -1;
-        return conv_wreg_eligible(p, dtype) ? 0 : 1;
-    case 6: pl.kind = CK_PP; return conv_pp_eligible(p, dtype) ? 0 : 1;
-    case 7: pl.kind = CK_MHEAD; return mask_head_eligible(p, dtype) ? 0 : 1;
-    default: pl.kind = CK_IGEMM; pl.tile = tile_from_code(code, p, dtype); return 0;
-    }
-}
-
-int smk_op_conv2d_ex(int dtype, int algo, const smk_conv_geom *g, const float *x_dev, const float *w_host,
-                     const float *b_host, const float *res_dev, const int32_t *pos_host, float *y_dev,
-                     void *stream) {
-    if (!g || !x_dev || !w_host || !y_dev) return fail(SMK_E_ARG, "smk_op_conv2d_ex: null argument");
-    if (dtype != DT_F32 && dtype != DT_F16 && dtype != DT_F16X3) return fail(SMK_E_ARG, "bad dtype");
-    // DT_F16X3 (unit parity of the split-operand convolution): x, res -> [hi | lo] planes, the pack tripled per tap ([w_hi | w_lo | w_hi]), conv_igemm_kernel's
-    // (or wreg_tile's) splitting epilogue, the output read back as hi + lo.  NHWC epilogue only, whole channel range.
-    const bool x3 = dtype == DT_F16X3;
-    if (x3 && (((algo & 0xff) != 0 && (algo & 0xff) != 5) || g->cin_off || g->cin_len))
-        return fail(SMK_E_ARG, "smk_op_conv2d_ex: split-operand convolutions: algo 0 (conv_igemm_kernel) or 5 (conv_wreg_kernel), no channel slice");
-    const int ctx_dtype = dtype;
-    dtype = kdtype(dtype);
-    hipStream_t s = (hipStream_t)stream;
-    PackedConv pc; Act in; ConvOpt o; int Ho, Wo;
-    CHK(fill_geom(g, pc, in, o, Ho, Wo));
-    std::vector<float> rows, bias;
-    pack_host(g, pc, w_host, b_host, rows, bias);
-    if (x3) {
-        const int Ci0 = pc.Ci, K1 = pc.Kpad;
-        pc.x3 = true;
-        pc.alg_k = g->k * g->k * Ci0;
-        pc.Ci = 3 * Ci0;
-        pc.K = g->k * g->k * pc.Ci;
-        pc.Kpad = rup(pc.K, KPAD_ALIGN);
-        std::vector<float> osc;
-        split_rows_x3(rows, pc.rows, K1, pc.Kpad, g->k * g->k, Ci0, osc);
-        CHK(upload_oscale(pc, osc));
-        in.C *= X3_PLANES;
-    }
-    std::vector<float> fused;
-    if (x3 && g_tune.x3_fused && fuse_rows_x3(rows, pc, g->k * g->k, pc.Ci / 3, fused)) CHK(upload_packed(pc, rows, bias, dtype, &fused));
-    else
-    CHK(upload_packed(pc, rows, bias, dtype));
-    TmpBufs tmp;
-    tmp.v.push_back(pc.w); tmp.v.push_back(pc.bias);
-    if (pc.w_frag) tmp.v.push_back(pc.w_frag);
-    if (pc.w_frag16) tmp.v.push_back(pc.w_frag16);
-    if (pc.oscale) tmp.v.push_back(pc.oscale);
-    const size_t es = esize(dtype);
-    CHK(tmp.alloc(&in.p, (size_t)g->B * g->H * g->W * in.C * es));
-    CvtInParams ci{x_dev, in.p, g->B, g->Cin, g->H, g->W, x3 ? in.C / X3_PLANES : in.C, 0, x3 ? 1 : 0};
-    if (x3 ? launch_cvt_in_x3(ci, s) : launch_cvt_in(ci, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    int *pos_dev = nullptr;
-    if (pos_host) {
-        CHK(tmp.alloc((void **)&pos_dev, sizeof(int) * 2 * g->B));
-        HIPCHK(hipMemcpyAsync(pos_dev, pos_host, sizeof(int) * 2 * g->B, hipMemcpyHostToDevice, s));
-        o.pos = pos_dev;
-    }
-    const int mode = algo & 0xff;
-    const bool nchw = (mode == 2 || mode == 3 || mode == 7);
-    if (mode == 4) {                                   // halo kernel (3x3 stride 1): its chunk-major pack (f16: + the fragment-order copy)
-        CHK(upload_halo_pack(pc, rows, dtype));
-        if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);
-        if (pc.w_halo) tmp.v.push_back(pc.w_halo);
-    }
-    Act out, res;
-    out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8) * (x3 ? X3_PLANES : 1);
-    if (res_dev && g->res_mode) {
-        if (nchw) return fail(SMK_E_ARG, "residual is not supported with the NCHW epilogue");
-        res = out;
-        CHK(tmp.alloc(&res.p, (size_t)g->B * Ho * Wo * out.C * es));
-        CvtInParams cr{res_dev, res.p, g->B, g->Cout, Ho, Wo, x3 ? out.C / X3_PLANES : out.C, 0, x3 ? 1 : 0};
-        if (x3 ? launch_cvt_in_x3(cr, s) : launch_cvt_in(cr, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-        o.res = &res; o.res_mode = g->res_mode;
-    }
-    ConvEnv env;
-    env.dtype = ctx_dtype;
-    HIPCHK(hipGetDevice(&env.device));
-    CHK(op_ks_scratch(env));
-    ConvParams p;
-    if (nchw) {
-        o.nchw_out = y_dev;
-        CHK(conv_params(env, pc, in, nullptr, g->B, o, p));
-    } else {
-        CHK(tmp.alloc(&out.p, (size_t)g->B * Ho * Wo * out.C * es));
-        CHK(conv_params(env, pc, in, &out, g->B, o, p));
-    }
-    ConvPlan pl;
-    const int prc = plan_from_algo(algo, p, dtype, pl);
-    if (prc < 0) return fail(SMK_E_ARG, "smk_op_conv2d_ex: wreg tile code 1..8");
-    if (prc)
-        return fail(SMK_E_ARG, "smk_op_conv2d_ex: %s", pl.kind == CK_HALO ? "geometry is not eligible for the halo kernel"
-                    : (pl.kind == CK_WREG ? "geometry / dtype is not eligible for conv_wreg_kernel"
-                       : (pl.kind == CK_MHEAD ? "geometry / dtype is not eligible for mask_head_kernel (fp16, 1x1, Cin = 256, Cout <= 4096, no ReLU)"
-                          : "geometry / dtype is not eligible for conv_pp_kernel")));
-    ConvBatch cb;
-    cb.n = 1;
-    cb.p[0] = p;
-    CHK(launch_plan(pl, cb, pc.w_halo, dtype, s, "conv"));
-    if (!nchw) {
-        CvtOutParams co{out.p, y_dev, g->B, g->Cout, Ho, Wo, out.C, 0, x3 ? out.C / X3_PLANES : 0};
-        if (x3 ? launch_cvt_out_x3(co, s) : launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-// The layers of an smk_seq_op list as sequence records, with smk_op_conv_seq's validation and errors (smk_host_plan_seq shares
-// them): layer i's weights come from pack(i, pc), every output tensor from alloc(&p, bytes); xin is the list input.
-static int seq_op_records(const smk_seq_op *ops, int n, const Act &xin, int device, const std::function<int(int, PackedConv &)> &pack,
-                          const std::function<int(void **, size_t)> &alloc, std::vector<SeqRec> &rec, std::vector<Act> &outs) {
-    const int dtype = DT_F16, B = ops[0].g.B;
-    ConvEnv env;
-    env.dtype = dtype;
-    env.device = device;
-    rec.assign(n, SeqRec());
-    outs.assign(n, Act());
-    for (int i = 0; i < n; ++i) {
-        const smk_seq_op &op = ops[i];
-        if (!op.w_host) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d has no weights", i);
-        if (op.src >= i || op.res_src >= i) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d reads a later layer", i);
-        if (op.g.B != B || op.g.win || op.g.ups) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: one batch, no windows", i);
-        const Act &in = op.src < 0 ? xin : outs[op.src];
-        const int cin_have = op.src < 0 ? ops[0].g.Cin : ops[op.src].g.Cout;
-        if (op.g.H != in.H || op.g.W != in.W || op.g.Cin != cin_have)
-            return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d geometry does not match its source", i);
-        PackedConv pc; Act gin; ConvOpt o; int Ho, Wo;
-        CHK(fill_geom(&op.g, pc, gin, o, Ho, Wo));
-        CHK(pack(i, pc));
-        outs[i].H = Ho; outs[i].W = Wo; outs[i].C = rup(op.g.Cout, 8);
-        CHK(alloc(&outs[i].p, (size_t)B * Ho * Wo * outs[i].C * esize(dtype)));
-        Act res;
-        if (op.g.res_mode) {
-            if (op.res_src < -1) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d wants a residual without a source", i);
-            res = op.res_src < 0 ? xin : outs[op.res_src];
-            if (res.H != Ho || res.W != Wo || res.C != outs[i].C)
-                return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d: residual shape differs from the output", i);
-            o.res = &res; o.res_mode = op.g.res_mode;
-        }
-        ConvParams p;
-        CHK(conv_params(env, pc, in, &outs[i], B, o, p));
-        SeqLayer &L = rec[i].L;
-        const int force_halo = op.cfg == SEQ_CFG_HALO128 ? 128 : (op.cfg == SEQ_CFG_HALO64 ? 64 : (op.cfg >= 0 ? -1 : 0));
-        if (!seq_layer_from(p, dtype, L, force_halo)) return fail(SMK_E_ARG, "smk_op_conv_seq: layer %d cannot run inside a sequence%s", i, force_halo > 0 ? " on the patch-sharing tile" : "");
-        if (op.cfg >= 0 && force_halo <= 0) {
-#ifdef SMK_MEASURE
-            if (op.cfg > 18) return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..18");
-#else
-            if (op.cfg > 9 || (op.cfg >= 6 && op.cfg <= 8))
-                return fail(SMK_E_ARG, "smk_op_conv_seq: cfg 0..5, 9 (6..8, 10..18 are measurement tiles: `make MEASURE=1`)");
-#endif
-            L.cfg = (signed char)op.cfg;
-        }
-        if (op.kstag >= 0) L.kstag = (signed char)(op.kstag != 0);
-        L.sync = (signed char)(op.sync != 0);
-        rec[i].wstd = pc.w_frag;
-        rec[i].id = "op" + std::to_string(i);
-    }
-    return 0;
-}
-
-// plan_seq on an smk_seq_op list: a layer with a cfg of its own is locked, the outputs the caller reads back are read behind the list
-static SeqPlanStats plan_seq_ops(const smk_seq_op *ops, std::vector<SeqRec> &rec, const std::vector<Act> &outs, int grid) {
-    std::vector<char> locked(rec.size());
-    std::vector<const void *> read_after;
-    for (size_t i = 0; i < rec.size(); ++i) {
-        locked[i] = ops[i].cfg >= 0;
-        if (ops[i].y_dev) read_after.push_back(outs[i].p);
-    }
-    return plan_seq(rec, {ops[0].g.B, grid >> 3, true}, locked.data(), read_after);
-}
-
-// A sequence of convolutions through conv_seq_kernel on caller-described layers (unit parity of the persistent kernel:
-// every tile configuration, residual and independent-member cases; micro-benchmarks of its K loop).  fp16 only.
-int smk_op_conv_seq(const smk_seq_op *ops, int n, const float *x_dev, int iters, float *usec_out, float *clk_us_out,
-                    int *n_fused_out, void *stream) {
-    if (!ops || !x_dev || n < 1 || n > SEQ_MAX || iters < 1) return fail(SMK_E_ARG, "smk_op_conv_seq: bad argument (1..%d layers)", SEQ_MAX);
-    hipStream_t s = (hipStream_t)stream;
-    const int dtype = DT_F16;
-    const size_t es = esize(dtype);
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, dev));
-    const int grid = seq_grid_for(prop.multiProcessorCount);
-    if (!grid) return fail(SMK_E_STATE, "smk_op_conv_seq: the XCD placement / occupancy check failed on this device");
-    TmpBufs tmp;
-    const int B = ops[0].g.B;
-    Act xin;
-    xin.H = ops[0].g.H; xin.W = ops[0].g.W; xin.C = rup(ops[0].g.Cin, 8);
-    CHK(tmp.alloc(&xin.p, (size_t)B * xin.H * xin.W * xin.C * es));
-    CvtInParams ci{x_dev, xin.p, B, ops[0].g.Cin, xin.H, xin.W, xin.C, 0};
-    if (launch_cvt_in(ci, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    std::vector<PackedConv> packs(n);
-    auto pack = [&](int i, PackedConv &pc) -> int {
-        const smk_seq_op &op = ops[i];
-        int same = -1;                                    // a layer that names the SAME host weights re-uses the device copy
-        for (int j = 0; j < i && same < 0; ++j)           // (micro-benchmarks: L2-warm weights)
-            if (ops[j].w_host == op.w_host && ops[j].b_host == op.b_host && ops[j].g.Cout == op.g.Cout &&
-                ops[j].g.Cin == op.g.Cin && ops[j].g.k == op.g.k && ops[j].g.cin_len == op.g.cin_len) same = j;
-        if (same >= 0) {
-            pc.w = packs[same].w; pc.bias = packs[same].bias; pc.w_frag = packs[same].w_frag; pc.w_frag_halo = packs[same].w_frag_halo;
-        } else {
-            std::vector<float> rows, bias;
-            pack_host(&op.g, pc, op.w_host, op.b_host, rows, bias);
-            CHK(upload_packed(pc, rows, bias, dtype));
-            if (pc.k == 3) CHK(upload_halo_pack(pc, rows, dtype));       // (+ its fragment-order form: the patch-sharing tile)
-            tmp.v.push_back(pc.w); tmp.v.push_back(pc.bias);
-            if (pc.w_frag) tmp.v.push_back(pc.w_frag);
-            if (pc.w_frag16) tmp.v.push_back(pc.w_frag16);
-            if (pc.w_halo) tmp.v.push_back(pc.w_halo);
-            if (pc.w_frag_halo) tmp.v.push_back(pc.w_frag_halo);
-        }
-        packs[i] = pc;
-        return 0;
-    };
-    std::vector<SeqRec> rec;
-    std::vector<Act> outs;
-    CHK(seq_op_records(ops, n, xin, dev, pack, [&](void **p, size_t bytes) { return tmp.alloc(p, bytes); }, rec, outs));
-    g_seq_last = plan_seq_ops(ops, rec, outs, grid);          // what the engine does with its own lists (smk_tune "seq_fuse", ...)
-    SeqArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n = n; a.B = B;
-    a.flags = g_tune.seq_spoll ? 1 : 0;
-    for (int i = 0; i < n; ++i) a.L[i] = rec[i].L;
-    unsigned *bar = nullptr;
-    int *err = nullptr;
-    unsigned long long *clk = nullptr, *clk2 = nullptr;
-    CHK(tmp.alloc((void **)&bar, 8 * 32 * sizeof(unsigned)));
-    CHK(tmp.alloc((void **)&err, sizeof(int)));
-    CHK(tmp.alloc((void **)&clk, sizeof(unsigned long long) * (2 * SEQ_MAX + 1)));
-    const char *ck = getenv("SMK_SEQ_CLK");
-    const bool want2 = ck && !strcmp(ck, "2");
-    if (want2) CHK(tmp.alloc((void **)&clk2, sizeof(unsigned long long) * (12 + 32) * SEQ_MAX));
-    float *xch = nullptr;
-    CHK(tmp.alloc((void **)&xch, SEQ_XCH_BYTES));
-    a.bar = bar; a.xch = xch; a.err = err; a.err_host = nullptr; a.clk = clk; a.clk2 = clk2;
-    if (n_fused_out) {
-        *n_fused_out = 0;
-        for (int i = 0; i < n; ++i) *n_fused_out += a.L[i].cfg == SEQ_CFG_C3C1_2ND;
-    }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    // The outputs and the timed launches come from the instantiation the engine's own lists run (no stamp pointers: the stamps
-    // live in the CLK build of the kernel); one more launch of the CLK build then writes the per-layer stamps (same results).
-    SeqArgs a_run = a;
-    a_run.clk = nullptr; a_run.clk2 = nullptr;
-    if (launch_conv_seq(a_run, grid, s)) return fail(SMK_E_HIP, "conv_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipEventRecord(e0, s));
-    for (int it = 1; it < iters; ++it)
-        if (launch_conv_seq(a_run, grid, s)) return fail(SMK_E_HIP, "conv_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipEventRecord(e1, s));
-    if (launch_conv_seq(a, grid, s)) return fail(SMK_E_HIP, "conv_seq launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIPCHK(hipStreamSynchronize(s));
-    float ms = 0.f;
-    if (iters > 1) HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (usec_out) *usec_out = iters > 1 ? ms * 1000.f / (iters - 1) : 0.f;
-    int e = 0;
-    HIPCHK(hipMemcpy(&e, err, sizeof(int), hipMemcpyDeviceToHost));
-    if (e) return fail(SMK_E_HIP, "conv_seq_kernel reported %s", e == 1 ? "an uneven distribution of workgroups over the XCDs" : "a team-barrier time-out");
-    {
-        unsigned long long h[2 * SEQ_MAX + 1], h2[(12 + 32) * SEQ_MAX];
-        HIPCHK(hipMemcpy(h, clk, sizeof(h), hipMemcpyDeviceToHost));
-        if (clk_us_out)
-            for (int i = 0; i < n; ++i) {
-                clk_us_out[2 * i] = (float)((h[1 + 2 * i] - h[2 * i]) / 100.0);
-                clk_us_out[2 * i + 1] = (float)((h[2 + 2 * i] - h[1 + 2 * i]) / 100.0);
-            }
-        if (ck) {
-            if (want2) HIPCHK(hipMemcpy(h2, clk2, sizeof(h2), hipMemcpyDeviceToHost));
-            seq_print_clk(a, rec.data(), "smk_op_conv_seq", h, want2 ? h2 : nullptr);
-        }
-    }
-    for (int i = 0; i < n; ++i)
-        if (ops[i].y_dev) {
-            CvtOutParams co{outs[i].p, ops[i].y_dev, B, ops[i].g.Cout, outs[i].H, outs[i].W, outs[i].C, 0};
-            if (launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-        }
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-int smk_op_conv2d(int dtype, int algo, const float *x_dev, int B, int Cin, int H, int W, const float *w_host,
-                  const float *b_host, int Cout, int k, int stride, int pad, int dil, int relu,
-                  const float *res_dev, float *y_dev, void *stream) {
-    smk_conv_geom g;
-    memset(&g, 0, sizeof(g));
-    g.B = B; g.Cin = Cin; g.H = H; g.W = W; g.Cout = Cout; g.k = k; g.stride = stride; g.pad = pad; g.dil = dil;
-    g.relu = relu; g.res_mode = res_dev ? RES_PRE_RELU : RES_NONE;
-    return smk_op_conv2d_ex(dtype, algo, &g, x_dev, w_host, b_host, res_dev, nullptr, y_dev, stream);
-}
-
-int smk_op_dw_xcorr(int dtype, const float *x_dev, const float *k_dev, int B, int C, int H, int W, int kh, int kw,
-                    float *y_dev, void *stream) {
-    if (!x_dev || !k_dev || !y_dev) return fail(SMK_E_ARG, "smk_op_dw_xcorr: null argument");
-    if (C % 64 != 0) return fail(SMK_E_ARG, "smk_op_dw_xcorr: C must be a multiple of 64");
-    if (kh > 5 || kw > 5 || kh > H || kw > W || (W - kw + 1 + 1) / 2 > 13)
-        return fail(SMK_E_ARG, "smk_op_dw_xcorr: unsupported geometry");
-    hipStream_t s = (hipStream_t)stream;
-    TmpBufs tmp;
-    const size_t es = esize(dtype);
-    const int Ho = H - kh + 1, Wo = W - kw + 1;
-    void *x, *k, *y;
-    CHK(tmp.alloc(&x, (size_t)B * H * W * C * es));
-    CHK(tmp.alloc(&k, (size_t)B * kh * kw * C * es));
-    CHK(tmp.alloc(&y, (size_t)B * Ho * Wo * C * es));
-    CvtInParams cx{x_dev, x, B, C, H, W, C, 0}, ck{k_dev, k, B, C, kh, kw, C, 0};
-    if (launch_cvt_in(cx, dtype, s) || launch_cvt_in(ck, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    XcorrParams xp{x, k, y, B, H, W, kh, kw, Ho, Wo, C, C};
-    if (launch_xcorr(xp, dtype, s)) return fail(SMK_E_HIP, "xcorr launch failed");
-    CvtOutParams co{y, y_dev, B, C, Ho, Wo, C, 0};
-    if (launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-int smk_op_maxpool3x3s2(int dtype, const float *x_dev, int B, int C, int H, int W, float *y_dev, void *stream) {
-    if (!x_dev || !y_dev) return fail(SMK_E_ARG, "smk_op_maxpool3x3s2: null argument");
-    if (C % 8 != 0) return fail(SMK_E_ARG, "smk_op_maxpool3x3s2: C must be a multiple of 8");
-    hipStream_t s = (hipStream_t)stream;
-    TmpBufs tmp;
-    const size_t es = esize(dtype);
-    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-    void *x, *y;
-    CHK(tmp.alloc(&x, (size_t)B * H * W * C * es));
-    CHK(tmp.alloc(&y, (size_t)B * Ho * Wo * C * es));
-    CvtInParams cx{x_dev, x, B, C, H, W, C, 0};
-    if (launch_cvt_in(cx, dtype, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    PoolParams pp{x, y, B, H, W, C, Ho, Wo};
-    if (launch_maxpool(pp, dtype, s)) return fail(SMK_E_HIP, "maxpool launch failed");
-    CvtOutParams co{y, y_dev, B, C, Ho, Wo, C, 0};
-    if (launch_cvt_out(co, dtype, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
-}
-
-// ---- the fused front end on caller tensors: stem_pool_kernel, l1_block_kernel -----------------------------------------
-// An output buffer of these two entries: NHWC fp16, every byte 0xFF before the launch (fp16 NaN: a pixel the kernel does not
-// write surfaces as NaN in the result) between two guard bands of a fixed byte.  A band that changed means that a tile wrote
-// outside its image -- inside this allocation; a write further out is not seen.
-constexpr size_t OP_GUARD = 4096;
-constexpr int OP_GUARD_BYTE = 0xA5;
-struct GuardedBuf {
-    unsigned char *base = nullptr;
-    size_t bytes = 0;
-    void *p() const { return base + OP_GUARD; }
-    int alloc(TmpBufs &tmp, size_t n, hipStream_t s) {
-        HIPCHK(hipMalloc((void **)&base, n + 2 * OP_GUARD));
-        tmp.v.push_back(base);
-        bytes = n;
-        HIPCHK(hipMemsetAsync(base, OP_GUARD_BYTE, OP_GUARD, s));
-        HIPCHK(hipMemsetAsync(base + OP_GUARD, 0xFF, n, s));
-        HIPCHK(hipMemsetAsync(base + OP_GUARD + n, OP_GUARD_BYTE, OP_GUARD, s));
-        return 0;
-    }
-    // after the stream has been synchronised: both bands intact?
-    int check(const char *entry, const char *name) const {
-        std::vector<unsigned char> h(2 * OP_GUARD);
-        HIPCHK(hipMemcpy(h.data(), base, OP_GUARD, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h.data() + OP_GUARD, base + OP_GUARD + bytes, OP_GUARD, hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < 2 * OP_GUARD; ++i)
-            if (h[i] != OP_GUARD_BYTE)
-                return fail(SMK_E_STATE, "%s: the kernel wrote outside the %s buffer (guard band %s it, byte %d)", entry, name,
-                            i < OP_GUARD ? "before" : "after", (int)(i % OP_GUARD));
-        return 0;
-    }
-};
-
-// one convolution's weights for a per-op entry: pack_host -> upload_packed (fp16), the device copies owned by tmp
-static int op_pack(TmpBufs &tmp, PackedConv &pc, int Cin, int Cout, int k, const float *w, const float *b) {
-    smk_conv_geom g;
-    memset(&g, 0, sizeof(g));
-    g.B = 1; g.Cin = Cin; g.H = g.W = k; g.Cout = Cout; g.k = k; g.stride = 1; g.dil = 1;
-    Act in; ConvOpt o; int Ho, Wo;
-    CHK(fill_geom(&g, pc, in, o, Ho, Wo));
-    std::vector<float> rows, bias;
-    pack_host(&g, pc, w, b, rows, bias);
-    const int rc = upload_packed(pc, rows, bias, DT_F16);
-    for (void *q : {pc.w, (void *)pc.bias, pc.w_frag, pc.w_frag16})
-        if (q) tmp.v.push_back(q);
-    return rc;
-}
-
-int smk_op_stem_pool(const float *x_dev, const float *w_host, const float *b_host, int S, int B, float *p0_dev, float *x1_dev,
-                     void *stream) {
-    if (!x_dev || !w_host || !b_host || !p0_dev || !x1_dev) return fail(SMK_E_ARG, "smk_op_stem_pool: null argument");
-    if (S < 7 || S > 8192) return fail(SMK_E_ARG, "smk_op_stem_pool: S = %d (7 .. 8192)", S);
-    if (B < 1 || B > 1024) return fail(SMK_E_ARG, "smk_op_stem_pool: B = %d (1 .. 1024)", B);
-    hipStream_t s = (hipStream_t)stream;
-    const int s0 = (S - 7) / 2 + 1, s1 = (s0 - 1) / 2 + 1;
-    // the context's pack: pixel-pair rows -> upload_packed -> the fragment-order copy the kernel reads
-    PackedConv pc = stem_pack_geom();
-    std::vector<float> rows((size_t)pc.rows * pc.Kpad, 0.f), bias(pc.rows, 0.f);
-    const std::vector<double> one(64, 1.0), shift(b_host, b_host + 64);
-    stem_pair_rows(rows, bias, pc.Kpad, w_host, one.data(), shift.data());
-    TmpBufs tmp;
-    const int rc = upload_packed(pc, rows, bias, DT_F16);
-    for (void *q : {pc.w, (void *)pc.bias, pc.w_frag, pc.w_frag16})
-        if (q) tmp.v.push_back(q);
-    CHK(rc);
-    if (!pc.w_frag) return fail(SMK_E_STATE, "smk_op_stem_pool: internal: the stem has no fragment-order pack");
-    GuardedBuf p0, x1;
-    CHK(p0.alloc(tmp, (size_t)B * s0 * s0 * 64 * 2, s));
-    CHK(x1.alloc(tmp, (size_t)B * s1 * s1 * 64 * 2, s));
-    StemPoolParams sp{x_dev, pc.w_frag, pc.bias, p0.p(), x1.p(), B, S, s0, s1, pc.Kpad, 0};
-    if (launch_stem_pool(sp, s)) return fail(SMK_E_HIP, "stem_pool launch failed: %s", hipGetErrorString(hipGetLastError()));
-    CvtOutParams c0{p0.p(), p0_dev, B, 64, s0, s0, 64, 0}, c1{x1.p(), x1_dev, B, 64, s1, s1, 64, 0};
-    if (launch_cvt_out(c0, DT_F16, s) || launch_cvt_out(c1, DT_F16, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-    HIPCHK(hipStreamSynchronize(s));
-    CHK(p0.check("smk_op_stem_pool", "p0"));
-    CHK(x1.check("smk_op_stem_pool", "x1"));
-    return 0;
-}
-
-int smk_op_l1_block(const float *x_dev, const float *w1_host, const float *b1_host, const float *w2_host, const float *b2_host,
-                    const float *w3_host, const float *b3_host, const float *wd_host, const float *bd_host, int Cin, int S, int B,
-                    float *y_dev, void *stream) {
-    if (!x_dev || !w1_host || !b1_host || !w2_host || !b2_host || !w3_host || !b3_host || !y_dev)
-        return fail(SMK_E_ARG, "smk_op_l1_block: null argument");
-    if (Cin != 64 && Cin != 256) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = %d (64: block 0 with its projection, 256)", Cin);
-    if (Cin == 64 && (!wd_host || !bd_host)) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = 64 needs the projection shortcut wd, bd");
-    if (Cin == 256 && (wd_host || bd_host)) return fail(SMK_E_ARG, "smk_op_l1_block: Cin = 256 has an identity shortcut: wd, bd must be null");
-    if (S < 1 || S > 4096) return fail(SMK_E_ARG, "smk_op_l1_block: S = %d (1 .. 4096)", S);
-    if (B < 1 || B > 1024) return fail(SMK_E_ARG, "smk_op_l1_block: B = %d (1 .. 1024)", B);
-    hipStream_t s = (hipStream_t)stream;
-    TmpBufs tmp;
-    PackedConv p1, p2, p3, pd;
-    CHK(op_pack(tmp, p1, Cin, 64, 1, w1_host, b1_host));
-    CHK(op_pack(tmp, p2, 64, 64, 3, w2_host, b2_host));
-    CHK(op_pack(tmp, p3, 64, 256, 1, w3_host, b3_host));
-    if (Cin == 64) CHK(op_pack(tmp, pd, 64, 256, 1, wd_host, bd_host));
-    if (!p1.w_frag16 || !p2.w_frag16 || !p3.w_frag16 || (Cin == 64 && !pd.w_frag16))
-        return fail(SMK_E_STATE, "smk_op_l1_block: internal: a layer has no 16x16x32 fragment-order pack");
-    void *x;
-    CHK(tmp.alloc(&x, (size_t)B * S * S * Cin * 2));
-    CvtInParams ci{x_dev, x, B, Cin, S, S, Cin, 0};
-    if (launch_cvt_in(ci, DT_F16, s)) return fail(SMK_E_HIP, "cvt_in launch failed");
-    GuardedBuf y;
-    CHK(y.alloc(tmp, (size_t)B * S * S * 256 * 2, s));
-    L1BlockParams lp;
-    memset(&lp, 0, sizeof(lp));
-    lp.x = x; lp.y = y.p();
-    lp.w1 = p1.w_frag16; lp.w2 = p2.w_frag16; lp.w3 = p3.w_frag16;
-    lp.b1 = p1.bias; lp.b2 = p2.bias; lp.b3 = p3.bias;
-    lp.K1pad = p1.Kpad; lp.K2pad = p2.Kpad; lp.K3pad = p3.Kpad;
-    if (Cin == 64) { lp.wd = pd.w_frag16; lp.bd = pd.bias; lp.Kdpad = pd.Kpad; }
-    lp.B = B; lp.S = S; lp.Cin = Cin;
-    if (launch_l1_block(lp, s)) return fail(SMK_E_HIP, "l1_block launch failed: %s", hipGetErrorString(hipGetLastError()));
-    CvtOutParams co{y.p(), y_dev, B, 256, S, S, 256, 0};
-    if (launch_cvt_out(co, DT_F16, s)) return fail(SMK_E_HIP, "cvt_out launch failed");
-    HIPCHK(hipStreamSynchronize(s));
-    CHK(y.check("smk_op_l1_block", "y"));
-    return 0;
-}
-
-// ---- image ops either side of the network ------------------------------
-int smk_crop_resize(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const int32_t *boxes,
-                    const uint8_t *avg_bgr, int B, int model_sz, float *out_dev, void *stream) {
-    if (!frames_dev || !boxes || !avg_bgr || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize: null argument");
-    if (H < 1 || W < 1 || model_sz < 1 || B < 1) return fail(SMK_E_ARG, "smk_crop_resize: bad geometry");
-    for (int b0 = 0; b0 < B; b0 += CROP_MAX_B) {
-        const int nb = B - b0 < CROP_MAX_B ? B - b0 : CROP_MAX_B;
-        CropParams p;
-        memset(&p, 0, sizeof(p));
-        p.frames = frames_dev + (size_t)b0 * frame_stride_bytes;
-        p.frame_stride = frame_stride_bytes;
-        p.out = out_dev + (size_t)b0 * 3 * model_sz * model_sz;
-        p.H = H; p.W = W; p.model_sz = model_sz;
-        for (int i = 0; i < nb; ++i) {
-            const int32_t *bx = boxes + 3 * (b0 + i);
-            if (bx[2] < 1 || bx[2] > 32768) return fail(SMK_E_ARG, "smk_crop_resize: window size %d out of range", bx[2]);
-            p.box[i][0] = bx[0]; p.box[i][1] = bx[1]; p.box[i][2] = bx[2];
-            for (int k = 0; k < 3; ++k) p.avg[i][k] = avg_bgr[3 * (b0 + i) + k];
-        }
-        if (launch_crop_resize(p, nb, stream)) return fail(SMK_E_HIP, "crop_resize launch failed");
-    }
-    return 0;
-}
-
-int smk_paste_mask(const float *logits_dev, int mask_size, const double *inv_map, int B, int W, int H, float seg_thr,
-                   float border, uint8_t *mask_out_dev, float *prob_out_dev, void *stream) {
-    if (!logits_dev || !inv_map || (!mask_out_dev && !prob_out_dev)) return fail(SMK_E_ARG, "smk_paste_mask: null argument");
-    if (W < 1 || H < 1 || mask_size < 1 || B < 1) return fail(SMK_E_ARG, "smk_paste_mask: bad geometry");
-    for (int b0 = 0; b0 < B; b0 += CROP_MAX_B) {
-        const int nb = B - b0 < CROP_MAX_B ? B - b0 : CROP_MAX_B;
-        PasteParams p;
-        memset(&p, 0, sizeof(p));
-        p.logits = logits_dev + (size_t)b0 * mask_size * mask_size;
-        p.mask_out = mask_out_dev ? mask_out_dev + (size_t)b0 * H * W : nullptr;
-        p.prob_out = prob_out_dev ? prob_out_dev + (size_t)b0 * H * W : nullptr;
-        p.ms = mask_size; p.W = W; p.H = H; p.seg_thr = seg_thr; p.border = border;
-        for (int i = 0; i < nb; ++i)
-            for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * (b0 + i) + k];
-        if (launch_paste_mask(p, nb, stream)) return fail(SMK_E_HIP, "paste_mask launch failed");
-    }
-    return 0;
-}
-
-int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H,
-                     float seg_thr, float border, uint8_t *labels_out_dev, void *stream) {
-    if (!logits_dev || !inv_map || !labels_out_dev) return fail(SMK_E_ARG, "smk_paste_labels: null argument");
-    if (W < 1 || H < 1 || mask_size < 1 || n_obj < 1 || n_obj > CROP_MAX_B)
-        return fail(SMK_E_ARG, "smk_paste_labels: bad geometry (1..%d objects)", CROP_MAX_B);
-    PasteParams p;
-    memset(&p, 0, sizeof(p));
-    p.logits = logits_dev; p.mask_out = labels_out_dev;
-    p.ms = mask_size; p.W = W; p.H = H; p.seg_thr = seg_thr; p.border = border;
-    for (int i = 0; i < n_obj; ++i)
-        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
-    if (launch_paste_labels(p, n_obj, stream)) return fail(SMK_E_HIP, "paste_labels launch failed");
-    return 0;
-}
-
-// ---- rotated box of the largest external contour (tools/test.py:283-300; mask_rbox.hip) ---------
-static const int RBOX_MAX_DIM = 4096;
-static inline size_t rup256(size_t x) { return (x + 255) / 256 * 256; }
-
-size_t smk_mask_rbox_workspace(int B, int W, int H) {
-    if (B < 1 || W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM) return 0;
-    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
-    return rup256(b * sizeof(RboxHdr)) + rup256(b * H * 2 * sizeof(int)) + rup256(b * H * Wq * 8) + rup256(b * H * Wh * sizeof(int));
-}
-
-int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev, size_t ws_bytes,
-                  double *out_dev, void *stream) {
-    if (!mask_dev || !ws_dev || !out_dev) return fail(SMK_E_ARG, "smk_mask_rbox: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_mask_rbox: batch %d", B);
-    if (W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM)
-        return fail(SMK_E_ARG, "smk_mask_rbox: frame %d x %d outside 1..%d", W, H, RBOX_MAX_DIM);
-    if (!(min_area >= 0)) return fail(SMK_E_ARG, "smk_mask_rbox: min_area must be >= 0");
-    const size_t need = smk_mask_rbox_workspace(B, W, H);
-    if (ws_bytes < need) return fail(SMK_E_ARG, "smk_mask_rbox: workspace of %zu bytes, %zu needed", ws_bytes, need);
-    if ((uintptr_t)ws_dev % 16) return fail(SMK_E_ARG, "smk_mask_rbox: workspace must be 16-byte aligned");
-    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
-    char *w = (char *)ws_dev;
-    RboxHdr *hdr = (RboxHdr *)w;                       w += rup256(b * sizeof(RboxHdr));
-    int *rows = (int *)w;                              w += rup256(b * H * 2 * sizeof(int));
-    unsigned long long *bits = (unsigned long long *)w; w += rup256(b * H * Wq * 8);
-    int *parent = (int *)w;
-    const int GRID_Y = 32768;                          // streams per launch (grid.y)
-    for (int b0 = 0; b0 < B; b0 += GRID_Y) {
-        RboxParams p;
-        p.mask = mask_dev + (size_t)b0 * H * W;
-        p.B = B - b0 < GRID_Y ? B - b0 : GRID_Y;
-        p.W = W; p.H = H; p.Wq = (int)Wq; p.Wh = (int)Wh;
-        p.min_area = min_area;
-        p.hdr = hdr + b0; p.rows = rows + (size_t)b0 * H * 2; p.bits = bits + (size_t)b0 * H * Wq;
-        p.parent = parent + (size_t)b0 * H * Wh;
-        p.out = out_dev + (size_t)b0 * 12;
-        if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
-    }
-    return 0;
-}
-
-// ---- tracker state on the device (tools/test.py:173-311; tracker_state.hip / tracker_state.h) ---------------------------
-size_t smk_trk_state_bytes(int B) { return B < 1 ? 0 : (size_t)B * (sizeof(smk_trk_stream) + 2 * sizeof(double)); }
-
-static int trk_cfg_check(const char *who, const smk_trk_cfg *cfg) {
-    if (!cfg) return fail(SMK_E_ARG, "%s: null configuration", who);
-    if (cfg->exemplar_size < 1 || cfg->instance_size < cfg->exemplar_size || cfg->total_stride < 1 || cfg->base_size < 0 ||
-        cfg->score_size < 1 || cfg->score_size > 1024 || cfg->mask_size < 1)
-        return fail(SMK_E_ARG, "%s: bad configuration", who);
-    return 0;
-}
-
-int smk_trk_set(void *state_dev, int B, const double *target_pos, const double *target_sz, const uint8_t *avg_bgr, int im_w,
-                int im_h, void *stream) {
-    if (!state_dev || !target_pos || !target_sz || !avg_bgr) return fail(SMK_E_ARG, "smk_trk_set: null argument");
-    if (B < 1 || im_w < 1 || im_h < 1) return fail(SMK_E_ARG, "smk_trk_set: bad geometry");
-    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_set: the state block must be 8-byte aligned");
-    for (int b0 = 0; b0 < B; b0 += TRK_SET_MAX_B) {
-        TrkSetArgs a;
-        memset(&a, 0, sizeof(a));
-        a.n = B - b0 < TRK_SET_MAX_B ? B - b0 : TRK_SET_MAX_B;
-        a.im_w = im_w; a.im_h = im_h;
-        for (int i = 0; i < a.n; ++i)
-            for (int k = 0; k < 2; ++k) {
-                a.pos[i][k] = target_pos[2 * (b0 + i) + k];
-                a.sz[i][k] = target_sz[2 * (b0 + i) + k];
-            }
-        for (int i = 0; i < a.n; ++i)
-            for (int k = 0; k < 3; ++k) a.avg[i][k] = avg_bgr[3 * (b0 + i) + k];
-        if (launch_trk_set((smk_trk_stream *)state_dev + b0, a, stream)) return fail(SMK_E_HIP, "trk_set launch failed");
-    }
-    return 0;
-}
-
-int smk_trk_plan(void *state_dev, int B, const smk_trk_cfg *cfg, void *stream) {
-    if (!state_dev) return fail(SMK_E_ARG, "smk_trk_plan: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_trk_plan: batch %d", B);
-    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_plan: the state block must be 8-byte aligned");
-    CHK(trk_cfg_check("smk_trk_plan", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state_dev;
-    if (launch_trk_step(st, (double *)(st + B), B, *cfg, nullptr, 0, nullptr, 2, stream)) return fail(SMK_E_HIP, "trk_step launch failed");
-    return 0;
-}
-
-int smk_trk_advance(void *state_dev, int B, const smk_trk_cfg *cfg, const double *box_dev, int slot, double *result_row_dev,
-                    int plan_next, void *stream) {
-    if (!state_dev || !box_dev) return fail(SMK_E_ARG, "smk_trk_advance: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_trk_advance: batch %d", B);
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_trk_advance: slot %d (0 or 1)", slot);
-    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_advance: the state block must be 8-byte aligned");
-    CHK(trk_cfg_check("smk_trk_advance", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state_dev;
-    if (launch_trk_step(st, (double *)(st + B), B, *cfg, box_dev, slot, result_row_dev, plan_next ? 3 : 1, stream))
-        return fail(SMK_E_HIP, "trk_step launch failed");
-    return 0;
-}
-
-int smk_trk_advance_hp(void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev, int slot,
-                       double *result_row_dev, int plan_next, void *stream) {
-    if (!state_dev || !box_dev || !hp_dev) return fail(SMK_E_ARG, "smk_trk_advance_hp: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_trk_advance_hp: batch %d", B);
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_trk_advance_hp: slot %d (0 or 1)", slot);
-    if ((uintptr_t)state_dev % 8 || (uintptr_t)hp_dev % 8)
-        return fail(SMK_E_ARG, "smk_trk_advance_hp: the state block and the hp table must be 8-byte aligned");
-    CHK(trk_cfg_check("smk_trk_advance_hp", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state_dev;
-    if (launch_trk_step(st, (double *)(st + B), B, *cfg, box_dev, slot, result_row_dev, plan_next ? 3 : 1, stream, hp_dev))
-        return fail(SMK_E_HIP, "trk_step launch failed");
-    return 0;
-}
-
-int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg) {
-    if (!state) return fail(SMK_E_ARG, "smk_host_trk_plan: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_plan: batch %d", B);
-    CHK(trk_cfg_check("smk_host_trk_plan", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state;
-    double *twh = (double *)(st + B);
-    for (int b = 0; b < B; ++b) trk_plan(st[b], *cfg, twh + 2 * b);
-    return 0;
-}
-
-int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const double *box, int slot, double *result_row,
-                         int plan_next) {
-    if (!state || !box) return fail(SMK_E_ARG, "smk_host_trk_advance: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_advance: batch %d", B);
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_host_trk_advance: slot %d (0 or 1)", slot);
-    CHK(trk_cfg_check("smk_host_trk_advance", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state;
-    double *twh = (double *)(st + B);
-    for (int b = 0; b < B; ++b) {
-        trk_advance(st[b], *cfg, cfg->lr, box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
-        if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
-    }
-    return 0;
-}
-
-int smk_host_trk_advance_hp(void *state, int B, const smk_trk_cfg *cfg, const double *hp, const double *box, int slot,
-                            double *result_row, int plan_next) {
-    if (!state || !box || !hp) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: null argument");
-    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: batch %d", B);
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: slot %d (0 or 1)", slot);
-    CHK(trk_cfg_check("smk_host_trk_advance_hp", cfg));
-    smk_trk_stream *st = (smk_trk_stream *)state;
-    double *twh = (double *)(st + B);
-    for (int b = 0; b < B; ++b) {
-        trk_advance(st[b], *cfg, hp[SMK_HP_STRIDE * b + 2], box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
-        if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
-    }
-    return 0;
-}
-
-int smk_crop_resize_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev, int B,
-                        int model_sz, float *out_dev, void *stream) {
-    if (!frames_dev || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev: null argument");
-    if (H < 1 || W < 1 || model_sz < 1 || B < 1 || B > 65535 || frame_stride_bytes < 0)
-        return fail(SMK_E_ARG, "smk_crop_resize_dev: bad geometry");
-    CropDevParams p;
-    p.frames = frames_dev; p.frame_stride = frame_stride_bytes; p.out = out_dev;
-    p.H = H; p.W = W; p.model_sz = model_sz;
-    p.st = (const smk_trk_stream *)state_dev;
-    if (launch_crop_resize_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev launch failed");
-    return 0;
-}
-
-int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
-                       int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev, float *prob_out_dev,
-                       void *stream) {
-    if ((!logits_dev && !head_dev) || !state_dev || (!mask_out_dev && !prob_out_dev))
-        return fail(SMK_E_ARG, "smk_paste_mask_dev: null argument");
-    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || B < 1 || B > 65535 || (head_dev && (score_size < 1 || score_size > 1024)))
-        return fail(SMK_E_ARG, "smk_paste_mask_dev: bad geometry");
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev: slot %d (0 or 1)", slot);
-    PasteDevParams p;
-    p.logits = head_dev ? head_dev : logits_dev;
-    p.mask_out = mask_out_dev; p.prob_out = prob_out_dev;
-    p.ms = mask_size; p.W = W; p.H = H; p.head_S = head_dev ? score_size : 0; p.slot = slot;
-    p.seg_thr = seg_thr; p.border = border;
-    p.st = (const smk_trk_stream *)state_dev;
-    if (launch_paste_mask_dev(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev launch failed");
-    return 0;
-}
-
-// ---- VOS scoring (tools/test.py:421-456 MultiBatchIouMeter per frame, fused with the paste-back; image_kernels.hip) ------------
-static_assert(VOS_MAX_OBJ == CROP_MAX_B, "smk_vos_score takes as many objects as smk_paste_labels");
-
-// the checks and the fields both entries share; everything is refused here, before anything is enqueued
-static int vos_fill(const char *who, VosParams &p, const float *src, int mask_size, int n_obj, int W, int H, float border,
-                    const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
-                    float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev) {
-    if (!src || !gt_dev || !object_ids || !thrs || !counts_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
-    if (n_obj < 1 || n_obj > VOS_MAX_OBJ) return fail(SMK_E_ARG, "%s: %d objects (1..%d)", who, n_obj, VOS_MAX_OBJ);
-    if (n_thr < 1 || n_thr > VOS_MAX_THR) return fail(SMK_E_ARG, "%s: %d thresholds (1..%d)", who, n_thr, VOS_MAX_THR);
-    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || (int64_t)W * H > INT32_MAX)
-        return fail(SMK_E_ARG, "%s: bad geometry (%d x %d frame, mask %d)", who, W, H, mask_size);
-    memset(&p, 0, sizeof(p));
-    p.logits = src; p.gt = gt_dev; p.counts = counts_out_dev; p.labels = labels_out_dev;
-    p.ms = mask_size; p.W = W; p.H = H; p.n_obj = n_obj; p.n_thr = n_thr;
-    p.seg_thr = seg_thr; p.border = border; p.alive = alive_mask;
-    for (int k = 0; k < n_thr; ++k) p.thr[k] = thrs[k];
-    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
-    return 0;
-}
-
-// given_mask / init_labels_dev of the _ex entries: bits at or above n_obj are refused, and so is a mask without the label map
-static int vos_given(const char *who, VosParams &p, int n_obj, uint32_t given_mask, const uint8_t *init_labels_dev) {
-    if (n_obj < 32 && (given_mask >> n_obj)) return fail(SMK_E_ARG, "%s: given_mask %#x has bits at or above %d objects", who, given_mask, n_obj);
-    if (given_mask && !init_labels_dev) return fail(SMK_E_ARG, "%s: given_mask without init_labels_dev", who);
-    p.given = given_mask;
-    p.init_labels = given_mask ? init_labels_dev : nullptr;
-    return 0;
-}
-
-int smk_vos_score(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
-                  const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
-                  float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, void *stream) {
-    return smk_vos_score_ex(logits_dev, mask_size, inv_map, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
-                            seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
-}
-
-int smk_vos_score_ex(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
-                     const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
-                     float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, uint32_t given_mask,
-                     const uint8_t *init_labels_dev, void *stream) {
-    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_score: null argument");
-    VosParams p;
-    CHK(vos_fill("smk_vos_score", p, logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
-                 seg_thr, counts_out_dev, labels_out_dev));
-    CHK(vos_given("smk_vos_score_ex", p, n_obj, given_mask, init_labels_dev));
-    for (int i = 0; i < n_obj; ++i)
-        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
-    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
-    return 0;
-}
-
-int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
-                      int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
-                      uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
-                      uint8_t *labels_out_dev, void *stream) {
-    return smk_vos_score_dev_ex(logits_dev, head_dev, score_size, mask_size, state_dev, slot, n_obj, W, H, border, gt_dev,
-                                object_ids, alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
-}
-
-int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
-                         int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
-                         uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
-                         uint8_t *labels_out_dev, uint32_t given_mask, const uint8_t *init_labels_dev, void *stream) {
-    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_score_dev: null argument");
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_score_dev: slot %d (0 or 1)", slot);
-    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_score_dev: score_size %d", score_size);
-    VosParams p;
-    CHK(vos_fill("smk_vos_score_dev", p, head_dev ? head_dev : logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids,
-                 alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev));
-    CHK(vos_given("smk_vos_score_dev_ex", p, n_obj, given_mask, init_labels_dev));
-    p.head_S = head_dev ? score_size : 0; p.slot = slot;
-    p.st = (const smk_trk_stream *)state_dev;
-    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
-    return 0;
-}
-
-// ---- stream start on the device (tools/test.py:146-152,494-497; tracker_init.hip / tracker_state.h) -----------------------
-int smk_label_rects(const uint8_t *labels_dev, int W, int H, const uint8_t *object_ids, int n_obj, int32_t *rects_out_dev,
-                    void *stream) {
-    if (!labels_dev || !object_ids || !rects_out_dev) return fail(SMK_E_ARG, "smk_label_rects: null argument");
-    if (n_obj < 1 || n_obj > RECT_MAX_OBJ) return fail(SMK_E_ARG, "smk_label_rects: %d objects (1..%d)", n_obj, RECT_MAX_OBJ);
-    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_label_rects: bad geometry (%d x %d, 1..32768)", W, H);
-    if ((uintptr_t)rects_out_dev % 4) return fail(SMK_E_ARG, "smk_label_rects: rects_out_dev must be 4-byte aligned");
-    LabelRectsParams p;
-    memset(&p, 0, sizeof(p));
-    p.labels = labels_dev; p.rects = rects_out_dev; p.W = W; p.H = H; p.n_obj = n_obj;
-    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
-    if (launch_label_rects(p, stream)) return fail(SMK_E_HIP, "label_rects launch failed");
-    return 0;
-}
-
-int smk_frame_sums(const uint8_t *frames_dev, int64_t frame_stride_bytes, int n, int H, int W, uint64_t *sums_out_dev,
-                   void *stream) {
-    if (!frames_dev || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums: null argument");
-    if (n < 1 || n > 65535 || frame_stride_bytes < 0) return fail(SMK_E_ARG, "smk_frame_sums: %d frames (1..65535), stride %lld", n, (long long)frame_stride_bytes);
-    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_frame_sums: bad geometry (%d x %d, 1..32768)", W, H);
-    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums: sums_out_dev must be 8-byte aligned");
-    FrameSumsParams p;
-    p.frames = frames_dev; p.stride = (long)frame_stride_bytes; p.sums = (unsigned long long *)sums_out_dev;
-    p.bytes = (long)H * W * 3; p.n = n;
-    if (launch_frame_sums(p, stream)) return fail(SMK_E_HIP, "frame_sums launch failed");
-    return 0;
-}
-
-// the checks and the kernarg smk_trk_start and smk_host_trk_start share
-static int trk_start_fill(const char *who, TrkStartArgs &a, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
-                          const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
-                          int64_t sums_stride, int im_w, int im_h, int32_t *win_out, double *result_out) {
-    if (!state || !sums || !win_out || !result_out) return fail(SMK_E_ARG, "%s: null argument", who);
-    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
-    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, start_mask, B);
-    if ((rects != nullptr) == (pos_host != nullptr || sz_host != nullptr) || ((pos_host != nullptr) != (sz_host != nullptr)))
-        return fail(SMK_E_ARG, "%s: exactly one of the device rectangles and the host position / size pair is given", who);
-    if (im_w < 1 || im_h < 1 || im_w > 32768 || im_h > 32768) return fail(SMK_E_ARG, "%s: bad geometry (%d x %d, 1..32768)", who, im_w, im_h);
-    if (sums_stride < 0) return fail(SMK_E_ARG, "%s: sums_stride %lld", who, (long long)sums_stride);
-    if ((uintptr_t)state % 8 || (uintptr_t)sums % 8 || (uintptr_t)result_out % 8 || (uintptr_t)win_out % 4 || (uintptr_t)rects % 4)
-        return fail(SMK_E_ARG, "%s: misaligned argument", who);
-    CHK(trk_cfg_check(who, cfg));
-    memset(&a, 0, sizeof(a));
-    a.cfg = *cfg; a.rects = rects; a.sums = (const unsigned long long *)sums; a.sums_stride = (long)sums_stride;
-    a.win = win_out; a.res = result_out; a.mask = start_mask; a.B = B; a.im_w = im_w; a.im_h = im_h;
-    if (pos_host)
-        for (int b = 0; b < B; ++b)
-            for (int k = 0; k < 2; ++k) {
-                a.pos[b][k] = pos_host[2 * b + k];
-                a.sz[b][k] = sz_host[2 * b + k];
-            }
-    return 0;
-}
-
-int smk_trk_start(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
-                  const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride, int im_w, int im_h,
-                  int32_t *win_out_dev, double *result_out_dev, void *stream) {
-    TrkStartArgs a;
-    CHK(trk_start_fill("smk_trk_start", a, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride, im_w,
-                       im_h, win_out_dev, result_out_dev));
-    smk_trk_stream *st = (smk_trk_stream *)state_dev;
-    if (launch_trk_start(st, (double *)(st + B), a, stream)) return fail(SMK_E_HIP, "trk_start launch failed");
-    return 0;
-}
-
-// trk_start on host memory for the streams of the mask; im_wh != nullptr: stream b on a frame of im_wh[2 b], im_wh[2 b + 1]
-static void trk_start_host(const TrkStartArgs &a, smk_trk_stream *st, const smk_trk_cfg &cfg, const int32_t *im_wh) {
-    double *twh = (double *)(st + a.B);
-    for (int b = 0; b < a.B; ++b) {
-        if (!((a.mask >> b) & 1)) continue;
-        double px, py, w, h;
-        if (a.rects) {
-            const int32_t *r = a.rects + 4 * b;
-            w = (double)r[2]; h = (double)r[3];
-            px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
-        } else {
-            px = a.pos[b][0]; py = a.pos[b][1]; w = a.sz[b][0]; h = a.sz[b][1];
-        }
-        trk_start(st[b], cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, im_wh ? im_wh[2 * b] : a.im_w,
-                  im_wh ? im_wh[2 * b + 1] : a.im_h, a.win + 3 * b, a.res + TRK_START_ROW * b, twh + 2 * b);
-    }
-}
-
-int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
-                       const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,
-                       double *result_out) {
-    TrkStartArgs a;
-    CHK(trk_start_fill("smk_host_trk_start", a, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_w, im_h, win_out,
-                       result_out));
-    trk_start_host(a, (smk_trk_stream *)state, *cfg, nullptr);
-    return 0;
-}
-
-int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev,
-                          const int32_t *win_dev, const double *result_dev, uint32_t start_mask, int B, int model_sz,
-                          float *z_all_dev, void *stream) {
-    if (!frames_dev || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: null argument");
-    if (H < 1 || W < 1 || H > 32768 || W > 32768 || model_sz < 1 || model_sz > 65535 || B < 1 || B > TRK_SET_MAX_B || frame_stride_bytes < 0)
-        return fail(SMK_E_ARG, "smk_crop_exemplar_dev: bad geometry");
-    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: start_mask %#x has bits at or above %d streams", start_mask, B);
-    CropExemplarParams p;
-    p.frames = frames_dev; p.frame_stride = (long)frame_stride_bytes; p.out = z_all_dev;
-    p.H = H; p.W = W; p.model_sz = model_sz;
-    p.st = (const smk_trk_stream *)state_dev; p.win = win_dev; p.res = result_dev; p.mask = start_mask;
-    if (launch_crop_exemplar_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev launch failed");
-    return 0;
-}
-
-// ---- VOT overlap (tools/test.py:354 vot_overlap; vot_overlap.hip / vot_overlap.h) ------------------------------------------
-int smk_vot_overlap(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev, int B, int im_w,
-                    int im_h, float *overlap_dev, int32_t *counts_dev, void *stream) {
-    if (!gt_dev || !overlap_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap: null argument");
-    if (pred_dev && pred_stride != 8 && pred_stride != 12)
-        return fail(SMK_E_ARG, "smk_vot_overlap: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
-    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap: %d pairs (1..65535)", B);
-    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
-        return fail(SMK_E_ARG, "smk_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
-    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)overlap_dev % 4 ||
-        (uintptr_t)counts_dev % 4)
-        return fail(SMK_E_ARG, "smk_vot_overlap: misaligned argument");
-    VotParams p;
-    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
-    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = im_w; p.im_h = im_h;
-    if (launch_vot_overlap(p, stream)) return fail(SMK_E_HIP, "vot_overlap launch failed");
-    return 0;
-}
-
-int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, int im_h, float *overlap, int32_t *counts) {
-    if (!pred || !gt || !overlap) return fail(SMK_E_ARG, "smk_host_vot_overlap: null argument");
-    if (n < 1) return fail(SMK_E_ARG, "smk_host_vot_overlap: %d pairs", n);
-    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
-        return fail(SMK_E_ARG, "smk_host_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
-    for (int i = 0; i < n; ++i)                                        // the annotation is the reference's first polygon (:354)
-        overlap[i] = vot_overlap_serial(gt + 8 * (size_t)i, pred + 8 * (size_t)i, im_w, im_h, counts ? counts + 4 * (size_t)i : nullptr);
-    return 0;
-}
-
-// ---- streams with their own frame sizes (image_kernels.hip, tracker_init.hip, vot_overlap.hip) ---------------------------------
-// the refs of the streams of `mask`, checked and copied into the kernarg; -> the largest h among them through max_h (may be null)
-static int image_refs_fill(const char *who, smk_image_ref *dst, const smk_image_ref *src, int B, uint32_t mask, int *max_h) {
-    if (!src) return fail(SMK_E_ARG, "%s: null argument", who);
-    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
-    if (B < 32 && (mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, mask, B);
-    memset(dst, 0, sizeof(smk_image_ref) * TRK_SET_MAX_B);
-    int mh = 0;
-    for (int b = 0; b < B; ++b) {
-        if (!((mask >> b) & 1)) continue;
-        const smk_image_ref &r = src[b];
-        if (!r.data) return fail(SMK_E_ARG, "%s: image %d has no data", who, b);
-        if (r.w < 1 || r.h < 1 || r.w > 32768 || r.h > 32768) return fail(SMK_E_ARG, "%s: image %d is %d x %d (1..32768)", who, b, r.w, r.h);
-        if (r.row_bytes < 3 * (int64_t)r.w) return fail(SMK_E_ARG, "%s: image %d: row_bytes %lld < 3 * %d", who, b, (long long)r.row_bytes, r.w);
-        dst[b] = r;
-        mh = r.h > mh ? r.h : mh;
-    }
-    if (max_h) *max_h = mh;
-    return 0;
-}
-static uint32_t all_streams(int B) { return B >= 32 ? 0xffffffffu : (B < 1 ? 0u : (1u << B) - 1u); }
-
-int smk_crop_resize_dev_v(const smk_image_ref *images_host, const void *state_dev, int B, int model_sz, float *out_dev, void *stream) {
-    if (!images_host || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: null argument");
-    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: model_sz %d", model_sz);
-    CropVParams p;
-    CHK(image_refs_fill("smk_crop_resize_dev_v", p.im, images_host, B, all_streams(B), nullptr));
-    p.out = out_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
-    p.win = nullptr; p.res = nullptr; p.mask = 0;
-    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev_v launch failed");
-    return 0;
-}
-
-int smk_crop_exemplar_dev_v(const smk_image_ref *images_host, const void *state_dev, const int32_t *win_dev,
-                            const double *result_dev, uint32_t start_mask, int B, int model_sz, float *z_all_dev, void *stream) {
-    if (!images_host || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: null argument");
-    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: model_sz %d", model_sz);
-    CropVParams p;
-    CHK(image_refs_fill("smk_crop_exemplar_dev_v", p.im, images_host, B, start_mask, nullptr));
-    p.out = z_all_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
-    p.win = win_dev; p.res = result_dev; p.mask = start_mask;
-    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev_v launch failed");
-    return 0;
-}
-
-int smk_frame_sums_v(const smk_image_ref *images_host, int n, uint64_t *sums_out_dev, void *stream) {
-    if (!images_host || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums_v: null argument");
-    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums_v: sums_out_dev must be 8-byte aligned");
-    FrameSumsVParams p;
-    CHK(image_refs_fill("smk_frame_sums_v", p.im, images_host, n, all_streams(n), &p.max_h));
-    p.sums = (unsigned long long *)sums_out_dev; p.n = n;
-    if (launch_frame_sums_v(p, stream)) return fail(SMK_E_HIP, "frame_sums_v launch failed");
-    return 0;
-}
-
-// the checks and the kernarg smk_trk_start_v and smk_host_trk_start_v share: trk_start_fill's, with a size per stream of the mask
-static int trk_start_fill_v(const char *who, TrkStartVArgs &v, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
-                            const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
-                            int64_t sums_stride, const int32_t *im_wh, int32_t *win_out, double *result_out) {
-    if (!im_wh) return fail(SMK_E_ARG, "%s: null argument", who);
-    CHK(trk_start_fill(who, v.a, state, B, cfg, start_mask, rects, pos_host, sz_host, sums, sums_stride, 1, 1, win_out, result_out));
-    memset(v.im_wh, 0, sizeof(v.im_wh));
-    for (int b = 0; b < B; ++b) {
-        if (!((start_mask >> b) & 1)) continue;
-        const int w = im_wh[2 * b], h = im_wh[2 * b + 1];
-        if (w < 1 || h < 1 || w > 32768 || h > 32768) return fail(SMK_E_ARG, "%s: bad geometry of stream %d (%d x %d, 1..32768)", who, b, w, h);
-        v.im_wh[b][0] = w; v.im_wh[b][1] = h;
-    }
-    v.a.im_w = 0; v.a.im_h = 0;
-    return 0;
-}
-
-int smk_trk_start_v(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
-                    const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride,
-                    const int32_t *im_wh_host, int32_t *win_out_dev, double *result_out_dev, void *stream) {
-    TrkStartVArgs v;
-    CHK(trk_start_fill_v("smk_trk_start_v", v, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride,
-                         im_wh_host, win_out_dev, result_out_dev));
-    smk_trk_stream *st = (smk_trk_stream *)state_dev;
-    if (launch_trk_start_v(st, (double *)(st + B), v, stream)) return fail(SMK_E_HIP, "trk_start_v launch failed");
-    return 0;
-}
-
-int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
-                         const double *sz, const uint64_t *sums, int64_t sums_stride, const int32_t *im_wh, int32_t *win_out,
-                         double *result_out) {
-    TrkStartVArgs v;
-    CHK(trk_start_fill_v("smk_host_trk_start_v", v, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_wh, win_out,
-                         result_out));
-    trk_start_host(v.a, (smk_trk_stream *)state, *cfg, &v.im_wh[0][0]);
-    return 0;
-}
-
-int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
-                         int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, float seg_thr, float border,
-                         uint8_t *canvas_out_dev, void *stream) {
-    if ((!logits_dev && !head_dev) || !state_dev || !canvas_out_dev) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: null argument");
-    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: %d streams (1..%d)", B, TRK_SET_MAX_B);
-    if (canvas_w < 1 || canvas_h < 1 || canvas_h > 65535 || mask_size < 1 || (head_dev && (score_size < 1 || score_size > 1024)))
-        return fail(SMK_E_ARG, "smk_paste_mask_dev_v: bad geometry");
-    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: slot %d (0 or 1)", slot);
-    if (im_wh_host)
-        for (int b = 0; b < B; ++b)
-            if (im_wh_host[2 * b] > canvas_w || im_wh_host[2 * b + 1] > canvas_h)
-                return fail(SMK_E_ARG, "smk_paste_mask_dev_v: stream %d is %d x %d, the canvas %d x %d", b, im_wh_host[2 * b],
-                            im_wh_host[2 * b + 1], canvas_w, canvas_h);
-    PasteDevParams p;
-    p.logits = head_dev ? head_dev : logits_dev;
-    p.mask_out = canvas_out_dev; p.prob_out = nullptr;
-    p.ms = mask_size; p.W = canvas_w; p.H = canvas_h; p.head_S = head_dev ? score_size : 0; p.slot = slot;
-    p.seg_thr = seg_thr; p.border = border;
-    p.st = (const smk_trk_stream *)state_dev;
-    if (launch_paste_mask_dev_v(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev_v launch failed");
-    return 0;
-}
-
-int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
-                        const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
-    if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");
-    if (pred_dev && pred_stride != 8 && pred_stride != 12)
-        return fail(SMK_E_ARG, "smk_vot_overlap_dev: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
-    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap_dev: %d pairs (1..65535)", B);
-    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)state_dev % 8 ||
-        (uintptr_t)overlap_dev % 4 || (uintptr_t)counts_dev % 4)
-        return fail(SMK_E_ARG, "smk_vot_overlap_dev: misaligned argument");
-    VotParams p;
-    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
-    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = 0; p.im_h = 0;
-    if (launch_vot_overlap_dev(p, state_dev, stream)) return fail(SMK_E_HIP, "vot_overlap_dev launch failed");
-    return 0;
-}
-
-// time repeated launches of one conv geometry (operands are pseudo-random, not zeros: DVFS hygiene)
-int smk_bench_conv(int dtype, int algo, const smk_conv_geom *g, int with_res, int iters, float *usec_out,
-                   void *stream) {
-    if (!g || !usec_out || iters < 1) return fail(SMK_E_ARG, "smk_bench_conv: bad argument");
-    if (dtype != DT_F32 && dtype != DT_F16) return fail(SMK_E_ARG, "bad dtype");
-    hipStream_t s = (hipStream_t)stream;
-    PackedConv pc; Act in; ConvOpt o; int Ho, Wo;
-    CHK(fill_geom(g, pc, in, o, Ho, Wo));
-    const size_t es = esize(dtype);
-    TmpBufs tmp;
-    // SMK_BENCH_FILL (measurement aid): what the ACTIVATIONS hold -- uniform [-1, 1) (default), "zero", "relu" (negative values -> 0).  The
-    // matrix pipes' clock under load depends on the operand bits (MI355X_MICROARCH.md: zero-filled operands +15..21 % TF/s).
-    const char *fm = getenv("SMK_BENCH_FILL");
-    const int fill_mode = !fm ? 0 : (!strcmp(fm, "zero") ? 1 : (!strcmp(fm, "relu") ? 2 : 0));
-    auto fill = [&](void **dst, size_t elems, float scale, unsigned seed) -> int {
-        CHK(tmp.alloc(dst, elems * es));
-        std::vector<unsigned char> h(elems * es);
-        unsigned st = seed * 2654435761u + 12345u;
-        for (size_t i = 0; i < elems; ++i) {
-            st = st * 1664525u + 1013904223u;
-            float v = ((int)((st >> 9) & 0xffff) - 32768) * (scale / 32768.f);
-            if (seed == 1 && fill_mode == 1) v = 0.f;                       // SMK_BENCH_FILL=zero: activations all zero
-            if (seed == 1 && fill_mode == 2) v = v > 0.f ? v : 0.f;         // SMK_BENCH_FILL=relu: half of them zero, like a ReLU output
-            if (dtype == DT_F16) ((_Float16 *)h.data())[i] = (_Float16)v; else ((float *)h.data())[i] = v;
-        }
-        HIPCHK(hipMemcpy(*dst, h.data(), elems * es, hipMemcpyHostToDevice));
-        return 0;
-    };
-    CHK(fill(&in.p, (size_t)g->B * g->H * g->W * in.C, 1.0f, 1));
-    CHK(fill(&pc.w, (size_t)pc.rows * pc.Kpad, 0.05f, 2));
-    CHK(tmp.alloc((void **)&pc.bias, (size_t)pc.rows * 4));
-    int *pos_dev = nullptr;
-    if (g->pos_mul) {
-        CHK(tmp.alloc((void **)&pos_dev, sizeof(int) * 2 * g->B));
-        std::vector<int> ph(2 * g->B);
-        for (int i = 0; i < 2 * g->B; ++i) ph[i] = 8 + (i * 5) % 9;
-        HIPCHK(hipMemcpy(pos_dev, ph.data(), ph.size() * 4, hipMemcpyHostToDevice));
-        o.pos = pos_dev;
-    }
-    const int mode = algo & 0xff;
-    if (mode == 5 || mode == 7) pc.w_frag = pc.w;       // timing only: the fragment order is irrelevant
-    Act out, res;
-    out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8);
-    float *nchw = nullptr;
-    const bool nchw_mode = mode == 2 || mode == 7;
-    if (nchw_mode) {
-        CHK(tmp.alloc((void **)&nchw, (size_t)g->B * g->Cout * Ho * Wo * 4));
-        o.nchw_out = nchw;
-    } else {
-        CHK(tmp.alloc(&out.p, (size_t)g->B * Ho * Wo * out.C * es));
-        if (with_res) {
-            res = out;
-            CHK(fill(&res.p, (size_t)g->B * Ho * Wo * out.C, 1.0f, 3));
-            o.res = &res; o.res_mode = RES_PRE_RELU;
-        }
-    }
-    ConvEnv env;
-    env.dtype = dtype;
-    HIPCHK(hipGetDevice(&env.device));
-    CHK(op_ks_scratch(env));
-    ConvParams p;
-    CHK(conv_params(env, pc, in, nchw_mode ? nullptr : &out, g->B, o, p));
-    ConvPlan pl;
-    const int prc = plan_from_algo(mode == 1 || mode == 3 ? algo & ~0xff : algo, p, dtype, pl);     // (no naive kernel here: 1 / 3 time the MFMA one)
-    if (prc < 0) return fail(SMK_E_ARG, "smk_bench_conv: wreg tile code 1..8");
-    if (prc && pl.kind == CK_HALO) return fail(SMK_E_HIP, "conv launch failed or geometry not eligible");
-    if (prc) return fail(SMK_E_ARG, "smk_bench_conv: not eligible for %s", pl.kind == CK_WREG ? "conv_wreg_kernel" : (pl.kind == CK_MHEAD ? "mask_head_kernel" : "conv_pp_kernel"));
-    auto launch = [&]() {
-        ConvBatch cb;                                    // (a launcher writes its grid layout into the batch)
-        cb.n = 1;
-        cb.p[0] = p;
-        return launch_plan(pl, cb, p.wgt, dtype, s, "conv");     // (halo kernel, timing only: the K order is irrelevant)
-    };
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int i = 0; i < 3; ++i) CHK(launch());
-    HIPCHK(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) CHK(launch());
-    HIPCHK(hipEventRecord(e1, s));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *usec_out = ms * 1000.f / iters;
-    return 0;
-}
-
-// host-only walk of the packed matrix + the kernels' gather function (no GPU needed)
-int smk_host_conv2d_ex(const smk_conv_geom *g, const float *x, const float *w, const float *b, const float *res,
-                       const int32_t *pos, float *y) {
-    if (!g || !x || !w || !y) return fail(SMK_E_ARG, "smk_host_conv2d_ex: null argument");
-    PackedConv pc; Act in; ConvOpt o; int Ho, Wo;
-    CHK(fill_geom(g, pc, in, o, Ho, Wo));
-    std::vector<float> rows, bias;
-    pack_host(g, pc, w, b, rows, bias);
-    // NCHW -> NHWC (channel padded) on the host, mirroring cvt_in_kernel
-    std::vector<float> xin((size_t)g->B * g->H * g->W * in.C, 0.f);
-    for (int bb = 0; bb < g->B; ++bb)
-        for (int c = 0; c < g->Cin; ++c)
-            for (int yy = 0; yy < g->H; ++yy)
-                for (int xx = 0; xx < g->W; ++xx)
-                    xin[(((size_t)bb * g->H + yy) * g->W + xx) * in.C + c] =
-                        x[(((size_t)bb * g->Cin + c) * g->H + yy) * g->W + xx];
-    in.p = xin.data();
-    pc.w = rows.data();
-    pc.bias = bias.data();
-    o.pos = pos;
-    Act out;
-    out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8);
-    std::vector<float> obuf((size_t)g->B * Ho * Wo * out.C, 0.f);
-    out.p = obuf.data();
-    ConvEnv env;
-    env.device = -1;
-    ConvParams p;
-    CHK(conv_params(env, pc, in, &out, g->B, o, p));
-    for (int m = 0; m < p.M; ++m) {
-        const RowInfo r = row_info(p, m, p.pos);
-        for (int n = 0; n < g->Cout; ++n) {
-            double acc = 0.0;
-            for (int kvec = 0; kvec < p.K; kvec += 4) {
-                const KDecode d = decode_k(kvec, p.Ci, p.kw);
-                const long off = gather_offset(p, r, d, p.cin_off);
-                if (off < 0) continue;
-                for (int e = 0; e < 4; ++e) acc += (double)xin[off + e] * (double)rows[(size_t)n * p.Kpad + kvec + e];
-            }
-            double v = acc + bias[n];
-            const int hw = Ho * Wo, bb = m / hw, ps = m - bb * hw;
-            const double rv = (res && g->res_mode) ? res[((size_t)bb * g->Cout + n) * hw + ps] : 0.0;
-            if (g->res_mode == RES_PRE_RELU) v += rv;
-            if (g->relu) v = v > 0 ? v : 0;
-            if (g->res_mode == RES_POST_RELU) v += rv;
-            y[((size_t)bb * g->Cout + n) * hw + ps] = (float)v;
-        }
-    }
-    return 0;
-}
-
-// the pack the packer would make, with every derived copy it would make (host-only planning: nothing is dereferenced)
-static void fake_pack(PackedConv &pc, int dtype) {
-    static float dummy[64];
-    pc.w = dummy; pc.bias = dummy;
-    if (has_frag_pack(pc, dtype)) pc.w_frag = dummy;
-    if (has_frag16_pack(pc, dtype)) pc.w_frag16 = dummy;
-    if (has_halo_pack(pc, dtype)) pc.w_halo = dummy;
-    if (has_frag_halo_pack(pc, dtype)) pc.w_frag_halo = dummy;
-}
-
-// Which kernel and workgroup shape does the engine pick for one convolution of this geometry?  Host only (CPU tests pin the
-// measured layer rules with it): plan_conv, as run_conv calls it, on a pack whose derived copies are the ones the packer would
-// make, for the MI355X's 256 CUs; *seq_cfg = the conv_seq_kernel tile code the layer gets inside a persistent sequence, or -1
-// when it cannot be part of one.
-int smk_host_plan_conv(const smk_conv_geom *g, int dtype, int with_res, int *kernel, int *bm, int *bn, int *seq_cfg) {
-    if (!g || !kernel || !bm || !bn || !seq_cfg) return fail(SMK_E_ARG, "smk_host_plan_conv: null argument");
-    if (dtype != DT_F32 && dtype != DT_F16) return fail(SMK_E_ARG, "smk_host_plan_conv: dtype");
-    PackedConv pc; Act in; ConvOpt o; int Ho, Wo;
-    CHK(fill_geom(g, pc, in, o, Ho, Wo));
-    static float dummy[64];
-    in.p = dummy;
-    fake_pack(pc, dtype);
-    Act out, res;
-    out.H = Ho; out.W = Wo; out.C = rup(g->Cout, 8); out.p = dummy;
-    res = out;
-    if (with_res) { o.res = &res; o.res_mode = RES_PRE_RELU; }
-    ConvEnv env;
-    env.device = -1;
-    env.dtype = dtype;
-    ConvParams p;
-    CHK(conv_params(env, pc, in, &out, g->B, o, p));
-    const ConvPlan pl = plan_conv(p, o, pc, dtype, g->B, MI355X_CUS);
-    switch (pl.kind) {
-    case CK_PP: *kernel = 3; *bm = 256; *bn = 256; break;
-    case CK_WREG: *kernel = 2; *bm = WREG_TILE[pl.wreg][0]; *bn = WREG_TILE[pl.wreg][1]; break;
-    case CK_HALO: *kernel = 1; *bm = pl.halo_bm; *bn = 128; break;
-    default: *kernel = 0; *bm = pl.tile.bm; *bn = pl.tile.bn;
-    }
-    SeqLayer L;
-    *seq_cfg = seq_layer_from(p, dtype, L) ? (int)L.cfg : -1;
-    return 0;
-}
-
-// The marks plan_seq puts on an smk_op_conv_seq list of up to 4 * SEQ_MAX layers (launched as SEQ_MAX slices) on a grid of
-// `grid` workgroups.  Host only: the records are smk_op_conv_seq's, on distinct fake tensors and fake packs with the copies the
-// packer would make.  The "last launch" diagnostics are left alone.
-int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *sync, int *a_stage) {
-    if (!ops || n < 1 || n > 4 * SEQ_MAX || grid < 8 || grid % 8 || !cfg || !sync || !a_stage)
-        return fail(SMK_E_ARG, "smk_host_plan_seq: bad argument (1..%d layers, a grid of whole teams)", 4 * SEQ_MAX);
-    static char tensors[4 * SEQ_MAX + 1];             // one address per tensor: the list input, then the layers' outputs
-    Act xin;
-    xin.H = ops[0].g.H; xin.W = ops[0].g.W; xin.C = rup(ops[0].g.Cin, 8); xin.p = tensors;
-    int next = 1;
-    std::vector<SeqRec> rec;
-    std::vector<Act> outs;
-    CHK(seq_op_records(ops, n, xin, -1, [](int, PackedConv &pc) { fake_pack(pc, DT_F16); return 0; },
-                       [&](void **p, size_t) { *p = tensors + next++; return 0; }, rec, outs));
-    plan_seq_ops(ops, rec, outs, grid);
-    for (int i = 0; i < n; ++i) {
-        cfg[i] = rec[i].L.cfg;
-        sync[i] = rec[i].L.sync;
-        a_stage[i] = rec[i].L.a_stage;
-    }
-    return 0;
 }
 
 // What build_arena (pipe_depth 0) and smk_set_pipeline allocate for a context of this kind, from the ARENA table: elements per image, one plane

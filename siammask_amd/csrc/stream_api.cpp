@@ -1,0 +1,599 @@
+// stream_api.cpp -- the stateless product ABI either side of the network (include/siammask_hip.h): crop / paste / labels,
+// smk_mask_rbox, the tracker state on the device (smk_trk_*), VOS scoring, stream start, the VOT overlap, the *_v entries for
+// streams with their own frame sizes -- argument checks and kernargs, one launch each -- and the smk_host_* entries that run the
+// device code's inline functions (tracker_state.h, vot_overlap.h) on the CPU for the bit-exact host tests.
+#include <cstdint>
+#include <cstring>
+
+#include "../../include/siammask_hip_test.h"
+#include "engine_internal.h"
+#include "tracker_state.h"
+#include "vot_overlap.h"
+
+using namespace smk;
+
+extern "C" {
+
+// ---- image ops either side of the network ------------------------------
+int smk_crop_resize(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const int32_t *boxes,
+                    const uint8_t *avg_bgr, int B, int model_sz, float *out_dev, void *stream) {
+    if (!frames_dev || !boxes || !avg_bgr || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize: null argument");
+    if (H < 1 || W < 1 || model_sz < 1 || B < 1) return fail(SMK_E_ARG, "smk_crop_resize: bad geometry");
+    for (int b0 = 0; b0 < B; b0 += CROP_MAX_B) {
+        const int nb = B - b0 < CROP_MAX_B ? B - b0 : CROP_MAX_B;
+        CropParams p;
+        memset(&p, 0, sizeof(p));
+        p.frames = frames_dev + (size_t)b0 * frame_stride_bytes;
+        p.frame_stride = frame_stride_bytes;
+        p.out = out_dev + (size_t)b0 * 3 * model_sz * model_sz;
+        p.H = H; p.W = W; p.model_sz = model_sz;
+        for (int i = 0; i < nb; ++i) {
+            const int32_t *bx = boxes + 3 * (b0 + i);
+            if (bx[2] < 1 || bx[2] > 32768) return fail(SMK_E_ARG, "smk_crop_resize: window size %d out of range", bx[2]);
+            p.box[i][0] = bx[0]; p.box[i][1] = bx[1]; p.box[i][2] = bx[2];
+            for (int k = 0; k < 3; ++k) p.avg[i][k] = avg_bgr[3 * (b0 + i) + k];
+        }
+        if (launch_crop_resize(p, nb, stream)) return fail(SMK_E_HIP, "crop_resize launch failed");
+    }
+    return 0;
+}
+
+int smk_paste_mask(const float *logits_dev, int mask_size, const double *inv_map, int B, int W, int H, float seg_thr,
+                   float border, uint8_t *mask_out_dev, float *prob_out_dev, void *stream) {
+    if (!logits_dev || !inv_map || (!mask_out_dev && !prob_out_dev)) return fail(SMK_E_ARG, "smk_paste_mask: null argument");
+    if (W < 1 || H < 1 || mask_size < 1 || B < 1) return fail(SMK_E_ARG, "smk_paste_mask: bad geometry");
+    for (int b0 = 0; b0 < B; b0 += CROP_MAX_B) {
+        const int nb = B - b0 < CROP_MAX_B ? B - b0 : CROP_MAX_B;
+        PasteParams p;
+        memset(&p, 0, sizeof(p));
+        p.logits = logits_dev + (size_t)b0 * mask_size * mask_size;
+        p.mask_out = mask_out_dev ? mask_out_dev + (size_t)b0 * H * W : nullptr;
+        p.prob_out = prob_out_dev ? prob_out_dev + (size_t)b0 * H * W : nullptr;
+        p.ms = mask_size; p.W = W; p.H = H; p.seg_thr = seg_thr; p.border = border;
+        for (int i = 0; i < nb; ++i)
+            for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * (b0 + i) + k];
+        if (launch_paste_mask(p, nb, stream)) return fail(SMK_E_HIP, "paste_mask launch failed");
+    }
+    return 0;
+}
+
+int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H,
+                     float seg_thr, float border, uint8_t *labels_out_dev, void *stream) {
+    if (!logits_dev || !inv_map || !labels_out_dev) return fail(SMK_E_ARG, "smk_paste_labels: null argument");
+    if (W < 1 || H < 1 || mask_size < 1 || n_obj < 1 || n_obj > CROP_MAX_B)
+        return fail(SMK_E_ARG, "smk_paste_labels: bad geometry (1..%d objects)", CROP_MAX_B);
+    PasteParams p;
+    memset(&p, 0, sizeof(p));
+    p.logits = logits_dev; p.mask_out = labels_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.seg_thr = seg_thr; p.border = border;
+    for (int i = 0; i < n_obj; ++i)
+        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
+    if (launch_paste_labels(p, n_obj, stream)) return fail(SMK_E_HIP, "paste_labels launch failed");
+    return 0;
+}
+
+// ---- rotated box of the largest external contour (tools/test.py:283-300; mask_rbox.hip) ---------
+static const int RBOX_MAX_DIM = 4096;
+static inline size_t rup256(size_t x) { return (x + 255) / 256 * 256; }
+
+size_t smk_mask_rbox_workspace(int B, int W, int H) {
+    if (B < 1 || W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM) return 0;
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+    return rup256(b * sizeof(RboxHdr)) + rup256(b * H * 2 * sizeof(int)) + rup256(b * H * Wq * 8) + rup256(b * H * Wh * sizeof(int));
+}
+
+int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev, size_t ws_bytes,
+                  double *out_dev, void *stream) {
+    if (!mask_dev || !ws_dev || !out_dev) return fail(SMK_E_ARG, "smk_mask_rbox: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_mask_rbox: batch %d", B);
+    if (W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_mask_rbox: frame %d x %d outside 1..%d", W, H, RBOX_MAX_DIM);
+    if (!(min_area >= 0)) return fail(SMK_E_ARG, "smk_mask_rbox: min_area must be >= 0");
+    const size_t need = smk_mask_rbox_workspace(B, W, H);
+    if (ws_bytes < need) return fail(SMK_E_ARG, "smk_mask_rbox: workspace of %zu bytes, %zu needed", ws_bytes, need);
+    if ((uintptr_t)ws_dev % 16) return fail(SMK_E_ARG, "smk_mask_rbox: workspace must be 16-byte aligned");
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+    char *w = (char *)ws_dev;
+    RboxHdr *hdr = (RboxHdr *)w;                       w += rup256(b * sizeof(RboxHdr));
+    int *rows = (int *)w;                              w += rup256(b * H * 2 * sizeof(int));
+    unsigned long long *bits = (unsigned long long *)w; w += rup256(b * H * Wq * 8);
+    int *parent = (int *)w;
+    const int GRID_Y = 32768;                          // streams per launch (grid.y)
+    for (int b0 = 0; b0 < B; b0 += GRID_Y) {
+        RboxParams p;
+        p.mask = mask_dev + (size_t)b0 * H * W;
+        p.B = B - b0 < GRID_Y ? B - b0 : GRID_Y;
+        p.W = W; p.H = H; p.Wq = (int)Wq; p.Wh = (int)Wh;
+        p.min_area = min_area;
+        p.hdr = hdr + b0; p.rows = rows + (size_t)b0 * H * 2; p.bits = bits + (size_t)b0 * H * Wq;
+        p.parent = parent + (size_t)b0 * H * Wh;
+        p.out = out_dev + (size_t)b0 * 12;
+        if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
+    }
+    return 0;
+}
+
+// ---- tracker state on the device (tools/test.py:173-311; tracker_state.hip / tracker_state.h) ---------------------------
+size_t smk_trk_state_bytes(int B) { return B < 1 ? 0 : (size_t)B * (sizeof(smk_trk_stream) + 2 * sizeof(double)); }
+
+static int trk_cfg_check(const char *who, const smk_trk_cfg *cfg) {
+    if (!cfg) return fail(SMK_E_ARG, "%s: null configuration", who);
+    if (cfg->exemplar_size < 1 || cfg->instance_size < cfg->exemplar_size || cfg->total_stride < 1 || cfg->base_size < 0 ||
+        cfg->score_size < 1 || cfg->score_size > 1024 || cfg->mask_size < 1)
+        return fail(SMK_E_ARG, "%s: bad configuration", who);
+    return 0;
+}
+
+int smk_trk_set(void *state_dev, int B, const double *target_pos, const double *target_sz, const uint8_t *avg_bgr, int im_w,
+                int im_h, void *stream) {
+    if (!state_dev || !target_pos || !target_sz || !avg_bgr) return fail(SMK_E_ARG, "smk_trk_set: null argument");
+    if (B < 1 || im_w < 1 || im_h < 1) return fail(SMK_E_ARG, "smk_trk_set: bad geometry");
+    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_set: the state block must be 8-byte aligned");
+    for (int b0 = 0; b0 < B; b0 += TRK_SET_MAX_B) {
+        TrkSetArgs a;
+        memset(&a, 0, sizeof(a));
+        a.n = B - b0 < TRK_SET_MAX_B ? B - b0 : TRK_SET_MAX_B;
+        a.im_w = im_w; a.im_h = im_h;
+        for (int i = 0; i < a.n; ++i)
+            for (int k = 0; k < 2; ++k) {
+                a.pos[i][k] = target_pos[2 * (b0 + i) + k];
+                a.sz[i][k] = target_sz[2 * (b0 + i) + k];
+            }
+        for (int i = 0; i < a.n; ++i)
+            for (int k = 0; k < 3; ++k) a.avg[i][k] = avg_bgr[3 * (b0 + i) + k];
+        if (launch_trk_set((smk_trk_stream *)state_dev + b0, a, stream)) return fail(SMK_E_HIP, "trk_set launch failed");
+    }
+    return 0;
+}
+
+int smk_trk_plan(void *state_dev, int B, const smk_trk_cfg *cfg, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_trk_plan: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_trk_plan: batch %d", B);
+    if ((uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_trk_plan: the state block must be 8-byte aligned");
+    CHK(trk_cfg_check("smk_trk_plan", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_step(st, (double *)(st + B), B, *cfg, nullptr, 0, nullptr, 2, stream)) return fail(SMK_E_HIP, "trk_step launch failed");
+    return 0;
+}
+
+// smk_trk_advance (hp_dev == nullptr: cfg->lr for every stream) and smk_trk_advance_hp (the per-stream table, which that entry requires)
+static int trk_advance_dev(const char *who, void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev,
+                           int slot, double *result_row_dev, int plan_next, void *stream) {
+    if (!state_dev || !box_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1) return fail(SMK_E_ARG, "%s: batch %d", who, B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "%s: slot %d (0 or 1)", who, slot);
+    if ((uintptr_t)state_dev % 8 || (uintptr_t)hp_dev % 8)
+        return fail(SMK_E_ARG, "%s: the state block%s must be 8-byte aligned", who, hp_dev ? " and the hp table" : "");
+    CHK(trk_cfg_check(who, cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_step(st, (double *)(st + B), B, *cfg, box_dev, slot, result_row_dev, plan_next ? 3 : 1, stream, hp_dev))
+        return fail(SMK_E_HIP, "trk_step launch failed");
+    return 0;
+}
+
+int smk_trk_advance(void *state_dev, int B, const smk_trk_cfg *cfg, const double *box_dev, int slot, double *result_row_dev,
+                    int plan_next, void *stream) {
+    return trk_advance_dev("smk_trk_advance", state_dev, B, cfg, nullptr, box_dev, slot, result_row_dev, plan_next, stream);
+}
+
+int smk_trk_advance_hp(void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev, int slot,
+                       double *result_row_dev, int plan_next, void *stream) {
+    if (!hp_dev) return fail(SMK_E_ARG, "smk_trk_advance_hp: null argument");
+    return trk_advance_dev("smk_trk_advance_hp", state_dev, B, cfg, hp_dev, box_dev, slot, result_row_dev, plan_next, stream);
+}
+
+int smk_host_trk_plan(void *state, int B, const smk_trk_cfg *cfg) {
+    if (!state) return fail(SMK_E_ARG, "smk_host_trk_plan: null argument");
+    if (B < 1) return fail(SMK_E_ARG, "smk_host_trk_plan: batch %d", B);
+    CHK(trk_cfg_check("smk_host_trk_plan", cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) trk_plan(st[b], *cfg, twh + 2 * b);
+    return 0;
+}
+
+// the same on host memory: stream b learns at hp[SMK_HP_STRIDE b + 2], or (hp == nullptr) at cfg->lr
+static int trk_advance_host(const char *who, void *state, int B, const smk_trk_cfg *cfg, const double *hp, const double *box, int slot,
+                            double *result_row, int plan_next) {
+    if (!state || !box) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1) return fail(SMK_E_ARG, "%s: batch %d", who, B);
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "%s: slot %d (0 or 1)", who, slot);
+    CHK(trk_cfg_check(who, cfg));
+    smk_trk_stream *st = (smk_trk_stream *)state;
+    double *twh = (double *)(st + B);
+    for (int b = 0; b < B; ++b) {
+        trk_advance(st[b], *cfg, hp ? hp[SMK_HP_STRIDE * b + 2] : cfg->lr, box + 8 * b, slot, result_row ? result_row + 16 * b : nullptr);
+        if (plan_next) trk_plan(st[b], *cfg, twh + 2 * b);
+    }
+    return 0;
+}
+
+int smk_host_trk_advance(void *state, int B, const smk_trk_cfg *cfg, const double *box, int slot, double *result_row,
+                         int plan_next) {
+    return trk_advance_host("smk_host_trk_advance", state, B, cfg, nullptr, box, slot, result_row, plan_next);
+}
+
+int smk_host_trk_advance_hp(void *state, int B, const smk_trk_cfg *cfg, const double *hp, const double *box, int slot,
+                            double *result_row, int plan_next) {
+    if (!hp) return fail(SMK_E_ARG, "smk_host_trk_advance_hp: null argument");
+    return trk_advance_host("smk_host_trk_advance_hp", state, B, cfg, hp, box, slot, result_row, plan_next);
+}
+
+int smk_crop_resize_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev, int B,
+                        int model_sz, float *out_dev, void *stream) {
+    if (!frames_dev || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev: null argument");
+    if (H < 1 || W < 1 || model_sz < 1 || B < 1 || B > 65535 || frame_stride_bytes < 0)
+        return fail(SMK_E_ARG, "smk_crop_resize_dev: bad geometry");
+    CropDevParams p;
+    p.frames = frames_dev; p.frame_stride = frame_stride_bytes; p.out = out_dev;
+    p.H = H; p.W = W; p.model_sz = model_sz;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_crop_resize_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev launch failed");
+    return 0;
+}
+
+int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                       int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev, float *prob_out_dev,
+                       void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev || (!mask_out_dev && !prob_out_dev))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev: null argument");
+    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || B < 1 || B > 65535 || (head_dev && (score_size < 1 || score_size > 1024)))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev: slot %d (0 or 1)", slot);
+    PasteDevParams p;
+    p.logits = head_dev ? head_dev : logits_dev;
+    p.mask_out = mask_out_dev; p.prob_out = prob_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.seg_thr = seg_thr; p.border = border;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_paste_mask_dev(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev launch failed");
+    return 0;
+}
+
+// ---- VOS scoring (tools/test.py:421-456 MultiBatchIouMeter per frame, fused with the paste-back; image_kernels.hip) ------------
+static_assert(VOS_MAX_OBJ == CROP_MAX_B, "smk_vos_score takes as many objects as smk_paste_labels");
+
+// the checks and the fields both entries share; everything is refused here, before anything is enqueued
+static int vos_fill(const char *who, VosParams &p, const float *src, int mask_size, int n_obj, int W, int H, float border,
+                    const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                    float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev) {
+    if (!src || !gt_dev || !object_ids || !thrs || !counts_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (n_obj < 1 || n_obj > VOS_MAX_OBJ) return fail(SMK_E_ARG, "%s: %d objects (1..%d)", who, n_obj, VOS_MAX_OBJ);
+    if (n_thr < 1 || n_thr > VOS_MAX_THR) return fail(SMK_E_ARG, "%s: %d thresholds (1..%d)", who, n_thr, VOS_MAX_THR);
+    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || (int64_t)W * H > INT32_MAX)
+        return fail(SMK_E_ARG, "%s: bad geometry (%d x %d frame, mask %d)", who, W, H, mask_size);
+    memset(&p, 0, sizeof(p));
+    p.logits = src; p.gt = gt_dev; p.counts = counts_out_dev; p.labels = labels_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.n_obj = n_obj; p.n_thr = n_thr;
+    p.seg_thr = seg_thr; p.border = border; p.alive = alive_mask;
+    for (int k = 0; k < n_thr; ++k) p.thr[k] = thrs[k];
+    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
+    return 0;
+}
+
+// given_mask / init_labels_dev of the _ex entries: bits at or above n_obj are refused, and so is a mask without the label map
+static int vos_given(const char *who, VosParams &p, int n_obj, uint32_t given_mask, const uint8_t *init_labels_dev) {
+    if (n_obj < 32 && (given_mask >> n_obj)) return fail(SMK_E_ARG, "%s: given_mask %#x has bits at or above %d objects", who, given_mask, n_obj);
+    if (given_mask && !init_labels_dev) return fail(SMK_E_ARG, "%s: given_mask without init_labels_dev", who);
+    p.given = given_mask;
+    p.init_labels = given_mask ? init_labels_dev : nullptr;
+    return 0;
+}
+
+int smk_vos_score(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                  const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                  float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, void *stream) {
+    return smk_vos_score_ex(logits_dev, mask_size, inv_map, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
+                            seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
+}
+
+int smk_vos_score_ex(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                     const uint8_t *gt_dev, const uint8_t *object_ids, uint32_t alive_mask, const double *thrs, int n_thr,
+                     float seg_thr, int32_t *counts_out_dev, uint8_t *labels_out_dev, uint32_t given_mask,
+                     const uint8_t *init_labels_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_score: null argument");
+    VosParams p;
+    CHK(vos_fill("smk_vos_score", p, logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids, alive_mask, thrs, n_thr,
+                 seg_thr, counts_out_dev, labels_out_dev));
+    CHK(vos_given("smk_vos_score_ex", p, n_obj, given_mask, init_labels_dev));
+    for (int i = 0; i < n_obj; ++i)
+        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
+    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
+    return 0;
+}
+
+int smk_vos_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                      uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                      uint8_t *labels_out_dev, void *stream) {
+    return smk_vos_score_dev_ex(logits_dev, head_dev, score_size, mask_size, state_dev, slot, n_obj, W, H, border, gt_dev,
+                                object_ids, alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev, 0, nullptr, stream);
+}
+
+int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int n_obj, int W, int H, float border, const uint8_t *gt_dev, const uint8_t *object_ids,
+                         uint32_t alive_mask, const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev,
+                         uint8_t *labels_out_dev, uint32_t given_mask, const uint8_t *init_labels_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_score_dev: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_score_dev: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_score_dev: score_size %d", score_size);
+    VosParams p;
+    CHK(vos_fill("smk_vos_score_dev", p, head_dev ? head_dev : logits_dev, mask_size, n_obj, W, H, border, gt_dev, object_ids,
+                 alive_mask, thrs, n_thr, seg_thr, counts_out_dev, labels_out_dev));
+    CHK(vos_given("smk_vos_score_dev_ex", p, n_obj, given_mask, init_labels_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_score(p, stream)) return fail(SMK_E_HIP, "vos_score launch failed");
+    return 0;
+}
+
+// ---- stream start on the device (tools/test.py:146-152,494-497; tracker_init.hip / tracker_state.h) -----------------------
+int smk_label_rects(const uint8_t *labels_dev, int W, int H, const uint8_t *object_ids, int n_obj, int32_t *rects_out_dev,
+                    void *stream) {
+    if (!labels_dev || !object_ids || !rects_out_dev) return fail(SMK_E_ARG, "smk_label_rects: null argument");
+    if (n_obj < 1 || n_obj > RECT_MAX_OBJ) return fail(SMK_E_ARG, "smk_label_rects: %d objects (1..%d)", n_obj, RECT_MAX_OBJ);
+    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_label_rects: bad geometry (%d x %d, 1..32768)", W, H);
+    if ((uintptr_t)rects_out_dev % 4) return fail(SMK_E_ARG, "smk_label_rects: rects_out_dev must be 4-byte aligned");
+    LabelRectsParams p;
+    memset(&p, 0, sizeof(p));
+    p.labels = labels_dev; p.rects = rects_out_dev; p.W = W; p.H = H; p.n_obj = n_obj;
+    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
+    if (launch_label_rects(p, stream)) return fail(SMK_E_HIP, "label_rects launch failed");
+    return 0;
+}
+
+int smk_frame_sums(const uint8_t *frames_dev, int64_t frame_stride_bytes, int n, int H, int W, uint64_t *sums_out_dev,
+                   void *stream) {
+    if (!frames_dev || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums: null argument");
+    if (n < 1 || n > 65535 || frame_stride_bytes < 0) return fail(SMK_E_ARG, "smk_frame_sums: %d frames (1..65535), stride %lld", n, (long long)frame_stride_bytes);
+    if (W < 1 || H < 1 || W > 32768 || H > 32768) return fail(SMK_E_ARG, "smk_frame_sums: bad geometry (%d x %d, 1..32768)", W, H);
+    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums: sums_out_dev must be 8-byte aligned");
+    FrameSumsParams p;
+    p.frames = frames_dev; p.stride = (long)frame_stride_bytes; p.sums = (unsigned long long *)sums_out_dev;
+    p.bytes = (long)H * W * 3; p.n = n;
+    if (launch_frame_sums(p, stream)) return fail(SMK_E_HIP, "frame_sums launch failed");
+    return 0;
+}
+
+// the checks and the kernarg smk_trk_start and smk_host_trk_start share
+static int trk_start_fill(const char *who, TrkStartArgs &a, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
+                          const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
+                          int64_t sums_stride, int im_w, int im_h, int32_t *win_out, double *result_out) {
+    if (!state || !sums || !win_out || !result_out) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
+    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, start_mask, B);
+    if ((rects != nullptr) == (pos_host != nullptr || sz_host != nullptr) || ((pos_host != nullptr) != (sz_host != nullptr)))
+        return fail(SMK_E_ARG, "%s: exactly one of the device rectangles and the host position / size pair is given", who);
+    if (im_w < 1 || im_h < 1 || im_w > 32768 || im_h > 32768) return fail(SMK_E_ARG, "%s: bad geometry (%d x %d, 1..32768)", who, im_w, im_h);
+    if (sums_stride < 0) return fail(SMK_E_ARG, "%s: sums_stride %lld", who, (long long)sums_stride);
+    if ((uintptr_t)state % 8 || (uintptr_t)sums % 8 || (uintptr_t)result_out % 8 || (uintptr_t)win_out % 4 || (uintptr_t)rects % 4)
+        return fail(SMK_E_ARG, "%s: misaligned argument", who);
+    CHK(trk_cfg_check(who, cfg));
+    memset(&a, 0, sizeof(a));
+    a.cfg = *cfg; a.rects = rects; a.sums = (const unsigned long long *)sums; a.sums_stride = (long)sums_stride;
+    a.win = win_out; a.res = result_out; a.mask = start_mask; a.B = B; a.im_w = im_w; a.im_h = im_h;
+    if (pos_host)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < 2; ++k) {
+                a.pos[b][k] = pos_host[2 * b + k];
+                a.sz[b][k] = sz_host[2 * b + k];
+            }
+    return 0;
+}
+
+int smk_trk_start(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                  const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride, int im_w, int im_h,
+                  int32_t *win_out_dev, double *result_out_dev, void *stream) {
+    TrkStartArgs a;
+    CHK(trk_start_fill("smk_trk_start", a, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride, im_w,
+                       im_h, win_out_dev, result_out_dev));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_start(st, (double *)(st + B), a, stream)) return fail(SMK_E_HIP, "trk_start launch failed");
+    return 0;
+}
+
+// trk_start on host memory for the streams of the mask; im_wh != nullptr: stream b on a frame of im_wh[2 b], im_wh[2 b + 1]
+static void trk_start_host(const TrkStartArgs &a, smk_trk_stream *st, const smk_trk_cfg &cfg, const int32_t *im_wh) {
+    double *twh = (double *)(st + a.B);
+    for (int b = 0; b < a.B; ++b) {
+        if (!((a.mask >> b) & 1)) continue;
+        double px, py, w, h;
+        if (a.rects) {
+            const int32_t *r = a.rects + 4 * b;
+            w = (double)r[2]; h = (double)r[3];
+            px = t_rect_centre(r[0], r[2]); py = t_rect_centre(r[1], r[3]);
+        } else {
+            px = a.pos[b][0]; py = a.pos[b][1]; w = a.sz[b][0]; h = a.sz[b][1];
+        }
+        trk_start(st[b], cfg, px, py, w, h, a.sums + 3 * (size_t)b * a.sums_stride, im_wh ? im_wh[2 * b] : a.im_w,
+                  im_wh ? im_wh[2 * b + 1] : a.im_h, a.win + 3 * b, a.res + TRK_START_ROW * b, twh + 2 * b);
+    }
+}
+
+int smk_host_trk_start(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
+                       const double *sz, const uint64_t *sums, int64_t sums_stride, int im_w, int im_h, int32_t *win_out,
+                       double *result_out) {
+    TrkStartArgs a;
+    CHK(trk_start_fill("smk_host_trk_start", a, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_w, im_h, win_out,
+                       result_out));
+    trk_start_host(a, (smk_trk_stream *)state, *cfg, nullptr);
+    return 0;
+}
+
+int smk_crop_exemplar_dev(const uint8_t *frames_dev, int64_t frame_stride_bytes, int H, int W, const void *state_dev,
+                          const int32_t *win_dev, const double *result_dev, uint32_t start_mask, int B, int model_sz,
+                          float *z_all_dev, void *stream) {
+    if (!frames_dev || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: null argument");
+    if (H < 1 || W < 1 || H > 32768 || W > 32768 || model_sz < 1 || model_sz > 65535 || B < 1 || B > TRK_SET_MAX_B || frame_stride_bytes < 0)
+        return fail(SMK_E_ARG, "smk_crop_exemplar_dev: bad geometry");
+    if (B < 32 && (start_mask >> B)) return fail(SMK_E_ARG, "smk_crop_exemplar_dev: start_mask %#x has bits at or above %d streams", start_mask, B);
+    CropExemplarParams p;
+    p.frames = frames_dev; p.frame_stride = (long)frame_stride_bytes; p.out = z_all_dev;
+    p.H = H; p.W = W; p.model_sz = model_sz;
+    p.st = (const smk_trk_stream *)state_dev; p.win = win_dev; p.res = result_dev; p.mask = start_mask;
+    if (launch_crop_exemplar_dev(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev launch failed");
+    return 0;
+}
+
+// ---- VOT overlap (tools/test.py:354 vot_overlap; vot_overlap.hip / vot_overlap.h) ------------------------------------------
+int smk_vot_overlap(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev, int B, int im_w,
+                    int im_h, float *overlap_dev, int32_t *counts_dev, void *stream) {
+    if (!gt_dev || !overlap_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap: null argument");
+    if (pred_dev && pred_stride != 8 && pred_stride != 12)
+        return fail(SMK_E_ARG, "smk_vot_overlap: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
+    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap: %d pairs (1..65535)", B);
+    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
+    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)overlap_dev % 4 ||
+        (uintptr_t)counts_dev % 4)
+        return fail(SMK_E_ARG, "smk_vot_overlap: misaligned argument");
+    VotParams p;
+    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
+    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = im_w; p.im_h = im_h;
+    if (launch_vot_overlap(p, stream)) return fail(SMK_E_HIP, "vot_overlap launch failed");
+    return 0;
+}
+
+int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, int im_h, float *overlap, int32_t *counts) {
+    if (!pred || !gt || !overlap) return fail(SMK_E_ARG, "smk_host_vot_overlap: null argument");
+    if (n < 1) return fail(SMK_E_ARG, "smk_host_vot_overlap: %d pairs", n);
+    if (im_w < 1 || im_h < 1 || im_w > VOT_MAX_DIM || im_h > VOT_MAX_DIM)
+        return fail(SMK_E_ARG, "smk_host_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
+    for (int i = 0; i < n; ++i)                                        // the annotation is the reference's first polygon (:354)
+        overlap[i] = vot_overlap_serial(gt + 8 * (size_t)i, pred + 8 * (size_t)i, im_w, im_h, counts ? counts + 4 * (size_t)i : nullptr);
+    return 0;
+}
+
+// ---- streams with their own frame sizes (image_kernels.hip, tracker_init.hip, vot_overlap.hip) ---------------------------------
+// the refs of the streams of `mask`, checked and copied into the kernarg; -> the largest h among them through max_h (may be null)
+static int image_refs_fill(const char *who, smk_image_ref *dst, const smk_image_ref *src, int B, uint32_t mask, int *max_h) {
+    if (!src) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
+    if (B < 32 && (mask >> B)) return fail(SMK_E_ARG, "%s: start_mask %#x has bits at or above %d streams", who, mask, B);
+    memset(dst, 0, sizeof(smk_image_ref) * TRK_SET_MAX_B);
+    int mh = 0;
+    for (int b = 0; b < B; ++b) {
+        if (!((mask >> b) & 1)) continue;
+        const smk_image_ref &r = src[b];
+        if (!r.data) return fail(SMK_E_ARG, "%s: image %d has no data", who, b);
+        if (r.w < 1 || r.h < 1 || r.w > 32768 || r.h > 32768) return fail(SMK_E_ARG, "%s: image %d is %d x %d (1..32768)", who, b, r.w, r.h);
+        if (r.row_bytes < 3 * (int64_t)r.w) return fail(SMK_E_ARG, "%s: image %d: row_bytes %lld < 3 * %d", who, b, (long long)r.row_bytes, r.w);
+        dst[b] = r;
+        mh = r.h > mh ? r.h : mh;
+    }
+    if (max_h) *max_h = mh;
+    return 0;
+}
+static uint32_t all_streams(int B) { return B >= 32 ? 0xffffffffu : (B < 1 ? 0u : (1u << B) - 1u); }
+
+int smk_crop_resize_dev_v(const smk_image_ref *images_host, const void *state_dev, int B, int model_sz, float *out_dev, void *stream) {
+    if (!images_host || !state_dev || !out_dev) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: null argument");
+    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_resize_dev_v: model_sz %d", model_sz);
+    CropVParams p;
+    CHK(image_refs_fill("smk_crop_resize_dev_v", p.im, images_host, B, all_streams(B), nullptr));
+    p.out = out_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
+    p.win = nullptr; p.res = nullptr; p.mask = 0;
+    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_resize_dev_v launch failed");
+    return 0;
+}
+
+int smk_crop_exemplar_dev_v(const smk_image_ref *images_host, const void *state_dev, const int32_t *win_dev,
+                            const double *result_dev, uint32_t start_mask, int B, int model_sz, float *z_all_dev, void *stream) {
+    if (!images_host || !state_dev || !win_dev || !result_dev || !z_all_dev) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: null argument");
+    if (model_sz < 1 || model_sz > 65535) return fail(SMK_E_ARG, "smk_crop_exemplar_dev_v: model_sz %d", model_sz);
+    CropVParams p;
+    CHK(image_refs_fill("smk_crop_exemplar_dev_v", p.im, images_host, B, start_mask, nullptr));
+    p.out = z_all_dev; p.model_sz = model_sz; p.st = (const smk_trk_stream *)state_dev;
+    p.win = win_dev; p.res = result_dev; p.mask = start_mask;
+    if (launch_crop_v(p, B, stream)) return fail(SMK_E_HIP, "crop_exemplar_dev_v launch failed");
+    return 0;
+}
+
+int smk_frame_sums_v(const smk_image_ref *images_host, int n, uint64_t *sums_out_dev, void *stream) {
+    if (!images_host || !sums_out_dev) return fail(SMK_E_ARG, "smk_frame_sums_v: null argument");
+    if ((uintptr_t)sums_out_dev % 8) return fail(SMK_E_ARG, "smk_frame_sums_v: sums_out_dev must be 8-byte aligned");
+    FrameSumsVParams p;
+    CHK(image_refs_fill("smk_frame_sums_v", p.im, images_host, n, all_streams(n), &p.max_h));
+    p.sums = (unsigned long long *)sums_out_dev; p.n = n;
+    if (launch_frame_sums_v(p, stream)) return fail(SMK_E_HIP, "frame_sums_v launch failed");
+    return 0;
+}
+
+// the checks and the kernarg smk_trk_start_v and smk_host_trk_start_v share: trk_start_fill's, with a size per stream of the mask
+static int trk_start_fill_v(const char *who, TrkStartVArgs &v, const void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask,
+                            const int32_t *rects, const double *pos_host, const double *sz_host, const uint64_t *sums,
+                            int64_t sums_stride, const int32_t *im_wh, int32_t *win_out, double *result_out) {
+    if (!im_wh) return fail(SMK_E_ARG, "%s: null argument", who);
+    CHK(trk_start_fill(who, v.a, state, B, cfg, start_mask, rects, pos_host, sz_host, sums, sums_stride, 1, 1, win_out, result_out));
+    memset(v.im_wh, 0, sizeof(v.im_wh));
+    for (int b = 0; b < B; ++b) {
+        if (!((start_mask >> b) & 1)) continue;
+        const int w = im_wh[2 * b], h = im_wh[2 * b + 1];
+        if (w < 1 || h < 1 || w > 32768 || h > 32768) return fail(SMK_E_ARG, "%s: bad geometry of stream %d (%d x %d, 1..32768)", who, b, w, h);
+        v.im_wh[b][0] = w; v.im_wh[b][1] = h;
+    }
+    v.a.im_w = 0; v.a.im_h = 0;
+    return 0;
+}
+
+int smk_trk_start_v(void *state_dev, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects_dev,
+                    const double *pos_host, const double *sz_host, const uint64_t *sums_dev, int64_t sums_stride,
+                    const int32_t *im_wh_host, int32_t *win_out_dev, double *result_out_dev, void *stream) {
+    TrkStartVArgs v;
+    CHK(trk_start_fill_v("smk_trk_start_v", v, state_dev, B, cfg, start_mask, rects_dev, pos_host, sz_host, sums_dev, sums_stride,
+                         im_wh_host, win_out_dev, result_out_dev));
+    smk_trk_stream *st = (smk_trk_stream *)state_dev;
+    if (launch_trk_start_v(st, (double *)(st + B), v, stream)) return fail(SMK_E_HIP, "trk_start_v launch failed");
+    return 0;
+}
+
+int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t start_mask, const int32_t *rects, const double *pos,
+                         const double *sz, const uint64_t *sums, int64_t sums_stride, const int32_t *im_wh, int32_t *win_out,
+                         double *result_out) {
+    TrkStartVArgs v;
+    CHK(trk_start_fill_v("smk_host_trk_start_v", v, state, B, cfg, start_mask, rects, pos, sz, sums, sums_stride, im_wh, win_out,
+                         result_out));
+    trk_start_host(v.a, (smk_trk_stream *)state, *cfg, &v.im_wh[0][0]);
+    return 0;
+}
+
+int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                         int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, float seg_thr, float border,
+                         uint8_t *canvas_out_dev, void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev || !canvas_out_dev) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: null argument");
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: %d streams (1..%d)", B, TRK_SET_MAX_B);
+    if (canvas_w < 1 || canvas_h < 1 || canvas_h > 65535 || mask_size < 1 || (head_dev && (score_size < 1 || score_size > 1024)))
+        return fail(SMK_E_ARG, "smk_paste_mask_dev_v: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_mask_dev_v: slot %d (0 or 1)", slot);
+    if (im_wh_host)
+        for (int b = 0; b < B; ++b)
+            if (im_wh_host[2 * b] > canvas_w || im_wh_host[2 * b + 1] > canvas_h)
+                return fail(SMK_E_ARG, "smk_paste_mask_dev_v: stream %d is %d x %d, the canvas %d x %d", b, im_wh_host[2 * b],
+                            im_wh_host[2 * b + 1], canvas_w, canvas_h);
+    PasteDevParams p;
+    p.logits = head_dev ? head_dev : logits_dev;
+    p.mask_out = canvas_out_dev; p.prob_out = nullptr;
+    p.ms = mask_size; p.W = canvas_w; p.H = canvas_h; p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.seg_thr = seg_thr; p.border = border;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_paste_mask_dev_v(p, B, stream)) return fail(SMK_E_HIP, "paste_mask_dev_v launch failed");
+    return 0;
+}
+
+int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
+                        const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
+    if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");
+    if (pred_dev && pred_stride != 8 && pred_stride != 12)
+        return fail(SMK_E_ARG, "smk_vot_overlap_dev: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", pred_stride);
+    if (B < 1 || B > 65535) return fail(SMK_E_ARG, "smk_vot_overlap_dev: %d pairs (1..65535)", B);
+    if ((uintptr_t)pred_dev % 8 || (uintptr_t)adv_rows_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)state_dev % 8 ||
+        (uintptr_t)overlap_dev % 4 || (uintptr_t)counts_dev % 4)
+        return fail(SMK_E_ARG, "smk_vot_overlap_dev: misaligned argument");
+    VotParams p;
+    p.pred = pred_dev; p.adv = adv_rows_dev; p.gt = gt_dev; p.overlap = overlap_dev; p.counts = counts_dev;
+    p.pred_stride = pred_dev ? pred_stride : 0; p.B = B; p.im_w = 0; p.im_h = 0;
+    if (launch_vot_overlap_dev(p, state_dev, stream)) return fail(SMK_E_HIP, "vot_overlap_dev launch failed");
+    return 0;
+}
+
+}  // extern "C"

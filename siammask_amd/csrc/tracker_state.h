@@ -1,6 +1,6 @@
 // tracker_state.h -- the scalar stage of the tracker loop (tools/test.py:173-311 siamese_track, as restated by
 // siammask_amd/tracker.py DeviceTracker.track) written ONCE for host and device: tracker_state.hip runs it one lane per stream,
-// smk_host_trk_plan / smk_host_trk_advance (engine.cpp) run the same functions on the CPU for the bit-exact host tests.
+// smk_host_trk_plan / smk_host_trk_advance (stream_api.cpp) run the same functions on the CPU for the bit-exact host tests.
 // Every operation is an IEEE float64 basic operation (+ - * /, sqrt, round half to even, compare) in the host loop's order; the
 // operators are compiled under `fp contract(off)` on both sides.
 #ifndef SMK_TRACKER_STATE_H

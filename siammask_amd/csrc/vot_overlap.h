@@ -2,7 +2,7 @@
 // what tools/test.py:354 asks of utils/pyvotkit (region.c:848-945 compute_polygon_overlap with compute_bounds, bounds_round,
 // bounds_intersection, bounds_overlap and the non-legacy rasterize_polygon), restated ONCE for host and device the way
 // tracker_state.h is: vot_overlap.hip runs it one workgroup per pair with the rows of the joint window spread over the lanes,
-// smk_host_vot_overlap (engine.cpp) runs the same functions on the CPU for the bit-exact host tests.
+// smk_host_vot_overlap (stream_api.cpp) runs the same functions on the CPU for the bit-exact host tests.
 //
 // The result carries the reference's bits, so its arithmetic is kept: vertices are float32, bounds and offsets float32, the
 // minimum / maximum are `a < b ? a : b` / `a > b ? a : b` (a NaN goes where the reference's macros send it), the node

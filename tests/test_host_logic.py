@@ -34,6 +34,24 @@ def test_library_exports_every_declared_symbol():
     assert L.smk_version() >> 16 == 1
 
 
+def test_every_declared_function_resolves():
+    """The entry points are defined in several translation units.  A definition that does not see its extern "C" declaration gets
+    a mangled name, and ctypes would notice only when that one function is first called -- for most of them inside a GPU test.
+    Here every function either header declares is looked up in the loaded library, whatever _lib.SYMBOLS lists."""
+    L = _lib.lib()
+    for header in ("siammask_hip.h", "siammask_hip_test.h"):
+        hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", header)).read(), flags=re.S)
+        names = sorted(set(re.findall(r"\b(smk_[a-z0-9_]+)\s*\(", hdr)))
+        assert names, header
+        unresolved = []
+        for name in names:
+            try:
+                getattr(L, name)
+            except AttributeError:
+                unresolved.append(name)
+        assert not unresolved, "%s declares functions the library does not export: %s" % (header, unresolved)
+
+
 def test_no_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():
@@ -202,7 +220,7 @@ def test_tuning_knobs_read_back():
     with pytest.raises(RuntimeError):
         _lib.tune(no_such_knob=1)
     # one table drives smk_tune and smk_tune_get: every knob takes back what it reads, in a fresh interpreter (the defaults)
-    src = open(os.path.join(REPO, "siammask_amd", "csrc", "engine.cpp")).read()
+    src = open(os.path.join(REPO, "siammask_amd", "csrc", "tune.cpp")).read()
     table = src[src.index("static const Knob KNOBS[] = {"):]
     table = table[:table.index("};")]
     names = re.findall(r'\{"(\w+)", &\w+(?:\.\w+)?, "', table)            # (read-only diagnostics have no accepted values)
@@ -271,9 +289,10 @@ def test_arena_sizes(variant, dtype):
 
 def test_arena_tensors_are_stated_once():
     """every launch takes its view of an arena tensor from the engine's one table (act / ACT with a table id): no tensor is looked up by
-    name, and none restates a shape beside a name"""
-    src = open(os.path.join(REPO, "siammask_amd", "csrc", "engine.cpp")).read()
-    assert "static const ArenaRow ARENA[T_COUNT] = {" in src
+    name, and none restates a shape beside a name -- in any host translation unit"""
+    csrc = os.path.join(REPO, "siammask_amd", "csrc")
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(".cpp"))
+    assert src.count("static const ArenaRow ARENA[T_COUNT] = {") == 1
     assert not re.findall(r'\b(?:act|ACT)\([^\n;]*"', src)             # a call of act / ACT with a string literal among its arguments
     assert "buf.at(" not in src and "buf.find(" not in src
 
