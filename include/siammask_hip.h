@@ -488,6 +488,33 @@ int smk_set_stream_hp(smk_ctx *ctx, const double *hp_dev);
 int smk_trk_advance_hp(void *state_dev, int B, const smk_trk_cfg *cfg, const double *hp_dev, const double *box_dev, int slot,
                        double *result_row_dev, int plan_next, void *stream);
 
+/* ---- per-stream IoU counts fused with the paste-back (utils/average_meter_helper.py:71-113 IouMeter; additive; smk_version()
+ * keeps reporting 1.10, the presence of these symbols is the probe) ----------------------------------------------------------
+ * tools/tune_vos.py scores every tracked frame's probability map with IouMeter: one object, target = anno > 0, 11 thresholds.
+ * smk_vos_score fuses its objects per pixel and matches gt == id; here the B (1..32) streams are INDEPENDENT -- B grid points of
+ * one video -- and nothing of a frame but 2 * n_thr integers per stream has to reach memory.  Per stream b and frame pixel:
+ *   prob = the warped probability smk_paste_mask / smk_paste_mask_dev write to prob_out (the same bits);
+ *   for each of the n_thr (1..16) thresholds k, in any order: pred = (double)prob > thrs[k] -- a FLOAT64 comparison, as IouMeter.add
+ *   (:86) compares the float32 map with the float64 values of np.arange(0.3, 0.81, 0.05);  tgt = gt[y][x] > 0;
+ *     counts[b][k][0] += pred && tgt (intersection);  counts[b][k][1] += pred || tgt (union).
+ * gt_dev: uint8 [H][W], the plane of stream b at b * gt_stride_bytes; 0 = one annotation shared by all streams, otherwise at least
+ * W * H.  thrs (host): n_thr doubles.  counts_out_dev: int32 [B][n_thr][2], fully defined by the call (zeroed on `stream` by the call
+ * itself), exact and reproducible (integer sums).  mask_out_dev (may be NULL): uint8 [B][H][W] = prob > seg_thr with the float32
+ * comparison of smk_paste_mask -- the same bytes, for a caller who wants masks and scores from one pass.  W * H < 2^31,
+ * H <= 65535.  inv_map (host): B x 6 doubles as for smk_paste_mask.  Host arrays travel as kernel arguments: nothing of the
+ * caller's host memory is read after the call returns.  No context; asynchronous on `stream`, no host synchronisation; bad
+ * arguments (a null pointer, a range above, a negative stride or a non-zero one below W * H) give SMK_E_ARG before anything is
+ * enqueued.  The mean over a video's frames is left to the host: siammask_amd.vos.iou_meter. */
+int smk_iou_score(const float *logits_dev, int mask_size, const double *inv_map, int B, int W, int H, float border,
+                  const uint8_t *gt_dev, int64_t gt_stride_bytes, const double *thrs, int n_thr, float seg_thr,
+                  int32_t *counts_out_dev, uint8_t *mask_out_dev, void *stream);
+/* smk_iou_score with inv_map[slot] -- and, with head_dev != NULL (logits_dev ignored), the column delta_yx[slot] of the mask head
+ * [B][ms*ms][score_size][score_size] -- of stream b read from the tracker's state block, exactly as smk_paste_mask_dev reads them:
+ * behind smk_trk_advance on the same stream it scores the frame that was just advanced. */
+int smk_iou_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int B, int W, int H, float border, const uint8_t *gt_dev, int64_t gt_stride_bytes,
+                      const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev, uint8_t *mask_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ SYMBOLS = (
     "smk_crop_resize_dev_v", "smk_crop_exemplar_dev_v", "smk_frame_sums_v", "smk_trk_start_v", "smk_host_trk_start_v",
     "smk_paste_mask_dev_v", "smk_vot_overlap_dev",
     "smk_set_stream_hp", "smk_trk_advance_hp", "smk_host_trk_advance_hp",
+    "smk_iou_score", "smk_iou_score_dev",
 )
 
 
@@ -175,6 +176,8 @@ def lib():
     L.smk_set_stream_hp.argtypes = [vp, vp]
     L.smk_trk_advance_hp.argtypes = [vp, ci, cp, vp, vp, ci, vp, ci, vp]
     L.smk_host_trk_advance_hp.argtypes = [vp, ci, cp, vp, vp, ci, vp, ci]
+    L.smk_iou_score.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, i64, vp, ci, cf, vp, vp, vp]
+    L.smk_iou_score_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, vp, i64, vp, ci, cf, vp, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

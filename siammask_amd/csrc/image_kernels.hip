@@ -435,6 +435,87 @@ int launch_vos_score(const VosParams &p, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ------------------------------------------------------------------------------------------
+// Per-stream IoU counts (utils/average_meter_helper.py:71-113 IouMeter.add, the per-frame part) fused with the paste-back: the B
+// streams are INDEPENDENT single-object runs (B grid points of one video, tools/tune_vos.py), each scored against gt > 0:
+//   pred = (double)prob > thr[k] (the float32 map against np.arange's float64 values),  tgt = gt > 0,
+//   counts[b][k][0] += pred && tgt,  counts[b][k][1] += pred || tgt.
+// The union of a non-predicted pixel is tgt whatever k is, so the wave counts tgt once per row and, per k, only pred and
+// pred && tgt (ballot + popcount, lane 0 adds to the workgroup's LDS counters; a row of a wave with nothing predicted costs the one
+// tgt count); the workgroup's union is pred + tgt - (pred && tgt) and goes out as one global atomic per non-zero counter.
+// A workgroup covers 256 columns of IOU_ROWS consecutive rows of stream blockIdx.z.  prob IS warped_prob's value (outside the
+// patch its taps are the border without a sigmoid already), so the counts are those of smk_paste_mask's prob_out bit for bit.
+constexpr int IOU_ROWS = 4;
+
+template <bool DEV>
+__global__ __launch_bounds__(256) void iou_score_kernel(const IouParams p) {
+    __shared__ int cnt[IOU_MAX_THR * 2 + 1];                          // [k][0] pred && tgt, [k][1] pred; [2 K] tgt
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int K = p.n_thr, b = blockIdx.z;
+    if (tid < 2 * K + 1) cnt[tid] = 0;
+    __syncthreads();
+    const double *M;
+    const float *lg = p.logits + (size_t)b * p.ms * p.ms;
+    int ls = 1;
+    if constexpr (DEV) {
+        const smk_trk_stream *s = p.st + b;
+        if (p.head_S) {
+            ls = p.head_S * p.head_S;
+            const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1), dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+            lg = p.logits + (size_t)b * p.ms * p.ms * ls + dy * p.head_S + dx;
+        }
+        M = s->inv_map[p.slot];
+    } else {
+        M = p.inv_map[b];
+    }
+    const unsigned char *gt = p.gt + (size_t)b * p.gt_stride;
+    const int x = blockIdx.x * 256 + tid;
+    const bool in_x = x < p.W;
+    const int y0 = blockIdx.y * IOU_ROWS, y1 = min(y0 + IOU_ROWS, p.H);
+    for (int y = y0; y < y1; ++y) {
+        bool tgt = false;
+        unsigned abv = 0;                                             // bit k: (double)prob > thr[k]
+        if (in_x) {
+            const float v = warped_prob(p, M, lg, ls, x, y);
+            const size_t px = (size_t)y * p.W + x;
+            tgt = gt[px] > 0;
+            for (int k = 0; k < K; ++k) abv |= ((double)v > p.thr[k] ? 1u : 0u) << k;
+            if (p.mask_out) p.mask_out[(size_t)b * p.H * p.W + px] = v > p.seg_thr ? 1 : 0;
+        }
+        const int nt = __popcll(__ballot(tgt));
+        if (lane == 0 && nt) atomicAdd(&cnt[2 * K], nt);
+        if (__ballot(abv != 0) == 0) continue;                        // wave-uniform
+        for (int k = 0; k < K; ++k) {
+            const bool pred = (abv >> k) & 1;
+            const int np = __popcll(__ballot(pred));
+            if (np == 0) continue;                                    // wave-uniform
+            const int ni = __popcll(__ballot(pred && tgt));
+            if (lane == 0) {
+                atomicAdd(&cnt[2 * k + 1], np);
+                if (ni) atomicAdd(&cnt[2 * k], ni);
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < K) {
+        const int it = cnt[2 * tid], un = cnt[2 * tid + 1] + cnt[2 * K] - it;
+        int *c = p.counts + ((size_t)b * K + tid) * 2;
+        if (it) atomicAdd(c, it);
+        if (un) atomicAdd(c + 1, un);
+    }
+}
+
+int launch_iou_score(const IouParams &p, int B, void *stream) {
+    if (B < 1 || B > IOU_MAX_B || p.n_thr < 1 || p.n_thr > IOU_MAX_THR || !p.logits || !p.gt || !p.counts) return -1;
+    if (p.W < 1 || p.H < 1 || p.H > 65535 * IOU_ROWS) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * B * p.n_thr, s) != hipSuccess) return -4;
+    dim3 grid((p.W + 255) / 256, (p.H + IOU_ROWS - 1) / IOU_ROWS, B);
+    if (p.st) hipLaunchKernelGGL((iou_score_kernel<true>), grid, dim3(256), 0, s, p);
+    else      hipLaunchKernelGGL((iou_score_kernel<false>), grid, dim3(256), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_paste_mask(const PasteParams &p, int B, void *stream) {
     if (B < 1 || B > CROP_MAX_B) return -1;
     dim3 grid((p.W + 255) / 256, p.H, B);

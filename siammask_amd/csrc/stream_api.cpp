@@ -327,6 +327,56 @@ int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int sco
     return 0;
 }
 
+// ---- per-stream IoU counts (utils/average_meter_helper.py:71-113 IouMeter.add per frame, fused with the paste-back) ------------
+static_assert(IOU_MAX_B == TRK_SET_MAX_B, "smk_iou_score takes as many streams as a state block of the tracker");
+
+// the checks and the fields both entries share; everything is refused here, before anything is enqueued
+static int iou_fill(const char *who, IouParams &p, const float *src, int mask_size, int B, int W, int H, float border,
+                    const uint8_t *gt_dev, int64_t gt_stride_bytes, const double *thrs, int n_thr, float seg_thr,
+                    int32_t *counts_out_dev, uint8_t *mask_out_dev) {
+    if (!src || !gt_dev || !thrs || !counts_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > IOU_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, IOU_MAX_B);
+    if (n_thr < 1 || n_thr > IOU_MAX_THR) return fail(SMK_E_ARG, "%s: %d thresholds (1..%d)", who, n_thr, IOU_MAX_THR);
+    if (W < 1 || H < 1 || H > 65535 || mask_size < 1 || (int64_t)W * H > INT32_MAX)
+        return fail(SMK_E_ARG, "%s: bad geometry (%d x %d frame, mask %d)", who, W, H, mask_size);
+    if (gt_stride_bytes < 0 || (gt_stride_bytes != 0 && gt_stride_bytes < (int64_t)W * H))
+        return fail(SMK_E_ARG, "%s: gt stride %lld (0, or at least W * H)", who, (long long)gt_stride_bytes);
+    memset(&p, 0, sizeof(p));
+    p.logits = src; p.gt = gt_dev; p.gt_stride = (long)gt_stride_bytes; p.counts = counts_out_dev; p.mask_out = mask_out_dev;
+    p.ms = mask_size; p.W = W; p.H = H; p.n_thr = n_thr;
+    p.seg_thr = seg_thr; p.border = border;
+    for (int k = 0; k < n_thr; ++k) p.thr[k] = thrs[k];
+    return 0;
+}
+
+int smk_iou_score(const float *logits_dev, int mask_size, const double *inv_map, int B, int W, int H, float border,
+                  const uint8_t *gt_dev, int64_t gt_stride_bytes, const double *thrs, int n_thr, float seg_thr,
+                  int32_t *counts_out_dev, uint8_t *mask_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_iou_score: null argument");
+    IouParams p;
+    CHK(iou_fill("smk_iou_score", p, logits_dev, mask_size, B, W, H, border, gt_dev, gt_stride_bytes, thrs, n_thr, seg_thr,
+                 counts_out_dev, mask_out_dev));
+    for (int i = 0; i < B; ++i)
+        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
+    if (launch_iou_score(p, B, stream)) return fail(SMK_E_HIP, "iou_score launch failed");
+    return 0;
+}
+
+int smk_iou_score_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int B, int W, int H, float border, const uint8_t *gt_dev, int64_t gt_stride_bytes,
+                      const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev, uint8_t *mask_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_iou_score_dev: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_iou_score_dev: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_iou_score_dev: score_size %d", score_size);
+    IouParams p;
+    CHK(iou_fill("smk_iou_score_dev", p, head_dev ? head_dev : logits_dev, mask_size, B, W, H, border, gt_dev, gt_stride_bytes,
+                 thrs, n_thr, seg_thr, counts_out_dev, mask_out_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_iou_score(p, B, stream)) return fail(SMK_E_HIP, "iou_score launch failed");
+    return 0;
+}
+
 // ---- stream start on the device (tools/test.py:146-152,494-497; tracker_init.hip / tracker_state.h) -----------------------
 int smk_label_rects(const uint8_t *labels_dev, int W, int H, const uint8_t *object_ids, int n_obj, int32_t *rects_out_dev,
                     void *stream) {

@@ -220,6 +220,22 @@ struct VosParams {
     unsigned given;
 };
 int launch_vos_score(const VosParams &p, void *stream);
+// smk_iou_score / smk_iou_score_dev: the per-frame counts of IouMeter (utils/average_meter_helper.py:71-113) for B independent
+// streams, fused with the paste-back
+constexpr int IOU_MAX_B = 32, IOU_MAX_THR = 16;
+struct IouParams {
+    const float *logits;            // [B][ms*ms], or the head [B][ms*ms][S][S] when head_S != 0
+    const unsigned char *gt;        // [H][W] per stream, gt_stride bytes apart (0: one plane for all streams); target = gt > 0
+    long gt_stride;
+    int *counts;                    // [B][K][2] (intersection, union), zeroed in-stream before the launch
+    unsigned char *mask_out;        // [B][H][W] = prob > seg_thr, or nullptr
+    int ms, W, H, n_thr, head_S, slot;
+    float seg_thr, border;
+    const smk_trk_stream *st;       // != nullptr: inv_map[slot] / delta_yx[slot] of the state block, inv_map below unused
+    double thr[IOU_MAX_THR];
+    double inv_map[IOU_MAX_B][6];
+};
+int launch_iou_score(const IouParams &p, int B, void *stream);
 
 // ---- stream start on the device (tracker_init.hip; the exemplar crop is image_kernels.hip's, beside crop_pixel) ----------
 constexpr int RECT_MAX_OBJ = 32, RECT_ROWS = 4;

@@ -264,6 +264,90 @@ def vos_score_dev(logits, state, slot, im_wh, gt, object_ids, thrs, alive=None, 
     return (counts, labels) if labels is not None else counts
 
 
+def _iou_args(B, gt, thrs, W, H, device):
+    """the checked arguments iou_score / iou_score_dev share -> (gt stride in bytes, thrs float64 [K])"""
+    _need_cuda(gt, "gt")
+    if gt.dtype != torch.uint8 or tuple(gt.shape) not in ((H, W), (B, H, W)) or not gt.is_contiguous() or gt.device != device:
+        raise ValueError("gt must be a contiguous uint8 CUDA tensor [%d,%d] or [%d,%d,%d] on the logits' device" % (H, W, B, H, W))
+    if not 1 <= B <= 32:
+        raise ValueError("1..32 streams, got %d" % B)
+    thr = np.ascontiguousarray(thrs, dtype=np.float64)
+    if thr.ndim != 1 or not 1 <= thr.size <= 16:
+        raise ValueError("thrs must be 1..16 values")
+    return (H * W if gt.dim() == 3 else 0), thr
+
+
+def _iou_outs(B, K, W, H, device, out, mask_out, want_mask):
+    counts = out if out is not None else torch.empty((B, K, 2), dtype=torch.int32, device=device)
+    if counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or tuple(counts.shape) != (B, K, 2):
+        raise ValueError("out must be a contiguous int32 CUDA tensor [%d,%d,2]" % (B, K))
+    mask = mask_out
+    if mask is None and want_mask:
+        mask = torch.empty((B, H, W), dtype=torch.uint8, device=device)
+    if mask is not None and (mask.dtype != torch.uint8 or not mask.is_cuda or not mask.is_contiguous() or
+                             tuple(mask.shape) != (B, H, W)):
+        raise ValueError("mask_out must be a contiguous uint8 CUDA tensor [%d,%d,%d]" % (B, H, W))
+    return counts, mask
+
+
+def iou_score(logits, back_boxes, im_wh, gt, thrs, seg_thr=0.35, padding=-1.0, out=None, mask_out=None, want_mask=False):
+    """The per-frame counts of IouMeter.add (utils/average_meter_helper.py:71-113) fused with the paste-back, for B INDEPENDENT
+    streams (logits / back_boxes as for paste_masks): stream b's probability map against gt > 0 at every threshold of thrs
+    (1..16 float64 values in any order; the comparison is in float64).  gt: uint8 CUDA [im_h, im_w] shared by all streams, or
+    [B, im_h, im_w].  -> int32 CUDA [B, K, 2] = (intersection, union) [, uint8 masks [B, im_h, im_w] = paste_masks at seg_thr].
+    siammask_amd.vos.iou_meter turns the counts of a video into the meter's result."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    B = logits.shape[0]
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != B:
+        raise ValueError("logits must be [B, ms*ms] with one back_box per stream")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    stride, thr = _iou_args(B, gt, thrs, W, H, logits.device)
+    inv = np.ascontiguousarray(np.stack([invert_affine(crop_back_map(bb, (W, H))) for bb in back_boxes]))
+    counts, mask = _iou_outs(B, int(thr.size), W, H, logits.device, out, mask_out, want_mask)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.lib().smk_iou_score(
+            logits.data_ptr(), ms, inv.ctypes.data_as(ctypes.c_void_p), B, W, H, float(padding), gt.data_ptr(), stride,
+            thr.ctypes.data_as(ctypes.c_void_p), int(thr.size), float(seg_thr), counts.data_ptr(),
+            mask.data_ptr() if mask is not None else None, _lib.current_stream_ptr()))
+    return (counts, mask) if mask is not None else counts
+
+
+def iou_score_dev(logits, state, slot, im_wh, gt, thrs, seg_thr=0.35, padding=-1.0, head=None, mask_size=None, out=None,
+                  mask_out=None, want_mask=False):
+    """iou_score with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of each stream read on the device
+    from the tracker's state block, as paste_masks_dev reads them.  out: int32 CUDA [B, K, 2] to write the counts into;
+    mask_out: uint8 CUDA [B, im_h, im_w] to write the masks into (implies want_mask)."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = src.shape[0]
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    stride, thr = _iou_args(B, gt, thrs, W, H, src.device)
+    K = int(thr.size)
+    counts, mask = _iou_outs(B, K, W, H, src.device, out, mask_out, want_mask)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().smk_iou_score_dev(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, W, H, float(padding), gt.data_ptr(), stride,
+            thr.ctypes.data_as(ctypes.c_void_p), K, float(seg_thr), counts.data_ptr(),
+            mask.data_ptr() if mask is not None else None, _lib.current_stream_ptr()))
+    return (counts, mask) if mask is not None else counts
+
+
 def label_rects(labels, ids, out=None):
     """cv2.boundingRect(labels == id) (tools/test.py:494) for up to 32 ids in one pass over a label map on the device.
     labels: uint8 CUDA [H,W]; ids: O integers in 0..255 (duplicates allowed; they need not occur).

@@ -18,6 +18,9 @@ csrc/tracker_state.hip) -- any number of frames is enqueued without a host synch
     res = tr.run(frames)                                           # frames uint8 CUDA [T,H,W,3] or [T,B,H,W,3]
     res = tr.run(frames, gt=gt_u8_cuda, vos={'object_ids': ids, 'thrs': vos.THRS})   # B objects on a shared frame, scored
     res['vos_counts'], res['labels']                               # against gt on the device (tools/test.py:421-456, 521-523)
+    res = tr.run(frames, iou={'gt': gt_u8_cuda, 'thrs': tune.THRS_VOS, 'masks': False})   # B independent runs of one video (B hp
+    res['iou_counts']                                              # points, set_hp), each scored against gt > 0 as IouMeter does
+                                                                   # (tools/tune_vos.py); score-only frames write no mask
 track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
 
 Streams that start on their own frames (siamese_init per stream on the device, enqueue-only; csrc/tracker_init.hip):
@@ -110,18 +113,23 @@ def _box_corners(pos, sz):
 # one frame's paste-back: Refine logits or the mask head, the state slot, the mask to write, its rbox rows or None, a _Score or
 # None, and a hook called behind them as after(rbox rows, advance rows) (run(vot=) enqueues its overlap there)
 # sizes: None, or (mixed sizes) the int32 [B,2] (w, h) of the streams' frames when the frame was enqueued: mask is then the canvas
-_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes")
+# iou: None, or the _Iou of a frame enqueued with iou= (mask is then None for a score-only frame)
+_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou", defaults=(None,))
 # a checked VOS request as the C entry takes it (_vos_spec); enqueue() adds the frame's count row and label map
 _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels")
+# a checked iou= request (_iou_spec): annotation, thresholds, masks wanted, frame scored; enqueue() adds the frame's count row
+_Iou = collections.namedtuple("_Iou", "gt thrs masks scored row")
+_IOU_MAX_THR = 16
 _Event = collections.namedtuple("_Event", "t streams res")            # one start(): chunk index, streams, device rows [B,START_ROW]
 
 
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
-    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "events", "z_snapped", "start", "sizes")
+    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
+        self.iou_k = None                                             # thresholds of a chunk enqueued with iou=
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
         self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
@@ -129,10 +137,10 @@ class _Chunk(object):
 
 class _Queue(object):
     """what the free-running mode keeps across chunks: the device state block ``dev`` and its chunk-start copy ``snap``, the
-    network inputs ``x`` / ``twh``, the per-block device rows (``rows``, ``rbox``, ``vos``), the host arrays the device agrees with
+    network inputs ``x`` / ``twh``, the per-block device rows (``rows``, ``rbox``, ``vos``, ``iou``), the host arrays the device agrees with
     (``synced``), the buffers of start() (``can_start``: they exist), the launch guard, and the pending ``chunk``"""
     __slots__ = ("B", "H", "W", "device", "dev", "snap", "x", "twh", "cfg", "z_all", "z_snap", "win", "rects", "sums", "can_start",
-                 "rows", "rbox", "vos", "synced", "chunk", "launch")
+                 "rows", "rbox", "vos", "iou", "synced", "chunk", "launch")
 
 
 class _Launching(object):
@@ -187,12 +195,12 @@ def _apply_events(st, events, ev_rows, T):
     return out
 
 
-def collect_host(host, T, B, poly, K, events, ev_rows, state):
+def collect_host(host, T, B, poly, K, events, ev_rows, state, counts_key="vos_counts"):
     """The host half of collect(), pure numpy.  host: float64 [T,B,n], a frame's RESULT_ROW columns (0:2 pos, 2:4 size, 4 score,
     5 best_id, 6:8 delta_yx, 8:12 pos / size before the clip, 12:15 crop box), then 12 rbox columns if any frame asked for a
-    polygon (``poly``: T flags), then 2 K count columns (K None: not scored); events: [(t, streams)] with ev_rows
-    [E,B,START_ROW]; state: tr.state.  -> (collect()'s dict without its device tensors, what tr.state becomes; nothing given
-    is modified)"""
+    polygon (``poly``: T flags), then 2 K count columns (K None: not scored) returned under ``counts_key`` ('vos_counts' of gt= /
+    vos=, 'iou_counts' of iou=); events: [(t, streams)] with ev_rows [E,B,START_ROW]; state: tr.state.  -> (collect()'s dict
+    without its device tensors, what tr.state becomes; nothing given is modified)"""
     st, res = dict(state), {}
     if T:
         n_row = host.shape[2] - (2 * K if K is not None else 0)
@@ -201,7 +209,7 @@ def collect_host(host, T, B, poly, K, events, ev_rows, state):
                "best_id": r[:, :, 5].astype(np.int64), "delta_yx": r[:, :, 6:8].astype(np.int64),
                "crop_box": np.stack([r[:, :, 12], r[:, :, 13], r[:, :, 14], r[:, :, 14]], axis=2), "mask": None}
         if K is not None:                                             # int32 counts rode along as float64 (exact)
-            res["vos_counts"] = host[:, :, n_row:].astype(np.int64).reshape(T, B, K, 2)
+            res[counts_key] = host[:, :, n_row:].astype(np.int64).reshape(T, B, K, 2)
         if any(poly):
             q = host[:, :, RESULT_ROW:n_row]
             asked = np.asarray(poly, dtype=bool)
@@ -598,7 +606,7 @@ class DeviceTracker(object):
         q = self._fr = _Queue()
         q.B, q.H, q.W, q.device, q.chunk = B, H, W, device, _Chunk()
         q.launch = _Launching(self)
-        q.rows, q.rbox, q.vos, q.synced = [], [], [], None
+        q.rows, q.rbox, q.vos, q.iou, q.synced = [], [], [], [], None
         n = int(L.smk_trk_state_bytes(B))
         with torch.cuda.device(device):
             q.dev = torch.zeros(n, dtype=torch.uint8, device=device)
@@ -716,8 +724,37 @@ class DeviceTracker(object):
         return _Score(gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits,
                       init.contiguous() if gbits else None, None, None)
 
+    def _iou_spec(self, mixed, want_mask, want_polygon, mask_out, scored_vos, iou):
+        """the checked iou= request of one frame (before anything is launched) -> None, or an _Iou (row still None)"""
+        if iou is None:
+            return None
+        q = self._fr
+        B, H, W = q.B, q.H, q.W
+        if scored_vos:
+            raise ValueError("iou= (independent streams against gt > 0) or gt= / vos= (the objects of one frame, fused), not both")
+        if mixed:
+            raise ValueError("iou=: one annotation of one frame size; these streams have their own sizes")
+        if self.model.variant == "rpn" or not want_mask:
+            raise ValueError("iou= scoring needs want_mask and a variant with a mask branch")
+        if B > 32:
+            raise ValueError("iou= scoring takes up to 32 streams, the tracker has %d" % B)
+        if not isinstance(iou, dict) or set(iou) - {"gt", "thrs", "masks", "score"} or "gt" not in iou or "thrs" not in iou:
+            raise ValueError("iou = {'gt': uint8 CUDA [%d,%d], 'thrs': 1..%d thresholds[, 'masks': bool][, 'score': bool]}"
+                             % (H, W, _IOU_MAX_THR))
+        if not _u8_cuda(iou["gt"], (H, W)) or iou["gt"].device != q.device:
+            raise ValueError("iou['gt'] must be a uint8 CUDA tensor [%d,%d] on %s" % (H, W, q.device))
+        thrs = np.ascontiguousarray(iou["thrs"], dtype=np.float64)
+        if thrs.ndim != 1 or not 1 <= thrs.size <= _IOU_MAX_THR:
+            raise ValueError("iou['thrs'] must be 1..%d values" % _IOU_MAX_THR)
+        if q.chunk.pending and q.chunk.iou_k is not None and q.chunk.iou_k != thrs.size:
+            raise ValueError("every frame of a chunk is scored at the same number of thresholds")
+        masks = bool(iou.get("masks", True))
+        if not masks and (want_polygon or mask_out is not None):
+            raise ValueError("iou['masks'] = False writes no mask: want_polygon / mask_out= need one")
+        return _Iou(iou["gt"].contiguous(), thrs, masks, bool(iou.get("score", True)), None)
+
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False):
+                _unsized=False, iou=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -725,6 +762,12 @@ class DeviceTracker(object):
         booleans]}): the B streams are the objects of one shared frame; behind the frame's paste-back the intersection / union
         counts of tools/test.py:421-456 and the fused label map (:521-523, at the tracker's seg_thr; labels_out: uint8 CUDA
         [im_h,im_w] to receive it) are computed on the device and come back from collect().
+        iou ({'gt': uint8 CUDA [im_h,im_w], 'thrs': 1..16 float64 thresholds[, 'masks': True][, 'score': True]}): the B streams are
+        INDEPENDENT runs on one video (B points of an hp grid, set_hp), each scored against gt > 0 as IouMeter.add scores a frame
+        (utils/average_meter_helper.py:71-113; smk_iou_score_dev): collect() returns res['iou_counts'].  'masks': False makes
+        the frame score-only -- no paste-back launch, no mask tensor, collect() reports no mask -- and 'masks': True without a
+        polygon writes masks and counts from the one launch.  'score': False tracks the frame and leaves its count row zero.
+        Either every frame of a chunk carries iou= or none does; not with gt= / vos=, mixed frame sizes, or without a mask.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -749,6 +792,9 @@ class DeviceTracker(object):
         self._mask_out(mask_out, want_mask=want_mask)
         if c.pending and (c.vos_k is not None) != (vos is not None or gt is not None):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
+        if c.pending and (c.iou_k is not None) != (iou is not None):
+            raise ValueError("every frame of a chunk carries iou=, or none does")
+        iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
         L, model = _lib.lib(), self.model
@@ -770,6 +816,11 @@ class DeviceTracker(object):
                 score = score._replace(row=q.vos[blk][i], labels=labels)
                 c.vos_k = int(score.thrs.size)
                 c.labels.append(labels)
+            if iou is not None:
+                if i == 0 and blk == len(q.iou):                      # count rows per block, like q.vos
+                    q.iou.append(torch.empty((_ROWS_PER_BLOCK, B, _IOU_MAX_THR, 2), dtype=torch.int32, device=q.device))
+                iou = iou._replace(row=q.iou[blk][i])
+                c.iou_k = int(iou.thrs.size)
             dev_ptr = q.dev.data_ptr()
             if mixed:
                 _lib.check(L.smk_crop_resize_dev_v(self._image_refs(frame, list(range(B))), dev_ptr, B, self.p.instance_size,
@@ -791,10 +842,11 @@ class DeviceTracker(object):
             self._fr_flush(sp, join=not refine or depth != 1)
             mask = None
             if want_mask:
-                mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
+                if iou is None or iou.masks:                          # (a score-only frame has no mask anywhere)
+                    mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
                            q.rbox[blk][i] if want_polygon else None, score, _after, q.rows[blk][i] if _after is not None else None,
-                           sizes if mixed else None)
+                           sizes if mixed else None, iou)
                 if depth:
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
@@ -806,12 +858,16 @@ class DeviceTracker(object):
             return t
 
     def _fr_paste(self, job, sp):
-        """the launches of one _Job, in this order on the stream: paste-back -> rotated box -> VOS scoring -> the job's hook"""
+        """the launches of one _Job, in this order on the stream: paste-back -> rotated box -> scoring -> the job's hook.  A frame
+        enqueued with iou= and no polygon has no paste-back launch: its scoring launch writes the mask, if it has one"""
         q, p, L = self._fr, self.p, _lib.lib()
-        logits, head, mask, s = job.logits, job.head, job.mask, job.score
+        logits, head, mask, s, u = job.logits, job.head, job.mask, job.score, job.iou
         shared = (logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
                   int(head.shape[-1]) if head is not None else 0, self.mask_size, q.dev.data_ptr(), job.slot, q.B, q.W, q.H)
-        if job.sizes is not None:                                     # the canvas: each stream at the size of its record, 0 elsewhere
+        fused = u is not None and u.scored and job.rbox is None      # smk_iou_score_dev writes the mask bytes itself
+        if mask is None or fused:
+            pass
+        elif job.sizes is not None:                                   # the canvas: each stream at the size of its record, 0 elsewhere
             _lib.check(L.smk_paste_mask_dev_v(*(shared + (job.sizes.ctypes.data, float(p.seg_thr), -1.0, mask.data_ptr(), sp))))
         else:
             _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
@@ -824,6 +880,11 @@ class DeviceTracker(object):
                 _lib.check(L.smk_vos_score_dev_ex(*(args + (s.gbits, s.init.data_ptr(), sp))))
             else:
                 _lib.check(L.smk_vos_score_dev(*(args + (sp,))))
+        if u is not None and not u.scored:                            # tracked, not scored (IouMeter scores 0 < f < T - 1): a zero row
+            u.row.zero_()
+        elif u is not None:
+            _lib.check(L.smk_iou_score_dev(*(shared + (-1.0, u.gt.data_ptr(), 0, u.thrs.ctypes.data, int(u.thrs.size), float(p.seg_thr),
+                                                       u.row.data_ptr(), mask.data_ptr() if fused and mask is not None else None, sp))))
         if job.after is not None:                                     # behind the rotated box, same stream
             job.after(job.rbox, job.adv)
 
@@ -868,7 +929,8 @@ class DeviceTracker(object):
         if st is None or q is None:
             raise RuntimeError("DeviceTracker.collect(): init() first")
         c, B = q.chunk, q.B
-        T, K, events = c.pending, c.vos_k, c.events
+        T, K, events = c.pending, c.vos_k if c.vos_k is not None else c.iou_k, c.events
+        counts = q.vos if c.vos_k is not None else q.iou             # per-block count rows, _IOU_MAX_THR or 8 thresholds wide
         if not self._chunk_open():
             return None
         with q.launch as sp:                                          # the device half: one tensor, one copy
@@ -882,8 +944,8 @@ class DeviceTracker(object):
                           for b in q.rbox[:nblk]]
                     rows = torch.cat([rows, torch.cat(rb)[:T]], dim=2)
                 if K is not None:                                     # int32 counts ride along as float64 (exact): [T,B,K*2]
-                    vc = torch.cat(q.vos[:nblk])[:T] if nblk > 1 else q.vos[0][:T]
-                    vc = vc.reshape(T, B * 16)[:, :B * K * 2].reshape(T, B, K * 2)      # a frame's row is packed [B][K][2]
+                    vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
+                    vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
             if events:                                                # the start events' result rows ride along
                 flat = torch.cat(([rows.reshape(-1)] if T else []) + [e.res.reshape(-1) for e in events]).cpu().numpy()
@@ -891,14 +953,15 @@ class DeviceTracker(object):
                 host, ev_rows = flat[:n].reshape(tuple(rows.shape) if T else (0, B, RESULT_ROW)), flat[n:].reshape(-1, B, START_ROW)
             else:
                 host, ev_rows = rows.cpu().numpy(), None              # the one synchronisation
-        res, new = collect_host(host, T, B, c.poly, K, [(e.t, e.streams) for e in events], ev_rows, st)
+        res, new = collect_host(host, T, B, c.poly, K, [(e.t, e.streams) for e in events], ev_rows, st,
+                                "vos_counts" if c.vos_k is not None else "iou_counts")
         if T:
             masks = c.masks
             if all(m is not None for m in masks):
                 res["mask"] = _masks if _masks is not None and _masks.shape[0] == T else torch.stack(masks)
             elif any(m is not None for m in masks):
                 res["mask"] = masks                                   # mixed chunk: per frame, None where no mask was asked for
-            if K is not None:
+            if c.vos_k is not None:
                 res["labels"] = _labels if _labels is not None and _labels.shape[0] == T else torch.stack(c.labels)
             new["mask"] = masks[-1]
             if any(z is not None for z in c.sizes):                   # [T,B,2] (w, h): the mask of (t, b) is mask[t, b, :h, :w]
@@ -910,7 +973,7 @@ class DeviceTracker(object):
         q.chunk = _Chunk()
         return res
 
-    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, vot=None):
+    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, vot=None, iou=None):
         """enqueue every frame of ``frames`` (uint8 CUDA [T,H,W,3], or [T,B,H,W,3] for per-stream frames), then collect().
         mask_out: uint8 CUDA [T,B,H,W] to receive the masks.
         gt (uint8 CUDA [T,im_h,im_w]) and vos (as for enqueue(); 'alive' may be [T,B]): every frame is scored against its
@@ -918,7 +981,10 @@ class DeviceTracker(object):
         [T,im_h,im_w].  vos with 'start' / 'end' (object id -> frame, as the dataset's dictionaries) [and 'init']: the objects
         start and end on their own frames of the WHOLE video ``frames`` (see tracker_loops.run_lifetimes).
         vot ({'gt': float64 [T,B,8][, 'skip': 5][, 'length': [B]]}, with want_polygon): the supervised loop of track_vot for B
-        videos in lock-step, frames [T,B,H,W,3] (see tracker_loops.run_vot)."""
+        videos in lock-step, frames [T,B,H,W,3] (see tracker_loops.run_vot).
+        iou (as for enqueue(), 'gt' uint8 CUDA [T,im_h,im_w]; 'score': [T] booleans, the frames that are scored -- the others are
+        tracked and their count rows are zero): the B streams as independent runs against gt > 0 -> res['iou_counts'] int64
+        [T,B,K,2] (siammask_amd.vos.iou_meter takes a stream's [T,K,2]).  With 'masks': False no mask is allocated or returned."""
         from . import tracker_loops
         q = self._fr
         if self.state is None or q is None:
@@ -933,6 +999,22 @@ class DeviceTracker(object):
         elif frames.dim() not in (4, 5):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T, labels, alive = int(frames.shape[0]), None, None
+        if iou is not None:                                           # checked for the whole run before the first launch
+            if vot is not None or gt is not None or vos is not None:
+                raise ValueError("run(): iou= (independent streams against gt > 0) or vot= / gt= / vos=, not both")
+            if isinstance(frames, _Videos):
+                raise ValueError("iou=: one annotation of one frame size; these streams have their own sizes")
+            g, scored = iou.get("gt") if isinstance(iou, dict) else None, np.ones(T, dtype=bool)
+            if not isinstance(g, torch.Tensor) or g.dim() != 3 or g.shape[0] != T:
+                raise ValueError("iou scoring: iou['gt'] uint8 CUDA [T,H,W], one annotation per frame")
+            if iou.get("score") is not None:
+                scored = np.asarray(iou["score"])
+                if scored.shape != (T,):
+                    raise ValueError("iou['score'] must be %d booleans, one per frame" % T)
+            iou = [dict(iou, gt=g[t], score=bool(scored[t])) for t in range(T)]
+            for t in range(T):
+                self._check_frame(frames[t])
+                self._iou_spec(False, want_mask, want_polygon and want_mask, mask_out, False, iou[t])
         if vot is not None:
             if gt is not None or vos is not None:
                 raise ValueError("run(): vot= (polygon annotations, the supervised loop) or gt= / vos= (label maps), not both")
@@ -950,11 +1032,12 @@ class DeviceTracker(object):
             for t in range(T):
                 self._vos_spec(3, want_mask, gt[t], self._vos_at(vos, alive, t))
             labels = torch.empty((T, q.H, q.W), dtype=torch.uint8, device=frames.device)
-        masks = self._mask_out(mask_out, (T,), frames.device) if want_mask and self.model.variant != "rpn" else None
+        score_only = iou is not None and T > 0 and not iou[0].get("masks", True)         # no mask tensor at all
+        masks = self._mask_out(mask_out, (T,), frames.device) if want_mask and self.model.variant != "rpn" and not score_only else None
         for t in range(T):
             self.enqueue(frames[t], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[t] if masks is not None else None,
                          gt=gt[t] if gt is not None else None, vos=self._vos_at(vos, alive, t) if vos is not None else None,
-                         labels_out=labels[t] if labels is not None else None)
+                         labels_out=labels[t] if labels is not None else None, iou=iou[t] if iou is not None else None)
         return self.collect(_masks=masks, _labels=labels)
 
     @staticmethod

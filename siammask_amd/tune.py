@@ -9,12 +9,22 @@ passes) and a sweep of G points is ceil(G / B) passes of run(vot=).
     out[i]['lost_times'], out[i]['lines']                             # of points[i]; lines: <video>_001.txt (tools/test.py:403-406)
     tune.result_dir('Custom_x', points[i])                            # the directory the tool would write them under (:64-68)
 
-The tool's result tree on disk and its finish.flag protocol are the caller's; so is tune_vos.py's loop."""
+tools/tune_vos.py is the same grid on a DAVIS video, scored by IouMeter at 11 thresholds instead of by losses: each pass is
+start() on frame 0 + run(iou=) with score-only frames -- the per-stream counts come from the device (smk_iou_score_dev), no
+mask reaches memory -- and the host finishes the meter (vos.iou_meter):
+
+    out = tune.sweep_vos(tr, frames, annos, rect, points)             # annos uint8 CUDA [T,H,W], rect (x, y, w, h) of frame 0
+    out[i]['iou'], out[i]['line']                                     # IouMeter.value('mean') [11]; the line of <video>.txt (:140)
+    tune.result_dir('Custom_x', points[i], refine=True)               # tune_vos.py:71-75
+
+The tools' result trees on disk, their finish.flag / 'Occ' protocols, the shuffles and the --search-region (instance_size) axis
+are the caller's."""
 import numpy as np
 
-from . import vot
+from . import vos, vot
 
 HP_KEYS = ("penalty_k", "window_influence", "lr")
+THRS_VOS = np.arange(0.3, 0.81, 0.05)   # tune_vos.py: thrs, the 11 float64 thresholds of its IouMeter
 
 
 def grid(penalty_k, window_influence, lr):
@@ -23,10 +33,10 @@ def grid(penalty_k, window_influence, lr):
             for k in penalty_k for w in window_influence for r in lr]
 
 
-def result_dir(network_name, hp, instance_size=255):
+def result_dir(network_name, hp, instance_size=255, refine=False):
     """the tracker directory of tune_vot.py:64-68 for one point: name, _r<instance_size>, the three values with three decimals,
-    every '.' replaced by '_'"""
-    return (network_name + "_r{}".format(instance_size) + "_penalty_k_{:.3f}".format(hp["penalty_k"]) +
+    every '.' replaced by '_'.  refine: tune_vos.py:71-75 puts '_refine' behind the name when it runs with --refine"""
+    return (network_name + ("_refine" if refine else "") + "_r{}".format(instance_size) + "_penalty_k_{:.3f}".format(hp["penalty_k"]) +
             "_window_influence_{:.3f}".format(hp["window_influence"]) + "_lr_{:.3f}".format(hp["lr"])).replace(".", "_")
 
 
@@ -70,6 +80,48 @@ def sweep_vot(tracker, frames, gt, points, skip=5):
                 out.append({"hp": points[idx[b]], "lost_times": int(res["lost_times"][b]),
                             "vot_code": res["vot_code"][:, b].copy(), "overlap": res["overlap"][:, b].copy(),
                             "lines": vot.region_lines(res, b)})
+    finally:
+        if not tracker._chunk_open():                                 # (a failed pass may have left one: the caller collects)
+            tracker.set_hp(before)
+    return out
+
+
+def sweep_vos(tracker, frames, annos, rect, points, thrs=THRS_VOS):
+    """tune_vos.py's loop (:97-140) over ONE video at every point of ``points`` (as for sweep_vot) on a tracker that is reserved
+    (reserve(B, H, W)) and has no chunk open.  frames: uint8 CUDA [T,H,W,3], T >= 3; annos: uint8 CUDA [T,H,W] (the target is
+    anno > 0); rect: (x, y, w, h) of the object on frame 0 (:102-104).  Each pass is set_hp(B points) + start(frames[0], every
+    stream, pos=, sz=) + run(frames[1:T-1], iou={'gt': annos[1:T-1], 'thrs': thrs, 'masks': False}): score-only frames.
+    The tool tracks frame T-1 as well, but scores only 0 < f < T-1 (:113) and writes nothing that depends on the last frame, so
+    the sweep leaves frame T-1 out.
+    -> one dict per point: 'hp' (the point), 'iou' float32 [K] = IouMeter(thrs, T - 2).value('mean'), 'line' (vos.iou_line of it,
+    the line of <video>.txt), 'counts' int64 [T-2,K,2].  The tracker's hp state (its table or none) is put back on exit."""
+    points = [dict(p) for p in points]
+    if not points or any(set(p) - set(HP_KEYS) for p in points):
+        raise ValueError("sweep_vos: at least one point, keys among %s" % (HP_KEYS,))
+    if getattr(frames, "ndim", 0) != 4 or frames.shape[0] < 3:
+        raise ValueError("sweep_vos: frames must be [T,H,W,3] with T >= 3 (frames 0 and T-1 are not scored)")
+    T = int(frames.shape[0])
+    if tuple(getattr(annos, "shape", ())) != tuple(frames.shape[:3]):
+        raise ValueError("sweep_vos: annos must be [T,H,W] = %s, one annotation per frame" % (tuple(frames.shape[:3]),))
+    rect = np.asarray(rect, dtype=np.float64).reshape(-1)
+    if rect.shape != (4,):
+        raise ValueError("sweep_vos: rect is (x, y, w, h) of frame 0")
+    if tracker.state is None or tracker._fr is None:
+        raise RuntimeError("sweep_vos: reserve() the tracker first")
+    B = tracker._fr.B
+    pos = np.tile([rect[0] + rect[2] / 2, rect[1] + rect[3] / 2], (B, 1))
+    sz = np.tile([rect[2], rect[3]], (B, 1))
+    before = tracker.get_hp()
+    out = []
+    try:
+        for idx, keep in pass_plan(len(points), B):
+            tracker.set_hp([points[i] for i in idx])
+            tracker.start(frames[0], list(range(B)), pos=pos, sz=sz)
+            res = tracker.run(frames[1:T - 1], iou={"gt": annos[1:T - 1], "thrs": thrs, "masks": False})
+            for b in range(keep):
+                counts = res["iou_counts"][:, b].copy()
+                mean, _ = vos.iou_meter(counts, "mean", T - 2)
+                out.append({"hp": points[idx[b]], "iou": mean, "line": vos.iou_line(mean), "counts": counts})
     finally:
         if not tracker._chunk_open():                                 # (a failed pass may have left one: the caller collects)
             tracker.set_hp(before)

@@ -1,6 +1,7 @@
 """The host half of the reference's VOS meter (tools/test.py:421-456 MultiBatchIouMeter): the per-frame intersection / union
 counts come from the device (preproc.vos_score, DeviceTracker.run(..., gt=, vos=) -> res['vos_counts']); what is left is the
-frame window, the per-frame ratio and the mean.  Pure numpy, no torch, no device."""
+frame window, the per-frame ratio and the mean.  iou_meter is the same for the single-object meter of tools/tune_vos.py (IouMeter,
+utils/average_meter_helper.py:71-113) over preproc.iou_score / run(..., iou=) -> res['iou_counts'].  Pure numpy, no torch, no device."""
 import numpy as np
 
 THRS = np.arange(0.3, 0.5, 0.05)        # tools/test.py: thrs, float64 (0.3, 0.35, 0.39999999999999997, 0.44999999999999996)
@@ -38,3 +39,37 @@ def mean_iou(counts, start=None, end=None, object_ids=None):
         for k in range(K):
             res[j, k] = np.mean(np.ascontiguousarray(iou[:, k]))       # the float64 mean of :455, stored as float32
     return res
+
+
+def iou_meter(counts, kind="mean", sz=None):
+    """counts: host integer array [T', K, 2] = (intersection, union) of the frames handed to IouMeter.add, in order (one stream of
+    res['iou_counts']) -> (IouMeter(thrs, sz).value(kind) [K], the meter's table float32 [sz, K]).  sz: the rows of the table
+    (tune_vos.py:97 len(ims) - 2; default T'); frames beyond sz are ignored as add() ignores them (:83-84), rows no frame filled
+    stay 0.  A frame's entry is float32(intersection / union), the float64 ratio narrowed on assignment (:92), or 1 where the
+    union is empty (:93-94).  value() keeps the reference's quirk (:98-99): nb = max(number of positive ENTRIES, 1) cuts the
+    table's ROWS, iou[:nb].  kind: 'mean' (float32 mean over the rows, what tune_vos.py writes), 'median', or a number t (the
+    share of the nb rows above t, float64)."""
+    c = np.asarray(counts)
+    if c.ndim != 3 or c.shape[2] != 2 or c.dtype.kind not in "iu":
+        raise ValueError("counts must be an integer array [T, K, 2]")
+    sz = c.shape[0] if sz is None else int(sz)
+    if sz < 0:
+        raise ValueError("sz must not be negative")
+    c = c[:sz]
+    table = np.zeros((sz, c.shape[1]), dtype=np.float32)
+    intxn, union = c[:, :, 0].astype(np.float64), c[:, :, 1].astype(np.float64)
+    table[:c.shape[0]] = np.where(union > 0, intxn / np.where(union > 0, union, 1.0), 1.0)
+    nb = max(int(np.sum(table > 0)), 1)
+    iou = table[:nb]
+    if kind == "mean":
+        res = np.mean(iou, axis=0)
+    elif kind == "median":
+        res = np.median(iou, axis=0)
+    else:
+        res = np.sum(iou > float(kind), axis=0) / float(nb)
+    return res, table
+
+
+def iou_line(mean):
+    """the line tune_vos.py:140 writes for one video (without its newline)"""
+    return ",".join(["%.5f" % i for i in mean])
