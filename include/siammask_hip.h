@@ -252,6 +252,25 @@ int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_m
 size_t smk_mask_rbox_workspace(int B, int W, int H);
 int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev,
                   size_t ws_bytes, double *out_dev, void *stream);
+/* The same rows by one of two forms (additive; smk_mask_rbox is smk_mask_rbox_ex with SMK_RBOX_TRACE, launch for launch):
+ *   SMK_RBOX_TRACE  : pack, union, one lane per component follows its outer border, rows, hull -- over the whole frame.
+ *   SMK_RBOX_CYCLES : a pass behind the pack pass reduces the bounding rectangle of the set pixels, and every later pass works
+ *     inside it.  The border rule is a permutation of the states (pixel, direction); the contour area of a component is the sum of
+ *     one local term per state of one cycle of it, so the area is summed in parallel (union-by-minimum over state ~ successor,
+ *     integer atomics: the order of the adds does not matter) and the rows are the same byte for byte.  States are numbered
+ *     densely inside the rectangle, at most SMK_RBOX_STATE_CAP per stream: a stream whose rectangle holds more than
+ *     SMK_RBOX_STATE_CAP / 8 = 2^19 pixels takes the serial trace instead, decided on the device, with the same result.
+ * Semantics, row layout and argument rules are those of smk_mask_rbox; a mode outside 0..1 is SMK_E_ARG (0 from the workspace
+ * query).  Asynchronous on `stream` in both modes; no host decision depends on the mask.
+ * smk_mask_rbox_workspace_ex(B, W, H, SMK_RBOX_CYCLES) = the SMK_RBOX_TRACE bytes
+ *   + B * 32 (rectangles) + B * H * ceil(W/2) * 8 (one 64-bit sum per possible run) + B * min(SMK_RBOX_STATE_CAP, 8 W H) * 4
+ *   (one parent per state), each term rounded up to 256: at most three times the SMK_RBOX_TRACE bytes plus the states. */
+#define SMK_RBOX_TRACE  0
+#define SMK_RBOX_CYCLES 1
+#define SMK_RBOX_STATE_CAP (1 << 22)
+size_t smk_mask_rbox_workspace_ex(int B, int W, int H, int mode);
+int smk_mask_rbox_ex(const unsigned char *mask_dev, int B, int W, int H, double min_area, int mode,
+                     void *ws_dev, size_t ws_bytes, double *out_dev, void *stream);
 
 /* ---- tracker state on the device (tools/test.py:173-311 siamese_track; ABI 1.8, additive) ------
  * The float64 scalars that connect one frame to the next live in a caller-owned device block, so that a tracker loop is

@@ -220,6 +220,11 @@ int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t st
  * NULL) as for smk_vot_overlap. */
 int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, int im_h, float *overlap, int32_t *counts);
 
+/* which path each stream took in the last smk_mask_rbox_ex(mode = SMK_RBOX_CYCLES) call on workspace `ws_dev` (same B, W, H):
+ * paths_host [B] = 0 parallel contour area, 1 serial trace (bounding rectangle beyond SMK_RBOX_STATE_CAP).  Synchronises the
+ * device, then copies.  Any other mode: SMK_E_ARG. */
+int smk_test_mask_rbox_paths(const void *ws_dev, int B, int W, int H, int mode, int *paths_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ SYMBOLS = (
     "smk_paste_mask_dev_v", "smk_vot_overlap_dev",
     "smk_set_stream_hp", "smk_trk_advance_hp", "smk_host_trk_advance_hp",
     "smk_iou_score", "smk_iou_score_dev",
+    "smk_mask_rbox_workspace_ex", "smk_mask_rbox_ex", "smk_test_mask_rbox_paths",
 )
 
 
@@ -144,6 +145,9 @@ def lib():
     L.smk_paste_labels.argtypes = [fp, ci, vp, ci, ci, ci, ctypes.c_float, ctypes.c_float, vp, vp]
     L.smk_mask_rbox_workspace.argtypes = [ci, ci, ci]
     L.smk_mask_rbox.argtypes = [vp, ci, ci, ci, ctypes.c_double, vp, ctypes.c_size_t, vp, vp]
+    L.smk_mask_rbox_workspace_ex.argtypes = [ci, ci, ci, ci]
+    L.smk_mask_rbox_ex.argtypes = [vp, ci, ci, ci, ctypes.c_double, ci, vp, ctypes.c_size_t, vp, vp]
+    L.smk_test_mask_rbox_paths.argtypes = [vp, ci, ci, ci, ci, vp]
     cp = ctypes.POINTER(TrkCfg)
     L.smk_trk_state_bytes.argtypes = [ci]
     L.smk_trk_set.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp]
@@ -184,7 +188,7 @@ def lib():
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
-            fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_trk_state_bytes") else ci
+            fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

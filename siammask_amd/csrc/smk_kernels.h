@@ -525,6 +525,20 @@ struct RboxParams {
     double *out;                       // [B][12]
 };
 int launch_mask_rbox(const RboxParams &p, void *stream);
+// mask_rbox_cycles.hip: the same rows with the contour area summed in parallel inside the bounding rectangle of the set pixels.
+// Further workspace, behind the four arrays above: cyc [B], acc [B][H][Wh] (one 64-bit sum per run slot), sparent [B][sstride]
+// (one union-find parent per state (pixel of the rectangle, direction); sstride = min(RBOX_STATE_CAP, 8 W H))
+#define RBOX_STATE_CAP (1 << 22)       // = SMK_RBOX_STATE_CAP
+struct RboxCyc {                       // written whole by the rectangle pass
+    int x1, y1, nx0, ny0;              // rectangle of the set pixels: last x + 1, last y + 1, 2^30 - first x, 2^30 - first y; x1 == 0: none
+    int path, pad[3];                  // 0: parallel area, 1: serial trace (rectangle beyond the state capacity)
+};
+struct RboxCycParams {
+    RboxParams r;
+    RboxCyc *cyc; long long *acc; int *sparent;
+    int sstride;
+};
+int launch_mask_rbox_cycles(const RboxCycParams &c, void *stream);
 const void *zero_page();   // device-resident 8 KB of zeros (allocated on first use, per device)
 
 }  // namespace smk

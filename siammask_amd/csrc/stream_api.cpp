@@ -76,31 +76,47 @@ int smk_paste_labels(const float *logits_dev, int mask_size, const double *inv_m
 static const int RBOX_MAX_DIM = 4096;
 static inline size_t rup256(size_t x) { return (x + 255) / 256 * 256; }
 
-size_t smk_mask_rbox_workspace(int B, int W, int H) {
-    if (B < 1 || W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM) return 0;
-    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+static size_t rbox_ws0(size_t b, size_t W, size_t H) {
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2;
     return rup256(b * sizeof(RboxHdr)) + rup256(b * H * 2 * sizeof(int)) + rup256(b * H * Wq * 8) + rup256(b * H * Wh * sizeof(int));
 }
+static size_t rbox_sstride(size_t W, size_t H) { return 8 * W * H < (size_t)RBOX_STATE_CAP ? 8 * W * H : (size_t)RBOX_STATE_CAP; }
 
-int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev, size_t ws_bytes,
-                  double *out_dev, void *stream) {
+size_t smk_mask_rbox_workspace_ex(int B, int W, int H, int mode) {
+    if (B < 1 || W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM || mode < SMK_RBOX_TRACE || mode > SMK_RBOX_CYCLES) return 0;
+    const size_t b = (size_t)B, Wh = (W + 1) / 2;
+    size_t n = rbox_ws0(b, W, H);
+    if (mode == SMK_RBOX_CYCLES)
+        n += rup256(b * sizeof(RboxCyc)) + rup256(b * H * Wh * sizeof(long long)) + rup256(b * rbox_sstride(W, H) * sizeof(int));
+    return n;
+}
+
+size_t smk_mask_rbox_workspace(int B, int W, int H) { return smk_mask_rbox_workspace_ex(B, W, H, SMK_RBOX_TRACE); }
+
+int smk_mask_rbox_ex(const unsigned char *mask_dev, int B, int W, int H, double min_area, int mode, void *ws_dev, size_t ws_bytes,
+                     double *out_dev, void *stream) {
     if (!mask_dev || !ws_dev || !out_dev) return fail(SMK_E_ARG, "smk_mask_rbox: null argument");
     if (B < 1) return fail(SMK_E_ARG, "smk_mask_rbox: batch %d", B);
     if (W < 1 || H < 1 || W > RBOX_MAX_DIM || H > RBOX_MAX_DIM)
         return fail(SMK_E_ARG, "smk_mask_rbox: frame %d x %d outside 1..%d", W, H, RBOX_MAX_DIM);
     if (!(min_area >= 0)) return fail(SMK_E_ARG, "smk_mask_rbox: min_area must be >= 0");
-    const size_t need = smk_mask_rbox_workspace(B, W, H);
+    if (mode < SMK_RBOX_TRACE || mode > SMK_RBOX_CYCLES) return fail(SMK_E_ARG, "smk_mask_rbox: mode %d", mode);
+    const size_t need = smk_mask_rbox_workspace_ex(B, W, H, mode);
     if (ws_bytes < need) return fail(SMK_E_ARG, "smk_mask_rbox: workspace of %zu bytes, %zu needed", ws_bytes, need);
     if ((uintptr_t)ws_dev % 16) return fail(SMK_E_ARG, "smk_mask_rbox: workspace must be 16-byte aligned");
-    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B;
+    const size_t Wq = (W + 63) / 64, Wh = (W + 1) / 2, b = (size_t)B, sstride = rbox_sstride(W, H);
     char *w = (char *)ws_dev;
     RboxHdr *hdr = (RboxHdr *)w;                       w += rup256(b * sizeof(RboxHdr));
     int *rows = (int *)w;                              w += rup256(b * H * 2 * sizeof(int));
     unsigned long long *bits = (unsigned long long *)w; w += rup256(b * H * Wq * 8);
-    int *parent = (int *)w;
+    int *parent = (int *)w;                            w += rup256(b * H * Wh * sizeof(int));
+    RboxCyc *cyc = (RboxCyc *)w;                       w += rup256(b * sizeof(RboxCyc));     // (mode 1 only, as what follows)
+    long long *acc = (long long *)w;                   w += rup256(b * H * Wh * sizeof(long long));
+    int *sparent = (int *)w;
     const int GRID_Y = 32768;                          // streams per launch (grid.y)
     for (int b0 = 0; b0 < B; b0 += GRID_Y) {
-        RboxParams p;
+        RboxCycParams c;
+        RboxParams &p = c.r;
         p.mask = mask_dev + (size_t)b0 * H * W;
         p.B = B - b0 < GRID_Y ? B - b0 : GRID_Y;
         p.W = W; p.H = H; p.Wq = (int)Wq; p.Wh = (int)Wh;
@@ -108,8 +124,31 @@ int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min
         p.hdr = hdr + b0; p.rows = rows + (size_t)b0 * H * 2; p.bits = bits + (size_t)b0 * H * Wq;
         p.parent = parent + (size_t)b0 * H * Wh;
         p.out = out_dev + (size_t)b0 * 12;
-        if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
+        if (mode == SMK_RBOX_TRACE) {
+            if (launch_mask_rbox(p, stream)) return fail(SMK_E_HIP, "mask_rbox launch failed");
+            continue;
+        }
+        c.cyc = cyc + b0; c.acc = acc + (size_t)b0 * H * Wh; c.sparent = sparent + (size_t)b0 * sstride;
+        c.sstride = (int)sstride;
+        if (launch_mask_rbox_cycles(c, stream)) return fail(SMK_E_HIP, "mask_rbox (cycles) launch failed");
     }
+    return 0;
+}
+
+int smk_mask_rbox(const unsigned char *mask_dev, int B, int W, int H, double min_area, void *ws_dev, size_t ws_bytes,
+                  double *out_dev, void *stream) {
+    return smk_mask_rbox_ex(mask_dev, B, W, H, min_area, SMK_RBOX_TRACE, ws_dev, ws_bytes, out_dev, stream);
+}
+
+// test-only (siammask_hip_test.h): which path each stream of the last SMK_RBOX_CYCLES call on this workspace took
+int smk_test_mask_rbox_paths(const void *ws_dev, int B, int W, int H, int mode, int *paths_host) {
+    if (!ws_dev || !paths_host || mode != SMK_RBOX_CYCLES || !smk_mask_rbox_workspace_ex(B, W, H, mode))
+        return fail(SMK_E_ARG, "smk_test_mask_rbox_paths: bad argument");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(SMK_E_HIP, "smk_test_mask_rbox_paths: synchronise failed");
+    const RboxCyc *cyc = (const RboxCyc *)((const char *)ws_dev + rbox_ws0((size_t)B, W, H));
+    for (int i = 0; i < B; ++i)
+        if (hipMemcpy(paths_host + i, &cyc[i].path, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
+            return fail(SMK_E_HIP, "smk_test_mask_rbox_paths: copy failed");
     return 0;
 }
 

@@ -390,15 +390,20 @@ def frame_sums(frames, out=None):
     return out
 
 
-_rbox_ws = {}      # (device, stream, B, W, H) -> scratch of smk_mask_rbox (sized for the worst case of ceil(W/2)*H runs per mask)
+_rbox_ws = {}      # (device, stream, B, W, H, mode) -> scratch of smk_mask_rbox_ex (sized for the worst case of ceil(W/2)*H runs per mask)
+RBOX_MODES = {"trace": 0, "cycles": 1}     # SMK_RBOX_TRACE, SMK_RBOX_CYCLES
 
 
-def mask_rboxes(mask, min_area=100.0, out=None):
+def mask_rboxes(mask, min_area=100.0, out=None, mode="trace"):
     """The rotated rectangle of the largest external contour of each mask (tools/test.py:285-294), on the device.
     mask: uint8 CUDA tensor [B,H,W] or [H,W] (a pixel is set when non-zero), H and W up to 4096.
     -> float64 CUDA tensor [B,12]: x0 y0 x1 y1 x2 y2 x3 y3 (corners in cyclic order), contour area of the selected component,
     found (1: area > min_area; 0: not; -1: the row is invalid), n_components, n_hull (include/siammask_hip.h: smk_mask_rbox).
-    out: a contiguous float64 CUDA tensor of B * 12 elements to write the rows into instead of a new one."""
+    out: a contiguous float64 CUDA tensor of B * 12 elements to write the rows into instead of a new one.
+    mode: "trace" (one lane follows each border, whole frame) or "cycles" (contour area summed in parallel inside the bounding
+    rectangle of the set pixels); the rows are the same byte for byte."""
+    if mode not in RBOX_MODES:
+        raise ValueError("mask_rboxes: mode must be one of %s, got %r" % (sorted(RBOX_MODES), mode))
     _need_cuda(mask, "mask")
     if mask.dtype != torch.uint8 or mask.dim() not in (2, 3):
         raise ValueError("mask must be uint8 [B,H,W] or [H,W]")
@@ -407,12 +412,12 @@ def mask_rboxes(mask, min_area=100.0, out=None):
         m = m[None]
     B, H, W = (int(v) for v in m.shape)
     L = _lib.lib()
-    need = L.smk_mask_rbox_workspace(B, W, H)
+    need = L.smk_mask_rbox_workspace_ex(B, W, H, RBOX_MODES[mode])
     if need == 0:
         raise ValueError("mask_rboxes: B >= 1 and H, W in 1..4096, got %s" % (tuple(m.shape),))
     with torch.cuda.device(m.device):
         stream = _lib.current_stream_ptr()
-        key = (m.device.index, stream.value, B, W, H)
+        key = (m.device.index, stream.value, B, W, H, mode)
         ws = _rbox_ws.get(key)
         if ws is None:
             ws = _rbox_ws[key] = torch.empty(need, dtype=torch.uint8, device=m.device)
@@ -420,7 +425,8 @@ def mask_rboxes(mask, min_area=100.0, out=None):
             out = torch.empty((B, 12), dtype=torch.float64, device=m.device)
         elif out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous() or out.numel() != B * 12:
             raise ValueError("mask_rboxes: out must be a contiguous float64 CUDA tensor of %d elements" % (B * 12))
-        _lib.check(L.smk_mask_rbox(m.data_ptr(), B, W, H, float(min_area), ws.data_ptr(), need, out.data_ptr(), stream))
+        _lib.check(L.smk_mask_rbox_ex(m.data_ptr(), B, W, H, float(min_area), RBOX_MODES[mode], ws.data_ptr(), need, out.data_ptr(),
+                                      stream))
     return out
 
 

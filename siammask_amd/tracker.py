@@ -237,12 +237,16 @@ def collect_host(host, T, B, poly, K, events, ev_rows, state, counts_key="vos_co
 
 
 class DeviceTracker(object):
-    def __init__(self, model, hp=None, pipeline=False):
-        """pipeline=True: the frame steps are software-pipelined (Custom.set_pipeline): the host reads the decoded box and updates
+    def __init__(self, model, hp=None, pipeline=False, rbox="trace"):
+        """rbox: the form of preproc.mask_rboxes behind want_polygon, "trace" or "cycles" -- the same polygons byte for byte.
+        pipeline=True: the frame steps are software-pipelined (Custom.set_pipeline): the host reads the decoded box and updates
         the tracker state (:240-250,302-305) while the Refine mask of the same frame is still being computed on a side stream; the
         mask is joined only where it is pasted back (:257-284) -- same results."""
+        if rbox not in preproc.RBOX_MODES:
+            raise ValueError("DeviceTracker: rbox must be one of %s, got %r" % (sorted(preproc.RBOX_MODES), rbox))
         self.model = model
         self.pipeline = bool(pipeline)
+        self.rbox = rbox
         self.p = TrackerConfig(hp)
         self.refine = model.variant == "sharp"
         # config_davis.json hp sets out_size 127 for the Refine output; the base head is 63x63
@@ -591,7 +595,7 @@ class DeviceTracker(object):
                 logits = m[idx, :, torch.as_tensor(delta_y, device=m.device), torch.as_tensor(delta_x, device=m.device)]
             masks = preproc.paste_masks(logits, bbs, (st["im_w"], st["im_h"]), seg_thr=p.seg_thr)
             if want_polygon:                                          # same stream, behind the paste-back (:285-303)
-                st["polygon"], st["polygon_found"] = rotated_boxes(masks, new_pos, new_sz)
+                st["polygon"], st["polygon_found"] = rotated_boxes(masks, new_pos, new_sz, mode=self.rbox)
         new_pos[:, 0] = np.clip(new_pos[:, 0], 0, st["im_w"])         # (:302-305)
         new_pos[:, 1] = np.clip(new_pos[:, 1], 0, st["im_h"])
         new_sz[:, 0] = np.clip(new_sz[:, 0], 10, st["im_w"])
@@ -872,7 +876,7 @@ class DeviceTracker(object):
         else:
             _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
         if job.rbox is not None:                                      # same stream, behind the paste-back (:285-303)
-            preproc.mask_rboxes(mask, out=job.rbox)
+            preproc.mask_rboxes(mask, out=job.rbox, mode=self.rbox)
         if s is not None:                                             # the same slot of the same state block, same stream
             args = shared + (-1.0, s.gt.data_ptr(), s.ids.ctypes.data, s.bits, s.thrs.ctypes.data, int(s.thrs.size),
                              float(p.seg_thr), s.row.data_ptr(), s.labels.data_ptr())
@@ -1046,10 +1050,10 @@ class DeviceTracker(object):
         return vos if alive is None or alive.ndim == 1 else dict(vos, alive=alive[t])
 
 
-def rotated_boxes(masks, target_pos, target_sz, min_area=100.0):
+def rotated_boxes(masks, target_pos, target_sz, min_area=100.0, mode="trace"):
     """tools/test.py:285-303: minAreaRect of the largest contour where its area exceeds 100, else the axis-aligned box of
     cxy_wh_2_rect(target_pos, target_sz) (the updated state before it is clipped) -> float64 [B,4,2], bool [B]"""
-    rows = preproc.mask_rboxes(masks, min_area=min_area).cpu().numpy()
+    rows = preproc.mask_rboxes(masks, min_area=min_area, **({} if mode == "trace" else {"mode": mode})).cpu().numpy()
     if (rows[:, 9] < 0).any():
         raise RuntimeError("mask_rboxes: a loop bound was exceeded for streams %s" % np.nonzero(rows[:, 9] < 0)[0].tolist())
     found = rows[:, 9] > 0
