@@ -331,6 +331,34 @@ int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score
                        int slot, int B, int W, int H, float seg_thr, float border, uint8_t *mask_out_dev,
                        float *prob_out_dev, void *stream);
 
+/* ---- the mask as COCO run-length codes, encoded on the device (data/coco/pycocotools/common/maskApi.c rleEncode; additive;
+ * smk_version() keeps reporting 1.10, the presence of these symbols is the probe) ------------------------------------------------
+ * For an H x W mask the pixels are numbered column-major, j = x * H + y, a = H * W.  A pixel is SET when its byte is non-zero
+ * (smk_rle_encode), resp. when warped_prob(x, y) > seg_thr (smk_paste_rle_dev) -- the float32 comparison smk_paste_mask_dev makes, so
+ * the bits are those of the bytes it writes for the same arguments, and no mask byte reaches memory.  With bit(-1) = 0, a transition
+ * is a j in 0 .. a - 1 with bit(j) != bit(j - 1); m = transitions + 1; counts[0 .. m - 1] are the gaps between consecutive transition
+ * positions: from 0 to the first, between transitions, from the last to a.  So counts[0] is the number of leading unset pixels (0
+ * when pixel 0 is set), the counts alternate unset / set and sum to a, an empty mask is [a], a full one [0, a].  On masks of bytes
+ * 0 / 1 -- what the paste entries write -- this is rleEncode exactly.  rleEncode itself compares byte VALUES (1 next to 7 starts a
+ * run there): masks with more than one non-zero value are outside the pinned equality; here every non-zero byte is the same `set`.
+ * counts_out_dev: uint32 [B][cap]; meta_out_dev: int32 [B][4] = (m, area, H, W) with m ALWAYS the true number of counts and area the
+ * number of set pixels.  If m > cap only counts[0 .. cap - 1] of that stream are written -- nothing at or past
+ * counts_out_dev + (b + 1) * cap ever is -- and the caller sees the overflow as m > cap.  Elements m .. cap - 1 are not written.
+ * No atomics: the bytes written are a function of the mask alone, nothing needs zeroing, a second call gives the same bytes.
+ * W, H in 1..4096 (a <= 2^24), cap in 1..a + 1, B in 1..65535.  ws_dev: smk_rle_workspace(B, W, H) = B * ceil(W * H / 64) * 8 bytes
+ * rounded up to 256 (0 for a bad geometry) -- one bit per pixel --, 8-byte aligned, owned by the call until it has completed on
+ * `stream`; the outputs 4-byte aligned.  Bad arguments (a null pointer, a range above, a short or misaligned workspace) give SMK_E_ARG
+ * before anything is enqueued.  No context; asynchronous on `stream`, no host synchronisation.
+ * smk_paste_rle_dev takes the arguments of smk_paste_mask_dev with the same meaning: both input forms (head_dev != NULL: the column
+ * delta_yx[slot] of the mask head) and inv_map[slot] of the state block.  The ASCII form (rleToString) is host work on m numbers:
+ * siammask_amd.rle. */
+size_t smk_rle_workspace(int B, int W, int H);
+int smk_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
+                   uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+int smk_paste_rle_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int B, int W, int H, float seg_thr, float border, int cap, void *ws_dev, size_t ws_bytes,
+                      uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+
 /* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
  * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
  * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:

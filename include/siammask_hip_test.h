@@ -225,6 +225,11 @@ int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, 
  * device, then copies.  Any other mode: SMK_E_ARG. */
 int smk_test_mask_rbox_paths(const void *ws_dev, int B, int W, int H, int mode, int *paths_host);
 
+/* smk_rle_encode with the byte source chosen: form 1 = 64 columns x H rows through LDS (what smk_rle_encode launches), 0 = one byte
+ * per lane at stride W.  The same counts and meta rows; everything else as smk_rle_encode.  A form outside 0..1: SMK_E_ARG. */
+int smk_test_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
+                        uint32_t *counts_out_dev, int32_t *meta_out_dev, int form, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ SYMBOLS = (
     "smk_set_stream_hp", "smk_trk_advance_hp", "smk_host_trk_advance_hp",
     "smk_iou_score", "smk_iou_score_dev",
     "smk_mask_rbox_workspace_ex", "smk_mask_rbox_ex", "smk_test_mask_rbox_paths",
+    "smk_rle_workspace", "smk_rle_encode", "smk_paste_rle_dev", "smk_test_rle_encode",
 )
 
 
@@ -182,13 +183,18 @@ def lib():
     L.smk_host_trk_advance_hp.argtypes = [vp, ci, cp, vp, vp, ci, vp, ci]
     L.smk_iou_score.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, i64, vp, ci, cf, vp, vp, vp]
     L.smk_iou_score_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, vp, i64, vp, ci, cf, vp, vp, vp]
+    L.smk_rle_workspace.argtypes = [ci, ci, ci]
+    L.smk_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_test_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, ci, vp]
+    L.smk_paste_rle_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, cf, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
-            fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes") else ci
+            fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes",
+                                                        "smk_rle_workspace") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

@@ -516,6 +516,140 @@ int launch_iou_score(const IouParams &p, int B, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- COCO run-length codes of the mask (data/coco/pycocotools/common/maskApi.c rleEncode; smk_rle_encode / smk_paste_rle_dev) ------
+// Pixels are numbered column-major, j = x * H + y.  rle_bits: one lane per j, the wave's 64 bits are one __ballot and lane 0 stores
+// the word (no lane leaves before the ballot; lanes at or past a = W * H vote 0, so the bits past a in the last word are 0).  The
+// fused source is the comparison paste_mask_dev_kernel makes, warped_prob(x, y) > seg_thr: the same bits, and no mask byte exists.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void rle_bits_kernel(const RleParams p) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int a = p.W * p.H, nw = (int)rle_words(p.W, p.H);
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6), j = k * 64 + lane;
+    bool bit = false;
+    if (j < a) {
+        const int x = j / p.H, y = j - x * p.H;
+        if constexpr (FUSED) {
+            const PasteDevParams &q = p.paste;
+            const smk_trk_stream *s = q.st + b;
+            const float *lg = q.logits + (size_t)b * q.ms * q.ms;
+            int ls = 1;
+            if (q.head_S) {
+                ls = q.head_S * q.head_S;
+                const int dy = min(max(s->delta_yx[q.slot][0], 0), q.head_S - 1), dx = min(max(s->delta_yx[q.slot][1], 0), q.head_S - 1);
+                lg = q.logits + (size_t)b * q.ms * q.ms * ls + dy * q.head_S + dx;
+            }
+            bit = warped_prob(q, s->inv_map[q.slot], lg, ls, x, y) > q.seg_thr;
+        } else {
+            bit = p.mask[((size_t)b * p.H + y) * p.W + x] != 0;       // 64 lines per wave load; the next 127 columns find them in L2
+        }
+    }
+    const unsigned long long w = __ballot(bit);
+    if (lane == 0 && k < nw) p.words[(size_t)b * nw + k] = w;
+}
+
+// the byte source through LDS: a workgroup takes 64 columns x H rows.  64 x0 H is a multiple of 64, so the columns [x0, x0 + 64) are
+// exactly the words [x0 / 64 * H, ...) -- H of them, fewer for a ragged last block, which ends at the stream's last word.  Pass 1
+// reads rows (lane = column, 64 consecutive bytes) and keeps one ballot per row; pass 2 gathers bit xl of row y for j = xl * H + y.
+__global__ __launch_bounds__(1024) void rle_bits_tile_kernel(const RleParams p) {
+    __shared__ unsigned long long rows[RLE_MAX_SIDE];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int H = p.H, x0 = blockIdx.x * 64, nc = min(64, p.W - x0);
+    const unsigned char *m = p.mask + (size_t)b * p.W * H + x0;
+    for (int y = wave; y < H; y += 16) {                              // (wave-uniform trip counts: every lane reaches the ballots)
+        const bool bit = lane < nc && m[(size_t)y * p.W + lane] != 0;
+        const unsigned long long r = __ballot(bit);
+        if (lane == 0) rows[y] = r;
+    }
+    __syncthreads();
+    const int nbits = nc * H, nloc = (nbits + 63) / 64;
+    unsigned long long *words = p.words + (size_t)b * rle_words(p.W, H) + (size_t)blockIdx.x * H;
+    for (int k = wave; k < nloc; k += 16) {
+        const int jl = 64 * k + lane;
+        bool bit = false;
+        if (jl < nbits) {
+            const int xl = jl / H, y = jl - xl * H;
+            bit = (rows[y] >> xl) & 1;
+        }
+        const unsigned long long w = __ballot(bit);
+        if (lane == 0) words[k] = w;
+    }
+}
+
+// rle_scan: one workgroup of 1024 per stream walks the words in chunks of 1024.  Per word t = w ^ ((w << 1) | last bit of the previous
+// word) marks the transitions (bit(-1) = 0), cut to j < a.  Two workgroup scans per chunk with a running carry: the exclusive sum of
+// popc(t) is a word's first output index, the exclusive max of the words' last transition positions is the position that precedes
+// its first transition (0 before the first one: counts[0] is the number of leading unset pixels).  Every thread writes the counts
+// of its own word; thread 0 writes the last count a - (last position) and the meta row.  No atomics: nothing needs zeroing, every
+// byte written is a function of the words alone.  Indices at or past cap are not written.
+__global__ __launch_bounds__(1024) void rle_scan_kernel(const RleParams p) {
+    __shared__ int s_sum[16], s_max[16], s_area[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const int a = p.W * p.H, nw = (int)rle_words(p.W, p.H), tail = a & 63;
+    const unsigned long long *words = p.words + (size_t)b * nw;
+    unsigned *out = p.counts + (size_t)b * p.cap;
+    int n_tr = 0, last = 0, area = 0;                                 // uniform carries: transitions, last position; private: set pixels
+    for (int k0 = 0; k0 < nw; k0 += 1024) {
+        const int k = k0 + tid;
+        unsigned long long w = 0, t = 0;
+        if (k < nw) {
+            w = words[k];
+            t = w ^ ((w << 1) | (k ? words[k - 1] >> 63 : 0ull));
+            if (k == nw - 1 && tail) t &= (1ull << tail) - 1;         // (a set last pixel is no transition at j = a)
+        }
+        area += __popcll(w);
+        const int c = __popcll(t);
+        int s = c, m = t ? 64 * k + 63 - __clzll((long long)t) : 0;   // inclusive over the wave below
+        for (int d = 1; d < 64; d <<= 1) {
+            const int s2 = __shfl_up(s, d), m2 = __shfl_up(m, d);
+            if (lane >= d) { s += s2; m = max(m, m2); }
+        }
+        if (lane == 63) { s_sum[wave] = s; s_max[wave] = m; }
+        __syncthreads();
+        int o = n_tr + s - c, prev = last, tot = 0, tmax = 0;
+        for (int v = 0; v < 16; ++v) {
+            const int sv = s_sum[v], mv = s_max[v];
+            if (v < wave) { o += sv; prev = max(prev, mv); }
+            tot += sv;
+            tmax = max(tmax, mv);
+        }
+        const int mp = __shfl_up(m, 1);
+        if (lane) prev = max(prev, mp);
+        while (t) {
+            const int pos = 64 * k + __ffsll((long long)t) - 1;
+            if (o < p.cap) out[o] = (unsigned)(pos - prev);
+            prev = pos;
+            ++o;
+            t &= t - 1;
+        }
+        n_tr += tot;
+        last = max(last, tmax);
+        __syncthreads();
+    }
+    for (int d = 32; d; d >>= 1) area += __shfl_down(area, d);
+    if (lane == 0) s_area[wave] = area;
+    __syncthreads();
+    if (tid == 0) {
+        int set = 0;
+        for (int v = 0; v < 16; ++v) set += s_area[v];
+        if (n_tr < p.cap) out[n_tr] = (unsigned)(a - last);
+        int *meta = p.meta + 4 * b;
+        meta[0] = n_tr + 1; meta[1] = set; meta[2] = p.H; meta[3] = p.W;
+    }
+}
+
+int launch_rle(const RleParams &p, int B, void *stream) {
+    if (B < 1 || B > 65535 || p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || p.cap < 1 || p.cap > p.W * p.H + 1) return -1;
+    if (!p.words || !p.counts || !p.meta || (!p.mask && (!p.paste.logits || !p.paste.st))) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 lanes((unsigned)((rle_words(p.W, p.H) + 3) / 4), B);
+    if (!p.mask)     hipLaunchKernelGGL((rle_bits_kernel<true>), lanes, dim3(256), 0, s, p);
+    else if (p.tile) hipLaunchKernelGGL(rle_bits_tile_kernel, dim3((p.W + 63) / 64, B), dim3(1024), 0, s, p);
+    else             hipLaunchKernelGGL((rle_bits_kernel<false>), lanes, dim3(256), 0, s, p);
+    if (hipGetLastError() != hipSuccess) return -4;
+    hipLaunchKernelGGL(rle_scan_kernel, dim3(B), dim3(1024), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_paste_mask(const PasteParams &p, int B, void *stream) {
     if (B < 1 || B > CROP_MAX_B) return -1;
     dim3 grid((p.W + 255) / 256, p.H, B);

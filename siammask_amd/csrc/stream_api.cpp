@@ -289,6 +289,72 @@ int smk_paste_mask_dev(const float *logits_dev, const float *head_dev, int score
     return 0;
 }
 
+// ---- COCO run-length codes (maskApi.c rleEncode; image_kernels.hip rle_bits / rle_scan) ------------------------------------------
+static bool rle_geometry(int B, int W, int H) {
+    return B >= 1 && B <= 65535 && W >= 1 && H >= 1 && W <= RLE_MAX_SIDE && H <= RLE_MAX_SIDE;
+}
+
+size_t smk_rle_workspace(int B, int W, int H) {
+    if (!rle_geometry(B, W, H)) return 0;
+    return ((size_t)B * (size_t)rle_words(W, H) * 8 + 255) & ~(size_t)255;
+}
+
+// the checks and the fields both entries share; everything is refused here, before anything is enqueued
+static int rle_fill(const char *who, RleParams &p, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
+                    uint32_t *counts_out_dev, int32_t *meta_out_dev) {
+    if (!ws_dev || !counts_out_dev || !meta_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (!rle_geometry(B, W, H)) return fail(SMK_E_ARG, "%s: bad geometry (B %d in 1..65535, W %d and H %d in 1..%d)", who, B, W, H, RLE_MAX_SIDE);
+    if (cap < 1 || cap > W * H + 1) return fail(SMK_E_ARG, "%s: cap %d (1..%d)", who, cap, W * H + 1);
+    if (ws_bytes < smk_rle_workspace(B, W, H))
+        return fail(SMK_E_ARG, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, smk_rle_workspace(B, W, H));
+    if (((uintptr_t)ws_dev & 7) || ((uintptr_t)counts_out_dev & 3) || ((uintptr_t)meta_out_dev & 3))
+        return fail(SMK_E_ARG, "%s: misaligned workspace (8 bytes) or output (4 bytes)", who);
+    memset(&p, 0, sizeof(p));
+    p.words = (unsigned long long *)ws_dev;
+    p.counts = counts_out_dev; p.meta = meta_out_dev;
+    p.W = W; p.H = H; p.cap = cap; p.tile = 1;
+    return 0;
+}
+
+int smk_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev,
+                   int32_t *meta_out_dev, void *stream) {
+    if (!mask_dev) return fail(SMK_E_ARG, "smk_rle_encode: null argument");
+    RleParams p;
+    CHK(rle_fill("smk_rle_encode", p, B, W, H, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    p.mask = mask_dev;
+    if (launch_rle(p, B, stream)) return fail(SMK_E_HIP, "rle_encode launch failed");
+    return 0;
+}
+
+// include/siammask_hip_test.h: smk_rle_encode with the byte source chosen (the A/B arm of DESIGN.md 3.15 and a tested path)
+int smk_test_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev,
+                        int32_t *meta_out_dev, int form, void *stream) {
+    if (!mask_dev || (form != 0 && form != 1)) return fail(SMK_E_ARG, "smk_test_rle_encode: null argument or form %d (0 or 1)", form);
+    RleParams p;
+    CHK(rle_fill("smk_test_rle_encode", p, B, W, H, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    p.mask = mask_dev;
+    p.tile = form;
+    if (launch_rle(p, B, stream)) return fail(SMK_E_HIP, "rle_encode launch failed");
+    return 0;
+}
+
+int smk_paste_rle_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                      int slot, int B, int W, int H, float seg_thr, float border, int cap, void *ws_dev, size_t ws_bytes,
+                      uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev) return fail(SMK_E_ARG, "smk_paste_rle_dev: null argument");
+    if (mask_size < 1 || (head_dev && (score_size < 1 || score_size > 1024))) return fail(SMK_E_ARG, "smk_paste_rle_dev: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_rle_dev: slot %d (0 or 1)", slot);
+    RleParams p;
+    CHK(rle_fill("smk_paste_rle_dev", p, B, W, H, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    PasteDevParams &q = p.paste;
+    q.logits = head_dev ? head_dev : logits_dev;
+    q.ms = mask_size; q.W = W; q.H = H; q.head_S = head_dev ? score_size : 0; q.slot = slot;
+    q.seg_thr = seg_thr; q.border = border;
+    q.st = (const smk_trk_stream *)state_dev;
+    if (launch_rle(p, B, stream)) return fail(SMK_E_HIP, "paste_rle_dev launch failed");
+    return 0;
+}
+
 // ---- VOS scoring (tools/test.py:421-456 MultiBatchIouMeter per frame, fused with the paste-back; image_kernels.hip) ------------
 static_assert(VOS_MAX_OBJ == CROP_MAX_B, "smk_vos_score takes as many objects as smk_paste_labels");
 

@@ -236,6 +236,20 @@ struct IouParams {
     double inv_map[IOU_MAX_B][6];
 };
 int launch_iou_score(const IouParams &p, int B, void *stream);
+// smk_rle_encode / smk_paste_rle_dev: COCO run lengths (column-major, j = x * H + y) of B masks.  rle_bits packs one bit per
+// pixel into `words` ([B][rle_words(W, H)] uint64, bit i of word k = pixel j = 64 k + i), rle_scan turns the words into counts
+constexpr int RLE_MAX_SIDE = 4096;
+SMK_TRK_HD long rle_words(int W, int H) { return ((long)W * H + 63) / 64; }
+struct RleParams {
+    const unsigned char *mask;      // byte source [B][H][W] (set = non-zero), or nullptr: the fused source `paste`
+    unsigned long long *words;      // workspace
+    unsigned *counts;               // [B][cap]
+    int *meta;                      // [B][4] = (m, area, H, W)
+    int W, H, cap;
+    int tile;                       // byte source: 1 = 64 columns x H rows through LDS (the product's), 0 = one byte per lane at stride W
+    PasteDevParams paste;           // mask_out / prob_out unused; W, H as above
+};
+int launch_rle(const RleParams &p, int B, void *stream);
 
 // ---- stream start on the device (tracker_init.hip; the exemplar crop is image_kernels.hip's, beside crop_pixel) ----------
 constexpr int RECT_MAX_OBJ = 32, RECT_ROWS = 4;

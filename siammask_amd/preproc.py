@@ -8,6 +8,7 @@ arguments but a frame that already lives on the MI355X.
   mask_rboxes            <- tools/test.py:285-294  (findContours -> largest contourArea -> minAreaRect -> boxPoints)
   vos_score              <- tools/test.py:421-456  (MultiBatchIouMeter: per-frame intersection / union counts, fused with the paste-back)
 No CPU fallback: CPU tensors raise."""
+import collections
 import ctypes
 
 import numpy as np
@@ -428,6 +429,96 @@ def mask_rboxes(mask, min_area=100.0, out=None, mode="trace"):
         _lib.check(L.smk_mask_rbox_ex(m.data_ptr(), B, W, H, float(min_area), RBOX_MODES[mode], ws.data_ptr(), need, out.data_ptr(),
                                       stream))
     return out
+
+
+# (device, stream, B, W, H) -> the bit workspace of smk_rle_encode / smk_paste_rle_dev (calls on one stream are ordered, so they share
+# it).  At most _RLE_WS_MAX entries, the least recently used dropped first: a service whose frame sizes or streams come and go does
+# not accumulate them.  A dropped tensor was allocated on the stream its calls run on, so the allocator re-uses it in stream order.
+_rle_ws = collections.OrderedDict()
+_RLE_WS_MAX = 8
+
+
+def _rle_buffers(device, B, W, H, cap, counts, meta):
+    """the checked cap and the workspace / outputs both RLE wrappers share -> (cap, ws, ws bytes, counts int32 [B,cap], meta [B,4])"""
+    from . import rle
+    L = _lib.lib()
+    need = L.smk_rle_workspace(B, W, H)
+    if need == 0:
+        raise ValueError("rle: B >= 1 and H, W in 1..4096, got B = %d, %d x %d" % (B, H, W))
+    cap = rle.default_cap(H, W) if cap is None else int(cap)
+    if not 1 <= cap <= H * W + 1:
+        raise ValueError("rle: cap must be in 1..%d, got %d" % (H * W + 1, cap))
+    key = (device.index, _lib.current_stream_ptr().value, B, W, H)
+    ws = _rle_ws.get(key)
+    if ws is None:
+        ws = _rle_ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+        while len(_rle_ws) > _RLE_WS_MAX:
+            _rle_ws.popitem(last=False)
+    else:
+        _rle_ws.move_to_end(key)
+    if counts is None:
+        counts = torch.empty((B, cap), dtype=torch.int32, device=device)
+    elif counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or tuple(counts.shape) != (B, cap):
+        raise ValueError("rle: counts must be a contiguous int32 CUDA tensor [%d,%d]" % (B, cap))
+    if meta is None:
+        meta = torch.empty((B, 4), dtype=torch.int32, device=device)
+    elif meta.dtype != torch.int32 or not meta.is_cuda or not meta.is_contiguous() or tuple(meta.shape) != (B, 4):
+        raise ValueError("rle: meta must be a contiguous int32 CUDA tensor [%d,4]" % B)
+    return cap, ws, need, counts, meta
+
+
+def rle_encode(mask, cap=None, counts=None, meta=None, _form=None):
+    """COCO run lengths of byte masks, on the device (include/siammask_hip.h: smk_rle_encode).  mask: uint8 CUDA [B,H,W] or
+    [H,W], a pixel is set when non-zero, H and W up to 4096.  cap: counts reserved per mask (rle.default_cap(H, W)).
+    -> (counts int32 CUDA [B,cap] -- the bits are uint32 --, meta int32 CUDA [B,4] = (m, area, H, W)): counts[b, :m] are the run
+    lengths column-major as pycocotools takes them; m > cap reports an overflow (only cap counts were written).  Elements past m
+    are not written.  counts / meta: tensors to write into.  siammask_amd.rle has the host side (strings, decode).
+    _form (private; tests and tools/measure/gpu_rle_cost.py): 0 / 1 = smk_test_rle_encode with the strided / the LDS-tile byte source."""
+    _need_cuda(mask, "mask")
+    if mask.dtype != torch.uint8 or mask.dim() not in (2, 3):
+        raise ValueError("mask must be uint8 [B,H,W] or [H,W]")
+    m = mask.contiguous()
+    if m.dim() == 2:
+        m = m[None]
+    B, H, W = (int(v) for v in m.shape)
+    with torch.cuda.device(m.device):
+        cap, ws, need, counts, meta = _rle_buffers(m.device, B, W, H, cap, counts, meta)
+        args = (m.data_ptr(), B, W, H, cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr())
+        if _form is None:
+            _lib.check(_lib.lib().smk_rle_encode(*(args + (_lib.current_stream_ptr(),))))
+        else:
+            _lib.check(_lib.lib().smk_test_rle_encode(*(args + (int(_form), _lib.current_stream_ptr()))))
+    return counts, meta
+
+
+def paste_rle(logits, state, slot, im_wh, seg_thr=0.35, padding=-1.0, head=None, mask_size=None, cap=None, counts=None, meta=None):
+    """paste_masks_dev whose result is the mask's COCO run lengths: the warped probability is thresholded and encoded without a
+    mask byte reaching memory (smk_paste_rle_dev).  Arguments as for paste_masks_dev; cap / counts / meta and the result as for
+    rle_encode: rle_encode(paste_masks_dev(...)) gives the same counts and meta."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = int(src.shape[0])
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    with torch.cuda.device(src.device):
+        cap, ws, need, counts, meta = _rle_buffers(src.device, B, W, H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_paste_rle_dev(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, W, H, float(seg_thr), float(padding), cap, ws.data_ptr(), need, counts.data_ptr(),
+            meta.data_ptr(), _lib.current_stream_ptr()))
+    return counts, meta
 
 
 def image_refs(frames):

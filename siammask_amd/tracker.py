@@ -21,6 +21,8 @@ csrc/tracker_state.hip) -- any number of frames is enqueued without a host synch
     res = tr.run(frames, iou={'gt': gt_u8_cuda, 'thrs': tune.THRS_VOS, 'masks': False})   # B independent runs of one video (B hp
     res['iou_counts']                                              # points, set_hp), each scored against gt > 0 as IouMeter does
                                                                    # (tools/tune_vos.py); score-only frames write no mask
+    res = tr.run(frames, rle=True)                                 # the masks as COCO run lengths, encoded by the paste-back itself:
+    res['rle'], res['mask']                                        # counts on the device + n / area on the host (siammask_amd.rle); None
 track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
 
 Streams that start on their own frames (siamese_init per stream on the device, enqueue-only; csrc/tracker_init.hip):
@@ -114,7 +116,10 @@ def _box_corners(pos, sz):
 # None, and a hook called behind them as after(rbox rows, advance rows) (run(vot=) enqueues its overlap there)
 # sizes: None, or (mixed sizes) the int32 [B,2] (w, h) of the streams' frames when the frame was enqueued: mask is then the canvas
 # iou: None, or the _Iou of a frame enqueued with iou= (mask is then None for a score-only frame)
-_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou", defaults=(None,))
+# rle: None, or the _Rle of a frame enqueued with rle= (mask is then None unless a polygon or the masks were asked for)
+_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou rle", defaults=(None, None))
+# a checked rle= request (_rle_spec): counts per stream, masks wanted; enqueue() adds the frame's counts [B,cap] and meta [B,4]
+_Rle = collections.namedtuple("_Rle", "cap masks counts meta")
 # a checked VOS request as the C entry takes it (_vos_spec); enqueue() adds the frame's count row and label map
 _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels")
 # a checked iou= request (_iou_spec): annotation, thresholds, masks wanted, frame scored; enqueue() adds the frame's count row
@@ -125,11 +130,12 @@ _Event = collections.namedtuple("_Event", "t streams res")            # one star
 
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
-    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes")
+    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes", "rle")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
         self.iou_k = None                                             # thresholds of a chunk enqueued with iou=
+        self.rle = None                                               # the _Rle of every frame of a chunk enqueued with rle=
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
         self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
@@ -757,8 +763,35 @@ class DeviceTracker(object):
             raise ValueError("iou['masks'] = False writes no mask: want_polygon / mask_out= need one")
         return _Iou(iou["gt"].contiguous(), thrs, masks, bool(iou.get("score", True)), None)
 
+    def _rle_spec(self, mixed, want_mask, other, rle):
+        """the checked rle= request of one frame (before anything is launched) -> None, or an _Rle (counts / meta still None).
+        other: the frame also carries gt= / vos= / iou= / the hook of run(vot=)"""
+        if rle is None or rle is False:
+            return None
+        q = self._fr
+        if other:
+            raise ValueError("rle= returns masks; not inside the VOS / VOT / IoU loops (gt= / vos=, vot=, iou=)")
+        if self.model.variant == "rpn" or not want_mask:
+            raise ValueError("rle= needs want_mask and a variant with a mask branch")
+        if mixed:
+            raise ValueError("rle=: one frame size per batch; these streams have their own sizes")
+        if rle is True:
+            rle = {}
+        if not isinstance(rle, dict) or set(rle) - {"cap", "masks"}:
+            raise ValueError("rle = True or {'cap': counts per stream[, 'masks': bool]}")
+        from . import rle as rle_host
+        cap = rle.get("cap")
+        cap = rle_host.default_cap(q.H, q.W) if cap is None else cap
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= q.H * q.W + 1:
+            raise ValueError("rle['cap'] must be an integer in 1..%d (H * W + 1), got %r" % (q.H * q.W + 1, cap))
+        if q.H > 4096 or q.W > 4096:
+            raise ValueError("rle=: frames of up to 4096 x 4096, these are %d x %d" % (q.H, q.W))
+        if q.chunk.pending and (q.chunk.rle is None or q.chunk.rle[0].cap != int(cap)):
+            raise ValueError("every frame of a chunk carries rle= with one cap, or none does")
+        return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
+
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -772,6 +805,12 @@ class DeviceTracker(object):
         the frame score-only -- no paste-back launch, no mask tensor, collect() reports no mask -- and 'masks': True without a
         polygon writes masks and counts from the one launch.  'score': False tracks the frame and leaves its count row zero.
         Either every frame of a chunk carries iou= or none does; not with gt= / vos=, mixed frame sizes, or without a mask.
+        rle (True, or {'cap': counts reserved per stream (rle.default_cap)[, 'masks': False]}): the frame's masks as COCO run
+        lengths (siammask_amd.rle), collect() returns res['rle'].  Without want_polygon, 'masks' and mask_out= the frame's
+        paste-back IS smk_paste_rle_dev: no mask tensor exists and collect() reports no mask; otherwise the paste-back runs as
+        always and smk_rle_encode follows it on the same stream.  Either every frame of a chunk carries rle= (one cap) or none
+        does; not with gt= / vos= / iou=, mixed frame sizes, the rpn variant or want_mask=False (ValueError before any launch).
+        _rle_out (private, run()): the frame's rows (counts int32 CUDA [B,cap], meta int32 CUDA [B,4]) of the run's tensors.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -798,6 +837,9 @@ class DeviceTracker(object):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
         if c.pending and (c.iou_k is not None) != (iou is not None):
             raise ValueError("every frame of a chunk carries iou=, or none does")
+        if c.pending and (c.rle is not None) != (rle is not None and rle is not False):
+            raise ValueError("every frame of a chunk carries rle=, or none does")
+        rle = self._rle_spec(mixed, want_mask, vos is not None or gt is not None or iou is not None or _after is not None, rle)
         iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
@@ -825,6 +867,10 @@ class DeviceTracker(object):
                     q.iou.append(torch.empty((_ROWS_PER_BLOCK, B, _IOU_MAX_THR, 2), dtype=torch.int32, device=q.device))
                 iou = iou._replace(row=q.iou[blk][i])
                 c.iou_k = int(iou.thrs.size)
+            if rle is not None:
+                rc, rm = _rle_out if _rle_out is not None else (torch.empty((B, rle.cap), dtype=torch.int32, device=q.device),
+                                                                torch.empty((B, 4), dtype=torch.int32, device=q.device))
+                rle = rle._replace(counts=rc, meta=rm)
             dev_ptr = q.dev.data_ptr()
             if mixed:
                 _lib.check(L.smk_crop_resize_dev_v(self._image_refs(frame, list(range(B))), dev_ptr, B, self.p.instance_size,
@@ -846,16 +892,20 @@ class DeviceTracker(object):
             self._fr_flush(sp, join=not refine or depth != 1)
             mask = None
             if want_mask:
-                if iou is None or iou.masks:                          # (a score-only frame has no mask anywhere)
+                if rle is not None and not (want_polygon or rle.masks or mask_out is not None):
+                    pass                                              # the paste-back emits the run lengths: no mask bytes anywhere
+                elif iou is None or iou.masks:                        # (a score-only frame has no mask anywhere)
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
                            q.rbox[blk][i] if want_polygon else None, score, _after, q.rows[blk][i] if _after is not None else None,
-                           sizes if mixed else None, iou)
+                           sizes if mixed else None, iou, rle)
                 if depth:
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
                     self._fr_paste(job, sp)
             c.masks.append(mask)
+            if rle is not None:                                       # (beside the frame count: a launch that raised leaves no row)
+                c.rle = (c.rle or []) + [rle]
             c.sizes.append(sizes if mixed else None)
             c.poly.append(bool(want_polygon))
             c.pending = t + 1
@@ -869,7 +919,11 @@ class DeviceTracker(object):
         shared = (logits.data_ptr() if logits is not None else None, head.data_ptr() if head is not None else None,
                   int(head.shape[-1]) if head is not None else 0, self.mask_size, q.dev.data_ptr(), job.slot, q.B, q.W, q.H)
         fused = u is not None and u.scored and job.rbox is None      # smk_iou_score_dev writes the mask bytes itself
-        if mask is None or fused:
+        r = job.rle
+        if r is not None and mask is None:                            # the paste-back IS the encoder (smk_paste_rle_dev)
+            preproc.paste_rle(logits, q.dev, job.slot, (q.W, q.H), seg_thr=p.seg_thr, head=head, mask_size=self.mask_size,
+                              cap=r.cap, counts=r.counts, meta=r.meta)
+        elif mask is None or fused:
             pass
         elif job.sizes is not None:                                   # the canvas: each stream at the size of its record, 0 elsewhere
             _lib.check(L.smk_paste_mask_dev_v(*(shared + (job.sizes.ctypes.data, float(p.seg_thr), -1.0, mask.data_ptr(), sp))))
@@ -877,6 +931,8 @@ class DeviceTracker(object):
             _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
         if job.rbox is not None:                                      # same stream, behind the paste-back (:285-303)
             preproc.mask_rboxes(mask, out=job.rbox, mode=self.rbox)
+        if r is not None and mask is not None:                        # the bytes exist: encode them, same stream
+            preproc.rle_encode(mask, cap=r.cap, counts=r.counts, meta=r.meta)
         if s is not None:                                             # the same slot of the same state block, same stream
             args = shared + (-1.0, s.gt.data_ptr(), s.ids.ctypes.data, s.bits, s.thrs.ctypes.data, int(s.thrs.size),
                              float(p.seg_thr), s.row.data_ptr(), s.labels.data_ptr())
@@ -920,15 +976,19 @@ class DeviceTracker(object):
                 replay()
                 _lib.check(_lib.lib().smk_seq_sync_check(model._ctx, _lib.current_stream_ptr(), None))
 
-    def collect(self, _masks=None, _labels=None):
+    def collect(self, _masks=None, _labels=None, _rle=None):
         """Join the frames enqueued since the last collect() -- ONE synchronisation -- and return host arrays
         target_pos [T,B,2], target_sz [T,B,2], score [T,B] (float64), best_id [T,B], delta_yx [T,B,2] (int64), crop_box [T,B,4],
         mask (uint8 CUDA [T,B,H,W], None without masks), and for frames enqueued with want_polygon polygon [T,B,4,2] /
         polygon_found [T,B]; for a chunk enqueued with gt= / vos=, vos_counts int64 [T,B,K,2] = (intersection, union) per frame,
-        object and threshold and labels (uint8 CUDA [T,H,W]); for a chunk with start() calls, events (T may then be 0).  Leaves
+        object and threshold and labels (uint8 CUDA [T,H,W]); for a chunk enqueued with rle=, rle = {'counts': int32 CUDA [T,B,cap]
+        (the bits are uint32), 'n': int32 [T,B] (counts of the mask; n > cap: an overflow, the counts are incomplete), 'area': int32
+        [T,B], 'cap', 'size': (H, W)} -- n and area ride with the one read-back, siammask_amd.rle.to_host fetches the counts;
+        for a chunk with start() calls, events (T may then be 0).  Leaves
         tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the tracker to the chunk's start when
         a persistent-sequence failure was reported: re-run the chunk.  _masks / _labels (private, run()): the [T,B,H,W] / [T,H,W]
-        tensors the frames' masks and labels were written into, returned in place of a stack."""
+        tensors the frames' masks and labels were written into, returned in place of a stack; _rle likewise: (counts [T,B,cap],
+        meta [T,B,4])."""
         q, st = self._fr, self.state
         if st is None or q is None:
             raise RuntimeError("DeviceTracker.collect(): init() first")
@@ -951,15 +1011,25 @@ class DeviceTracker(object):
                     vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
                     vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
+                if c.rle is not None:                                 # (m, area) of the meta rows ride along as float64 (exact)
+                    rmeta = _rle[1] if _rle is not None and _rle[1].shape[0] == T else torch.stack([r.meta for r in c.rle])
+                    rows = torch.cat([rows, rmeta[:, :, :2].to(torch.float64)], dim=2)
             if events:                                                # the start events' result rows ride along
                 flat = torch.cat(([rows.reshape(-1)] if T else []) + [e.res.reshape(-1) for e in events]).cpu().numpy()
                 n = flat.size - len(events) * B * START_ROW           # (the one synchronisation)
                 host, ev_rows = flat[:n].reshape(tuple(rows.shape) if T else (0, B, RESULT_ROW)), flat[n:].reshape(-1, B, START_ROW)
             else:
                 host, ev_rows = rows.cpu().numpy(), None              # the one synchronisation
+        rle_host = None
+        if T and c.rle is not None:
+            host, rle_host = host[:, :, :-2], host[:, :, -2:].astype(np.int32)
         res, new = collect_host(host, T, B, c.poly, K, [(e.t, e.streams) for e in events], ev_rows, st,
                                 "vos_counts" if c.vos_k is not None else "iou_counts")
         if T:
+            if rle_host is not None:
+                counts = _rle[0] if _rle is not None and _rle[0].shape[0] == T else torch.stack([r.counts for r in c.rle])
+                res["rle"] = {"counts": counts, "n": np.ascontiguousarray(rle_host[:, :, 0]), "area": np.ascontiguousarray(rle_host[:, :, 1]),
+                              "cap": c.rle[0].cap, "size": (q.H, q.W)}
             masks = c.masks
             if all(m is not None for m in masks):
                 res["mask"] = _masks if _masks is not None and _masks.shape[0] == T else torch.stack(masks)
@@ -977,7 +1047,7 @@ class DeviceTracker(object):
         q.chunk = _Chunk()
         return res
 
-    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, vot=None, iou=None):
+    def run(self, frames, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, vot=None, iou=None, rle=None):
         """enqueue every frame of ``frames`` (uint8 CUDA [T,H,W,3], or [T,B,H,W,3] for per-stream frames), then collect().
         mask_out: uint8 CUDA [T,B,H,W] to receive the masks.
         gt (uint8 CUDA [T,im_h,im_w]) and vos (as for enqueue(); 'alive' may be [T,B]): every frame is scored against its
@@ -988,7 +1058,9 @@ class DeviceTracker(object):
         videos in lock-step, frames [T,B,H,W,3] (see tracker_loops.run_vot).
         iou (as for enqueue(), 'gt' uint8 CUDA [T,im_h,im_w]; 'score': [T] booleans, the frames that are scored -- the others are
         tracked and their count rows are zero): the B streams as independent runs against gt > 0 -> res['iou_counts'] int64
-        [T,B,K,2] (siammask_amd.vos.iou_meter takes a stream's [T,K,2]).  With 'masks': False no mask is allocated or returned."""
+        [T,B,K,2] (siammask_amd.vos.iou_meter takes a stream's [T,K,2]).  With 'masks': False no mask is allocated or returned.
+        rle (as for enqueue()): the masks as COCO run lengths -> res['rle'] (see collect(); siammask_amd.rle.to_host / to_coco).
+        Without want_polygon, 'masks': True and mask_out= no [T,B,H,W] tensor is allocated and res['mask'] is None."""
         from . import tracker_loops
         q = self._fr
         if self.state is None or q is None:
@@ -1003,6 +1075,12 @@ class DeviceTracker(object):
         elif frames.dim() not in (4, 5):
             raise ValueError("frames must be uint8 [T,H,W,3] or [T,B,H,W,3]")
         T, labels, alive = int(frames.shape[0]), None, None
+        spec = None
+        if rle is not None and rle is not False:                      # checked for the whole run before the first launch
+            mixed = isinstance(frames, _Videos) or self._mixed()
+            spec = self._rle_spec(mixed, want_mask, vot is not None or gt is not None or vos is not None or iou is not None, rle)
+            for t in range(T):
+                self._check_frame(frames[t])
         if iou is not None:                                           # checked for the whole run before the first launch
             if vot is not None or gt is not None or vos is not None:
                 raise ValueError("run(): iou= (independent streams against gt > 0) or vot= / gt= / vos=, not both")
@@ -1037,12 +1115,19 @@ class DeviceTracker(object):
                 self._vos_spec(3, want_mask, gt[t], self._vos_at(vos, alive, t))
             labels = torch.empty((T, q.H, q.W), dtype=torch.uint8, device=frames.device)
         score_only = iou is not None and T > 0 and not iou[0].get("masks", True)         # no mask tensor at all
+        if spec is not None and not (want_polygon or spec.masks or mask_out is not None):
+            score_only = True                                         # the paste-back emits the run lengths: no [T,B,H,W] either
         masks = self._mask_out(mask_out, (T,), frames.device) if want_mask and self.model.variant != "rpn" and not score_only else None
+        rle_out = None
+        if spec is not None:
+            rle_out = (torch.empty((T, q.B, spec.cap), dtype=torch.int32, device=frames.device),
+                       torch.empty((T, q.B, 4), dtype=torch.int32, device=frames.device))
         for t in range(T):
             self.enqueue(frames[t], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[t] if masks is not None else None,
                          gt=gt[t] if gt is not None else None, vos=self._vos_at(vos, alive, t) if vos is not None else None,
-                         labels_out=labels[t] if labels is not None else None, iou=iou[t] if iou is not None else None)
-        return self.collect(_masks=masks, _labels=labels)
+                         labels_out=labels[t] if labels is not None else None, iou=iou[t] if iou is not None else None,
+                         rle=rle if spec is not None else None, _rle_out=(rle_out[0][t], rle_out[1][t]) if spec is not None else None)
+        return self.collect(_masks=masks, _labels=labels, _rle=rle_out)
 
     @staticmethod
     def _vos_at(vos, alive, t):
