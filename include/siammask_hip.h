@@ -562,6 +562,52 @@ int smk_iou_score_dev(const float *logits_dev, const float *head_dev, int score_
                       int slot, int B, int W, int H, float border, const uint8_t *gt_dev, int64_t gt_stride_bytes,
                       const double *thrs, int n_thr, float seg_thr, int32_t *counts_out_dev, uint8_t *mask_out_dev, void *stream);
 
+/* ---- VOT evaluation of result trajectories: per-frame overlaps and the expected average overlap (utils/pysot/evaluation/
+ * eao_benchmark.py, ar_benchmark.py, utils/pysot/utils/statistics.py; additive; smk_version() keeps reporting 1.10, the presence
+ * of these symbols is the probe) -------------------------------------------------------------------------------------------
+ * What tools/eval.py computes from the result files of G trackers (the points of a sweep) on V videos, without the files.  The
+ * frames of the videos are concatenated: N = sum of T_v, offsets int32 [V + 1] from 0 to N strictly ascending, wh int32 [V][2] =
+ * (width, height) in 2..4096, video_of int32 [N].  The small tables are given twice, on the HOST (read and checked during the
+ * call, nothing of it is read after the call returns) and on the DEVICE (what the kernels read; values outside the arrays are
+ * clamped, never followed).  A tracker is a row of N codes (int8: -1 tracked, 1 init, 2 lost, 0 skipped, as res['vot_code'])
+ * and N polygons (f64 [8], read on tracked frames only).  G in 1..65535, N in 1..2^30.
+ * smk_vot_traj_overlap: for every (tracker, frame) the overlap the evaluator gives the frame, twice:
+ *     ov_eao_dev f32 [G][N]: inside the bounds (w - 1, h - 1), no burn-in (EAOBenchmark);
+ *     ov_ar_dev  f32 [G][N]: inside (w, h), NaN on the `burnin` frames i .. i + burnin - 1 of its video behind every code-1
+ *                            frame i (AccuracyRobustnessBenchmark: burnin 10).
+ *   Both are NaN where the code is not -1 or where gt_dev[n][0] is NaN (an annotation row of one value).  Otherwise the value
+ *   is smk_vot_overlap's -- the same functions, bit for bit -- with the PREDICTION as the first polygon and the annotation
+ *   (gt_dev f64 [N][8], shared by the trackers) as the second, as calculate_accuracy passes them.  quantise != 0: every
+ *   coordinate of the prediction is first replaced by the value its "%.4f" result line parses back to,
+ *   rint((double)(float)x * 1e4) / 1e4 (exact: the evaluator sees the file, not the tracker's doubles); 0: used as given.
+ *   One wave per pair, four pairs per workgroup, no workspace.
+ * smk_eao_curve: from ov_eao and the codes, per tracker the expected-overlap curve and its mean over the sequence lengths
+ *   low .. high (tag 'all', one repetition per video):
+ *     fragments: a video without a code 2 is one fragment (its NaNs kept, NaN behind its end).  Otherwise points = [0] +
+ *       [x + skipping for failures x with x + skipping <= T]; overlaps[p_i : p_{i+1} + 1] with NaN -> 0, zero behind its end,
+ *       weight (frames in the slice) / (p_{i+1} - p_i + 1); the last one overlaps[p_last :] with NaN -> 0, NaN behind its end,
+ *       weight (T - p_last) / (T - p_last + 1e-16).
+ *     curve_dev f32 [G][max_len] (max_len = the longest video): [0] = 1; [i] over the fragments whose column i is not NaN
+ *       = sum_f (sum_{j=1..i} frag[f][j] / i) * w_f / sum_f w_f, 0 where there is none.  The ORDER is part of the contract: the
+ *       inner sum sequential in float64 over j ascending, both outer sums sequential in float64 in fragment order (video, then
+ *       position), the division by i before the multiplication by the weight, one rounding to float32 at the store.
+ *     eao_dev f64 [G] = the sequential float64 sum over i ascending of the values curve[low - 1 : high] (clipped to max_len)
+ *       that are not NaN, divided by their number (NaN where there is none).  n_fragments_dev int32 [G].
+ *   The reference sums pairwise where numpy is not replaced by numba; the curve then differs from it by at most one float32 ulp.
+ *   ws_dev: caller-owned, 16-byte aligned, at least smk_eao_workspace_bytes(F_max, max_len) bytes = one tracker's share; with
+ *   k times as much, k trackers run per launch (the launches of one call follow each other on `stream`).  F_max >= V: the most
+ *   fragments of a tracker (at most V + its number of code-2 frames); a tracker with more gets n_fragments = -(its number), eao
+ *   NaN and no curve.  skipping in 0..65535, 1 <= low <= high.
+ * No context; enqueue-only on `stream`, no host synchronisation, no allocation; bad arguments (a null or misaligned pointer, a
+ * range above, offsets that do not ascend from 0 to N, a short workspace) give SMK_E_ARG before anything is enqueued. */
+int smk_vot_traj_overlap(const int8_t *code_dev, const double *poly_dev, const double *gt_dev, const int32_t *video_of_dev,
+                         const int32_t *offsets_dev, const int32_t *wh_dev, const int32_t *offsets_host, const int32_t *wh_host,
+                         int N, int G, int V, int burnin, int quantise, float *ov_eao_dev, float *ov_ar_dev, void *stream);
+size_t smk_eao_workspace_bytes(int F_max, int max_len);
+int smk_eao_curve(const float *ov_eao_dev, const int8_t *code_dev, const int32_t *offsets_dev, const int32_t *offsets_host, int N,
+                  int G, int V, int skipping, int low, int high, int F_max, void *ws_dev, size_t ws_bytes, float *curve_dev,
+                  double *eao_dev, int32_t *n_fragments_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,17 @@ int smk_test_mask_rbox_paths(const void *ws_dev, int B, int W, int H, int mode, 
 int smk_test_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
                         uint32_t *counts_out_dev, int32_t *meta_out_dev, int form, void *stream);
 
+/* Host only: the VOT evaluation on HOST memory -- the very inline functions the kernels compile (csrc/vot_eval.h), one thread.
+ * Arguments as for smk_vot_traj_overlap / smk_eao_curve with one (host) copy of the tables and no workspace.
+ * smk_host_vot_quantise: out[i] = the value the "%.4f" line of x[i] parses back to.
+ * smk_host_eao_curve: frag_out (may be NULL) int32 [G][F_cap][4] <- first frame (in the concatenation), length, kind (0 inner,
+ *   1 last, 2 a video without a failure), video; weight_out (may be NULL) f64 [G][F_cap]; the first F_cap fragments of a tracker. */
+int smk_host_vot_quantise(const double *x, int n, double *out);
+int smk_host_vot_traj_overlap(const int8_t *code, const double *poly, const double *gt, const int32_t *offsets, const int32_t *wh,
+                              int N, int G, int V, int burnin, int quantise, float *ov_eao, float *ov_ar);
+int smk_host_eao_curve(const float *ov_eao, const int8_t *code, const int32_t *offsets, int N, int G, int V, int skipping, int low,
+                       int high, float *curve, double *eao, int32_t *n_fragments, int32_t *frag_out, double *weight_out, int F_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,8 @@ SYMBOLS = (
     "smk_iou_score", "smk_iou_score_dev",
     "smk_mask_rbox_workspace_ex", "smk_mask_rbox_ex", "smk_test_mask_rbox_paths",
     "smk_rle_workspace", "smk_rle_encode", "smk_paste_rle_dev", "smk_test_rle_encode",
+    "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
+    "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
 )
 
 
@@ -187,6 +189,12 @@ def lib():
     L.smk_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_test_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, ci, vp]
     L.smk_paste_rle_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, cf, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_vot_traj_overlap.argtypes = [vp] * 8 + [ci] * 5 + [vp, vp, vp]
+    L.smk_eao_workspace_bytes.argtypes = [ci, ci]
+    L.smk_eao_curve.argtypes = [vp] * 4 + [ci] * 7 + [vp, ctypes.c_size_t, vp, vp, vp, vp]
+    L.smk_host_vot_quantise.argtypes = [vp, ci, vp]
+    L.smk_host_vot_traj_overlap.argtypes = [vp] * 5 + [ci] * 5 + [vp, vp]
+    L.smk_host_eao_curve.argtypes = [vp] * 3 + [ci] * 6 + [vp] * 5 + [ci]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
@@ -194,7 +202,7 @@ def lib():
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
             fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes",
-                                                        "smk_rle_workspace") else ci
+                                                        "smk_rle_workspace", "smk_eao_workspace_bytes") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

@@ -1,14 +1,16 @@
 // stream_api.cpp -- the stateless product ABI either side of the network (include/siammask_hip.h): crop / paste / labels,
-// smk_mask_rbox, the tracker state on the device (smk_trk_*), VOS scoring, stream start, the VOT overlap, the *_v entries for
-// streams with their own frame sizes -- argument checks and kernargs, one launch each -- and the smk_host_* entries that run the
-// device code's inline functions (tracker_state.h, vot_overlap.h) on the CPU for the bit-exact host tests.
+// smk_mask_rbox, the tracker state on the device (smk_trk_*), VOS scoring, stream start, the VOT overlap and evaluation, the *_v
+// entries for streams with their own frame sizes -- argument checks and kernargs, one launch each -- and the smk_host_* entries that run the
+// device code's inline functions (tracker_state.h, vot_overlap.h, vot_eval.h) on the CPU for the bit-exact host tests.
 #include <cstdint>
 #include <cstring>
+#include <vector>
 
 #include "../../include/siammask_hip_test.h"
 #include "engine_internal.h"
 #include "tracker_state.h"
 #include "vot_overlap.h"
+#include "vot_eval.h"
 
 using namespace smk;
 
@@ -616,6 +618,138 @@ int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, 
         return fail(SMK_E_ARG, "smk_host_vot_overlap: bad geometry (%d x %d, 1..%d)", im_w, im_h, VOT_MAX_DIM);
     for (int i = 0; i < n; ++i)                                        // the annotation is the reference's first polygon (:354)
         overlap[i] = vot_overlap_serial(gt + 8 * (size_t)i, pred + 8 * (size_t)i, im_w, im_h, counts ? counts + 4 * (size_t)i : nullptr);
+    return 0;
+}
+
+// ---- VOT evaluation of result trajectories (vot_eval.hip / vot_eval.h) ---------------------------------------
+// the host's copy of the tables: offsets [V + 1] from 0 to N strictly ascending, wh [V][2] (may be null) in 2..VOT_MAX_DIM;
+// -> the longest video through max_len
+static int eval_tables(const char *who, const int32_t *offsets, const int32_t *wh, int N, int G, int V, int *max_len) {
+    if (!offsets) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (N < 1 || N > (1 << 30) || G < 1 || G > 65535 || V < 1 || V > N)
+        return fail(SMK_E_ARG, "%s: %d frames (1..2^30) of %d videos (1..frames), %d trackers (1..65535)", who, N, V, G);
+    if (offsets[0] != 0 || offsets[V] != N) return fail(SMK_E_ARG, "%s: offsets run from %d to %d, not 0 to %d", who, offsets[0], offsets[V], N);
+    int longest = 0;
+    for (int v = 0; v < V; ++v) {
+        if (offsets[v + 1] <= offsets[v]) return fail(SMK_E_ARG, "%s: offsets not ascending at video %d", who, v);
+        longest = offsets[v + 1] - offsets[v] > longest ? offsets[v + 1] - offsets[v] : longest;
+        if (wh && (wh[2 * v] < VOT_EVAL_MIN_DIM || wh[2 * v + 1] < VOT_EVAL_MIN_DIM || wh[2 * v] > VOT_MAX_DIM || wh[2 * v + 1] > VOT_MAX_DIM))
+            return fail(SMK_E_ARG, "%s: video %d is %d x %d (%d..%d)", who, v, wh[2 * v], wh[2 * v + 1], VOT_EVAL_MIN_DIM, VOT_MAX_DIM);
+    }
+    *max_len = longest;
+    return 0;
+}
+
+static int eao_range(const char *who, int skipping, int low, int high) {
+    if (skipping < 0 || skipping > EAO_MAX_SKIP) return fail(SMK_E_ARG, "%s: skipping %d (0..%d)", who, skipping, EAO_MAX_SKIP);
+    if (low < 1 || high < low) return fail(SMK_E_ARG, "%s: low %d, high %d (1 <= low <= high)", who, low, high);
+    return 0;
+}
+
+int smk_vot_traj_overlap(const int8_t *code_dev, const double *poly_dev, const double *gt_dev, const int32_t *video_of_dev,
+                         const int32_t *offsets_dev, const int32_t *wh_dev, const int32_t *offsets_host, const int32_t *wh_host,
+                         int N, int G, int V, int burnin, int quantise, float *ov_eao_dev, float *ov_ar_dev, void *stream) {
+    if (!code_dev || !poly_dev || !gt_dev || !video_of_dev || !offsets_dev || !wh_dev || !wh_host || !ov_eao_dev || !ov_ar_dev)
+        return fail(SMK_E_ARG, "smk_vot_traj_overlap: null argument");
+    int max_len = 0;
+    if (int rc = eval_tables("smk_vot_traj_overlap", offsets_host, wh_host, N, G, V, &max_len)) return rc;
+    if (burnin < 0) return fail(SMK_E_ARG, "smk_vot_traj_overlap: burnin %d", burnin);
+    if ((uintptr_t)poly_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)video_of_dev % 4 || (uintptr_t)offsets_dev % 4 ||
+        (uintptr_t)wh_dev % 4 || (uintptr_t)ov_eao_dev % 4 || (uintptr_t)ov_ar_dev % 4)
+        return fail(SMK_E_ARG, "smk_vot_traj_overlap: misaligned argument");
+    VotTrajParams p;
+    p.code = code_dev; p.poly = poly_dev; p.gt = gt_dev; p.video_of = video_of_dev; p.offsets = offsets_dev; p.wh = wh_dev;
+    p.ov_eao = ov_eao_dev; p.ov_ar = ov_ar_dev;
+    p.N = N; p.G = G; p.V = V; p.burnin = burnin; p.quantise = quantise ? 1 : 0;
+    if (launch_vot_traj_overlap(p, stream)) return fail(SMK_E_HIP, "vot_traj_overlap launch failed");
+    return 0;
+}
+
+size_t smk_eao_workspace_bytes(int F_max, int max_len) {
+    if (F_max < 1 || max_len < 1) return 0;
+    return eao_tracker_bytes(F_max, max_len);
+}
+
+int smk_eao_curve(const float *ov_eao_dev, const int8_t *code_dev, const int32_t *offsets_dev, const int32_t *offsets_host, int N,
+                  int G, int V, int skipping, int low, int high, int F_max, void *ws_dev, size_t ws_bytes, float *curve_dev,
+                  double *eao_dev, int32_t *n_fragments_dev, void *stream) {
+    if (!ov_eao_dev || !code_dev || !offsets_dev || !ws_dev || !curve_dev || !eao_dev || !n_fragments_dev)
+        return fail(SMK_E_ARG, "smk_eao_curve: null argument");
+    int max_len = 0;
+    if (int rc = eval_tables("smk_eao_curve", offsets_host, nullptr, N, G, V, &max_len)) return rc;
+    if (int rc = eao_range("smk_eao_curve", skipping, low, high)) return rc;
+    if (F_max < V) return fail(SMK_E_ARG, "smk_eao_curve: F_max %d below the %d videos (a video has at least one fragment)", F_max, V);
+    const size_t per = eao_tracker_bytes(F_max, max_len);
+    if (ws_bytes < per) return fail(SMK_E_ARG, "smk_eao_curve: workspace of %zu bytes, one tracker needs %zu", ws_bytes, per);
+    if ((uintptr_t)ov_eao_dev % 4 || (uintptr_t)offsets_dev % 4 || (uintptr_t)ws_dev % 16 || (uintptr_t)curve_dev % 4 ||
+        (uintptr_t)eao_dev % 8 || (uintptr_t)n_fragments_dev % 4)
+        return fail(SMK_E_ARG, "smk_eao_curve: misaligned argument");
+    EaoParams p;
+    p.ov = ov_eao_dev; p.code = code_dev; p.offsets = offsets_dev; p.ws = ws_dev; p.curve = curve_dev; p.eao = eao_dev;
+    p.n_fragments = n_fragments_dev;
+    p.N = N; p.G = G; p.V = V; p.F_max = F_max; p.max_len = max_len; p.skipping = skipping; p.low = low; p.high = high;
+    // as many trackers per launch as the workspace holds; the launches follow each other on the stream and share it
+    const size_t fit = ws_bytes / per;
+    const int batch = fit < (size_t)G ? (int)fit : G;
+    for (p.g0 = 0; p.g0 < G; p.g0 += batch) {
+        p.trackers = G - p.g0 < batch ? G - p.g0 : batch;
+        if (launch_eao_curve(p, stream)) return fail(SMK_E_HIP, "eao_curve launch failed");
+    }
+    return 0;
+}
+
+int smk_host_vot_quantise(const double *x, int n, double *out) {
+    if (!x || !out || n < 1) return fail(SMK_E_ARG, "smk_host_vot_quantise: bad argument");
+    for (int i = 0; i < n; ++i) out[i] = vot_quantise(x[i]);
+    return 0;
+}
+
+int smk_host_vot_traj_overlap(const int8_t *code, const double *poly, const double *gt, const int32_t *offsets, const int32_t *wh,
+                              int N, int G, int V, int burnin, int quantise, float *ov_eao, float *ov_ar) {
+    if (!code || !poly || !gt || !wh || !ov_eao || !ov_ar) return fail(SMK_E_ARG, "smk_host_vot_traj_overlap: null argument");
+    int max_len = 0;
+    if (int rc = eval_tables("smk_host_vot_traj_overlap", offsets, wh, N, G, V, &max_len)) return rc;
+    if (burnin < 0) return fail(SMK_E_ARG, "smk_host_vot_traj_overlap: burnin %d", burnin);
+    for (int g = 0; g < G; ++g)
+        for (int v = 0; v < V; ++v)
+            for (int n = offsets[v]; n < offsets[v + 1]; ++n) {
+                const size_t at = (size_t)g * N + n;
+                vot_traj_pair_serial(code + (size_t)g * N, poly + 8 * at, gt + 8 * (size_t)n, n, offsets[v], wh[2 * v], wh[2 * v + 1],
+                                     burnin, quantise ? 1 : 0, ov_eao + at, ov_ar + at);
+            }
+    return 0;
+}
+
+int smk_host_eao_curve(const float *ov_eao, const int8_t *code, const int32_t *offsets, int N, int G, int V, int skipping, int low,
+                       int high, float *curve, double *eao, int32_t *n_fragments, int32_t *frag_out, double *weight_out, int F_cap) {
+    if (!ov_eao || !code || !curve || !eao || !n_fragments) return fail(SMK_E_ARG, "smk_host_eao_curve: null argument");
+    int max_len = 0;
+    if (int rc = eval_tables("smk_host_eao_curve", offsets, nullptr, N, G, V, &max_len)) return rc;
+    if (int rc = eao_range("smk_host_eao_curve", skipping, low, high)) return rc;
+    if ((frag_out || weight_out) && F_cap < 1) return fail(SMK_E_ARG, "smk_host_eao_curve: F_cap %d", F_cap);
+    for (int g = 0; g < G; ++g) {
+        const int8_t *c = code + (size_t)g * N;
+        const float *ov = ov_eao + (size_t)g * N;
+        int F = 0;
+        for (int v = 0; v < V; ++v) F += eao_video_count(c + offsets[v], offsets[v + 1] - offsets[v], skipping);
+        std::vector<char> mem(eao_tracker_bytes(F, max_len));
+        const EaoWorkspace ws = eao_workspace(mem.data(), F, max_len);
+        int at = 0;
+        for (int v = 0; v < V; ++v) {
+            const int T = offsets[v + 1] - offsets[v];
+            eao_video_fragments(c + offsets[v], T, skipping, offsets[v], v, ws.frag + at, ws.weight + at);
+            at += eao_video_count(c + offsets[v], T, skipping);
+        }
+        for (int f = 0; f < F; ++f) eao_prefix(ov, ws.frag[f], ws.prefix + (size_t)f * max_len);
+        float *row = curve + (size_t)g * max_len;
+        for (int i = 0; i < max_len; ++i) row[i] = i == 0 ? 1.0f : eao_column(ov, ws.frag, ws.weight, ws.prefix, max_len, F, i);
+        eao[g] = eao_mean(row, max_len, low, high);
+        n_fragments[g] = F;
+        for (int f = 0; f < F && f < F_cap; ++f) {
+            if (frag_out) memcpy(frag_out + 4 * ((size_t)g * F_cap + f), &ws.frag[f], sizeof(EaoFrag));
+            if (weight_out) weight_out[(size_t)g * F_cap + f] = ws.weight[f];
+        }
+    }
     return 0;
 }
 

@@ -8,6 +8,8 @@ passes) and a sweep of G points is ceil(G / B) passes of run(vot=).
     out = tune.sweep_vot(tr, frames, gt, points)                      # frames uint8 CUDA [T,H,W,3], gt float64 [T,8]
     out[i]['lost_times'], out[i]['lines']                             # of points[i]; lines: <video>_001.txt (tools/test.py:403-406)
     tune.result_dir('Custom_x', points[i])                            # the directory the tool would write them under (:64-68)
+    table = tune.eval_vot({'video': out, ...}, sizes, dataset='VOT2018')          # what tools/eval.py makes of those files: EAO,
+    table['eao'], table['best']                                       # accuracy, robustness per point, on the device, no file
 
 tools/tune_vos.py is the same grid on a DAVIS video, scored by IouMeter at 11 thresholds instead of by losses: each pass is
 start() on frame 0 + run(iou=) with score-only frames -- the per-stream counts come from the device (smk_iou_score_dev), no
@@ -21,7 +23,7 @@ The tools' result trees on disk, their finish.flag / 'Occ' protocols, the shuffl
 are the caller's."""
 import numpy as np
 
-from . import vos, vot
+from . import evaluate, vos, vot
 
 HP_KEYS = ("penalty_k", "window_influence", "lr")
 THRS_VOS = np.arange(0.3, 0.81, 0.05)   # tune_vos.py: thrs, the 11 float64 thresholds of its IouMeter
@@ -59,7 +61,9 @@ def sweep_vot(tracker, frames, gt, points, skip=5):
     chunk open.  frames: uint8 CUDA [T,H,W,3]; gt: float64 [T,8], the video's 4-corner regions.  Each pass is
     set_hp(B points) + run(frames, want_polygon=True, vot={'gt': gt tiled over the streams, 'skip': skip}).
     -> one dict per point: 'hp' (the point), 'lost_times' (int), 'vot_code' int8 [T], 'overlap' float32 [T], 'lines' (the lines
-    of the result file, vot.region_lines).  The tracker's hp state (its table or none) is put back on exit."""
+    of the result file, vot.region_lines), 'polygon' float64 [T,8] (the tracker's unrounded corners) and 'gt' (the annotation
+    the pass was supervised with, one array shared by the points; eval_vot takes both).  The tracker's hp state (its table or none)
+    is put back on exit."""
     points = [dict(p) for p in points]
     if not points or any(set(p) - set(HP_KEYS) for p in points):
         raise ValueError("sweep_vot: at least one point, keys among %s" % (HP_KEYS,))
@@ -79,10 +83,38 @@ def sweep_vot(tracker, frames, gt, points, skip=5):
             for b in range(keep):
                 out.append({"hp": points[idx[b]], "lost_times": int(res["lost_times"][b]),
                             "vot_code": res["vot_code"][:, b].copy(), "overlap": res["overlap"][:, b].copy(),
-                            "lines": vot.region_lines(res, b)})
+                            "lines": vot.region_lines(res, b),
+                            "polygon": np.asarray(res["polygon"], dtype=np.float64)[:, b].reshape(-1, 8).copy(), "gt": gt})
     finally:
         if not tracker._chunk_open():                                 # (a failed pass may have left one: the caller collects)
             tracker.set_hp(before)
+    return out
+
+
+def eval_vot(sweeps, sizes, dataset=None, **kw):
+    """rank a VOT sweep as tools/eval.py ranks the result trees of tools/tune_vot.py, without a file: sweeps: {video: what
+    sweep_vot returned for it} with the same points for every video, sizes: {video: (w, h)}.  The annotation of a
+    video is the 'gt' its sweep carries.  dataset and the further keywords (low=, high=, skipping=, burnin=, quantise=) are evaluate.vot's.
+    -> evaluate.vot's table over the points (one read-back) plus 'hp' (the points) and 'best' (the index of the largest EAO; a NaN
+    EAO ranks last)."""
+    names = list(sweeps)
+    if not names:
+        raise ValueError("eval_vot: at least one video")
+    G = len(sweeps[names[0]])
+    for name in names:
+        if len(sweeps[name]) != G or [p["hp"] for p in sweeps[name]] != [p["hp"] for p in sweeps[names[0]]]:
+            raise ValueError("eval_vot: video %r was swept over other points than %r" % (name, names[0]))
+        if name not in sizes:
+            raise ValueError("eval_vot: no size for video %r" % (name,))
+    if G < 1:
+        raise ValueError("eval_vot: at least one point")
+    evaluate._window(dataset, kw.get("low"), kw.get("high"))            # (refused before anything is uploaded)
+    packed = evaluate.pack([{"name": name, "size": sizes[name], "gt": sweeps[name][0]["gt"],
+                             "code": np.stack([p["vot_code"] for p in sweeps[name]]),
+                             "polygon": np.stack([p["polygon"] for p in sweeps[name]])} for name in names])
+    out = evaluate.vot(packed, dataset=dataset, **kw)
+    out["hp"] = [p["hp"] for p in sweeps[names[0]]]
+    out["best"] = int(np.argmax(np.where(np.isnan(out["eao"]), -np.inf, out["eao"])))
     return out
 
 
