@@ -359,6 +359,35 @@ int smk_paste_rle_dev(const float *logits_dev, const float *head_dev, int score_
                       int slot, int B, int W, int H, float seg_thr, float border, int cap, void *ws_dev, size_t ws_bytes,
                       uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
 
+/* ---- the fused label map of a VOS frame as per-object COCO run-length codes (tools/test.py:521-523 + rleEncode; additive;
+ * smk_version() keeps reporting 1.10, the presence of these symbols is the probe) ------------------------------------------------
+ * The n_obj (1..32) objects of one W x H frame.  LABEL: label(x, y) = best > seg_thr ? arg + 1 : 0 with best / arg the maximum and
+ * the FIRST argmax over prob_o exactly as smk_vos_score_ex defines them below -- prob_o = bit o of given_mask ?
+ * (init_labels[y][x] == object_ids[o] ? 1.0f : 0.0f) : bit o of alive_mask ? the warped probability : -1.0f, a strict > scan
+ * upwards, the float32 comparison of smk_paste_labels -- so the label is byte-equal to what smk_vos_score*_ex write to labels_out
+ * for the same arguments.  PLANE o is label == o + 1 (smk_labels_rle_encode: byte == o + 1 of the given map; bytes above n_obj
+ * belong to no plane); the planes are disjoint.  The code of plane o is that of smk_rle_encode above: column-major j = x * H + y,
+ * counts_out_dev uint32 [n_obj][cap], meta_out_dev int32 [n_obj][4] = (m, area, H, W), m the true number of counts even when
+ * m > cap, indices at or past cap not written, elements m .. cap - 1 not written.  An object no pixel carries (idle, or beaten
+ * everywhere) has the code [W * H], m = 1, area = 0.
+ * smk_vos_rle / smk_vos_rle_dev compute the label per pixel and pack the bits: neither a mask byte nor a label byte reaches memory.
+ * Every word of the workspace's n_obj bit planes is written exactly once per call: nothing needs zeroing, a second call gives the
+ * same bytes.  ws_dev: smk_rle_workspace(n_obj, W, H), 8-byte aligned; W, H in 1..4096, cap in 1..W * H + 1.  inv_map and
+ * object_ids are HOST arrays that travel as kernel arguments (nothing of the caller's memory is read after the call returns);
+ * logits_dev / head_dev / state_dev / slot as for smk_vos_score / smk_vos_score_dev.  Bad arguments -- a null pointer, n_obj
+ * outside 1..32, a range above, given_mask bits at or above n_obj, given_mask without init_labels_dev, a slot outside 0..1, a
+ * short or misaligned workspace, a misaligned output -- give SMK_E_ARG before anything is enqueued.  No context; asynchronous on
+ * `stream`, no host synchronisation. */
+int smk_labels_rle_encode(const uint8_t *labels_dev, int n_obj, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
+                          uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+int smk_vos_rle(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, const uint8_t *init_labels_dev,
+                int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+int smk_vos_rle_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                    int n_obj, int W, int H, float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr,
+                    uint32_t given_mask, const uint8_t *init_labels_dev, int cap, void *ws_dev, size_t ws_bytes,
+                    uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+
 /* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
  * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
  * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:

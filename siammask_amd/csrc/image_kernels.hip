@@ -550,13 +550,16 @@ __global__ __launch_bounds__(256) void rle_bits_kernel(const RleParams p) {
 // the byte source through LDS: a workgroup takes 64 columns x H rows.  64 x0 H is a multiple of 64, so the columns [x0, x0 + 64) are
 // exactly the words [x0 / 64 * H, ...) -- H of them, fewer for a ragged last block, which ends at the stream's last word.  Pass 1
 // reads rows (lane = column, 64 consecutive bytes) and keeps one ballot per row; pass 2 gathers bit xl of row y for j = xl * H + y.
+// LABELS (smk_labels_rle_encode): p.mask is ONE label map [H][W] and plane b = blockIdx.y is byte == b + 1; every plane re-reads
+// the map (from L2).  A compile-time switch: without it the kernel is the one it was.
+template <bool LABELS>
 __global__ __launch_bounds__(1024) void rle_bits_tile_kernel(const RleParams p) {
     __shared__ unsigned long long rows[RLE_MAX_SIDE];
     const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int H = p.H, x0 = blockIdx.x * 64, nc = min(64, p.W - x0);
-    const unsigned char *m = p.mask + (size_t)b * p.W * H + x0;
+    const unsigned char *m = p.mask + (LABELS ? (size_t)0 : (size_t)b * p.W * H) + x0;
     for (int y = wave; y < H; y += 16) {                              // (wave-uniform trip counts: every lane reaches the ballots)
-        const bool bit = lane < nc && m[(size_t)y * p.W + lane] != 0;
+        const bool bit = lane < nc && (LABELS ? m[(size_t)y * p.W + lane] == b + 1 : m[(size_t)y * p.W + lane] != 0);
         const unsigned long long r = __ballot(bit);
         if (lane == 0) rows[y] = r;
     }
@@ -643,10 +646,97 @@ int launch_rle(const RleParams &p, int B, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     const dim3 lanes((unsigned)((rle_words(p.W, p.H) + 3) / 4), B);
     if (!p.mask)     hipLaunchKernelGGL((rle_bits_kernel<true>), lanes, dim3(256), 0, s, p);
-    else if (p.tile) hipLaunchKernelGGL(rle_bits_tile_kernel, dim3((p.W + 63) / 64, B), dim3(1024), 0, s, p);
+    else if (p.tile) hipLaunchKernelGGL((rle_bits_tile_kernel<false>), dim3((p.W + 63) / 64, B), dim3(1024), 0, s, p);
     else             hipLaunchKernelGGL((rle_bits_kernel<false>), lanes, dim3(256), 0, s, p);
     if (hipGetLastError() != hipSuccess) return -4;
     hipLaunchKernelGGL(rle_scan_kernel, dim3(B), dim3(1024), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- the fused label map of a VOS frame as O bit planes (smk_vos_rle / smk_vos_rle_dev) -----------------------------------------------
+// One lane per column-major pixel j, as rle_bits_kernel.  The lane computes the label vos_score_kernel writes -- the same loop over
+// the objects (prob_o from the init labels, warped_prob or -1; strict > upwards keeps the first maximum; the float32 comparison
+// with seg_thr) -- and plane o's bit is label == o + 1.  O wave-uniform ballots; lane o keeps the word of plane o, so the wave's O
+// words leave in ONE store instruction by lanes 0 .. O - 1 (O <= 32 < 64).  Every word of every plane is written exactly once,
+// all-zero words of idle objects included: nothing is zeroed beforehand.  No lane leaves before the last ballot; lanes at or past
+// a = W * H carry label 0 and vote 0 everywhere.
+template <bool DEV, bool GIVEN>
+__global__ __launch_bounds__(256) void rle_bits_labels_kernel(const VosRleParams p) {
+    const int lane = threadIdx.x & 63, O = p.n_obj;
+    const int a = p.W * p.H, nw = (int)rle_words(p.W, p.H);
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6), j = k * 64 + lane;
+    int label = 0;
+    if (j < a) {
+        const int x = j / p.H, y = j - x * p.H;
+        float best = -1.f;
+        int arg = 0;
+        for (int o = 0; o < O; ++o) {
+            float v = -1.f;
+            bool given = false;
+            if constexpr (GIVEN) {
+                given = (p.given >> o) & 1;
+                if (given) v = p.init_labels[(size_t)y * p.W + x] == p.ids[o] ? 1.f : 0.f;
+            }
+            if (!given && ((p.alive >> o) & 1)) {
+                if constexpr (DEV) {
+                    const smk_trk_stream *s = p.st + o;
+                    const float *lg = p.logits + (size_t)o * p.ms * p.ms;
+                    int ls = 1;
+                    if (p.head_S) {
+                        ls = p.head_S * p.head_S;
+                        const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1);
+                        const int dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+                        lg = p.logits + (size_t)o * p.ms * p.ms * ls + dy * p.head_S + dx;
+                    }
+                    v = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y);
+                } else {
+                    v = warped_prob(p, p.inv_map[o], p.logits + (size_t)o * p.ms * p.ms, 1, x, y);
+                }
+            }
+            if (o == 0 || v > best) { best = v; arg = o; }            // np.argmax keeps the first maximum
+        }
+        label = best > p.seg_thr ? arg + 1 : 0;
+    }
+    unsigned long long mine = 0;
+    for (int o = 0; o < O; ++o) {                                     // (wave-uniform: every lane reaches every ballot)
+        const unsigned long long w = __ballot(label == o + 1);
+        if (lane == o) mine = w;
+    }
+    if (lane < O && k < nw) p.words[(size_t)lane * nw + k] = mine;
+}
+
+static RleParams scan_params(unsigned long long *words, unsigned *counts, int *meta, int W, int H, int cap) {
+    RleParams r = {};
+    r.words = words; r.counts = counts; r.meta = meta;
+    r.W = W; r.H = H; r.cap = cap;
+    return r;
+}
+
+int launch_vos_rle(const VosRleParams &p, void *stream) {
+    if (p.n_obj < 1 || p.n_obj > VOS_MAX_OBJ || p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE) return -1;
+    if (p.cap < 1 || p.cap > p.W * p.H + 1 || !p.words || !p.counts || !p.meta || !p.logits || p.ms < 1) return -1;
+    if (p.given && !p.init_labels) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((rle_words(p.W, p.H) + 3) / 4));
+    if (p.given) {
+        if (p.st) hipLaunchKernelGGL((rle_bits_labels_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((rle_bits_labels_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (p.st) hipLaunchKernelGGL((rle_bits_labels_kernel<true, false>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((rle_bits_labels_kernel<false, false>), grid, dim3(256), 0, s, p);
+    }
+    if (hipGetLastError() != hipSuccess) return -4;
+    hipLaunchKernelGGL(rle_scan_kernel, dim3(p.n_obj), dim3(1024), 0, s, scan_params(p.words, p.counts, p.meta, p.W, p.H, p.cap));
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+int launch_rle_labels(const RleParams &p, int O, void *stream) {
+    if (O < 1 || O > VOS_MAX_OBJ || p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || p.cap < 1 || p.cap > p.W * p.H + 1) return -1;
+    if (!p.mask || !p.words || !p.counts || !p.meta) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL((rle_bits_tile_kernel<true>), dim3((p.W + 63) / 64, O), dim3(1024), 0, s, p);
+    if (hipGetLastError() != hipSuccess) return -4;
+    hipLaunchKernelGGL(rle_scan_kernel, dim3(O), dim3(1024), 0, s, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

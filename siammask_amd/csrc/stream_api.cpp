@@ -434,6 +434,69 @@ int smk_vos_score_dev_ex(const float *logits_dev, const float *head_dev, int sco
     return 0;
 }
 
+// ---- the fused label map of a VOS frame as per-object run lengths (image_kernels.hip rle_bits_labels / rle_bits_tile<true>) ------
+int smk_labels_rle_encode(const uint8_t *labels_dev, int n_obj, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
+                          uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!labels_dev) return fail(SMK_E_ARG, "smk_labels_rle_encode: null argument");
+    if (n_obj < 1 || n_obj > VOS_MAX_OBJ) return fail(SMK_E_ARG, "smk_labels_rle_encode: %d objects (1..%d)", n_obj, VOS_MAX_OBJ);
+    RleParams p;
+    CHK(rle_fill("smk_labels_rle_encode", p, n_obj, W, H, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    p.mask = labels_dev;
+    if (launch_rle_labels(p, n_obj, stream)) return fail(SMK_E_HIP, "labels_rle_encode launch failed");
+    return 0;
+}
+
+// the checks and the fields both fused entries share: those of vos_fill / vos_given and of rle_fill; everything is refused here
+static int vos_rle_fill(const char *who, VosRleParams &p, const float *src, int mask_size, int n_obj, int W, int H, float border,
+                        const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask,
+                        const uint8_t *init_labels_dev, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev,
+                        int32_t *meta_out_dev) {
+    if (!src || !object_ids) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (n_obj < 1 || n_obj > VOS_MAX_OBJ) return fail(SMK_E_ARG, "%s: %d objects (1..%d)", who, n_obj, VOS_MAX_OBJ);
+    if (mask_size < 1) return fail(SMK_E_ARG, "%s: bad geometry (mask %d)", who, mask_size);
+    if (n_obj < 32 && (given_mask >> n_obj)) return fail(SMK_E_ARG, "%s: given_mask %#x has bits at or above %d objects", who, given_mask, n_obj);
+    if (given_mask && !init_labels_dev) return fail(SMK_E_ARG, "%s: given_mask without init_labels_dev", who);
+    RleParams r;
+    CHK(rle_fill(who, r, n_obj, W, H, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    memset(&p, 0, sizeof(p));
+    p.words = r.words; p.counts = r.counts; p.meta = r.meta;
+    p.W = W; p.H = H; p.cap = cap;
+    p.logits = src; p.init_labels = given_mask ? init_labels_dev : nullptr;
+    p.ms = mask_size; p.n_obj = n_obj;
+    p.seg_thr = seg_thr; p.border = border; p.alive = alive_mask; p.given = given_mask;
+    for (int i = 0; i < n_obj; ++i) p.ids[i] = object_ids[i];
+    return 0;
+}
+
+int smk_vos_rle(const float *logits_dev, int mask_size, const double *inv_map, int n_obj, int W, int H, float border,
+                const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, const uint8_t *init_labels_dev,
+                int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_rle: null argument");
+    VosRleParams p;
+    CHK(vos_rle_fill("smk_vos_rle", p, logits_dev, mask_size, n_obj, W, H, border, object_ids, alive_mask, seg_thr, given_mask,
+                     init_labels_dev, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    for (int i = 0; i < n_obj; ++i)
+        for (int k = 0; k < 6; ++k) p.inv_map[i][k] = inv_map[6 * i + k];
+    if (launch_vos_rle(p, stream)) return fail(SMK_E_HIP, "vos_rle launch failed");
+    return 0;
+}
+
+int smk_vos_rle_dev(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                    int n_obj, int W, int H, float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr,
+                    uint32_t given_mask, const uint8_t *init_labels_dev, int cap, void *ws_dev, size_t ws_bytes,
+                    uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_rle_dev: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_rle_dev: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_rle_dev: score_size %d", score_size);
+    VosRleParams p;
+    CHK(vos_rle_fill("smk_vos_rle_dev", p, head_dev ? head_dev : logits_dev, mask_size, n_obj, W, H, border, object_ids, alive_mask,
+                     seg_thr, given_mask, init_labels_dev, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_rle(p, stream)) return fail(SMK_E_HIP, "vos_rle launch failed");
+    return 0;
+}
+
 // ---- per-stream IoU counts (utils/average_meter_helper.py:71-113 IouMeter.add per frame, fused with the paste-back) ------------
 static_assert(IOU_MAX_B == TRK_SET_MAX_B, "smk_iou_score takes as many streams as a state block of the tracker");
 

@@ -250,6 +250,27 @@ struct RleParams {
     PasteDevParams paste;           // mask_out / prob_out unused; W, H as above
 };
 int launch_rle(const RleParams &p, int B, void *stream);
+// smk_labels_rle_encode: p.mask is ONE label map [H][W], plane o of the O planes is byte == o + 1 (rle_bits_tile_kernel<true>, then
+// rle_scan over the O planes); p.tile / p.paste unused
+int launch_rle_labels(const RleParams &p, int O, void *stream);
+// smk_vos_rle / smk_vos_rle_dev: the label vos_score_kernel writes (max + first argmax over prob_o, best > seg_thr ? arg + 1 : 0)
+// computed per pixel in column-major order and packed straight into the O bit planes `words` ([O][rle_words(W, H)]); no label
+// byte exists.  The output fields are those of RleParams (rle_scan follows with B := O), the rest those of VosParams
+struct VosRleParams {
+    unsigned long long *words;      // workspace
+    unsigned *counts;               // [O][cap]
+    int *meta;                      // [O][4] = (m, area, H, W)
+    int W, H, cap;
+    const float *logits;            // [O][ms*ms], or the head [O][ms*ms][S][S] when head_S != 0
+    const unsigned char *init_labels;
+    int ms, n_obj, head_S, slot;
+    float seg_thr, border;
+    unsigned alive, given;          // as VosParams
+    const smk_trk_stream *st;       // != nullptr: inv_map[slot] / delta_yx[slot] of the state block, inv_map below unused
+    unsigned char ids[VOS_MAX_OBJ];
+    double inv_map[VOS_MAX_OBJ][6];
+};
+int launch_vos_rle(const VosRleParams &p, void *stream);
 
 // ---- stream start on the device (tracker_init.hip; the exemplar crop is image_kernels.hip's, beside crop_pixel) ----------
 constexpr int RECT_MAX_OBJ = 32, RECT_ROWS = 4;

@@ -521,6 +521,111 @@ def paste_rle(logits, state, slot, im_wh, seg_thr=0.35, padding=-1.0, head=None,
     return counts, meta
 
 
+def labels_rle(labels, n_obj, cap=None, counts=None, meta=None):
+    """The per-object COCO run lengths of a fused label map, on the device (include/siammask_hip.h: smk_labels_rle_encode).
+    labels: uint8 CUDA [H,W] (what paste_labels / vos_score write); plane o of the n_obj (1..32) planes is labels == o + 1.
+    cap / counts / meta and the result as for rle_encode with B = n_obj: (counts int32 CUDA [O,cap], meta int32 CUDA [O,4])."""
+    _need_cuda(labels, "labels")
+    if labels.dtype != torch.uint8 or labels.dim() != 2:
+        raise ValueError("labels must be uint8 [H,W]")
+    O = int(n_obj)
+    if not 1 <= O <= 32:
+        raise ValueError("1..32 objects, got %d" % O)
+    lab = labels.contiguous()
+    H, W = (int(v) for v in lab.shape)
+    with torch.cuda.device(lab.device):
+        cap, ws, need, counts, meta = _rle_buffers(lab.device, O, W, H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_labels_rle_encode(lab.data_ptr(), O, W, H, cap, ws.data_ptr(), need, counts.data_ptr(),
+                                                    meta.data_ptr(), _lib.current_stream_ptr()))
+    return counts, meta
+
+
+def _vos_rle_args(O, object_ids, alive, given, init, W, H, device):
+    """the checked arguments vos_rle / vos_rle_dev share -> (ids uint8 [O], alive bit mask, given bit mask, init labels or None)"""
+    if not 1 <= O <= 32:
+        raise ValueError("1..32 objects, got %d" % O)
+    ids = np.asarray(object_ids)
+    if ids.shape != (O,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+        raise ValueError("object_ids must be %d integers in 0..255" % O)
+    bits, gbits = (1 << O) - 1, 0
+    if alive is not None:
+        al = np.asarray(alive)
+        if al.shape != (O,):
+            raise ValueError("alive must be %d booleans" % O)
+        bits = sum(1 << o for o in range(O) if al[o])
+    if given is not None:
+        gv = np.asarray(given)
+        if gv.shape != (O,):
+            raise ValueError("given must be %d booleans" % O)
+        gbits = sum(1 << o for o in range(O) if gv[o])
+    if gbits:
+        if not isinstance(init, torch.Tensor) or not init.is_cuda or init.dtype != torch.uint8 or tuple(init.shape) != (H, W) or \
+                not init.is_contiguous() or init.device != device:
+            raise ValueError("given comes with init, a contiguous uint8 CUDA tensor [%d,%d] on the logits' device" % (H, W))
+    return np.ascontiguousarray(ids.astype(np.uint8)), bits, gbits, init if gbits else None
+
+
+def vos_rle(logits, back_boxes, im_wh, object_ids, alive=None, given=None, init=None, seg_thr=0.35, padding=-1.0, cap=None,
+            counts=None, meta=None):
+    """The fused label map of one VOS frame as per-object COCO run lengths, without a mask or a label byte reaching memory
+    (include/siammask_hip.h: smk_vos_rle).  logits / back_boxes / im_wh / object_ids / alive / seg_thr / padding as for vos_score;
+    given (O booleans) with init (uint8 CUDA [im_h,im_w]): the probability of a given object is init == its id (an object's start
+    frame).  Plane o is labels == o + 1 of vos_score(..., want_labels=True): labels_rle of that map gives the same counts and
+    meta.  cap / counts / meta and the result as for rle_encode with B = O."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    O = logits.shape[0]
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != O:
+        raise ValueError("logits must be [O, ms*ms] with one back_box per object")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    ids, bits, gbits, init = _vos_rle_args(O, object_ids, alive, given, init, W, H, logits.device)
+    inv = np.ascontiguousarray(np.stack([invert_affine(crop_back_map(bb, (W, H))) for bb in back_boxes]))
+    with torch.cuda.device(logits.device):
+        cap, ws, need, counts, meta = _rle_buffers(logits.device, O, W, H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_vos_rle(
+            logits.data_ptr(), ms, inv.ctypes.data_as(ctypes.c_void_p), O, W, H, float(padding), ids.ctypes.data_as(ctypes.c_void_p),
+            bits, float(seg_thr), gbits, init.data_ptr() if init is not None else None, cap, ws.data_ptr(), need,
+            counts.data_ptr(), meta.data_ptr(), _lib.current_stream_ptr()))
+    return counts, meta
+
+
+def vos_rle_dev(logits, state, slot, im_wh, object_ids, alive=None, given=None, init=None, seg_thr=0.35, padding=-1.0, head=None,
+                mask_size=None, cap=None, counts=None, meta=None, _bits=None):
+    """vos_rle with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of each object read on the device
+    from the tracker's state block, as vos_score_dev reads them (smk_vos_rle_dev).
+    _bits (private, the tracker's paste job): (alive, given) as the bit masks its checked spec already holds."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    O = int(src.shape[0])
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [O, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [O, ms*ms]")
+    W, H = int(im_wh[0]), int(im_wh[1])
+    if _bits is not None:
+        ids, (bits, gbits) = object_ids, _bits
+    else:
+        ids, bits, gbits, init = _vos_rle_args(O, object_ids, alive, given, init, W, H, src.device)
+    with torch.cuda.device(src.device):
+        cap, ws, need, counts, meta = _rle_buffers(src.device, O, W, H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_vos_rle_dev(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), O, W, H, float(padding), ids.ctypes.data_as(ctypes.c_void_p), bits, float(seg_thr), gbits,
+            init.data_ptr() if init is not None else None, cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr(),
+            _lib.current_stream_ptr()))
+    return counts, meta
+
+
 def image_refs(frames):
     """smk_image_ref array of a list of uint8 CUDA tensors [h,w,3] (packed pixels, rows at any pitch >= 3 w; no copy)"""
     refs = (_lib.ImageRef * len(frames))()

@@ -7,6 +7,14 @@ run (0 when pixel 0 is set); they sum to h * w.  An empty mask is [h * w], a ful
     r = tr.run(frames, rle=True)['rle']                 # counts on the device, n / area on the host
     per = rle.to_host(r)                                # ONE copy of counts[..., :n.max()] -> [T][B] numpy arrays (None: n > cap)
     rle.to_coco(per[t][b], *r['size'])                  # {'size': [h, w], 'counts': b'...'}: what pycocotools takes
+
+The fused label map of a VOS frame as one code per object (smk_vos_rle / smk_labels_rle_encode, run(vos={..., 'rle': True})):
+plane o is labels == o + 1, so the planes are disjoint and a frame's map is their union.
+
+    r = tr.run(frames, vos={'object_ids': ids, 'rle': True, ...})['label_rle']      # the layout of res['rle'], B = the objects
+    per = rle.to_host(r)
+    rle.labels_decode(per[t], *r['size'])               # uint8 [h, w] label map of frame t
+    rle.labels_to_coco(per[t], *r['size'], object_ids=ids)      # [{'size', 'counts', 'label', 'object_id'}] of the non-empty planes
 """
 import numpy as np
 
@@ -98,6 +106,35 @@ def to_bbox(counts, h, w):
 def to_coco(counts, h, w):
     """the dict pycocotools' mask API takes"""
     return {"size": [int(h), int(w)], "counts": to_string(counts)}
+
+
+def labels_decode(per_object_counts, h, w):
+    """the label map of O per-object codes (plane o = labels == o + 1) -> uint8 [h, w]; ValueError where two planes overlap"""
+    out = np.zeros((int(h), int(w)), dtype=np.uint8)
+    if len(per_object_counts) > 255:
+        raise ValueError("a uint8 label map holds up to 255 objects, got %d" % len(per_object_counts))
+    for o, c in enumerate(per_object_counts):
+        m = decode(c, h, w) != 0
+        if out[m].any():
+            raise ValueError("the planes of objects %d and %d overlap" % (int(out[m].max()) - 1, o))
+        out[m] = o + 1
+    return out
+
+
+def labels_to_coco(per_object_counts, h, w, object_ids=None):
+    """one to_coco dict per NON-EMPTY plane, with 'label' = o + 1 (the value in the label map) and, given object_ids, 'object_id'
+    = object_ids[o] (the dataset's id of the object on stream o)"""
+    if object_ids is not None and len(object_ids) != len(per_object_counts):
+        raise ValueError("%d object_ids for %d planes" % (len(object_ids), len(per_object_counts)))
+    out = []
+    for o, c in enumerate(per_object_counts):
+        if area(c) == 0:
+            continue
+        d = dict(to_coco(c, h, w), label=o + 1)
+        if object_ids is not None:
+            d["object_id"] = int(object_ids[o])
+        out.append(d)
+    return out
 
 
 def to_host(r):

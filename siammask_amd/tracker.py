@@ -23,6 +23,8 @@ csrc/tracker_state.hip) -- any number of frames is enqueued without a host synch
                                                                    # (tools/tune_vos.py); score-only frames write no mask
     res = tr.run(frames, rle=True)                                 # the masks as COCO run lengths, encoded by the paste-back itself:
     res['rle'], res['mask']                                        # counts on the device + n / area on the host (siammask_amd.rle); None
+    res = tr.run(frames, vos={'object_ids': ids, 'rle': True, 'start': {...}, 'end': {...}, 'init': labels0})   # VOS without annotation:
+    res['label_rle']                                               # the fused label map as one run-length code per object, no mask / label bytes
 track() and enqueue() can be mixed; both leave tr.state as the reference's loop would.
 
 Streams that start on their own frames (siamese_init per stream on the device, enqueue-only; csrc/tracker_init.hip):
@@ -121,7 +123,11 @@ _Job = collections.namedtuple("_Job", "logits head slot mask rbox score after ad
 # a checked rle= request (_rle_spec): counts per stream, masks wanted; enqueue() adds the frame's counts [B,cap] and meta [B,4]
 _Rle = collections.namedtuple("_Rle", "cap masks counts meta")
 # a checked VOS request as the C entry takes it (_vos_spec); enqueue() adds the frame's count row and label map
-_Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels")
+# rle: None, or the _LabelRle of a frame whose spec carries vos['rle']; gt / thrs / row are then None when the frame is not scored
+_Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels rle", defaults=(None,))
+# a checked vos['rle'] request (_vos_spec): counts per object, masks / label map wanted beside the counts; enqueue() adds the
+# frame's counts [B,cap] and meta [B,4]
+_LabelRle = collections.namedtuple("_LabelRle", "cap masks labels counts meta")
 # a checked iou= request (_iou_spec): annotation, thresholds, masks wanted, frame scored; enqueue() adds the frame's count row
 _Iou = collections.namedtuple("_Iou", "gt thrs masks scored row")
 _IOU_MAX_THR = 16
@@ -130,12 +136,14 @@ _Event = collections.namedtuple("_Event", "t streams res")            # one star
 
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
-    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes", "rle")
+    __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes", "rle",
+                 "label_rle")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
         self.iou_k = None                                             # thresholds of a chunk enqueued with iou=
         self.rle = None                                               # the _Rle of every frame of a chunk enqueued with rle=
+        self.label_rle = None                                         # the _LabelRle of every frame of a chunk enqueued with vos['rle']
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
         self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
@@ -686,33 +694,42 @@ class DeviceTracker(object):
 
     def _vos_spec(self, frame_dim, want_mask, gt, vos, labels_out=None):
         """the checked VOS request of one frame (before anything is launched) -> None, or a _Score (row and labels still None)
-        with the host arrays the C entry takes"""
+        with the host arrays the C entry takes.  With vos['rle'] its .rle is the checked _LabelRle and gt may be None (the frame
+        is then not scored: gt / thrs of the _Score are None)"""
         if gt is None and vos is None:
             if labels_out is not None:
                 raise ValueError("labels_out comes with gt= and vos=")
             return None
         q = self._fr
         B, H, W = q.B, q.H, q.W
-        if gt is None or vos is None:
+        lr = vos.get("rle") if isinstance(vos, dict) else None        # the label map as per-object run lengths: gt is optional
+        lr = None if lr is False else lr
+        if vos is None or (gt is None and lr is None):
             raise ValueError("gt= and vos= come together")
         if frame_dim != 3 or not want_mask or self.model.variant == "rpn":
             raise ValueError("VOS scoring needs one frame shared by the B objects, want_mask and a variant with a mask branch")
-        if not _u8_cuda(gt, (H, W)):
+        if gt is not None and not _u8_cuda(gt, (H, W)):
             raise ValueError("gt must be a uint8 CUDA tensor [%d,%d]" % (H, W))
         if B > 32:
             raise ValueError("VOS scoring takes up to 32 objects, the tracker has %d" % B)
-        unknown = set(vos) - {"object_ids", "thrs", "alive", "given", "init"}
-        if unknown or "object_ids" not in vos or "thrs" not in vos:
+        unknown = set(vos) - {"object_ids", "thrs", "alive", "given", "init", "rle"}
+        if unknown or "object_ids" not in vos or (vos.get("thrs") is None and gt is not None):
             raise ValueError("vos = {'object_ids': B ids, 'thrs': 1..8 thresholds[, 'alive': B booleans][, 'given': B booleans, "
-                             "'init': uint8 CUDA labels]}")
+                             "'init': uint8 CUDA labels][, 'rle': True or {'cap', 'masks', 'labels'}]}")
         ids = np.asarray(vos["object_ids"])
         if ids.shape != (B,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
             raise ValueError("vos['object_ids'] must be %d integers in 0..255" % B)
-        thrs = np.ascontiguousarray(vos["thrs"], dtype=np.float64)
-        if thrs.ndim != 1 or not 1 <= thrs.size <= 8:
-            raise ValueError("vos['thrs'] must be 1..8 values")
-        if q.chunk.pending and q.chunk.vos_k != thrs.size:
+        thrs = None
+        if vos.get("thrs") is not None:
+            thrs = np.ascontiguousarray(vos["thrs"], dtype=np.float64)
+            if thrs.ndim != 1 or not 1 <= thrs.size <= 8:
+                raise ValueError("vos['thrs'] must be 1..8 values")
+        if q.chunk.pending and q.chunk.vos_k != (thrs.size if gt is not None else None):
             raise ValueError("every frame of a chunk is scored at the same number of thresholds, or none is")
+        if lr is not None:
+            lr = self._label_rle_spec(lr, gt is not None)
+        if q.chunk.pending and ((q.chunk.label_rle is None) != (lr is None) or (lr is not None and q.chunk.label_rle[0].cap != lr.cap)):
+            raise ValueError("every frame of a chunk carries vos['rle'] with one cap, or none does")
         alive = vos.get("alive")
         bits = (1 << B) - 1
         if alive is not None:
@@ -722,6 +739,8 @@ class DeviceTracker(object):
             bits = sum(1 << b for b in range(B) if alive[b])
         if labels_out is not None and not _u8_cuda(labels_out, (H, W), contiguous=True):
             raise ValueError("labels_out must be a contiguous uint8 CUDA tensor [%d,%d]" % (H, W))
+        if labels_out is not None and gt is None:
+            raise ValueError("labels_out: the label map comes from the scoring launch, which needs gt=")
         given, init = vos.get("given"), vos.get("init")
         gbits = 0
         if given is not None:                                         # an object's start frame: its probability is the init mask
@@ -731,8 +750,26 @@ class DeviceTracker(object):
             gbits = sum(1 << b for b in range(B) if given[b])
         if gbits and not _u8_cuda(init, (H, W)):
             raise ValueError("vos['given'] comes with vos['init'], a uint8 CUDA tensor [%d,%d]" % (H, W))
-        return _Score(gt.contiguous(), np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits,
-                      init.contiguous() if gbits else None, None, None)
+        return _Score(gt.contiguous() if gt is not None else None, np.ascontiguousarray(ids.astype(np.uint8)), thrs, bits, gbits,
+                      init.contiguous() if gbits else None, None, None, lr)
+
+    def _label_rle_spec(self, lr, scored):
+        """the checked vos['rle'] of one frame -> a _LabelRle (counts / meta still None).  scored: the frame has gt="""
+        q = self._fr
+        if lr is True:
+            lr = {}
+        if not isinstance(lr, dict) or set(lr) - {"cap", "masks", "labels"}:
+            raise ValueError("vos['rle'] = True or {'cap': counts per object[, 'masks': bool][, 'labels': bool]}")
+        from . import rle as rle_host
+        cap = lr.get("cap")
+        cap = rle_host.default_cap(q.H, q.W) if cap is None else cap
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= q.H * q.W + 1:
+            raise ValueError("vos['rle']['cap'] must be an integer in 1..%d (H * W + 1), got %r" % (q.H * q.W + 1, cap))
+        if q.H > 4096 or q.W > 4096:
+            raise ValueError("vos['rle']: frames of up to 4096 x 4096, these are %d x %d" % (q.H, q.W))
+        if lr.get("labels", False) and not scored:
+            raise ValueError("vos['rle']['labels']: the label map comes from the scoring launch, which needs gt=")
+        return _LabelRle(int(cap), bool(lr.get("masks", False)), bool(lr.get("labels", False)), None, None)
 
     def _iou_spec(self, mixed, want_mask, want_polygon, mask_out, scored_vos, iou):
         """the checked iou= request of one frame (before anything is launched) -> None, or an _Iou (row still None)"""
@@ -810,6 +847,13 @@ class DeviceTracker(object):
         paste-back IS smk_paste_rle_dev: no mask tensor exists and collect() reports no mask; otherwise the paste-back runs as
         always and smk_rle_encode follows it on the same stream.  Either every frame of a chunk carries rle= (one cap) or none
         does; not with gt= / vos= / iou=, mixed frame sizes, the rpn variant or want_mask=False (ValueError before any launch).
+        vos['rle'] (True, or {'cap': counts reserved per object (rle.default_cap)[, 'masks': False][, 'labels': False]}): the fused
+        label map of the frame as one COCO run-length code per object -- plane o is labels == o + 1 -- and collect() returns
+        res['label_rle'].  Without want_polygon, 'masks' and mask_out= smk_vos_rle_dev stands in the paste-back's place: no mask
+        tensor and no label tensor exist, collect() reports mask and labels None, and the scoring launch (with gt) writes no label
+        map.  'labels': True (needs gt) keeps the label map and encodes its bytes (smk_labels_rle_encode).  gt may then be None:
+        nothing is scored, 'thrs' is optional and collect() has no vos_counts.  Either every frame of a chunk carries vos['rle']
+        (one cap; scored or not as the first) or none does; the top-level rle= with gt= / vos= stays refused.
         _rle_out (private, run()): the frame's rows (counts int32 CUDA [B,cap], meta int32 CUDA [B,4]) of the run's tensors.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
@@ -833,7 +877,7 @@ class DeviceTracker(object):
         want_mask = want_mask and self.model.variant != "rpn"
         want_polygon = want_polygon and want_mask
         self._mask_out(mask_out, want_mask=want_mask)
-        if c.pending and (c.vos_k is not None) != (vos is not None or gt is not None):
+        if c.pending and (c.vos_k is not None or c.label_rle is not None) != (vos is not None or gt is not None):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
         if c.pending and (c.iou_k is not None) != (iou is not None):
             raise ValueError("every frame of a chunk carries iou=, or none does")
@@ -856,11 +900,18 @@ class DeviceTracker(object):
             if want_polygon and q.rbox[blk] is None:
                 q.rbox[blk] = torch.zeros((_ROWS_PER_BLOCK, B, 12), dtype=torch.float64, device=q.device)
             if score is not None:
-                if i == 0 and blk == len(q.vos):                      # count rows per block, like q.rows
-                    q.vos.append(torch.empty((_ROWS_PER_BLOCK, B, 8, 2), dtype=torch.int32, device=q.device))
-                labels = labels_out if labels_out is not None else torch.empty((H, W), dtype=torch.uint8, device=q.device)
-                score = score._replace(row=q.vos[blk][i], labels=labels)
-                c.vos_k = int(score.thrs.size)
+                lr, labels = score.rle, None
+                if score.gt is not None:
+                    if i == 0 and blk == len(q.vos):                  # count rows per block, like q.rows
+                        q.vos.append(torch.empty((_ROWS_PER_BLOCK, B, 8, 2), dtype=torch.int32, device=q.device))
+                    if lr is None or lr.labels or labels_out is not None:      # (vos['rle'] alone: no label byte anywhere)
+                        labels = labels_out if labels_out is not None else torch.empty((H, W), dtype=torch.uint8, device=q.device)
+                    score = score._replace(row=q.vos[blk][i], labels=labels)
+                    c.vos_k = int(score.thrs.size)
+                if lr is not None:
+                    rc, rm = _rle_out if _rle_out is not None else (torch.empty((B, lr.cap), dtype=torch.int32, device=q.device),
+                                                                    torch.empty((B, 4), dtype=torch.int32, device=q.device))
+                    score = score._replace(rle=lr._replace(counts=rc, meta=rm))
                 c.labels.append(labels)
             if iou is not None:
                 if i == 0 and blk == len(q.iou):                      # count rows per block, like q.vos
@@ -892,8 +943,11 @@ class DeviceTracker(object):
             self._fr_flush(sp, join=not refine or depth != 1)
             mask = None
             if want_mask:
+                lr = score.rle if score is not None else None
                 if rle is not None and not (want_polygon or rle.masks or mask_out is not None):
                     pass                                              # the paste-back emits the run lengths: no mask bytes anywhere
+                elif lr is not None and not (want_polygon or lr.masks or mask_out is not None):
+                    pass                                              # smk_vos_rle_dev stands in the paste-back's place: likewise
                 elif iou is None or iou.masks:                        # (a score-only frame has no mask anywhere)
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
@@ -906,6 +960,8 @@ class DeviceTracker(object):
             c.masks.append(mask)
             if rle is not None:                                       # (beside the frame count: a launch that raised leaves no row)
                 c.rle = (c.rle or []) + [rle]
+            if score is not None and score.rle is not None:
+                c.label_rle = (c.label_rle or []) + [score.rle]
             c.sizes.append(sizes if mixed else None)
             c.poly.append(bool(want_polygon))
             c.pending = t + 1
@@ -920,6 +976,7 @@ class DeviceTracker(object):
                   int(head.shape[-1]) if head is not None else 0, self.mask_size, q.dev.data_ptr(), job.slot, q.B, q.W, q.H)
         fused = u is not None and u.scored and job.rbox is None      # smk_iou_score_dev writes the mask bytes itself
         r = job.rle
+        lr = s.rle if s is not None else None
         if r is not None and mask is None:                            # the paste-back IS the encoder (smk_paste_rle_dev)
             preproc.paste_rle(logits, q.dev, job.slot, (q.W, q.H), seg_thr=p.seg_thr, head=head, mask_size=self.mask_size,
                               cap=r.cap, counts=r.counts, meta=r.meta)
@@ -933,13 +990,18 @@ class DeviceTracker(object):
             preproc.mask_rboxes(mask, out=job.rbox, mode=self.rbox)
         if r is not None and mask is not None:                        # the bytes exist: encode them, same stream
             preproc.rle_encode(mask, cap=r.cap, counts=r.counts, meta=r.meta)
-        if s is not None:                                             # the same slot of the same state block, same stream
+        if lr is not None and s.labels is None:                       # the fused label planes, in the paste-back's place: no label byte
+            preproc.vos_rle_dev(logits, q.dev, job.slot, (q.W, q.H), s.ids, init=s.init, seg_thr=p.seg_thr, head=head,
+                                mask_size=self.mask_size, cap=lr.cap, counts=lr.counts, meta=lr.meta, _bits=(s.bits, s.gbits))
+        if s is not None and s.gt is not None:                        # the same slot of the same state block, same stream
             args = shared + (-1.0, s.gt.data_ptr(), s.ids.ctypes.data, s.bits, s.thrs.ctypes.data, int(s.thrs.size),
-                             float(p.seg_thr), s.row.data_ptr(), s.labels.data_ptr())
+                             float(p.seg_thr), s.row.data_ptr(), s.labels.data_ptr() if s.labels is not None else None)
             if s.gbits:                                               # an object's start frame (tools/test.py:493,503-504)
                 _lib.check(L.smk_vos_score_dev_ex(*(args + (s.gbits, s.init.data_ptr(), sp))))
             else:
                 _lib.check(L.smk_vos_score_dev(*(args + (sp,))))
+        if lr is not None and s.labels is not None:                   # the label map was asked for: encode its bytes, same stream
+            preproc.labels_rle(s.labels, q.B, cap=lr.cap, counts=lr.counts, meta=lr.meta)
         if u is not None and not u.scored:                            # tracked, not scored (IouMeter scores 0 < f < T - 1): a zero row
             u.row.zero_()
         elif u is not None:
@@ -995,6 +1057,7 @@ class DeviceTracker(object):
         c, B = q.chunk, q.B
         T, K, events = c.pending, c.vos_k if c.vos_k is not None else c.iou_k, c.events
         counts = q.vos if c.vos_k is not None else q.iou             # per-block count rows, _IOU_MAX_THR or 8 thresholds wide
+        enc = c.rle if c.rle is not None else c.label_rle             # a chunk's frames carry rle=, vos['rle'], or neither
         if not self._chunk_open():
             return None
         with q.launch as sp:                                          # the device half: one tensor, one copy
@@ -1011,8 +1074,8 @@ class DeviceTracker(object):
                     vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
                     vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
-                if c.rle is not None:                                 # (m, area) of the meta rows ride along as float64 (exact)
-                    rmeta = _rle[1] if _rle is not None and _rle[1].shape[0] == T else torch.stack([r.meta for r in c.rle])
+                if enc is not None:                                   # (m, area) of the meta rows ride along as float64 (exact)
+                    rmeta = _rle[1] if _rle is not None and _rle[1].shape[0] == T else torch.stack([r.meta for r in enc])
                     rows = torch.cat([rows, rmeta[:, :, :2].to(torch.float64)], dim=2)
             if events:                                                # the start events' result rows ride along
                 flat = torch.cat(([rows.reshape(-1)] if T else []) + [e.res.reshape(-1) for e in events]).cpu().numpy()
@@ -1021,21 +1084,24 @@ class DeviceTracker(object):
             else:
                 host, ev_rows = rows.cpu().numpy(), None              # the one synchronisation
         rle_host = None
-        if T and c.rle is not None:
+        if T and enc is not None:
             host, rle_host = host[:, :, :-2], host[:, :, -2:].astype(np.int32)
         res, new = collect_host(host, T, B, c.poly, K, [(e.t, e.streams) for e in events], ev_rows, st,
                                 "vos_counts" if c.vos_k is not None else "iou_counts")
         if T:
             if rle_host is not None:
-                counts = _rle[0] if _rle is not None and _rle[0].shape[0] == T else torch.stack([r.counts for r in c.rle])
-                res["rle"] = {"counts": counts, "n": np.ascontiguousarray(rle_host[:, :, 0]), "area": np.ascontiguousarray(rle_host[:, :, 1]),
-                              "cap": c.rle[0].cap, "size": (q.H, q.W)}
+                counts = _rle[0] if _rle is not None and _rle[0].shape[0] == T else torch.stack([r.counts for r in enc])
+                res["rle" if c.rle is not None else "label_rle"] = {
+                    "counts": counts, "n": np.ascontiguousarray(rle_host[:, :, 0]), "area": np.ascontiguousarray(rle_host[:, :, 1]),
+                    "cap": enc[0].cap, "size": (q.H, q.W)}
             masks = c.masks
             if all(m is not None for m in masks):
                 res["mask"] = _masks if _masks is not None and _masks.shape[0] == T else torch.stack(masks)
             elif any(m is not None for m in masks):
                 res["mask"] = masks                                   # mixed chunk: per frame, None where no mask was asked for
-            if c.vos_k is not None:
+            if c.label_rle is not None and not all(x is not None for x in c.labels):
+                res["labels"] = None                                  # vos['rle'] without 'labels': no label byte was written
+            elif c.vos_k is not None:
                 res["labels"] = _labels if _labels is not None and _labels.shape[0] == T else torch.stack(c.labels)
             new["mask"] = masks[-1]
             if any(z is not None for z in c.sizes):                   # [T,B,2] (w, h): the mask of (t, b) is mask[t, b, :h, :w]
@@ -1060,7 +1126,11 @@ class DeviceTracker(object):
         tracked and their count rows are zero): the B streams as independent runs against gt > 0 -> res['iou_counts'] int64
         [T,B,K,2] (siammask_amd.vos.iou_meter takes a stream's [T,K,2]).  With 'masks': False no mask is allocated or returned.
         rle (as for enqueue()): the masks as COCO run lengths -> res['rle'] (see collect(); siammask_amd.rle.to_host / to_coco).
-        Without want_polygon, 'masks': True and mask_out= no [T,B,H,W] tensor is allocated and res['mask'] is None."""
+        Without want_polygon, 'masks': True and mask_out= no [T,B,H,W] tensor is allocated and res['mask'] is None.
+        vos['rle'] (as for enqueue(); with or without lifetimes): the fused label maps as per-object run lengths ->
+        res['label_rle'], the layout of res['rle'] with B = the objects (siammask_amd.rle.to_host / labels_decode /
+        labels_to_coco); res['mask'] and res['labels'] are None unless asked for.  gt may then be None (nothing is scored, no
+        res['vos_counts']); with lifetimes vos['init'] is required in that case."""
         from . import tracker_loops
         q = self._fr
         if self.state is None or q is None:
@@ -1104,7 +1174,9 @@ class DeviceTracker(object):
         if isinstance(vos, dict) and ("start" in vos or "end" in vos or "init" in vos):
             return tracker_loops.run_lifetimes(self, frames, want_mask, want_polygon, mask_out, gt, vos)
         if gt is not None or vos is not None:                         # checked for the whole run before the first launch
-            if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T or not isinstance(vos, dict):
+            unscored = gt is None and isinstance(vos, dict) and vos.get("rle") not in (None, False)      # label planes only
+            if frames.dim() != 4 or not isinstance(vos, dict) or \
+                    (not unscored and (not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T)):
                 raise ValueError("VOS scoring: frames [T,H,W,3] shared by the objects, gt uint8 CUDA [T,H,W] and a vos spec")
             alive = vos.get("alive")
             if alive is not None:
@@ -1112,8 +1184,11 @@ class DeviceTracker(object):
                 if alive.shape not in ((q.B,), (T, q.B)):
                     raise ValueError("vos['alive'] must be [B] or [T,B] booleans")
             for t in range(T):
-                self._vos_spec(3, want_mask, gt[t], self._vos_at(vos, alive, t))
-            labels = torch.empty((T, q.H, q.W), dtype=torch.uint8, device=frames.device)
+                if vos.get("rle") not in (None, False):
+                    self._check_frame(frames[t])
+                spec = self._vos_spec(3, want_mask, gt[t] if gt is not None else None, self._vos_at(vos, alive, t)).rle
+            if spec is None or spec.labels:
+                labels = torch.empty((T, q.H, q.W), dtype=torch.uint8, device=frames.device)
         score_only = iou is not None and T > 0 and not iou[0].get("masks", True)         # no mask tensor at all
         if spec is not None and not (want_polygon or spec.masks or mask_out is not None):
             score_only = True                                         # the paste-back emits the run lengths: no [T,B,H,W] either

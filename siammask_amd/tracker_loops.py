@@ -16,14 +16,19 @@ def run_lifetimes(tr, frames, want_mask, want_polygon, mask_out, gt, vos):
     on start < f <= end it is tracked and alive; otherwise idle: mask zeros, not alive.  -> collect()'s dict plus
     'alive' bool [T,B] (tracked frames); the scalar rows (target_pos, score, ...) of a stream on a frame where it is not
     alive are unspecified, and so is everything of a stream whose object was absent from its init labels
-    (res['events'] says which started)."""
+    (res['events'] says which started).  With vos['rle'] (see enqueue()) the label planes come back as res['label_rle'], start
+    frames and idle objects included (the kernel takes 'given' and 'alive'), and without a polygon, 'masks' or mask_out= there is
+    no mask tensor to fix up; gt may then be None, and vos['init'] is required because the init labels cannot default to it."""
     T, B, H, W = int(frames.shape[0]), tr._fr.B, tr._fr.H, tr._fr.W
     if tr.get_hp() is not None:
         raise ValueError("run() with lifetimes: the objects of one video share one configuration -- set_hp(None) first")
     if "start" not in vos or "end" not in vos:
         raise ValueError("vos['start'] and vos['end'] come together")
-    if frames.dim() != 4 or not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T:
+    unscored = gt is None and vos.get("rle") not in (None, False)   # vos['rle'] alone: the label planes, nothing is scored
+    if frames.dim() != 4 or (not unscored and (not isinstance(gt, torch.Tensor) or gt.dim() != 3 or gt.shape[0] != T)):
         raise ValueError("VOS scoring: frames [T,H,W,3] shared by the objects, gt uint8 CUDA [T,H,W] and a vos spec")
+    if unscored and "init" not in vos:
+        raise ValueError("without gt the init labels cannot default to it: vos['init']")
     if "alive" in vos or "given" in vos:
         raise ValueError("with vos['start'] / vos['end'] the lifetimes decide 'alive' and 'given'")
     base = {k: vos[k] for k in vos if k not in ("start", "end", "init")}
@@ -49,26 +54,36 @@ def run_lifetimes(tr, frames, want_mask, want_polygon, mask_out, gt, vos):
     alive = (f_idx > first[None]) & (f_idx <= last[None])
     init_at = (lambda f: init[f]) if init.dim() == 3 else (lambda f: init)
     specs = [dict(base, alive=alive[f], given=given[f], init=init_at(f)) for f in range(T)]
+    lr = None
     for f in range(T):                                                # everything is checked before the first launch
-        tr._vos_spec(3, want_mask, gt[f], specs[f])
+        lr = tr._vos_spec(3, want_mask, gt[f] if gt is not None else None, specs[f]).rle
         if given[f].any():
             tr._start_spec(frames[f], np.nonzero(given[f])[0], None, None, init_at(f), ids[given[f]])
     if tr._chunk_open():
         raise ValueError("run() with lifetimes starts its own chunk: collect() first")
-    masks = tr._mask_out(mask_out, (T,), frames.device)
-    labels = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device)
+    # vos['rle'] without a polygon, 'masks' or mask_out=: the label planes stand in for the masks, no [T,B,H,W] tensor
+    no_mask = lr is not None and not (want_polygon or lr.masks or mask_out is not None)
+    masks = None if no_mask else tr._mask_out(mask_out, (T,), frames.device)
+    labels = torch.empty((T, H, W), dtype=torch.uint8, device=frames.device) if lr is None or lr.labels else None
+    rle_out = None
+    if lr is not None:
+        rle_out = (torch.empty((T, B, lr.cap), dtype=torch.int32, device=frames.device),
+                   torch.empty((T, B, 4), dtype=torch.int32, device=frames.device))
     for f in range(T):
-        tr.enqueue(frames[f], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[f], gt=gt[f], vos=specs[f],
-                   labels_out=labels[f])
+        tr.enqueue(frames[f], want_mask=want_mask, want_polygon=want_polygon, mask_out=masks[f] if masks is not None else None,
+                   gt=gt[f] if gt is not None else None, vos=specs[f], labels_out=labels[f] if labels is not None else None,
+                   _rle_out=(rle_out[0][f], rle_out[1][f]) if rle_out is not None else None)
         if given[f].any():                                            # behind the step: the stream's first tracked frame is f + 1
             tr.start(frames[f], np.nonzero(given[f])[0], labels=init_at(f), object_ids=ids[given[f]])
-    res = tr.collect(_masks=masks, _labels=labels)
-    # the mask rows the tracker did not produce: the init mask at a start frame, zeros while idle
-    for f, j in np.argwhere(given):
-        res["mask"][f, j] = (init_at(f) == int(ids[j])).to(torch.uint8)
-    idle = ~(given | alive)
-    if idle.any():
-        res["mask"][torch.from_numpy(idle).to(res["mask"].device)] = 0
+    res = tr.collect(_masks=masks, _labels=labels, _rle=rle_out)
+    # the mask rows the tracker did not produce: the init mask at a start frame, zeros while idle (the label planes of
+    # vos['rle'] need no fix-up: the kernel takes 'given' and 'alive')
+    if res["mask"] is not None:
+        for f, j in np.argwhere(given):
+            res["mask"][f, j] = (init_at(f) == int(ids[j])).to(torch.uint8)
+        idle = ~(given | alive)
+        if idle.any():
+            res["mask"][torch.from_numpy(idle).to(res["mask"].device)] = 0
     res["alive"] = alive
     return res
 
