@@ -637,6 +637,29 @@ int smk_eao_curve(const float *ov_eao_dev, const int8_t *code_dev, const int32_t
                   int G, int V, int skipping, int low, int high, int F_max, void *ws_dev, size_t ws_bytes, float *curve_dev,
                   double *eao_dev, int32_t *n_fragments_dev, void *stream);
 
+/* ---- One-pass (OTB-style) evaluation: success and precision counts of result trajectories (utils/pysot/utils/statistics.py
+ * overlap_ratio, success_overlap, success_error; additive; smk_version() keeps reporting 1.10, the presence of this symbol is
+ * the probe) ---------------------------------------------------------------------------------------------------------------
+ * G trackers (the points of a sweep) on V videos whose frames are concatenated as above (N, offsets).  pred_dev f64 [G][N][4] and
+ * gt_dev f64 [N][4] hold x, y, w, h rows; frame 0 of a video is counted like any other (the tools write the annotation there).
+ * Per frame, in float64 with every operation rounded on its own:
+ *     iou  = max(min(1, intersect / union), 0), intersect = max(0, right - left) * max(0, bottom - top) with left / top the
+ *            maxima, right / bottom the minima of x + w / y + h, union = w1 h1 + w2 h2 - intersect; numpy's maximum / minimum:
+ *            0 / 0 stays NaN, and a NaN is above no threshold.  -1 where the annotation row does not have all four values > 0.
+ *     dist = sqrt(dx dx + dy dy) of the centres (x + w / 2, y + h / 2), correctly rounded.  -1 where the annotation's centre does
+ *            not have both values > 0 -- which is within EVERY threshold >= 0, as in success_error.
+ *   quantise != 0: the four predicted values are first replaced by what their "%.4f" row parses back to (as smk_vot_traj_overlap).
+ * counts_dev int32 [G][V][K1 + K2]: per (tracker, video) the number of its frames with iou > thr_overlap[k] (k < K1), then with
+ * dist <= thr_error[k] (k < K2) -- exact integers; success / precision are counts / T_v.  The thresholds are HOST arrays of f64,
+ * copied during the call (K1 in 1..32, K2 in 1..64).  iou_dev / dist_dev: f64 [G][N] each, or NULL (not written).
+ * One wave per (tracker, video), four per workgroup, no workspace.  No context; enqueue-only on `stream`, no host
+ * synchronisation, no allocation; bad arguments (a null or misaligned pointer, K1 / K2 / N / G / V outside their range, offsets
+ * that do not ascend from 0 to N) give SMK_E_ARG before anything is enqueued.  The device's copy of the offsets is clamped into
+ * the arrays, never followed outside. */
+int smk_ope_curve(const double *pred_dev, const double *gt_dev, const int32_t *offsets_dev, const int32_t *offsets_host, int N, int G,
+                  int V, const double *thr_overlap, int K1, const double *thr_error, int K2, int quantise, int32_t *counts_dev,
+                  double *iou_dev, double *dist_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

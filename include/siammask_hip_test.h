@@ -241,6 +241,11 @@ int smk_host_vot_traj_overlap(const int8_t *code, const double *poly, const doub
 int smk_host_eao_curve(const float *ov_eao, const int8_t *code, const int32_t *offsets, int N, int G, int V, int skipping, int low,
                        int high, float *curve, double *eao, int32_t *n_fragments, int32_t *frag_out, double *weight_out, int F_cap);
 
+/* Host only: smk_ope_curve on HOST memory -- the very inline functions the kernel compiles (csrc/ope_eval.h), one thread.
+ * Arguments as for smk_ope_curve with one (host) copy of the offsets; iou_out / dist_out may be NULL. */
+int smk_host_ope_curve(const double *pred, const double *gt, const int32_t *offsets, int N, int G, int V, const double *thr_overlap,
+                       int K1, const double *thr_error, int K2, int quantise, int32_t *counts, double *iou_out, double *dist_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,7 @@ SYMBOLS = (
     "smk_labels_rle_encode", "smk_vos_rle", "smk_vos_rle_dev",
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
+    "smk_ope_curve", "smk_host_ope_curve",
 )
 
 
@@ -200,6 +201,8 @@ def lib():
     L.smk_host_vot_quantise.argtypes = [vp, ci, vp]
     L.smk_host_vot_traj_overlap.argtypes = [vp] * 5 + [ci] * 5 + [vp, vp]
     L.smk_host_eao_curve.argtypes = [vp] * 3 + [ci] * 6 + [vp] * 5 + [ci]
+    L.smk_ope_curve.argtypes = [vp] * 4 + [ci] * 3 + [vp, ci, vp, ci, ci] + [vp] * 4
+    L.smk_host_ope_curve.argtypes = [vp] * 3 + [ci] * 3 + [vp, ci, vp, ci, ci] + [vp] * 3
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

@@ -1,7 +1,7 @@
 // stream_api.cpp -- the stateless product ABI either side of the network (include/siammask_hip.h): crop / paste / labels,
 // smk_mask_rbox, the tracker state on the device (smk_trk_*), VOS scoring, stream start, the VOT overlap and evaluation, the *_v
 // entries for streams with their own frame sizes -- argument checks and kernargs, one launch each -- and the smk_host_* entries that run the
-// device code's inline functions (tracker_state.h, vot_overlap.h, vot_eval.h) on the CPU for the bit-exact host tests.
+// device code's inline functions (tracker_state.h, vot_overlap.h, vot_eval.h, ope_eval.h) on the CPU for the bit-exact host tests.
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -11,6 +11,7 @@
 #include "tracker_state.h"
 #include "vot_overlap.h"
 #include "vot_eval.h"
+#include "ope_eval.h"
 
 using namespace smk;
 
@@ -813,6 +814,54 @@ int smk_host_eao_curve(const float *ov_eao, const int8_t *code, const int32_t *o
             if (weight_out) weight_out[(size_t)g * F_cap + f] = ws.weight[f];
         }
     }
+    return 0;
+}
+
+// ---- one-pass (OTB-style) success / precision counts (ope_eval.hip / ope_eval.h) ------------------------------
+static int ope_args(const char *who, const void *pred, const void *gt, const int32_t *offsets, int N, int G, int V,
+                    const double *thr_overlap, int K1, const double *thr_error, int K2, const void *counts) {
+    if (!pred || !gt || !offsets || !thr_overlap || !thr_error || !counts) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (K1 < 1 || K1 > OPE_MAX_K1 || K2 < 1 || K2 > OPE_MAX_K2)
+        return fail(SMK_E_ARG, "%s: %d overlap thresholds (1..%d), %d error thresholds (1..%d)", who, K1, OPE_MAX_K1, K2, OPE_MAX_K2);
+    int max_len = 0;
+    return eval_tables(who, offsets, nullptr, N, G, V, &max_len);
+}
+
+int smk_ope_curve(const double *pred_dev, const double *gt_dev, const int32_t *offsets_dev, const int32_t *offsets_host, int N, int G,
+                  int V, const double *thr_overlap, int K1, const double *thr_error, int K2, int quantise, int32_t *counts_dev,
+                  double *iou_dev, double *dist_dev, void *stream) {
+    if (!offsets_dev) return fail(SMK_E_ARG, "smk_ope_curve: null argument");
+    if (int rc = ope_args("smk_ope_curve", pred_dev, gt_dev, offsets_host, N, G, V, thr_overlap, K1, thr_error, K2, counts_dev)) return rc;
+    if ((uintptr_t)pred_dev % 8 || (uintptr_t)gt_dev % 8 || (uintptr_t)offsets_dev % 4 || (uintptr_t)counts_dev % 4 ||
+        (uintptr_t)iou_dev % 8 || (uintptr_t)dist_dev % 8)
+        return fail(SMK_E_ARG, "smk_ope_curve: misaligned argument");
+    OpeParams p;
+    memset(&p, 0, sizeof(p));
+    p.pred = pred_dev; p.gt = gt_dev; p.offsets = offsets_dev; p.counts = counts_dev; p.iou = iou_dev; p.dist = dist_dev;
+    p.N = N; p.G = G; p.V = V; p.K1 = K1; p.K2 = K2; p.quantise = quantise ? 1 : 0;
+    memcpy(p.thr_overlap, thr_overlap, sizeof(double) * K1);
+    memcpy(p.thr_error, thr_error, sizeof(double) * K2);
+    if (launch_ope_curve(p, stream)) return fail(SMK_E_HIP, "ope_curve launch failed");
+    return 0;
+}
+
+int smk_host_ope_curve(const double *pred, const double *gt, const int32_t *offsets, int N, int G, int V, const double *thr_overlap,
+                       int K1, const double *thr_error, int K2, int quantise, int32_t *counts, double *iou_out, double *dist_out) {
+    if (int rc = ope_args("smk_host_ope_curve", pred, gt, offsets, N, G, V, thr_overlap, K1, thr_error, K2, counts)) return rc;
+    for (int g = 0; g < G; ++g)
+        for (int v = 0; v < V; ++v) {
+            int32_t *row = counts + ((size_t)g * V + v) * (size_t)(K1 + K2);
+            for (int k = 0; k < K1 + K2; ++k) row[k] = 0;
+            for (int n = offsets[v]; n < offsets[v + 1]; ++n) {
+                const size_t at = (size_t)g * N + n;
+                double iou, dist;
+                ope_frame(gt + 4 * (size_t)n, pred + 4 * at, quantise ? 1 : 0, &iou, &dist);
+                if (iou_out) iou_out[at] = iou;
+                if (dist_out) dist_out[at] = dist;
+                for (int k = 0; k < K1; ++k) row[k] += iou > thr_overlap[k] ? 1 : 0;
+                for (int k = 0; k < K2; ++k) row[K1 + k] += dist <= thr_error[k] ? 1 : 0;
+            }
+        }
     return 0;
 }
 

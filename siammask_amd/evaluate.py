@@ -11,7 +11,18 @@ host (utils/pysot/evaluation/{eao,ar}_benchmark.py, utils/pysot/utils/statistics
 
 The per-frame overlaps (smk_vot_traj_overlap) and the expected-overlap curve (smk_eao_curve) are computed on the device, read
 back once; the accuracy / robustness scalars are finished here with the reference's own numpy calls on the device's overlaps, as
-vos.mean_iou finishes its meter.  Tags other than 'all', runs of 15 repetitions, OTB success / precision, F1 and plots stay out."""
+vos.mean_iou finishes its meter.  Tags other than 'all', runs of 15 repetitions, F1 and plots stay out.
+
+The one-pass (OTB / LaSOT / UAV123) protocol -- no overlap test, no re-initialisation, x,y,w,h rows -- is scored by success_overlap
+and success_error of utils/pysot/utils/statistics.py:
+
+    packed = evaluate.pack_ope([{'name': .., 'gt': [T,4], 'rect': [G,T,4]}, ...])
+    res = evaluate.ope(packed)                                         # one launch (smk_ope_curve), one read-back
+    res['success'] [G,V,21], res['precision'] [G,V,51], res['auc'] [G], res['precision_at'] [G] (at 20 pixels)
+
+    rect = evaluate.rects_from_lines(open('<video>.txt').read().split())            # an existing OTB result file
+
+Normalised precision, the 8-value rows a --mask run writes, plots and per-attribute tables stay out."""
 import ctypes
 
 import numpy as np
@@ -48,6 +59,17 @@ def from_lines(lines):
         else:
             raise ValueError("from_lines: row %d has %d values (a code 0 / 1 / 2, or 4 or 8 coordinates)" % (t, len(vals)))
     return code, poly
+
+
+def rects_from_lines(lines):
+    """the rows of an OTB result file (tools/test.py:407-413: x,y,w,h per frame, the first row the annotation) -> float64 [T,4]"""
+    rect = np.zeros((len(lines), 4), dtype=np.float64)
+    for t, line in enumerate(lines):
+        vals = [float(x) for x in line.strip().split(",")]
+        if len(vals) != 4:
+            raise ValueError("rects_from_lines: row %d has %d values, not x,y,w,h" % (t, len(vals)))
+        rect[t] = vals
+    return rect
 
 
 def pack(videos, device="cuda"):
@@ -177,4 +199,116 @@ def vot(packed, dataset=None, low=None, high=None, skipping=5, burnin=10, quanti
         a, b = int(packed["offsets"][v]), int(packed["offsets"][v + 1])
         out["videos"][name] = {"overlaps_ar": ov_ar[:, a:b], "overlaps_eao": ov_eao[:, a:b],
                                "failures": [np.nonzero(packed["code"][g, a:b] == 2)[0].tolist() for g in range(G)]}
+    return out
+
+
+# ---- the one-pass protocol: success / precision ---------------------------------------------------------------
+THR_OVERLAP = np.arange(0, 1.05, 0.05)      # success_overlap's thresholds (statistics.py:89)
+THR_ERROR = np.arange(0, 51, 1)             # the error thresholds of the OPE benchmark, in pixels
+MAX_K1, MAX_K2 = 32, 64                     # OPE_MAX_K1 / OPE_MAX_K2 of csrc/ope_eval.h
+
+
+def pack_ope(videos, device="cuda"):
+    """the videos concatenated along the frames -> dict: 'names', 'offsets' int32 [V+1], 'rect' float64 [G,N,4] (the G trackers'
+    x, y, w, h rows), 'gt' float64 [N,4] (numpy), and under 'dev' the same arrays as tensors on ``device`` (None: no upload -- for
+    the CPU test-suite only, see ope(host=True)).  Row 0 of a video is scored like any other: the tools write the annotation
+    there."""
+    videos = list(videos)
+    if not videos:
+        raise ValueError("pack_ope: at least one video")
+    names, rect, gt, G = [], [], [], None
+    for vid in videos:
+        g4 = np.asarray(vid["gt"], dtype=np.float64)
+        r = np.asarray(vid["rect"], dtype=np.float64)
+        if g4.ndim != 2 or g4.shape[1] != 4 or g4.shape[0] < 1:
+            raise ValueError("pack_ope: video %r: gt must be [T,4] rectangles (x, y, w, h), T >= 1" % (vid["name"],))
+        if r.ndim != 3 or r.shape[0] < 1 or r.shape[1:] != g4.shape:
+            raise ValueError("pack_ope: video %r: rect %s must be [G,T,4] with the T = %d frames of gt" % (vid["name"], r.shape, g4.shape[0]))
+        if G is not None and r.shape[0] != G:
+            raise ValueError("pack_ope: video %r has %d trackers, the videos before it %d" % (vid["name"], r.shape[0], G))
+        if not np.isfinite(r).all():
+            raise ValueError("pack_ope: video %r: a predicted value is not finite" % (vid["name"],))
+        G = r.shape[0]
+        names.append(vid["name"])
+        rect.append(r)
+        gt.append(g4)
+    lens = [g.shape[0] for g in gt]
+    out = {"names": names, "offsets": np.concatenate([[0], np.cumsum(lens)]).astype(np.int32),
+           "rect": np.ascontiguousarray(np.concatenate(rect, axis=1)), "gt": np.ascontiguousarray(np.concatenate(gt, axis=0)), "dev": None}
+    if device is not None:
+        import torch
+        out["dev"] = {k: torch.from_numpy(out[k]).to(device) for k in ("rect", "gt", "offsets")}
+    return out
+
+
+def _ope_host(packed, G, N, V, t1, t2, quantise, per_frame):
+    K = t1.size + t2.size
+    counts = np.empty((G, V, K), dtype=np.int32)
+    frames = np.empty((2, G, N), dtype=np.float64) if per_frame else None
+    _lib.check(_lib.lib().smk_host_ope_curve(_ptr(packed["rect"]), _ptr(packed["gt"]), _ptr(packed["offsets"]), N, G, V, _ptr(t1), t1.size,
+                                             _ptr(t2), t2.size, int(bool(quantise)), _ptr(counts),
+                                             _ptr(frames[0]) if per_frame else None, _ptr(frames[1]) if per_frame else None))
+    return counts, frames
+
+
+def _ope_device(packed, G, N, V, t1, t2, quantise, per_frame):
+    import torch
+    dev = packed["dev"]
+    if dev is None:
+        raise ValueError("evaluate.ope: pack_ope(..., device=None) has nothing on the device")
+    where = dev["rect"].device
+    K = t1.size + t2.size
+    # one block for the counts (as float64 words: [G*V*K] int32 padded to 8 bytes) and the per-frame values: one copy back
+    words = (G * V * K + 1) // 2
+    block = torch.empty(words + (2 * G * N if per_frame else 0), dtype=torch.float64, device=where)
+    counts = block[:words].view(torch.int32)[:G * V * K]
+    iou = block[words:words + G * N] if per_frame else None
+    dist = block[words + G * N:] if per_frame else None
+    with torch.cuda.device(where):
+        _lib.check(_lib.lib().smk_ope_curve(dev["rect"].data_ptr(), dev["gt"].data_ptr(), dev["offsets"].data_ptr(), _ptr(packed["offsets"]),
+                                            N, G, V, _ptr(t1), t1.size, _ptr(t2), t2.size, int(bool(quantise)), counts.data_ptr(),
+                                            iou.data_ptr() if per_frame else None, dist.data_ptr() if per_frame else None,
+                                            _lib.current_stream_ptr()))
+        host = torch.empty(block.shape, dtype=block.dtype, pin_memory=True)
+        host.copy_(block, non_blocking=True)
+        torch.cuda.current_stream().synchronize()                      # the one synchronisation
+    h = host.numpy()
+    frames = h[words:].reshape(2, G, N).copy() if per_frame else None
+    return h[:words].view(np.int32)[:G * V * K].reshape(G, V, K).copy(), frames
+
+
+def ope(packed, thr_overlap=THR_OVERLAP, thr_error=THR_ERROR, quantise=False, host=False, per_frame=False):
+    """success / precision of the G trackers of pack_ope()'s output, as success_overlap / success_error score the result files of
+    a one-pass run.  thr_overlap (at most 32, `iou > thr`) and thr_error (at most 64, `dist <= thr`) are float64 tables.
+    quantise: score what the "%.4f" rows tools/tune_vot.py writes would hold, False: the rectangles as given (tools/test.py writes
+    str(value), which parses back to the same double).  host=True is a TEST AID, not a product path and not a fallback: it
+    runs the same inline functions through the library's host-only entry (include/siammask_hip_test.h) on one CPU thread so that
+    the CPU test-suite can hold this module's packing and host arithmetic against the fixture; nothing selects it but the caller.
+    -> dict: 'success' float64 [G,V,K1] and 'precision' float64 [G,V,K2] (counts / T_v), 'auc' [G] (the mean over the videos of
+    the mean success curve), 'precision_at' [G] (the mean over the videos of the precision at 20 pixels; NaN when 20 is not among
+    thr_error), 'counts' int32 [G,V,K1+K2], 'thr_overlap', 'thr_error', 'videos': {name: {'success' [G,K1], 'precision' [G,K2],
+    'frames' T_v}} and, with per_frame, 'iou' / 'dist' float64 [G,N] (-1 where the reference masks the frame; in 'videos' cut
+    to [G,T_v])."""
+    t1 = np.ascontiguousarray(np.asarray(thr_overlap, dtype=np.float64).reshape(-1))
+    t2 = np.ascontiguousarray(np.asarray(thr_error, dtype=np.float64).reshape(-1))
+    if not 1 <= t1.size <= MAX_K1 or not 1 <= t2.size <= MAX_K2:
+        raise ValueError("evaluate.ope: 1..%d overlap thresholds and 1..%d error thresholds" % (MAX_K1, MAX_K2))
+    G, N = packed["rect"].shape[:2]
+    V = len(packed["names"])
+    run = _ope_host if host else _ope_device
+    counts, frames = run(packed, G, N, V, t1, t2, quantise, bool(per_frame))
+    lens = np.diff(packed["offsets"]).astype(np.int64)
+    success = counts[:, :, :t1.size] / lens[None, :, None].astype(np.float64)
+    precision = counts[:, :, t1.size:] / lens[None, :, None].astype(np.float64)
+    at = np.nonzero(t2 == 20.0)[0]
+    out = {"success": success, "precision": precision, "auc": success.mean(axis=2).mean(axis=1),
+           "precision_at": precision[:, :, at[0]].mean(axis=1) if at.size else np.full(G, np.nan),
+           "counts": counts, "thr_overlap": t1, "thr_error": t2, "videos": {}}
+    if per_frame:
+        out["iou"], out["dist"] = frames[0], frames[1]
+    for v, name in enumerate(packed["names"]):
+        a, b = int(packed["offsets"][v]), int(packed["offsets"][v + 1])
+        out["videos"][name] = {"success": success[:, v], "precision": precision[:, v], "frames": b - a}
+        if per_frame:
+            out["videos"][name].update(iou=frames[0][:, a:b], dist=frames[1][:, a:b])
     return out

@@ -19,6 +19,14 @@ mask reaches memory -- and the host finishes the meter (vos.iou_meter):
     out[i]['iou'], out[i]['line']                                     # IouMeter.value('mean') [11]; the line of <video>.txt (:140)
     tune.result_dir('Custom_x', points[i], refine=True)               # tune_vos.py:71-75
 
+On a dataset that is not VOT both tools track every video in ONE pass -- no overlap test, no re-initialisation -- and write one
+x,y,w,h row per frame, the first being the annotation (OTB, LaSOT, UAV123):
+
+    out = tune.sweep_ope(tr, frames, gt, points)                      # gt float64 [T,4]
+    out[i]['rect'], out[i]['lines']                                   # [T,4]; the rows of <video>.txt ('%.4f' or str())
+    table = tune.eval_ope({'video': out, ...})                        # success / precision per point on the device (evaluate.ope)
+    table['auc'], table['precision_at'], table['best']
+
 The tools' result trees on disk, their finish.flag / 'Occ' protocols, the shuffles and the --search-region (instance_size) axis
 are the caller's."""
 import numpy as np
@@ -115,6 +123,96 @@ def eval_vot(sweeps, sizes, dataset=None, **kw):
     out = evaluate.vot(packed, dataset=dataset, **kw)
     out["hp"] = [p["hp"] for p in sweeps[names[0]]]
     out["best"] = int(np.argmax(np.where(np.isnan(out["eao"]), -np.inf, out["eao"])))
+    return out
+
+
+def _first_box(gt):
+    """(cx, cy, w, h) of the annotation of frame 0 as the tools initialise from it (get_axis_aligned_bbox, bbox_helper.py:52-74):
+    a 4-value row x, y, w, h gives (x + w / 2, y + h / 2, w, h), an 8-value row goes through vot.axis_aligned_bbox"""
+    if gt.shape[1] == 8:
+        return tuple(float(v) for v in vot.axis_aligned_bbox(gt[0]))
+    x, y, w, h = (np.float64(v) for v in gt[0])
+    return float(x + w / 2), float(y + h / 2), float(w), float(h)
+
+
+def ope_lines(rect, fmt="%.4f"):
+    """the rows of <video>.txt for the [T,4] rectangles of a one-pass run.  fmt '%.4f': tools/tune_vot.py:166, every value through
+    vot_float2str("%.4f", .) (narrowed to float32 first); 'str': tools/test.py:413, str(value) of the float64"""
+    if fmt not in ("%.4f", "str"):
+        raise ValueError("ope_lines: fmt is '%.4f' (tune_vot.py) or 'str' (test.py)")
+    one = vot.format_value if fmt == "%.4f" else (lambda v: str(np.float64(v)))
+    return [",".join(one(v) for v in row) for row in np.asarray(rect, dtype=np.float64).reshape(-1, 4)]
+
+
+def sweep_ope(tracker, frames, gt, points, fmt="%.4f"):
+    """the unsupervised loop of the tools on a dataset that is not VOT (tools/tune_vot.py:94-111,136-137; tools/test.py:333,355-359:
+    OTB, LaSOT, UAV123 ...) over ONE video at every point of ``points`` (as for sweep_vot) on a tracker that is reserved
+    (reserve(B, H, W)) and has no chunk open: one pass over the frames, no overlap test, no re-initialisation.  frames: uint8 CUDA
+    [T,H,W,3]; gt: float64 [T,4] rows x, y, w, h, of which only row 0 is used here ([T,8] corner rows are taken as well: row 0
+    through get_axis_aligned_bbox, and row 0 of the result is then that box as a rectangle -- the tools would write the eight
+    values).  Each pass is set_hp(B points) + start(frames[0], every stream, pos=, sz=) + run(frames[1:], want_mask=False): the
+    box of a frame does not depend on the mask branch, and no mask is computed.
+    -> one dict per point: 'hp' (the point), 'rect' float64 [T,4] (row 0 is gt[0], row t is cxy_wh_2_rect(target_pos[t],
+    target_sz[t]) = (cx - w / 2, cy - h / 2, w, h)), 'score' float64 [T] (NaN on frame 0, which is not tracked), 'lines' (the rows
+    of <video>.txt in ``fmt``, see ope_lines) and 'gt' (the annotation as given, one array shared by the points; eval_ope takes
+    both).  The tracker's hp state (its table or none) is put back on exit."""
+    points = [dict(p) for p in points]
+    if not points or any(set(p) - set(HP_KEYS) for p in points):
+        raise ValueError("sweep_ope: at least one point, keys among %s" % (HP_KEYS,))
+    if fmt not in ("%.4f", "str"):
+        raise ValueError("sweep_ope: fmt is '%.4f' (tune_vot.py) or 'str' (test.py)")
+    if getattr(frames, "ndim", 0) != 4 or frames.shape[0] < 1:
+        raise ValueError("sweep_ope: frames must be [T,H,W,3] with T >= 1")
+    T = int(frames.shape[0])
+    gt = np.asarray(gt, dtype=np.float64)
+    if gt.ndim != 2 or gt.shape[1] not in (4, 8) or gt.shape[0] < 1:
+        raise ValueError("sweep_ope: gt must be [T,4] rectangles (or [T,8] corners), at least row 0")
+    if tracker.state is None or tracker._fr is None:
+        raise RuntimeError("sweep_ope: reserve() the tracker first")
+    B = tracker._fr.B
+    cx, cy, w, h = _first_box(gt)
+    pos, sz = np.tile([cx, cy], (B, 1)), np.tile([w, h], (B, 1))
+    row0 = gt[0] if gt.shape[1] == 4 else np.array([cx - w / 2, cy - h / 2, w, h])
+    before = tracker.get_hp()
+    out = []
+    try:
+        for idx, keep in pass_plan(len(points), B):
+            tracker.set_hp([points[i] for i in idx])
+            tracker.start(frames[0], list(range(B)), pos=pos, sz=sz)
+            res = tracker.run(frames[1:], want_mask=False)
+            for b in range(keep):
+                p, s = np.asarray(res["target_pos"], dtype=np.float64)[:, b], np.asarray(res["target_sz"], dtype=np.float64)[:, b]
+                rect = np.empty((T, 4), dtype=np.float64)
+                rect[0] = row0
+                rect[1:] = np.stack([p[:, 0] - s[:, 0] / 2, p[:, 1] - s[:, 1] / 2, s[:, 0], s[:, 1]], axis=1).reshape(T - 1, 4)
+                score = np.concatenate([[np.nan], np.asarray(res["score"], dtype=np.float64)[:, b]])
+                out.append({"hp": points[idx[b]], "rect": rect, "score": score, "lines": ope_lines(rect, fmt), "gt": gt})
+    finally:
+        if not tracker._chunk_open():                                 # (a failed pass may have left one: the caller collects)
+            tracker.set_hp(before)
+    return out
+
+
+def eval_ope(sweeps, **kw):
+    """rank a one-pass sweep by the success / precision scores of the result files, without a file: sweeps: {video: what sweep_ope
+    returned for it} with the same points for every video.  The annotation of a video is the 'gt' its sweep carries ([T,4]).  The
+    keywords (thr_overlap=, thr_error=, quantise=, host=, per_frame=) are evaluate.ope's.
+    -> evaluate.ope's table over the points (one launch, one read-back) plus 'hp' (the points) and 'best' (the index of the
+    largest AUC; a NaN AUC ranks last)."""
+    names = list(sweeps)
+    if not names:
+        raise ValueError("eval_ope: at least one video")
+    G = len(sweeps[names[0]])
+    for name in names:
+        if len(sweeps[name]) != G or [p["hp"] for p in sweeps[name]] != [p["hp"] for p in sweeps[names[0]]]:
+            raise ValueError("eval_ope: video %r was swept over other points than %r" % (name, names[0]))
+    if G < 1:
+        raise ValueError("eval_ope: at least one point")
+    packed = evaluate.pack_ope([{"name": name, "gt": sweeps[name][0]["gt"], "rect": np.stack([p["rect"] for p in sweeps[name]])}
+                                for name in names], device=None if kw.get("host") else "cuda")
+    out = evaluate.ope(packed, **kw)
+    out["hp"] = [p["hp"] for p in sweeps[names[0]]]
+    out["best"] = int(np.argmax(np.where(np.isnan(out["auc"]), -np.inf, out["auc"])))
     return out
 
 
