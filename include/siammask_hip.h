@@ -359,6 +359,32 @@ int smk_paste_rle_dev(const float *logits_dev, const float *head_dev, int score_
                       int slot, int B, int W, int H, float seg_thr, float border, int cap, void *ws_dev, size_t ws_bytes,
                       uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
 
+/* ---- run-length codes with a size per stream (additive; smk_version() keeps reporting 1.10, the presence of these symbols is the
+ * probe) -------------------------------------------------------------------------------------------------------------------------
+ * The two entries above for the B (1..32) streams of a mixed-size batch (the smk_*_v entries below): canvas_w x canvas_h, both in
+ * 1..4096, is the canvas of smk_paste_mask_dev_v.  Stream b's pixels are numbered column-major with ITS OWN height, j = x * h_b + y,
+ * a_b = h_b * w_b, and its code is that of smk_rle_encode on the h_b x w_b mask.
+ * smk_paste_rle_dev_v: (w_b, h_b) are im_w / im_h of stream b's record in the state block, clamped to the canvas -- what
+ * smk_paste_mask_dev_v reads -- so the bits are those of the bytes it writes into [0:h_b, 0:w_b] of plane b for the same arguments,
+ * and no mask byte reaches memory.  im_wh_host (may be NULL; [B][2] = (w, h), what the caller believes the records hold) is only
+ * checked: a size larger than the canvas is SMK_E_ARG.
+ * smk_rle_encode_v: canvas_dev is [B][canvas_h][canvas_w] (row pitch canvas_w), only [0:h_b, 0:w_b] of plane b is read, and
+ * (w_b, h_b) = im_wh_host[b] (required, each in 1..the canvas's) travel in the kernel arguments: no device table.
+ * live_mask: bit b clear = stream b has no frame this step: nothing of it is computed, no count of row b is written, and its meta
+ * row is (0, 0, h_b, w_b) -- m = 0 is "no code", a real code has m >= 1.  Bits at or above B select nothing.
+ * Outputs as above: counts_out_dev uint32 [B][cap], meta_out_dev int32 [B][4] = (m, area, h_b, w_b), m always the true number of
+ * counts, only counts[b][0 .. min(m, cap) - 1] written, no atomics, nothing needs zeroing, a second call gives the same bytes.
+ * cap in 1..canvas_w * canvas_h + 1 (a stream whose a_b + 1 is below cap never reaches it).  ws_dev: smk_rle_workspace(B, canvas_w,
+ * canvas_h); stream b owns the stride ceil(canvas_w * canvas_h / 64) words and uses its first ceil(a_b / 64); the words past those are
+ * neither written nor read.  Bad arguments give SMK_E_ARG before anything is enqueued.  No context; asynchronous on `stream`, no
+ * host synchronisation. */
+int smk_paste_rle_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                        int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask, float seg_thr,
+                        float border, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev,
+                        void *stream);
+int smk_rle_encode_v(const uint8_t *canvas_dev, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask,
+                     int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+
 /* ---- the fused label map of a VOS frame as per-object COCO run-length codes (tools/test.py:521-523 + rleEncode; additive;
  * smk_version() keeps reporting 1.10, the presence of these symbols is the probe) ------------------------------------------------
  * The n_obj (1..32) objects of one W x H frame.  LABEL: label(x, y) = best > seg_thr ? arg + 1 : 0 with best / arg the maximum and

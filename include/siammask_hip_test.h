@@ -230,6 +230,12 @@ int smk_test_mask_rbox_paths(const void *ws_dev, int B, int W, int H, int mode, 
 int smk_test_rle_encode(const uint8_t *mask_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes,
                         uint32_t *counts_out_dev, int32_t *meta_out_dev, int form, void *stream);
 
+/* smk_rle_encode_v with the byte source chosen, as smk_test_rle_encode: form 1 = the tile through LDS (what smk_rle_encode_v
+ * launches), 0 = one byte per lane at stride canvas_w.  A form outside 0..1: SMK_E_ARG. */
+int smk_test_rle_encode_v(const uint8_t *canvas_dev, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask,
+                          int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, int form,
+                          void *stream);
+
 /* Host only: the VOT evaluation on HOST memory -- the very inline functions the kernels compile (csrc/vot_eval.h), one thread.
  * Arguments as for smk_vot_traj_overlap / smk_eao_curve with one (host) copy of the tables and no workspace.
  * smk_host_vot_quantise: out[i] = the value the "%.4f" line of x[i] parses back to.

@@ -41,6 +41,7 @@ SYMBOLS = (
     "smk_iou_score", "smk_iou_score_dev",
     "smk_mask_rbox_workspace_ex", "smk_mask_rbox_ex", "smk_test_mask_rbox_paths",
     "smk_rle_workspace", "smk_rle_encode", "smk_paste_rle_dev", "smk_test_rle_encode",
+    "smk_paste_rle_dev_v", "smk_rle_encode_v", "smk_test_rle_encode_v",
     "smk_labels_rle_encode", "smk_vos_rle", "smk_vos_rle_dev",
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
@@ -191,6 +192,9 @@ def lib():
     L.smk_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_test_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, ci, vp]
     L.smk_paste_rle_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, cf, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_rle_encode_v.argtypes = [vp, ci, ci, ci, vp, u32, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_test_rle_encode_v.argtypes = [vp, ci, ci, ci, vp, u32, ci, vp, ctypes.c_size_t, vp, vp, ci, vp]
+    L.smk_paste_rle_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, vp, u32, cf, cf, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_labels_rle_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, vp]
     rle_tail = [u32, vp, ci, vp, ctypes.c_size_t, vp, vp, vp]        # given_mask, init labels, cap, workspace, its bytes, outputs, stream
     L.smk_vos_rle.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, u32, cf] + rle_tail

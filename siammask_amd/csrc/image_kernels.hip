@@ -653,6 +653,163 @@ int launch_rle(const RleParams &p, int B, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- run-length codes with a size per stream (smk_rle_encode_v / smk_paste_rle_dev_v) ------------------------------------------------
+// Written-out twins of the three kernels above (they keep their machine code).  p.W x p.H is the CANVAS: it sizes the grids, the
+// byte source's planes and the workspace stride rle_words(p.W, p.H) of a stream.  Stream b's own (W, H) -- im_w / im_h of its
+// record clamped to the canvas (FUSED, what paste_mask_dev_v_kernel reads), or p.wh[b] of the kernarg (byte source) -- give its
+// numbering j = x * H + y, a, nw and tail; it uses the first rle_words(W, H) words of its stride.  Every exit is wave-uniform and
+// stands before the ballots: a clear live bit (the block), k >= nw (the wave), x0 >= W (the tile block).
+template <bool FUSED>
+__device__ __forceinline__ void rle_v_size(const RleVParams &p, int b, int &W, int &H) {
+    if constexpr (FUSED) {
+        const smk_trk_stream *s = p.paste.st + b;
+        W = __builtin_amdgcn_readfirstlane(min(max(s->im_w, 0), p.W));
+        H = __builtin_amdgcn_readfirstlane(min(max(s->im_h, 0), p.H));
+    } else {
+        W = p.wh[b][0]; H = p.wh[b][1];
+    }
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(256) void rle_bits_v_kernel(const RleVParams p) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    if (!((p.live >> b) & 1)) return;
+    int W, H;
+    rle_v_size<FUSED>(p, b, W, H);
+    const int a = W * H, nw = (int)rle_words(W, H);
+    const int k = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), j = k * 64 + lane;
+    if (k >= nw) return;
+    bool bit = false;
+    if (j < a) {
+        const int x = j / H, y = j - x * H;
+        if constexpr (FUSED) {
+            const PasteDevParams &q = p.paste;
+            const smk_trk_stream *s = q.st + b;
+            const float *lg = q.logits + (size_t)b * q.ms * q.ms;
+            int ls = 1;
+            if (q.head_S) {
+                ls = q.head_S * q.head_S;
+                const int dy = min(max(s->delta_yx[q.slot][0], 0), q.head_S - 1), dx = min(max(s->delta_yx[q.slot][1], 0), q.head_S - 1);
+                lg = q.logits + (size_t)b * q.ms * q.ms * ls + dy * q.head_S + dx;
+            }
+            bit = warped_prob(q, s->inv_map[q.slot], lg, ls, x, y) > q.seg_thr;
+        } else {
+            bit = p.mask[((size_t)b * p.H + y) * p.W + x] != 0;
+        }
+    }
+    const unsigned long long w = __ballot(bit);
+    if (lane == 0) p.words[(size_t)b * rle_words(p.W, p.H) + k] = w;
+}
+
+__global__ __launch_bounds__(1024) void rle_bits_tile_v_kernel(const RleVParams p) {
+    __shared__ unsigned long long rows[RLE_MAX_SIDE];
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!((p.live >> b) & 1)) return;
+    const int W = p.wh[b][0], H = p.wh[b][1], x0 = blockIdx.x * 64;
+    if (x0 >= W) return;
+    const int nc = min(64, W - x0);
+    const unsigned char *m = p.mask + (size_t)b * p.W * p.H + x0;
+    for (int y = wave; y < H; y += 16) {
+        const bool bit = lane < nc && m[(size_t)y * p.W + lane] != 0;
+        const unsigned long long r = __ballot(bit);
+        if (lane == 0) rows[y] = r;
+    }
+    __syncthreads();
+    const int nbits = nc * H, nloc = (nbits + 63) / 64;
+    unsigned long long *words = p.words + (size_t)b * rle_words(p.W, p.H) + (size_t)blockIdx.x * H;
+    for (int k = wave; k < nloc; k += 16) {
+        const int jl = 64 * k + lane;
+        bool bit = false;
+        if (jl < nbits) {
+            const int xl = jl / H, y = jl - xl * H;
+            bit = (rows[y] >> xl) & 1;
+        }
+        const unsigned long long w = __ballot(bit);
+        if (lane == 0) words[k] = w;
+    }
+}
+
+// a stream that is not live gets the meta row (0, 0, H, W) -- a real code has m >= 1 -- and no count
+template <bool FUSED>
+__global__ __launch_bounds__(1024) void rle_scan_v_kernel(const RleVParams p) {
+    __shared__ int s_sum[16], s_max[16], s_area[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    int W, H;
+    rle_v_size<FUSED>(p, b, W, H);
+    int *meta = p.meta + 4 * b;
+    if (!((p.live >> b) & 1)) {
+        if (tid == 0) { meta[0] = 0; meta[1] = 0; meta[2] = H; meta[3] = W; }
+        return;
+    }
+    const int a = W * H, nw = (int)rle_words(W, H), tail = a & 63;
+    const unsigned long long *words = p.words + (size_t)b * rle_words(p.W, p.H);
+    unsigned *out = p.counts + (size_t)b * p.cap;
+    int n_tr = 0, last = 0, area = 0;
+    for (int k0 = 0; k0 < nw; k0 += 1024) {
+        const int k = k0 + tid;
+        unsigned long long w = 0, t = 0;
+        if (k < nw) {
+            w = words[k];
+            t = w ^ ((w << 1) | (k ? words[k - 1] >> 63 : 0ull));
+            if (k == nw - 1 && tail) t &= (1ull << tail) - 1;
+        }
+        area += __popcll(w);
+        const int c = __popcll(t);
+        int s = c, m = t ? 64 * k + 63 - __clzll((long long)t) : 0;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int s2 = __shfl_up(s, d), m2 = __shfl_up(m, d);
+            if (lane >= d) { s += s2; m = max(m, m2); }
+        }
+        if (lane == 63) { s_sum[wave] = s; s_max[wave] = m; }
+        __syncthreads();
+        int o = n_tr + s - c, prev = last, tot = 0, tmax = 0;
+        for (int v = 0; v < 16; ++v) {
+            const int sv = s_sum[v], mv = s_max[v];
+            if (v < wave) { o += sv; prev = max(prev, mv); }
+            tot += sv;
+            tmax = max(tmax, mv);
+        }
+        const int mp = __shfl_up(m, 1);
+        if (lane) prev = max(prev, mp);
+        while (t) {
+            const int pos = 64 * k + __ffsll((long long)t) - 1;
+            if (o < p.cap) out[o] = (unsigned)(pos - prev);
+            prev = pos;
+            ++o;
+            t &= t - 1;
+        }
+        n_tr += tot;
+        last = max(last, tmax);
+        __syncthreads();
+    }
+    for (int d = 32; d; d >>= 1) area += __shfl_down(area, d);
+    if (lane == 0) s_area[wave] = area;
+    __syncthreads();
+    if (tid == 0) {
+        int set = 0;
+        for (int v = 0; v < 16; ++v) set += s_area[v];
+        if (n_tr < p.cap) out[n_tr] = (unsigned)(a - last);
+        meta[0] = n_tr + 1; meta[1] = set; meta[2] = H; meta[3] = W;
+    }
+}
+
+int launch_rle_v(const RleVParams &p, int B, void *stream) {
+    if (B < 1 || B > TRK_SET_MAX_B || p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || p.cap < 1 || p.cap > p.W * p.H + 1) return -1;
+    if (!p.words || !p.counts || !p.meta || (!p.mask && (!p.paste.logits || !p.paste.st))) return -1;
+    if (p.mask)
+        for (int b = 0; b < B; ++b)
+            if (p.wh[b][0] < 1 || p.wh[b][1] < 1 || p.wh[b][0] > p.W || p.wh[b][1] > p.H) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 lanes((unsigned)((rle_words(p.W, p.H) + 3) / 4), B);
+    if (!p.mask)     hipLaunchKernelGGL((rle_bits_v_kernel<true>), lanes, dim3(256), 0, s, p);
+    else if (p.tile) hipLaunchKernelGGL(rle_bits_tile_v_kernel, dim3((p.W + 63) / 64, B), dim3(1024), 0, s, p);
+    else             hipLaunchKernelGGL((rle_bits_v_kernel<false>), lanes, dim3(256), 0, s, p);
+    if (hipGetLastError() != hipSuccess) return -4;
+    if (!p.mask) hipLaunchKernelGGL((rle_scan_v_kernel<true>), dim3(B), dim3(1024), 0, s, p);
+    else         hipLaunchKernelGGL((rle_scan_v_kernel<false>), dim3(B), dim3(1024), 0, s, p);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 // ---- the fused label map of a VOS frame as O bit planes (smk_vos_rle / smk_vos_rle_dev) -----------------------------------------------
 // One lane per column-major pixel j, as rle_bits_kernel.  The lane computes the label vos_score_kernel writes -- the same loop over
 // the objects (prob_o from the init labels, warped_prob or -1; strict > upwards keeps the first maximum; the float32 comparison

@@ -981,6 +981,72 @@ int smk_paste_mask_dev_v(const float *logits_dev, const float *head_dev, int sco
     return 0;
 }
 
+// ---- run-length codes with a size per stream -----------------------------------------------------------------
+// the checks and the fields both entries share on top of rle_fill (W x H is the canvas there); im_wh_host is [B][2] = (w, h)
+static int rle_fill_v(const char *who, RleVParams &v, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, bool need_wh,
+                      uint32_t live_mask, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev) {
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d streams (1..%d)", who, B, TRK_SET_MAX_B);
+    if (need_wh && !im_wh_host) return fail(SMK_E_ARG, "%s: null argument", who);
+    RleParams p;
+    CHK(rle_fill(who, p, B, canvas_w, canvas_h, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    memset(&v, 0, sizeof(v));                                         // (bits of live_mask at or above B select nothing)
+    if (im_wh_host)
+        for (int b = 0; b < B; ++b) {
+            const int w = im_wh_host[2 * b], h = im_wh_host[2 * b + 1];
+            if (w > canvas_w || h > canvas_h || (need_wh && (w < 1 || h < 1)))
+                return fail(SMK_E_ARG, "%s: stream %d is %d x %d, the canvas %d x %d", who, b, w, h, canvas_w, canvas_h);
+            v.wh[b][0] = w; v.wh[b][1] = h;
+        }
+    v.words = p.words; v.counts = p.counts; v.meta = p.meta;
+    v.W = canvas_w; v.H = canvas_h; v.cap = cap; v.tile = 1; v.live = live_mask;
+    return 0;
+}
+
+int smk_rle_encode_v(const uint8_t *canvas_dev, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask,
+                     int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!canvas_dev) return fail(SMK_E_ARG, "smk_rle_encode_v: null argument");
+    RleVParams p;
+    CHK(rle_fill_v("smk_rle_encode_v", p, B, canvas_w, canvas_h, im_wh_host, true, live_mask, cap, ws_dev, ws_bytes, counts_out_dev,
+                   meta_out_dev));
+    p.mask = canvas_dev;
+    if (launch_rle_v(p, B, stream)) return fail(SMK_E_HIP, "rle_encode_v launch failed");
+    return 0;
+}
+
+// include/siammask_hip_test.h: smk_rle_encode_v with the byte source chosen, as smk_test_rle_encode
+int smk_test_rle_encode_v(const uint8_t *canvas_dev, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask,
+                          int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, int form,
+                          void *stream) {
+    if (!canvas_dev || (form != 0 && form != 1))
+        return fail(SMK_E_ARG, "smk_test_rle_encode_v: null argument or form %d (0 or 1)", form);
+    RleVParams p;
+    CHK(rle_fill_v("smk_test_rle_encode_v", p, B, canvas_w, canvas_h, im_wh_host, true, live_mask, cap, ws_dev, ws_bytes,
+                   counts_out_dev, meta_out_dev));
+    p.mask = canvas_dev;
+    p.tile = form;
+    if (launch_rle_v(p, B, stream)) return fail(SMK_E_HIP, "rle_encode_v launch failed");
+    return 0;
+}
+
+int smk_paste_rle_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev,
+                        int slot, int B, int canvas_w, int canvas_h, const int32_t *im_wh_host, uint32_t live_mask, float seg_thr,
+                        float border, int cap, void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev,
+                        void *stream) {
+    if ((!logits_dev && !head_dev) || !state_dev) return fail(SMK_E_ARG, "smk_paste_rle_dev_v: null argument");
+    if (mask_size < 1 || (head_dev && (score_size < 1 || score_size > 1024))) return fail(SMK_E_ARG, "smk_paste_rle_dev_v: bad geometry");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_paste_rle_dev_v: slot %d (0 or 1)", slot);
+    RleVParams p;
+    CHK(rle_fill_v("smk_paste_rle_dev_v", p, B, canvas_w, canvas_h, im_wh_host, false, live_mask, cap, ws_dev, ws_bytes,
+                   counts_out_dev, meta_out_dev));
+    PasteDevParams &q = p.paste;
+    q.logits = head_dev ? head_dev : logits_dev;
+    q.ms = mask_size; q.W = canvas_w; q.H = canvas_h; q.head_S = head_dev ? score_size : 0; q.slot = slot;
+    q.seg_thr = seg_thr; q.border = border;
+    q.st = (const smk_trk_stream *)state_dev;
+    if (launch_rle_v(p, B, stream)) return fail(SMK_E_HIP, "paste_rle_dev_v launch failed");
+    return 0;
+}
+
 int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
                         const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
     if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");

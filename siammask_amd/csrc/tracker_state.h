@@ -326,6 +326,22 @@ struct CropVParams {                // smk_crop_resize_dev_v (win == nullptr) an
 int launch_crop_v(const CropVParams &p, int B, void *stream);
 // the canvas form of launch_paste_mask_dev: p.W x p.H is the canvas, each stream's size comes from its record; prob_out unused
 int launch_paste_mask_dev_v(const PasteDevParams &p, int B, void *stream);
+// smk_rle_encode_v / smk_paste_rle_dev_v: launch_rle with a size per stream.  W x H is the CANVAS (the byte source's planes and the
+// workspace stride rle_words(W, H) of a stream); stream b is numbered j = x * h_b + y with (w_b, h_b) = wh[b] (byte source, checked
+// against the canvas by the launcher) or im_w / im_h of its record clamped to the canvas (fused source).  Bit b of live clear:
+// nothing of stream b is computed, its meta row is (0, 0, h_b, w_b)
+struct RleVParams {
+    const unsigned char *mask;      // the canvas [B][H][W] smk_paste_mask_dev_v writes, or nullptr: the fused source `paste`
+    unsigned long long *words;      // workspace
+    unsigned *counts;               // [B][cap]
+    int *meta;                      // [B][4] = (m, area, h_b, w_b)
+    int W, H, cap;
+    int tile;                       // byte source: as RleParams
+    unsigned live;
+    PasteDevParams paste;           // mask_out / prob_out / W / H unused
+    int wh[TRK_SET_MAX_B][2];
+};
+int launch_rle_v(const RleVParams &p, int B, void *stream);
 struct FrameSumsVParams {
     smk_image_ref im[TRK_SET_MAX_B];
     unsigned long long *sums;       // [n][3]

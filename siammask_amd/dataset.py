@@ -1,0 +1,229 @@
+"""A dataset of videos through the B slots of one free-running tracker: V videos of different resolutions and
+lengths, every slot handed to the next video the moment its own ends, the masks as run-length codes at each video's own size.
+
+    res = dataset.run_videos(tr, videos, pos, sz)               # videos[v]: len() and [t] -> uint8 CUDA [h_v,w_v,3]
+    res['steps'], res['efficiency']                             # batch steps launched, tracked frames / (steps * B)
+    d = res['videos'][v]                                        # in the caller's order
+    d['target_pos'], d['target_sz'], d['score'], d['best_id']   # [T_v - 1, ...]: frames 1 .. T_v - 1 (frame 0 initialises)
+    rle.to_coco(d['rle'][t], *d['size'])                        # the mask of frame t + 1 (None where d['n'][t] > cap)
+    evaluate.ope(evaluate.pack_ope([dataset.ope_video(d, gt_v, name) for ...]))
+
+plan() is the scheduler alone, pure numpy: which (video, frame) every slot tracks at every step.  The rule: the first min(B, V)
+videos (in the given order, or stably sorted by descending length) go to slots 0, 1, ...; every further video goes to the slot
+that falls free earliest, the lowest index among equals.  A slot whose video tracks its frame 1 at step s is busy on steps
+s .. s + T_v - 2; its next video is started BEHIND step s + T_v - 2 (DeviceTracker.start runs behind the step of the old video's
+last frame, so a refill costs no step) and tracks its frame 1 at step s + T_v - 1.
+"""
+import numpy as np
+
+from . import rle as rle_host
+
+ORDERS = ("given", "longest")
+_ROWS = ("target_pos", "target_sz", "score", "best_id", "polygon", "polygon_found")
+
+
+class Plan(object):
+    """what plan() returns: G steps; table int32 [G,B,2] = (video, frame), -1 where the slot is idle; initial = the (slot, video)
+    pairs started before step 0; starts[g] = those started behind step g; slot_of [V], first_step [V] (the step of a video's frame
+    1); lengths [V]; efficiency = sum(T_v - 1) / (G B)"""
+    __slots__ = ("G", "B", "table", "initial", "starts", "slot_of", "first_step", "lengths", "efficiency")
+
+
+def plan(lengths, B, order="given"):
+    lengths = [int(n) for n in lengths]
+    if not lengths:
+        raise ValueError("plan: at least one video")
+    if min(lengths) < 2:
+        raise ValueError("plan: every video has at least 2 frames (frame 0 initialises, the others are tracked), got %d" % min(lengths))
+    if int(B) != B or B < 1:
+        raise ValueError("plan: B >= 1 slots, got %r" % (B,))
+    if order not in ORDERS:
+        raise ValueError("plan: order is one of %s, got %r" % (ORDERS, order))
+    B, V = int(B), len(lengths)
+    taken = sorted(range(V), key=lambda v: -lengths[v]) if order == "longest" else range(V)     # (sorted() is stable)
+    free = [0] * B                                                    # the step from which a slot has no video
+    p = Plan()
+    p.slot_of, p.first_step = np.zeros(V, dtype=np.int64), np.zeros(V, dtype=np.int64)
+    for v in taken:
+        s = min(range(B), key=lambda b: (free[b], b))
+        p.slot_of[v], p.first_step[v] = s, free[s]
+        free[s] += lengths[v] - 1
+    p.G, p.B, p.lengths = max(free), B, np.asarray(lengths, dtype=np.int64)
+    p.table = np.full((p.G, B, 2), -1, dtype=np.int32)
+    p.initial, p.starts = [], [[] for _ in range(p.G)]
+    for v in taken:
+        s, g, n = int(p.slot_of[v]), int(p.first_step[v]), lengths[v] - 1
+        p.table[g:g + n, s, 0], p.table[g:g + n, s, 1] = v, np.arange(1, n + 1)
+        (p.starts[g - 1] if g else p.initial).append((s, v))
+    p.efficiency = float(sum(lengths) - V) / (p.G * B)
+    return p
+
+
+class _Gather(object):
+    """the rows of the chunks, in step order, sorted to their videos.  add(): one collect()-shaped dict of numpy arrays [T,B,...]
+    (its 'rle' with 'counts' as a numpy array); the counts are cut to per-frame arrays at once, so nothing [T,B,cap] is kept"""
+
+    def __init__(self, pl):
+        self.pl, self.g, self.rows, self.codes = pl, 0, {}, None
+
+    def add(self, res):
+        T = int(np.asarray(res["score"]).shape[0])
+        if self.g + T > self.pl.G:
+            raise ValueError("gather: %d rows for the %d steps of the plan" % (self.g + T, self.pl.G))
+        for k in _ROWS:
+            if k in res:
+                self.rows.setdefault(k, []).append(np.asarray(res[k]))
+        r = res.get("rle")
+        if r is not None:
+            if self.codes is None:
+                self.codes = {"rle": [], "n": [], "area": [], "sizes": []}
+            self.codes["rle"] += rle_host.to_host_v(r)
+            for k in ("n", "area", "sizes"):
+                self.codes[k].append(np.asarray(r[k]))
+        self.g += T
+
+    def videos(self):
+        pl = self.pl
+        if self.g != pl.G:
+            raise ValueError("gather: %d rows for the %d steps of the plan" % (self.g, pl.G))
+        full = {k: np.concatenate(v) for k, v in self.rows.items()}
+        meta = {k: np.concatenate(self.codes[k]) for k in ("n", "area", "sizes")} if self.codes is not None else {}
+        out = []
+        for v in range(len(pl.lengths)):
+            s, g, n = int(pl.slot_of[v]), int(pl.first_step[v]), int(pl.lengths[v]) - 1
+            d = {"slot": s, "first_step": g}
+            d.update({k: a[g:g + n, s].copy() for k, a in full.items()})
+            if self.codes is not None:
+                d["rle"] = [self.codes["rle"][t][s] for t in range(g, g + n)]
+                d.update({k: a[g:g + n, s].copy() for k, a in meta.items()})
+            out.append(d)
+        return out
+
+
+def gather(pl, chunks):
+    """the per-video rows of a planned run from its chunks (collect()-shaped dicts of numpy arrays, in step order, any boundaries)
+    -> one dict per video in the plan's numbering: slot, first_step, the scalar rows [T_v - 1, ...] and, for chunks with 'rle',
+    rle (a list of T_v - 1 count arrays, None where n > cap), n, area and sizes [T_v - 1, 2] = (h, w)"""
+    g = _Gather(pl)
+    for c in chunks:
+        g.add(c)
+    return g.videos()
+
+
+def _video_size(videos, v):
+    """(h, w) of video v from its frame 0; a video given as a list of frames is checked through here, before any launch"""
+    import torch
+    f0 = videos[v][0]
+    if not isinstance(f0, torch.Tensor) or not f0.is_cuda:
+        raise RuntimeError("siammask_amd.dataset runs on the MI355X only: video %d's frames must be CUDA(HIP) tensors" % v)
+    if f0.dtype != torch.uint8 or f0.dim() != 3 or f0.shape[2] != 3:
+        raise ValueError("run_videos: video %d: frames must be uint8 [h,w,3], frame 0 is %s %s" % (v, f0.dtype, tuple(f0.shape)))
+    if isinstance(videos[v], (list, tuple)):                          # (a [T,h,w,3] tensor has one size; a lazy loader is checked per frame)
+        for t, f in enumerate(videos[v]):
+            if tuple(f.shape) != tuple(f0.shape):
+                raise ValueError("run_videos: video %d: frame %d is %s, frame 0 %s" % (v, t, tuple(f.shape), tuple(f0.shape)))
+    return int(f0.shape[0]), int(f0.shape[1])
+
+
+def run_videos(tracker, videos, pos, sz, B=None, order="longest", want_polygon=False, rle=True, chunk=256):
+    """Track every video of ``videos`` once (one pass, no re-initialisation) through the B slots of ``tracker``, which this call
+    reserves itself: tracker.reserve(B, Hc, Wc) with the canvas Hc x Wc = the largest h and the largest w over the videos; B
+    defaults to min(the model's batch, V).  videos[v]: anything with len() and [t] -> uint8 CUDA [h_v,w_v,3] (a [T,h,w,3] tensor, a
+    list of frames, a loader that uploads frame t on demand; pitched frames as start() / enqueue() take them), T_v >= 2; frame 0
+    gives the size and is the frame the video starts on at the box pos[v] / sz[v] ([V,2] each).  order: plan()'s.
+    rle: True or {'cap': n} (rle.default_cap of the canvas) -- every tracked frame's mask as a COCO run-length code at the
+    video's own size; no mask byte is allocated (with want_polygon: one canvas [B,Hc,Wc], re-used by every step).  rle=False: the
+    scalar rows only (and the polygons); no mask is returned.  chunk: steps per collect(); the rows of a chunk move to the host
+    at once (the counts as counts[..., :n.max()]), so device memory stays within chunk * B * (cap + n.max()) * 4 bytes whatever the
+    dataset's size (rle=False with want_polygon: the chunk's canvases, chunk * B * Hc * Wc, until its collect()).  The result does
+    not depend on chunk.  Refused before any launch (ValueError): a per-stream hp table on the tracker (rows belong to slots,
+    videos move between them), the rpn variant with rle, a video of fewer than 2 frames, pos / sz not [V,2].
+    -> {'videos': [one dict per video, in the caller's order: slot, first_step, size (h, w), target_pos, target_sz, score,
+    best_id over [T_v - 1, ...][, polygon, polygon_found][, rle: T_v - 1 int64 count arrays (None where n > cap), n, area]],
+    'steps': G, 'efficiency', 'events': what every start() did ('step': the step its videos' frame 1 is tracked at, 'videos')}"""
+    import torch
+    videos = list(videos)
+    V = len(videos)
+    lengths = [len(v) for v in videos]
+    if V and min(lengths) < 2:
+        raise ValueError("run_videos: every video has at least 2 frames (frame 0 initialises), video %d has %d"
+                         % (int(np.argmin(lengths)), min(lengths)))
+    pos, sz = np.asarray(pos, dtype=np.float64), np.asarray(sz, dtype=np.float64)
+    if pos.shape != (V, 2) or sz.shape != (V, 2):
+        raise ValueError("run_videos: pos and sz must be [%d,2], one box per video" % V)
+    if tracker.get_hp() is not None:
+        raise ValueError("run_videos: the tracker holds a per-stream hp table; its rows belong to slots and videos move between "
+                         "slots (set_hp(None) first)")
+    rle_on = rle is not None and rle is not False
+    if rle_on and tracker.model.variant == "rpn":
+        raise ValueError("run_videos: rle needs a variant with a mask branch")
+    if rle_on and rle is not True and (not isinstance(rle, dict) or set(rle) - {"cap"}):
+        raise ValueError("run_videos: rle = True, False or {'cap': counts per stream}")
+    if int(chunk) < 1:
+        raise ValueError("run_videos: chunk >= 1 steps, got %r" % (chunk,))
+    B = min(int(getattr(tracker.model, "_max_batch", 1)), V, 32) if B is None else int(B)
+    pl = plan(lengths, B, order)                                      # (refuses an empty list, B < 1, an unknown order)
+    sizes = [_video_size(videos, v) for v in range(V)]
+    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
+    cap = None
+    if rle_on:
+        cap = rle_host.default_cap(Hc, Wc) if rle is True or rle.get("cap") is None else rle["cap"]
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= Hc * Wc + 1 or max(Hc, Wc) > 4096:
+            raise ValueError("run_videos: rle['cap'] must be an integer in 1..%d on a canvas of up to 4096 x 4096, got %r"
+                             % (Hc * Wc + 1, cap))
+    want_polygon = bool(want_polygon) and tracker.model.variant != "rpn"
+    depth = int(getattr(tracker.model, "_pipeline", 0) or 0)
+    tracker.reserve(B, Hc, Wc, device=videos[0][0].device)
+    if tracker.pipeline and tracker.refine and depth > 1:             # (reserve() turns the pipeline on at depth 1: a model in
+        tracker.model.set_pipeline(depth)                             #  throughput mode stays in it)
+
+    def start(pairs):
+        vs = [v for _, v in pairs]
+        tracker.start([videos[v][0] for v in vs], [s for s, _ in pairs], pos=pos[vs], sz=sz[vs])
+        started.append(vs)
+
+    started, events, acc, g0, rows = [], [], _Gather(pl), 0, None
+    dev = tracker._fr.device
+    # an idle slot is fed the last frame it saw (the size its record still has); a slot that never had a video, a canvas of zeros
+    last = [None] * B
+    start(pl.initial)
+    for g in range(pl.G):
+        live = [bool(pl.table[g, b, 0] >= 0) for b in range(B)]
+        for b in range(B):
+            if live[b]:
+                last[b] = videos[pl.table[g, b, 0]][int(pl.table[g, b, 1])]
+            elif last[b] is None:
+                last[b] = torch.zeros((Hc, Wc, 3), dtype=torch.uint8, device=dev)
+        if rle_on and g == g0:                                        # the chunk's counts and meta rows: ONE tensor each, no stack
+            n = min(int(chunk), pl.G - g0)
+            rows = (torch.empty((n, B, cap), dtype=torch.int32, device=dev), torch.empty((n, B, 4), dtype=torch.int32, device=dev))
+        tracker.enqueue(list(last), want_mask=rle_on or want_polygon, want_polygon=want_polygon,
+                        _rle_v=(cap, live) if rle_on else None, _rle_out=(rows[0][g - g0], rows[1][g - g0]) if rle_on else None)
+        if pl.starts[g]:
+            start(pl.starts[g])
+        if g + 1 - g0 == int(chunk) or g + 1 == pl.G:
+            res = tracker.collect(_rle=rows)
+            res.pop("mask", None)                                     # (rle=False with a polygon: the chunk's canvases end here)
+            r = res.get("rle")
+            if r is not None:
+                k = int(min(r["n"].max(), r["cap"]))
+                res["rle"] = dict(r, counts=r["counts"][..., :k].cpu().numpy())
+            acc.add(res)
+            for e, vs in zip(res.get("events", []), started):
+                events.append(dict(e, step=g0 + e["t"], videos=vs))
+            started, g0, rows, res, r = [], g + 1, None, None, None      # (the chunk's device rows end here, before the next chunk's exist)
+    out = acc.videos()
+    for v, d in enumerate(out):
+        d["size"] = sizes[v]
+        if "sizes" in d and (d.pop("sizes") != np.asarray(sizes[v])).any():
+            raise RuntimeError("run_videos: video %d was encoded at another size than its frames'" % v)
+    return {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}
+
+
+def ope_video(d, gt, name):
+    """one video of run_videos with its annotation gt [T_v,4] (x, y, w, h) -> the dict evaluate.pack_ope takes (one tracker); its
+    'rect'[0] is what tune.ope_lines writes as <video>.txt.  Row 0 is the annotation, as the tools write it"""
+    gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4)
+    p, s = np.asarray(d["target_pos"], dtype=np.float64), np.asarray(d["target_sz"], dtype=np.float64)
+    rect = np.concatenate([gt[:1], np.stack([p[:, 0] - s[:, 0] / 2, p[:, 1] - s[:, 1] / 2, s[:, 0], s[:, 1]], axis=1)])
+    return {"name": name, "gt": gt, "rect": rect[None]}

@@ -693,6 +693,91 @@ def paste_masks_dev_v(logits, state, slot, canvas_wh, seg_thr=0.35, padding=-1.0
     return mask
 
 
+def _rle_v_args(B, canvas_wh, sizes, live, cap, need_sizes):
+    """host checks of the two *_v RLE wrappers, made before the library is touched -> (W, H, wh int32 [B,2] or None, live mask, cap)"""
+    from . import rle
+    W, H = int(canvas_wh[0]), int(canvas_wh[1])
+    if not 1 <= B <= 32:
+        raise ValueError("rle_v: 1..32 streams, got %d" % B)
+    if not (1 <= W <= 4096 and 1 <= H <= 4096):
+        raise ValueError("rle_v: canvas h, w in 1..4096, got %d x %d" % (H, W))
+    wh = None
+    if sizes is not None:
+        wh = np.ascontiguousarray(sizes, dtype=np.int32)
+        if wh.size != 2 * B:
+            raise ValueError("rle_v: sizes must be [%d,2] (w, h)" % B)
+        wh = wh.reshape(B, 2)
+        if (wh[:, 0] > W).any() or (wh[:, 1] > H).any() or (need_sizes and (wh < 1).any()):
+            raise ValueError("rle_v: a stream's size %s does not fit the canvas %d x %d (w x h)" % (wh.tolist(), W, H))
+    elif need_sizes:
+        raise ValueError("rle_v: sizes [B,2] (w, h) are required")
+    if live is None:
+        mask = (1 << B) - 1
+    else:
+        live = list(live)
+        if len(live) != B:
+            raise ValueError("rle_v: live must have %d entries, got %d" % (B, len(live)))
+        mask = sum(1 << b for b, v in enumerate(live) if v)
+    cap = rle.default_cap(H, W) if cap is None else int(cap)
+    if not 1 <= cap <= H * W + 1:
+        raise ValueError("rle: cap must be in 1..%d, got %d" % (H * W + 1, cap))
+    return W, H, wh, mask, cap
+
+
+def rle_encode_v(canvas, sizes, live=None, cap=None, counts=None, meta=None, _form=None):
+    """rle_encode for the canvas paste_masks_dev_v writes (smk_rle_encode_v): canvas uint8 CUDA [B,Hc,Wc], B <= 32; sizes [B,2] =
+    the streams' (w, h); only canvas[b, :h_b, :w_b] is read and stream b is numbered with its own height.  live: B booleans (None:
+    all); a stream that is not live costs nothing, none of its counts is written and its meta row is (0, 0, h_b, w_b).
+    -> (counts int32 CUDA [B,cap], meta int32 CUDA [B,4] = (m, area, h_b, w_b)); cap defaults to rle.default_cap of the canvas.
+    _form (private): 0 / 1 = smk_test_rle_encode_v with the strided / the LDS-tile byte source."""
+    if canvas.dtype != torch.uint8 or canvas.dim() != 3:
+        raise ValueError("canvas must be uint8 [B,Hc,Wc]")
+    B, H, W = (int(v) for v in canvas.shape)
+    W, H, wh, mask, cap = _rle_v_args(B, (W, H), sizes, live, cap, True)
+    _need_cuda(canvas, "canvas")
+    c = canvas.contiguous()
+    with torch.cuda.device(c.device):
+        cap, ws, need, counts, meta = _rle_buffers(c.device, B, W, H, cap, counts, meta)
+        args = (c.data_ptr(), B, W, H, wh.ctypes.data, mask, cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr())
+        if _form is None:
+            _lib.check(_lib.lib().smk_rle_encode_v(*(args + (_lib.current_stream_ptr(),))))
+        else:
+            _lib.check(_lib.lib().smk_test_rle_encode_v(*(args + (int(_form), _lib.current_stream_ptr()))))
+    return counts, meta
+
+
+def paste_rle_v(logits, state, slot, canvas_wh, sizes=None, live=None, seg_thr=0.35, padding=-1.0, head=None, mask_size=None,
+                cap=None, counts=None, meta=None):
+    """paste_rle for streams with their own frame sizes (smk_paste_rle_dev_v): stream b's size is im_w / im_h of its record, its
+    counts are those of rle_encode_v(paste_masks_dev_v(...)) and no mask byte reaches memory.  canvas_wh: the (w, h) every size fits
+    in (it sizes the workspace and the default cap); sizes: the streams' (w, h) [B,2] as the host knows them (checked against the
+    canvas); live as for rle_encode_v."""
+    src = head if head is not None else logits
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = int(src.shape[0])
+    W, H, wh, mask, cap = _rle_v_args(B, canvas_wh, sizes, live, cap, False)
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    with torch.cuda.device(src.device):
+        cap, ws, need, counts, meta = _rle_buffers(src.device, B, W, H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_paste_rle_dev_v(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, W, H, wh.ctypes.data if wh is not None else None, mask, float(seg_thr), float(padding),
+            cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr(), _lib.current_stream_ptr()))
+    return counts, meta
+
+
 def vot_overlap_dev(pred, gt, state, adv_rows=None, out=None, counts=None):
     """vot_overlap with the bounds of pair b taken on the device from record b of the tracker's state block (streams with
     their own frame sizes; include/siammask_hip.h: smk_vot_overlap_dev)"""

@@ -8,6 +8,9 @@ run (0 when pixel 0 is set); they sum to h * w.  An empty mask is [h * w], a ful
     per = rle.to_host(r)                                # ONE copy of counts[..., :n.max()] -> [T][B] numpy arrays (None: n > cap)
     rle.to_coco(per[t][b], *r['size'])                  # {'size': [h, w], 'counts': b'...'}: what pycocotools takes
 
+Streams with their own frame sizes (dataset.run_videos): r['sizes'] [T,B,2] = (h, w) per frame and stream stands for r['size'], and
+to_host_v(r) is to_host with None also where n == 0 (the slot had no video that step).
+
 The fused label map of a VOS frame as one code per object (smk_vos_rle / smk_labels_rle_encode, run(vos={..., 'rle': True})):
 plane o is labels == o + 1, so the planes are disjoint and a frame's map is their union.
 
@@ -147,3 +150,17 @@ def to_host(r):
     k = int(min(n.max(), cap))
     host = r["counts"][..., :k].cpu().numpy().view(np.uint32)
     return [[host[t, b, :n[t, b]].astype(np.int64) if n[t, b] <= cap else None for b in range(B)] for t in range(T)]
+
+
+def to_host_v(r):
+    """to_host for the res['rle'] of streams with their own sizes (dataset.run_videos; 'sizes' int32 [T,B,2] = (h, w) per frame and
+    stream in place of 'size'): None also where n == 0 -- the slot had no video that step, nothing was encoded.  The code of
+    (t, b) is that of an h x w mask with (h, w) = r['sizes'][t, b]: to_coco(per[t][b], *r['sizes'][t, b])."""
+    n, cap = np.asarray(r["n"]), int(r["cap"])
+    T, B = n.shape
+    if T == 0:
+        return []
+    k = int(min(n.max(), cap))
+    host = r["counts"][..., :k]
+    host = (host if isinstance(host, np.ndarray) else host.cpu().numpy()).view(np.uint32)
+    return [[host[t, b, :n[t, b]].astype(np.int64) if 0 < n[t, b] <= cap else None for b in range(B)] for t in range(T)]

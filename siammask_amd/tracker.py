@@ -41,6 +41,8 @@ Streams with their own frame sizes (B different videos in one free-running batch
     res['mask'], res['sizes']                                      # uint8 CUDA [T,B,H,W], zero outside each stream's image; (w, h) [T,B,2]
 tr.state['im_w'] / ['im_h'] are then per-stream arrays; a slot may be started again on a video of another size.  Free-running only:
 track(), gt= / vos= / labels_out= (the objects of VOS share one frame) raise ValueError in this mode.
+A whole dataset of such videos, of different lengths, through the B slots: siammask_amd.dataset.run_videos (the masks then leave as
+run-length codes at each video's own size, through the private _rle_v of enqueue(); the public rle= stays refused under mixed sizes).
 
 The VOT supervised loop (track_vot, :318-365) for B videos in lock-step, still enqueue-only: the overlap of every tracked polygon
 with its annotation is computed on the device (csrc/vot_overlap.hip), the host learns of a loss through a read-back that lags
@@ -121,7 +123,8 @@ def _box_corners(pos, sz):
 # rle: None, or the _Rle of a frame enqueued with rle= (mask is then None unless a polygon or the masks were asked for)
 _Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou rle", defaults=(None, None))
 # a checked rle= request (_rle_spec): counts per stream, masks wanted; enqueue() adds the frame's counts [B,cap] and meta [B,4]
-_Rle = collections.namedtuple("_Rle", "cap masks counts meta")
+# live: None, or (the private _rle_v of enqueue(): streams with their own sizes) the bit mask of the slots that have a video this step
+_Rle = collections.namedtuple("_Rle", "cap masks counts meta live", defaults=(None,))
 # a checked VOS request as the C entry takes it (_vos_spec); enqueue() adds the frame's count row and label map
 # rle: None, or the _LabelRle of a frame whose spec carries vos['rle']; gt / thrs / row are then None when the frame is not scored
 _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row labels rle", defaults=(None,))
@@ -154,7 +157,7 @@ class _Queue(object):
     network inputs ``x`` / ``twh``, the per-block device rows (``rows``, ``rbox``, ``vos``, ``iou``), the host arrays the device agrees with
     (``synced``), the buffers of start() (``can_start``: they exist), the launch guard, and the pending ``chunk``"""
     __slots__ = ("B", "H", "W", "device", "dev", "snap", "x", "twh", "cfg", "z_all", "z_snap", "win", "rects", "sums", "can_start",
-                 "rows", "rbox", "vos", "iou", "synced", "chunk", "launch")
+                 "rows", "rbox", "vos", "iou", "synced", "chunk", "launch", "canvas")
 
 
 class _Launching(object):
@@ -625,6 +628,7 @@ class DeviceTracker(object):
         q.B, q.H, q.W, q.device, q.chunk = B, H, W, device, _Chunk()
         q.launch = _Launching(self)
         q.rows, q.rbox, q.vos, q.iou, q.synced = [], [], [], [], None
+        q.canvas = None                                               # enqueue(_rle_v=, want_polygon): the one canvas [B,H,W]
         n = int(L.smk_trk_state_bytes(B))
         with torch.cuda.device(device):
             q.dev = torch.zeros(n, dtype=torch.uint8, device=device)
@@ -810,7 +814,7 @@ class DeviceTracker(object):
             raise ValueError("rle= returns masks; not inside the VOS / VOT / IoU loops (gt= / vos=, vot=, iou=)")
         if self.model.variant == "rpn" or not want_mask:
             raise ValueError("rle= needs want_mask and a variant with a mask branch")
-        if mixed:
+        if mixed:                                                     # (enqueue(_rle_v=) passes mixed=False: the per-size codes)
             raise ValueError("rle=: one frame size per batch; these streams have their own sizes")
         if rle is True:
             rle = {}
@@ -828,7 +832,7 @@ class DeviceTracker(object):
         return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None, rle=None, _rle_out=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -855,6 +859,11 @@ class DeviceTracker(object):
         nothing is scored, 'thrs' is optional and collect() has no vos_counts.  Either every frame of a chunk carries vos['rle']
         (one cap; scored or not as the first) or none does; the top-level rle= with gt= / vos= stays refused.
         _rle_out (private, run()): the frame's rows (counts int32 CUDA [B,cap], meta int32 CUDA [B,4]) of the run's tensors.
+        _rle_v (private, dataset.run_videos): (cap or None, live: B booleans or None) with a LIST of frames -- the masks of streams
+        with their own sizes as run lengths, stream b numbered with its own height (smk_paste_rle_dev_v in the paste-back's place;
+        with want_polygon smk_paste_mask_dev_v -> rotated box -> smk_rle_encode_v on one canvas the queue keeps, so collect()
+        reports no mask either way).  A slot that is not live is tracked, but nothing of its code is computed: n = 0.  The chunk
+        rule of rle= holds (every frame, one cap); collect() returns res['rle'] with 'sizes' int32 [T,B,2] (h, w) for 'size'.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -881,9 +890,23 @@ class DeviceTracker(object):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
         if c.pending and (c.iou_k is not None) != (iou is not None):
             raise ValueError("every frame of a chunk carries iou=, or none does")
+        live = None
+        if _rle_v is not None:                                        # the per-size codes: rle= itself stays refused under mixed sizes
+            if (rle is not None and rle is not False) or not mixed or mask_out is not None or B > 32:
+                raise ValueError("_rle_v comes with a list of frames (up to 32 streams), without rle= and mask_out=")
+            cap_v, live = _rle_v
+            live = [True] * B if live is None else list(live)
+            if len(live) != B:
+                raise ValueError("_rle_v: live must hold %d booleans, one per stream" % B)
+            rle = True if cap_v is None else {"cap": cap_v}
         if c.pending and (c.rle is not None) != (rle is not None and rle is not False):
             raise ValueError("every frame of a chunk carries rle=, or none does")
-        rle = self._rle_spec(mixed, want_mask, vos is not None or gt is not None or iou is not None or _after is not None, rle)
+        rle = self._rle_spec(mixed and _rle_v is None, want_mask,
+                             vos is not None or gt is not None or iou is not None or _after is not None, rle)
+        if _rle_v is not None:
+            rle = rle._replace(live=sum(1 << b for b in range(B) if live[b]))
+        if c.pending and c.rle is not None and (c.rle[0].live is None) != (rle.live is None):
+            raise ValueError("every frame of a chunk carries _rle_v, or none does")
         iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
@@ -946,6 +969,10 @@ class DeviceTracker(object):
                 lr = score.rle if score is not None else None
                 if rle is not None and not (want_polygon or rle.masks or mask_out is not None):
                     pass                                              # the paste-back emits the run lengths: no mask bytes anywhere
+                elif rle is not None and rle.live is not None:        # _rle_v with a polygon: ONE canvas, re-used in stream order
+                    if q.canvas is None:
+                        q.canvas = torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
+                    mask = q.canvas
                 elif lr is not None and not (want_polygon or lr.masks or mask_out is not None):
                     pass                                              # smk_vos_rle_dev stands in the paste-back's place: likewise
                 elif iou is None or iou.masks:                        # (a score-only frame has no mask anywhere)
@@ -957,7 +984,7 @@ class DeviceTracker(object):
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
                     self._fr_paste(job, sp)
-            c.masks.append(mask)
+            c.masks.append(mask if rle is None or rle.live is None else None)
             if rle is not None:                                       # (beside the frame count: a launch that raised leaves no row)
                 c.rle = (c.rle or []) + [rle]
             if score is not None and score.rle is not None:
@@ -977,7 +1004,12 @@ class DeviceTracker(object):
         fused = u is not None and u.scored and job.rbox is None      # smk_iou_score_dev writes the mask bytes itself
         r = job.rle
         lr = s.rle if s is not None else None
-        if r is not None and mask is None:                            # the paste-back IS the encoder (smk_paste_rle_dev)
+        rv = r is not None and r.live is not None                     # streams with their own sizes: the _v encoders
+        live = [bool(r.live >> b & 1) for b in range(q.B)] if rv else None
+        if rv and mask is None:                                       # smk_paste_rle_dev_v: no canvas exists
+            preproc.paste_rle_v(logits, q.dev, job.slot, (q.W, q.H), sizes=job.sizes, live=live, seg_thr=p.seg_thr, head=head,
+                                mask_size=self.mask_size, cap=r.cap, counts=r.counts, meta=r.meta)
+        elif r is not None and mask is None:                          # the paste-back IS the encoder (smk_paste_rle_dev)
             preproc.paste_rle(logits, q.dev, job.slot, (q.W, q.H), seg_thr=p.seg_thr, head=head, mask_size=self.mask_size,
                               cap=r.cap, counts=r.counts, meta=r.meta)
         elif mask is None or fused:
@@ -988,7 +1020,9 @@ class DeviceTracker(object):
             _lib.check(L.smk_paste_mask_dev(*(shared + (float(p.seg_thr), -1.0, mask.data_ptr(), None, sp))))
         if job.rbox is not None:                                      # same stream, behind the paste-back (:285-303)
             preproc.mask_rboxes(mask, out=job.rbox, mode=self.rbox)
-        if r is not None and mask is not None:                        # the bytes exist: encode them, same stream
+        if rv and mask is not None:                                   # the canvas exists: encode each stream's rectangle of it
+            preproc.rle_encode_v(mask, job.sizes, live=live, cap=r.cap, counts=r.counts, meta=r.meta)
+        elif r is not None and mask is not None:                      # the bytes exist: encode them, same stream
             preproc.rle_encode(mask, cap=r.cap, counts=r.counts, meta=r.meta)
         if lr is not None and s.labels is None:                       # the fused label planes, in the paste-back's place: no label byte
             preproc.vos_rle_dev(logits, q.dev, job.slot, (q.W, q.H), s.ids, init=s.init, seg_thr=p.seg_thr, head=head,
@@ -1045,7 +1079,9 @@ class DeviceTracker(object):
         polygon_found [T,B]; for a chunk enqueued with gt= / vos=, vos_counts int64 [T,B,K,2] = (intersection, union) per frame,
         object and threshold and labels (uint8 CUDA [T,H,W]); for a chunk enqueued with rle=, rle = {'counts': int32 CUDA [T,B,cap]
         (the bits are uint32), 'n': int32 [T,B] (counts of the mask; n > cap: an overflow, the counts are incomplete), 'area': int32
-        [T,B], 'cap', 'size': (H, W)} -- n and area ride with the one read-back, siammask_amd.rle.to_host fetches the counts;
+        [T,B], 'cap', 'size': (H, W)} -- n and area ride with the one read-back, siammask_amd.rle.to_host fetches the counts
+        (a chunk enqueued with _rle_v: 'sizes' int32 [T,B,2] = (h, w) of the meta rows in place of 'size', n = 0 where a slot was
+        not live; rle.to_host_v);
         for a chunk with start() calls, events (T may then be 0).  Leaves
         tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the tracker to the chunk's start when
         a persistent-sequence failure was reported: re-run the chunk.  _masks / _labels (private, run()): the [T,B,H,W] / [T,H,W]
@@ -1074,9 +1110,10 @@ class DeviceTracker(object):
                     vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
                     vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
+                nm = 4 if c.rle is not None and c.rle[0].live is not None else 2      # _rle_v: (h, w) of the meta rows as well
                 if enc is not None:                                   # (m, area) of the meta rows ride along as float64 (exact)
                     rmeta = _rle[1] if _rle is not None and _rle[1].shape[0] == T else torch.stack([r.meta for r in enc])
-                    rows = torch.cat([rows, rmeta[:, :, :2].to(torch.float64)], dim=2)
+                    rows = torch.cat([rows, rmeta[:, :, :nm].to(torch.float64)], dim=2)
             if events:                                                # the start events' result rows ride along
                 flat = torch.cat(([rows.reshape(-1)] if T else []) + [e.res.reshape(-1) for e in events]).cpu().numpy()
                 n = flat.size - len(events) * B * START_ROW           # (the one synchronisation)
@@ -1085,7 +1122,7 @@ class DeviceTracker(object):
                 host, ev_rows = rows.cpu().numpy(), None              # the one synchronisation
         rle_host = None
         if T and enc is not None:
-            host, rle_host = host[:, :, :-2], host[:, :, -2:].astype(np.int32)
+            host, rle_host = host[:, :, :-nm], host[:, :, -nm:].astype(np.int32)
         res, new = collect_host(host, T, B, c.poly, K, [(e.t, e.streams) for e in events], ev_rows, st,
                                 "vos_counts" if c.vos_k is not None else "iou_counts")
         if T:
@@ -1094,6 +1131,9 @@ class DeviceTracker(object):
                 res["rle" if c.rle is not None else "label_rle"] = {
                     "counts": counts, "n": np.ascontiguousarray(rle_host[:, :, 0]), "area": np.ascontiguousarray(rle_host[:, :, 1]),
                     "cap": enc[0].cap, "size": (q.H, q.W)}
+                if nm == 4:                                           # per (frame, stream): (h, w) as the kernel read them
+                    del res["rle"]["size"]
+                    res["rle"]["sizes"] = np.ascontiguousarray(rle_host[:, :, 2:4])
             masks = c.masks
             if all(m is not None for m in masks):
                 res["mask"] = _masks if _masks is not None and _masks.shape[0] == T else torch.stack(masks)
