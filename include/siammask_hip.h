@@ -414,6 +414,40 @@ int smk_vos_rle_dev(const float *logits_dev, const float *head_dev, int score_si
                     uint32_t given_mask, const uint8_t *init_labels_dev, int cap, void *ws_dev, size_t ws_bytes,
                     uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
 
+/* ---- the label planes of several videos in one launch (additive; smk_version() keeps reporting 1.10, the presence of these
+ * symbols is the probe) ---------------------------------------------------------------------------------------------------------------
+ * The grouped, per-size forms of smk_vos_rle / smk_vos_rle_dev: the B (1..32) slots of a mixed-size batch hold the objects of up
+ * to B videos.  GROUP g (n_groups in 1..B) is one video: group_masks[g] is a 32-bit mask over the slots -- non-empty, bits below
+ * B, pairwise disjoint --, (w_g, h_g) = group_wh[g] its frame size (each within canvas_w x canvas_h, both in 1..4096) and
+ * init_labels_dev[g] its init labels [h_g][w_g] at pitch w_g, or NULL (init_labels_dev itself may be NULL: no group has any).
+ * group_masks, group_wh and the pointer array init_labels_dev are HOST arrays that travel as kernel arguments: no device table.
+ * object_ids[B], alive_mask and given_mask are per SLOT; live_groups is a bit mask over the groups.
+ * For a pixel of group g the label is that of smk_vos_rle above over the members of g in ascending slot order: prob = bit b of
+ * given_mask ? (init_labels_dev[g][y][x] == object_ids[b] ? 1.0f : 0.0f) : bit b of alive_mask ? the warped probability of slot
+ * b's logits row through slot b's inverse map (inv_map[b] of the host array [B][6], or inv_map[slot] of record b) : -1.0f; a strict
+ * > scan keeps the first maximum, the comparison with seg_thr is in float32.  The PLANE of slot b is label == rank of b within
+ * its group + 1, numbered column-major with the group's height, j = x * h_g + y: the code of slot b is the code smk_vos_rle gives
+ * for object `rank` when called at (w_g, h_g) with the group's rows, maps and ids gathered.
+ * Outputs in the layout of smk_paste_rle_dev_v: counts_out_dev uint32 [B][cap], only counts[b][0 .. min(m, cap) - 1] written;
+ * meta_out_dev int32 [B][4] = (m, area, h_g, w_g), m the true count even when m > cap.  A slot whose group's live_groups bit is
+ * clear gets (0, 0, h_g, w_g), a slot in no group (0, 0, canvas_h, canvas_w); neither gets a count and nothing of either is
+ * computed.  A member that is neither alive nor given has the code [h_g * w_g].  Every word of every live plane is written
+ * exactly once: nothing is zeroed, no atomics, a second call gives the same bytes.  ws_dev: smk_rle_workspace(B, canvas_w,
+ * canvas_h), 8-byte aligned; slot b owns the canvas stride and uses its first ceil(h_g * w_g / 64) words.  cap in
+ * 1..canvas_w * canvas_h + 1.  Bad arguments -- a null pointer, B or n_groups out of range, an empty group, overlapping groups,
+ * member bits at or above B, a size outside the canvas, given_mask bits of a group without init labels, given_mask or alive_mask
+ * bits outside every group, a bad cap, a slot outside 0..1, a short or misaligned workspace, a misaligned output -- give
+ * SMK_E_ARG before anything is enqueued.  No context; asynchronous on `stream`, no host synchronisation. */
+int smk_vos_rle_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                  const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *init_labels_dev, uint32_t live_groups,
+                  float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap,
+                  void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+int smk_vos_rle_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                      int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                      const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                      uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
+                      uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
+
 /* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
  * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
  * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:

@@ -43,6 +43,7 @@ SYMBOLS = (
     "smk_rle_workspace", "smk_rle_encode", "smk_paste_rle_dev", "smk_test_rle_encode",
     "smk_paste_rle_dev_v", "smk_rle_encode_v", "smk_test_rle_encode_v",
     "smk_labels_rle_encode", "smk_vos_rle", "smk_vos_rle_dev",
+    "smk_vos_rle_v", "smk_vos_rle_dev_v",
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
     "smk_ope_curve", "smk_host_ope_curve",
@@ -199,6 +200,10 @@ def lib():
     rle_tail = [u32, vp, ci, vp, ctypes.c_size_t, vp, vp, vp]        # given_mask, init labels, cap, workspace, its bytes, outputs, stream
     L.smk_vos_rle.argtypes = [fp, ci, vp, ci, ci, ci, cf, vp, u32, cf] + rle_tail
     L.smk_vos_rle_dev.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci, cf, vp, u32, cf] + rle_tail
+    # groups (count, masks, sizes, init label pointers, live mask), border, ids, alive, seg_thr, given, cap, workspace, outputs, stream
+    rle_v_tail = [ci, vp, vp, vp, u32, cf, vp, u32, cf, u32, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_vos_rle_v.argtypes = [fp, ci, vp, ci, ci, ci] + rle_v_tail
+    L.smk_vos_rle_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci] + rle_v_tail
     L.smk_vot_traj_overlap.argtypes = [vp] * 8 + [ci] * 5 + [vp, vp, vp]
     L.smk_eao_workspace_bytes.argtypes = [ci, ci]
     L.smk_eao_curve.argtypes = [vp] * 4 + [ci] * 7 + [vp, ctypes.c_size_t, vp, vp, vp, vp]

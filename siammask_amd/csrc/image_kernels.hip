@@ -887,6 +887,94 @@ int launch_vos_rle(const VosRleParams &p, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- the label planes of G videos in one launch (smk_vos_rle_v / smk_vos_rle_dev_v) ---------------------------------------------------
+// rle_bits_labels_kernel per GROUP of slots, in the frame of rle_bits_v_kernel: blockIdx.y is the group, its member mask, size and
+// init labels are kernarg fields indexed by it (scalar registers), the wave's word index k goes through readfirstlane.  The two exits
+// -- a clear live_groups bit (the block), k >= nw_g (the wave) -- are wave-uniform and stand before the first ballot; lanes at or
+// past a_g = h_g * w_g carry label 0 and reach every ballot.  The members are walked by clearing the lowest set bit of the
+// (scalar) mask: the slot b of rank r is ffs of what is left, so logits row, record, id, alive and given bit of slot b are scalar
+// too.  One ballot per member; lane r keeps the word AND the slot of rank r in two registers of its own -- the rank-to-slot table
+// lives across the lanes, not in an indexed array, so nothing spills to scratch -- and lanes 0 .. n_g - 1 store to
+// words[slot of rank][k] in ONE instruction.  Every word of every live plane is written exactly once.
+template <bool DEV, bool GIVEN>
+__global__ __launch_bounds__(256) void rle_bits_labels_v_kernel(const VosRleVParams p) {
+    const int g = blockIdx.y, lane = threadIdx.x & 63;
+    if (!((p.live_groups >> g) & 1)) return;
+    const unsigned members = p.gmask[g];
+    const int W = p.gwh[g][0], H = p.gwh[g][1];
+    const int a = W * H, nw = (int)rle_words(W, H);
+    const int k = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), j = k * 64 + lane;
+    if (k >= nw) return;
+    int label = 0;
+    if (j < a) {
+        const int x = j / H, y = j - x * H;
+        float best = -1.f;
+        int arg = 0, r = 0;
+        for (unsigned m = members; m; m &= m - 1, ++r) {
+            const int b = __ffs(m) - 1;
+            float v = -1.f;
+            bool given = false;
+            if constexpr (GIVEN) {
+                given = (p.given >> b) & 1;
+                if (given) v = p.init[g][(size_t)y * W + x] == p.ids[b] ? 1.f : 0.f;
+            }
+            if (!given && ((p.alive >> b) & 1)) {
+                if constexpr (DEV) {
+                    const smk_trk_stream *s = p.st + b;
+                    const float *lg = p.logits + (size_t)b * p.ms * p.ms;
+                    int ls = 1;
+                    if (p.head_S) {
+                        ls = p.head_S * p.head_S;
+                        const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1);
+                        const int dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+                        lg = p.logits + (size_t)b * p.ms * p.ms * ls + dy * p.head_S + dx;
+                    }
+                    v = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y);
+                } else {
+                    v = warped_prob(p, p.inv_map[b], p.logits + (size_t)b * p.ms * p.ms, 1, x, y);
+                }
+            }
+            if (r == 0 || v > best) { best = v; arg = r; }            // np.argmax keeps the first maximum
+        }
+        label = best > p.seg_thr ? arg + 1 : 0;
+    }
+    unsigned long long mine = 0;
+    int to = 0, n = 0;
+    for (unsigned m = members; m; m &= m - 1, ++n) {                  // (wave-uniform: every lane reaches every ballot)
+        const unsigned long long w = __ballot(label == n + 1);
+        if (lane == n) { mine = w; to = __ffs(m) - 1; }
+    }
+    if (lane < n) p.words[(size_t)to * rle_words(p.W, p.H) + k] = mine;
+}
+
+int launch_vos_rle_v(const VosRleVParams &p, const RleVParams &scan, int B, void *stream) {
+    if (B < 1 || B > TRK_SET_MAX_B || p.n_groups < 1 || p.n_groups > B) return -1;
+    if (p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || scan.cap < 1 || scan.cap > p.W * p.H + 1) return -1;
+    if (!p.words || !p.logits || p.ms < 1 || scan.words != p.words || !scan.counts || !scan.meta || scan.W != p.W || scan.H != p.H) return -1;
+    unsigned seen = 0, given = 0;
+    for (int g = 0; g < p.n_groups; ++g) {                            // (the entry has said why; nothing out of range is launched)
+        const unsigned m = p.gmask[g];
+        if (!m || (m & seen) || (B < 32 && (m >> B))) return -1;
+        if (p.gwh[g][0] < 1 || p.gwh[g][1] < 1 || p.gwh[g][0] > p.W || p.gwh[g][1] > p.H) return -1;
+        if ((p.given & m) && !p.init[g]) return -1;
+        seen |= m;
+        if ((p.live_groups >> g) & 1) given |= p.given & m;
+    }
+    if ((p.given | p.alive) & ~seen) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((rle_words(p.W, p.H) + 3) / 4), p.n_groups);
+    if (given) {
+        if (p.st) hipLaunchKernelGGL((rle_bits_labels_v_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((rle_bits_labels_v_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (p.st) hipLaunchKernelGGL((rle_bits_labels_v_kernel<true, false>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((rle_bits_labels_v_kernel<false, false>), grid, dim3(256), 0, s, p);
+    }
+    if (hipGetLastError() != hipSuccess) return -4;
+    hipLaunchKernelGGL((rle_scan_v_kernel<false>), dim3(B), dim3(1024), 0, s, scan);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 int launch_rle_labels(const RleParams &p, int O, void *stream) {
     if (O < 1 || O > VOS_MAX_OBJ || p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || p.cap < 1 || p.cap > p.W * p.H + 1) return -1;
     if (!p.mask || !p.words || !p.counts || !p.meta) return -1;

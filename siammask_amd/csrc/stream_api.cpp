@@ -1047,6 +1047,86 @@ int smk_paste_rle_dev_v(const float *logits_dev, const float *head_dev, int scor
     return 0;
 }
 
+// ---- the label planes of G videos in one launch -----------------------------------------------------------------
+// the checks and the fields both entries share; everything is refused here, before anything is enqueued.  A slot in no group has no
+// size of its own: its meta row reports the canvas
+static int vos_rle_fill_v(const char *who, VosRleVParams &p, RleVParams &scan, const float *src, int mask_size, int B, int canvas_w,
+                          int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                          const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                          uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
+                          uint32_t *counts_out_dev, int32_t *meta_out_dev) {
+    if (!src || !object_ids || !group_masks || !group_wh) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d slots (1..%d)", who, B, TRK_SET_MAX_B);
+    if (n_groups < 1 || n_groups > B) return fail(SMK_E_ARG, "%s: %d groups (1..%d, the slots)", who, n_groups, B);
+    if (mask_size < 1) return fail(SMK_E_ARG, "%s: bad geometry (mask %d)", who, mask_size);
+    RleParams r;
+    CHK(rle_fill(who, r, B, canvas_w, canvas_h, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    memset(&p, 0, sizeof(p));
+    memset(&scan, 0, sizeof(scan));
+    for (int b = 0; b < B; ++b) { scan.wh[b][0] = canvas_w; scan.wh[b][1] = canvas_h; }
+    uint32_t seen = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const uint32_t m = group_masks[g];
+        const int w = group_wh[2 * g], h = group_wh[2 * g + 1];
+        if (!m) return fail(SMK_E_ARG, "%s: group %d is empty", who, g);
+        if (B < 32 && (m >> B)) return fail(SMK_E_ARG, "%s: group %d (%#x) has member bits at or above %d slots", who, g, m, B);
+        if (m & seen) return fail(SMK_E_ARG, "%s: group %d (%#x) overlaps an earlier group", who, g, m);
+        if (w < 1 || h < 1 || w > canvas_w || h > canvas_h)
+            return fail(SMK_E_ARG, "%s: group %d is %d x %d, the canvas %d x %d", who, g, w, h, canvas_w, canvas_h);
+        const uint8_t *init = init_labels_dev ? init_labels_dev[g] : nullptr;
+        if ((given_mask & m) && !init) return fail(SMK_E_ARG, "%s: given_mask %#x names members of group %d, which has no init labels", who, given_mask, g);
+        seen |= m;
+        p.gmask[g] = m; p.gwh[g][0] = w; p.gwh[g][1] = h; p.init[g] = init;
+        for (int b = 0; b < B; ++b)
+            if ((m >> b) & 1) { scan.wh[b][0] = w; scan.wh[b][1] = h; }
+        if ((live_groups >> g) & 1) scan.live |= m;
+    }
+    if (given_mask & ~seen) return fail(SMK_E_ARG, "%s: given_mask %#x has bits outside every group (%#x)", who, given_mask, seen);
+    if (alive_mask & ~seen) return fail(SMK_E_ARG, "%s: alive_mask %#x has bits outside every group (%#x)", who, alive_mask, seen);
+    p.words = r.words; p.logits = src;
+    p.W = canvas_w; p.H = canvas_h; p.ms = mask_size; p.n_groups = n_groups;
+    p.seg_thr = seg_thr; p.border = border; p.alive = alive_mask; p.given = given_mask; p.live_groups = live_groups;
+    for (int b = 0; b < B; ++b) p.ids[b] = object_ids[b];
+    scan.words = r.words; scan.counts = r.counts; scan.meta = r.meta;
+    scan.W = canvas_w; scan.H = canvas_h; scan.cap = cap; scan.tile = 1;
+    return 0;
+}
+
+int smk_vos_rle_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                  const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *init_labels_dev, uint32_t live_groups,
+                  float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap,
+                  void *ws_dev, size_t ws_bytes, uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_rle_v: null argument");
+    VosRleVParams p;
+    RleVParams scan;
+    CHK(vos_rle_fill_v("smk_vos_rle_v", p, scan, logits_dev, mask_size, B, canvas_w, canvas_h, n_groups, group_masks, group_wh,
+                       init_labels_dev, live_groups, border, object_ids, alive_mask, seg_thr, given_mask, cap, ws_dev, ws_bytes,
+                       counts_out_dev, meta_out_dev));
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < 6; ++k) p.inv_map[b][k] = inv_map[6 * b + k];
+    if (launch_vos_rle_v(p, scan, B, stream)) return fail(SMK_E_HIP, "vos_rle_v launch failed");
+    return 0;
+}
+
+int smk_vos_rle_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                      int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                      const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                      uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
+                      uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_rle_dev_v: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_rle_dev_v: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_rle_dev_v: score_size %d", score_size);
+    VosRleVParams p;
+    RleVParams scan;
+    CHK(vos_rle_fill_v("smk_vos_rle_dev_v", p, scan, head_dev ? head_dev : logits_dev, mask_size, B, canvas_w, canvas_h, n_groups,
+                       group_masks, group_wh, init_labels_dev, live_groups, border, object_ids, alive_mask, seg_thr, given_mask, cap,
+                       ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_rle_v(p, scan, B, stream)) return fail(SMK_E_HIP, "vos_rle_v launch failed");
+    return 0;
+}
+
 int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
                         const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
     if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");

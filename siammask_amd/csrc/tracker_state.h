@@ -342,6 +342,26 @@ struct RleVParams {
     int wh[TRK_SET_MAX_B][2];
 };
 int launch_rle_v(const RleVParams &p, int B, void *stream);
+// smk_vos_rle_v / smk_vos_rle_dev_v: launch_vos_rle for G groups of slots, each group the objects of one video at its own size.
+// W x H is the CANVAS (the grid and the workspace stride rle_words(W, H) of a slot); group g is numbered j = x * h_g + y with
+// (w_g, h_g) = gwh[g], its members are the set bits of gmask[g] in ascending slot order (pairwise disjoint, checked by the entry),
+// and the plane of member b is label == rank of b within its group + 1, written to slot b's stride.  Logits row, record, id, alive
+// and given bit are per SLOT.  Everything of a group travels in the kernarg; `scan` is the RleVParams rle_scan_v_kernel<false> runs on
+struct VosRleVParams {
+    unsigned long long *words;      // workspace, [B] strides of rle_words(W, H)
+    const float *logits;            // [B][ms*ms], or the head [B][ms*ms][S][S] when head_S != 0
+    int W, H, ms, head_S, slot, n_groups;
+    float seg_thr, border;
+    unsigned alive, given;          // per slot, as VosParams per object
+    unsigned live_groups;           // bit g clear: nothing of group g is computed
+    const smk_trk_stream *st;       // != nullptr: inv_map[slot] / delta_yx[slot] of the state block, inv_map below unused
+    unsigned gmask[TRK_SET_MAX_B];
+    int gwh[TRK_SET_MAX_B][2];
+    const unsigned char *init[TRK_SET_MAX_B];      // [h_g][w_g] per group, or nullptr (no given bit in the group)
+    unsigned char ids[TRK_SET_MAX_B];
+    double inv_map[TRK_SET_MAX_B][6];
+};
+int launch_vos_rle_v(const VosRleVParams &p, const RleVParams &scan, int B, void *stream);
 struct FrameSumsVParams {
     smk_image_ref im[TRK_SET_MAX_B];
     unsigned long long *sums;       // [n][3]

@@ -13,6 +13,15 @@ videos (in the given order, or stably sorted by descending length) go to slots 0
 that falls free earliest, the lowest index among equals.  A slot whose video tracks its frame 1 at step s is busy on steps
 s .. s + T_v - 2; its next video is started BEHIND step s + T_v - 2 (DeviceTracker.start runs behind the step of the old video's
 last frame, so a refill costs no step) and tracks its frame 1 at step s + T_v - 1.
+
+VOS datasets: the OBJECTS of several videos share the B slots, every video is fused on the device at its own size
+and leaves as one run-length code per object per frame.
+
+    res = dataset.run_vos(tr, videos)                           # videos[v] = {'frames', 'object_ids', 'start', 'end', 'init'}
+    d = res['videos'][v]                                        # slots, size (h, w), object_ids, n, area [T,O], started [O]
+    rle.labels_decode(d['label_rle'][t], *d['size'])            # frame t's label map; rle.labels_to_coco: the submission dicts
+
+plan_vos() is its scheduler: a video holds n_obj slots for as many steps as it has frames, first fit on the lowest free slots.
 """
 import numpy as np
 
@@ -217,6 +226,211 @@ def run_videos(tracker, videos, pos, sz, B=None, order="longest", want_polygon=F
         d["size"] = sizes[v]
         if "sizes" in d and (d.pop("sizes") != np.asarray(sizes[v])).any():
             raise RuntimeError("run_videos: video %d was encoded at another size than its frames'" % v)
+    return {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}
+
+
+# ---- VOS datasets: the objects of several videos share the B slots -------------------------------------------------
+class PlanVos(object):
+    """what plan_vos() returns: G steps on B slots; first_step [V] (the step of a video's frame 0), slots[v] (ascending: object j
+    of the video sits on slots[v][j]), steps[g] = [(video, slots)] in the order of their first slot -- the groups of that step --,
+    lengths [V], n_obj [V], efficiency = sum(n_obj * length) / (G B)"""
+    __slots__ = ("G", "B", "first_step", "slots", "steps", "lengths", "n_obj", "efficiency")
+
+
+def plan_vos(lengths, n_obj, B, order="given"):
+    """The scheduler of run_vos, pure numpy.  Video v holds n_obj[v] slots for lengths[v] consecutive steps and step k of the video
+    is its frame k (frame 0 costs a step: its label planes are output).  At every step the queue -- the given order, or stably
+    sorted by descending length -- is scanned once: every video that fits into the currently free slots is started (first fit: a
+    later video may overtake one that does not fit) on the LOWEST free slots, its objects in ascending slot order."""
+    lengths, n_obj = [int(n) for n in lengths], [int(n) for n in n_obj]
+    if not lengths or len(lengths) != len(n_obj):
+        raise ValueError("plan_vos: at least one video, and one object count per video")
+    if int(B) != B or B < 1:
+        raise ValueError("plan_vos: B >= 1 slots, got %r" % (B,))
+    if min(lengths) < 1:
+        raise ValueError("plan_vos: every video has at least 1 frame, got %d" % min(lengths))
+    if min(n_obj) < 1 or max(n_obj) > B:
+        raise ValueError("plan_vos: every video has 1..%d objects (the slots), got %d and %d" % (B, min(n_obj), max(n_obj)))
+    if order not in ORDERS:
+        raise ValueError("plan_vos: order is one of %s, got %r" % (ORDERS, order))
+    B, V = int(B), len(lengths)
+    queue = sorted(range(V), key=lambda v: -lengths[v]) if order == "longest" else list(range(V))
+    p = PlanVos()
+    p.first_step, p.slots, p.steps = np.zeros(V, dtype=np.int64), [None] * V, []
+    until = [0] * B                                                   # the step from which a slot is free
+    g = 0
+    while queue:
+        free = [b for b in range(B) if until[b] <= g]
+        for v in list(queue):
+            if n_obj[v] <= len(free):
+                p.slots[v], free = free[:n_obj[v]], free[n_obj[v]:]
+                p.first_step[v] = g
+                for b in p.slots[v]:
+                    until[b] = g + lengths[v]
+                queue.remove(v)
+        g += 1
+    p.G, p.B = max(until), B
+    p.lengths, p.n_obj = np.asarray(lengths, dtype=np.int64), np.asarray(n_obj, dtype=np.int64)
+    p.steps = [[] for _ in range(p.G)]
+    for v in sorted(range(V), key=lambda v: p.slots[v][0]):
+        for g in range(int(p.first_step[v]), int(p.first_step[v]) + lengths[v]):
+            p.steps[g].append((v, p.slots[v]))
+    p.efficiency = float(sum(n * t for n, t in zip(n_obj, lengths))) / (p.G * B)
+    return p
+
+
+def _vos_video(v, d, B):
+    """the checked dictionary of video v of run_vos -> (T, h, w, ids uint8 [O], first [O], last [O], init_at(frame) -> [h,w])"""
+    import torch
+    if not isinstance(d, dict) or set(d) - {"frames", "object_ids", "start", "end", "init"} or \
+            not all(k in d for k in ("frames", "object_ids", "start", "end", "init")):
+        raise ValueError("run_vos: video %d = {'frames', 'object_ids', 'start', 'end', 'init'}" % v)
+    fr = d["frames"]
+    if not isinstance(fr, torch.Tensor) or not fr.is_cuda:
+        raise RuntimeError("siammask_amd.dataset runs on the MI355X only: video %d's frames must be a CUDA(HIP) tensor" % v)
+    if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3 or fr.shape[0] < 1 or not fr.is_contiguous():
+        raise ValueError("run_vos: video %d: frames must be contiguous uint8 [T,h,w,3], got %s %s" % (v, fr.dtype, tuple(fr.shape)))
+    T, h, w = (int(n) for n in fr.shape[:3])
+    ids = np.asarray(d["object_ids"])
+    if ids.ndim != 1 or ids.size < 1 or ids.size > B:
+        raise ValueError("run_vos: video %d has %d objects, the tracker %d slots (1..B objects per video)" % (v, ids.size, B))
+    if ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any() or len(set(ids.tolist())) != ids.size:
+        raise ValueError("run_vos: video %d: object_ids must be distinct integers in 0..255" % v)
+    first, last = np.zeros(ids.size, dtype=np.int64), np.zeros(ids.size, dtype=np.int64)
+    for j, i in enumerate(ids.tolist()):
+        for src, out in ((d["start"], first), (d["end"], last)):
+            if str(i) in src:
+                out[j] = int(src[str(i)])
+            elif i in src:
+                out[j] = int(src[i])
+            else:
+                raise ValueError("run_vos: video %d: object id %d is missing from 'start' / 'end'" % (v, i))
+        if not 0 <= first[j] < T:
+            raise ValueError("run_vos: video %d: object id %d starts on frame %d, the video has %d" % (v, i, first[j], T))
+    init = d["init"]
+    ok = isinstance(init, torch.Tensor) and init.is_cuda and init.dtype == torch.uint8 and init.device == fr.device
+    if not ok or tuple(init.shape) not in ((h, w), (T, h, w)):
+        raise ValueError("run_vos: video %d: init must be a uint8 CUDA tensor [%d,%d] or [%d,%d,%d] on the frames' device"
+                         % (v, h, w, T, h, w))
+    init_at = (lambda f: init[f].contiguous()) if init.dim() == 3 else (lambda f: init.contiguous())
+    return T, h, w, np.ascontiguousarray(ids.astype(np.uint8)), first, last, init_at
+
+
+def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
+    """The VOS loop of track_vos (tools/test.py:459-520, without an annotation) for a DATASET: the objects of several videos share the
+    B slots of ``tracker``, which this call reserves itself on the canvas of the largest h and w.  videos[v] = {'frames': uint8
+    CUDA [T,h,w,3], 'object_ids': 1..B ids, 'start' / 'end': {id: frame} (the dataset's dictionaries, as run(vos=) with lifetimes
+    takes them), 'init': uint8 CUDA [h,w] or [T,h,w]}.  plan_vos(lengths, object counts, B, order) places the videos; a video's
+    object j runs on its j-th slot.  Per step every video is fused on the device at its own size (smk_vos_rle_dev_v in the
+    paste-back's place) and leaves as one COCO run-length code per object; no mask, label or frame byte is copied.  An object
+    whose start frame is this step is `given` in the step's label launch and started BEHIND the step from the bounding
+    rectangle of init == id, taken on the device; all starts of one step, across videos, are ONE start event.  A slot outside
+    every video, and a member whose object has not started yet, is fed as run_videos feeds an idle slot.  cap: counts per object
+    (rle.default_cap of the canvas); chunk: steps per collect(), as run_videos (device memory stays within chunk * B * cap * 4
+    bytes; the result does not depend on it).  An object that is absent from its init labels starts nothing (started False); its
+    planes are unspecified, as run(vos=) with lifetimes leaves them.
+    Refused before any launch (ValueError): the rpn variant, a per-stream hp table, a video with more objects than B or with none,
+    an id missing from 'start' / 'end', a start frame outside the video, 'init' of the wrong shape, a bad cap or chunk.
+    -> {'videos': [per video, in the caller's order: {'slots', 'first_step', 'size': (h, w), 'object_ids', 'label_rle': per frame
+    a list of O int64 count arrays (None where n > cap), 'n' / 'area' int32 [T,O], 'started' bool [O]}], 'steps', 'efficiency',
+    'events'}; rle.labels_decode(d['label_rle'][t], *d['size']) is frame t's label map, rle.labels_to_coco its submission form."""
+    import torch
+    videos = list(videos)
+    V = len(videos)
+    if tracker.model.variant == "rpn":
+        raise ValueError("run_vos: the label planes need a variant with a mask branch")
+    if tracker.get_hp() is not None:
+        raise ValueError("run_vos: the tracker holds a per-stream hp table; its rows belong to slots and videos move between "
+                         "slots (set_hp(None) first)")
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError("run_vos: chunk >= 1 steps, got %r" % (chunk,))
+    if not V:
+        raise ValueError("run_vos: at least one video")
+    n_max = int(getattr(tracker.model, "_max_batch", 1))
+    Bq = min(n_max, 32) if B is None else B
+    if isinstance(Bq, bool) or int(Bq) != Bq or not 1 <= Bq <= 32:
+        raise ValueError("run_vos: B in 1..32 slots, got %r" % (B,))
+    B = int(Bq)
+    info = [_vos_video(v, d, B) for v, d in enumerate(videos)]
+    if len(set(d["frames"].device for d in videos)) != 1:
+        raise ValueError("run_vos: the videos must be on one device")
+    Hc, Wc = max(i[1] for i in info), max(i[2] for i in info)
+    cap = rle_host.default_cap(Hc, Wc) if cap is None else cap
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= Hc * Wc + 1 or max(Hc, Wc) > 4096:
+        raise ValueError("run_vos: cap must be an integer in 1..%d on a canvas of up to 4096 x 4096, got %r" % (Hc * Wc + 1, cap))
+    cap = int(cap)
+    pl = plan_vos([i[0] for i in info], [i[3].size for i in info], B, order)        # (refuses an unknown order)
+    dev = videos[0]["frames"].device
+    depth = int(getattr(tracker.model, "_pipeline", 0) or 0)
+    tracker.reserve(B, Hc, Wc, device=dev)
+    if tracker.pipeline and tracker.refine and depth > 1:
+        tracker.model.set_pipeline(depth)
+
+    events, started, ev_objs = [], [np.zeros(i[3].size, dtype=bool) for i in info], []
+    out = [{"slots": list(pl.slots[v]), "first_step": int(pl.first_step[v]), "size": (info[v][1], info[v][2]),
+            "object_ids": info[v][3].astype(np.int64), "label_rle": [None] * info[v][0],
+            "n": np.zeros((info[v][0], info[v][3].size), dtype=np.int32), "area": np.zeros((info[v][0], info[v][3].size), dtype=np.int32)}
+           for v in range(V)]
+    last, g0, rows = [None] * B, 0, None
+    for g in range(pl.G):
+        ids, alive, given = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
+        groups, sizes, init, begun = [], [], [], []
+        fed = list(last)
+        for v, slots in pl.steps[g]:
+            T, h, w, vid, first, end, init_at = info[v]
+            k = g - int(pl.first_step[v])
+            for j, b in enumerate(slots):
+                ids[b], given[b], alive[b] = vid[j], k == first[j], first[j] < k <= end[j]
+                if k > first[j]:                                      # started behind an earlier step: the slot follows the video
+                    fed[b] = videos[v]["frames"][k]
+                elif k == first[j]:
+                    begun.append((v, j, b))
+            groups.append(list(slots))
+            sizes.append((w, h))
+            init.append(init_at(k) if any(given[b] for b in slots) else None)
+        for b in range(B):
+            if fed[b] is None:                                        # a slot that never had an object: a canvas of zeros
+                fed[b] = torch.zeros((Hc, Wc, 3), dtype=torch.uint8, device=dev)
+        last = fed
+        if g == g0:                                                   # the chunk's counts and meta rows: ONE tensor each, no stack
+            n = min(int(chunk), pl.G - g0)
+            rows = (torch.empty((n, B, cap), dtype=torch.int32, device=dev), torch.empty((n, B, 4), dtype=torch.int32, device=dev))
+        tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
+                        _rle_out=(rows[0][g - g0], rows[1][g - g0]))
+        if begun:                                                     # ONE start event for every object that starts on this step
+            slots_b = [b for _, _, b in begun]
+            frames_b = [videos[v]["frames"][g - int(pl.first_step[v])] for v, _, _ in begun]
+            by_labels = []
+            for v in sorted(set(v for v, _, _ in begun)):
+                ids_v = np.full(B, int(info[v][3][0]), dtype=np.uint8)               # (a row per SLOT; the others repeat an id)
+                mine = [(j, b) for u, j, b in begun if u == v]
+                for j, b in mine:
+                    ids_v[b] = info[v][3][j]
+                by_labels.append((info[v][6](g - int(pl.first_step[v])), ids_v, [b for _, b in mine]))
+            zero = np.zeros((len(slots_b), 2))
+            streams, bits, _, _, _ = tracker._start_spec(frames_b, slots_b, zero, zero, None, None)
+            tracker._start_mixed(frames_b, streams, bits, None, None, by_labels=by_labels)
+            ev_objs.append(begun)
+            for (_, _, b), f in zip(begun, frames_b):
+                last[b] = f
+        if g + 1 - g0 == int(chunk) or g + 1 == pl.G:
+            res = tracker.collect(_rle=rows)
+            r = res["label_rle"]
+            per = rle_host.to_host_v(dict(r, counts=r["counts"][..., :int(min(r["n"].max(), r["cap"]))].cpu().numpy()))
+            for t in range(g0, g + 1):
+                for v, slots in pl.steps[t]:
+                    k, d = t - int(pl.first_step[v]), out[v]
+                    if (r["sizes"][t - g0, slots] != np.asarray(d["size"])).any():
+                        raise RuntimeError("run_vos: video %d was encoded at another size than its frames'" % v)
+                    d["label_rle"][k] = [per[t - g0][b] for b in slots]
+                    d["n"][k], d["area"][k] = r["n"][t - g0, slots], r["area"][t - g0, slots]
+            for e, objs in zip(res.get("events", []), ev_objs):
+                for (v, j, _), ok in zip(objs, e["started"]):
+                    started[v][j] = bool(ok)
+                events.append(dict(e, step=g0 + e["t"], objects=[(v, j) for v, j, _ in objs]))
+            ev_objs, g0, rows, res, r, per = [], g + 1, None, None, None, None
+    for v in range(V):
+        out[v]["started"] = started[v]
     return {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}
 
 

@@ -778,6 +778,137 @@ def paste_rle_v(logits, state, slot, canvas_wh, sizes=None, live=None, seg_thr=0
     return counts, meta
 
 
+class VosGroups(object):
+    """The checked groups of vos_rle_v / vos_rle_dev_v as the C entries take them, pure host work (no library, no device):
+    groups = [slot lists], sizes = [(w, h)] per group, init = None or per group None / a contiguous uint8 CUDA tensor [h_g,w_g],
+    live = None (all) or one boolean per group, object_ids / alive / given per SLOT (alive None: every member; given None: none).
+    Refused (ValueError): B or G out of range, an empty group, a slot in two groups or outside 0..B-1, a size outside the canvas,
+    a given slot whose group has no init labels, alive / given slots outside every group."""
+
+    def __init__(self, B, canvas_wh, groups, sizes, object_ids, alive=None, given=None, init=None, live=None):
+        W, H = int(canvas_wh[0]), int(canvas_wh[1])
+        if not 1 <= B <= 32:
+            raise ValueError("vos_rle_v: 1..32 slots, got %d" % B)
+        if not (1 <= W <= 4096 and 1 <= H <= 4096):
+            raise ValueError("vos_rle_v: canvas h, w in 1..4096, got %d x %d" % (H, W))
+        groups = [[int(b) for b in g] for g in groups]
+        G = len(groups)
+        if not 1 <= G <= B or len(sizes) != G:
+            raise ValueError("vos_rle_v: 1..%d groups with one (w, h) each, got %d and %d sizes" % (B, G, len(sizes)))
+        seen, masks = 0, []
+        for g, slots in enumerate(groups):
+            if not slots or min(slots) < 0 or max(slots) >= B or len(set(slots)) != len(slots):
+                raise ValueError("vos_rle_v: group %d must hold distinct slots in 0..%d, got %s" % (g, B - 1, slots))
+            m = sum(1 << b for b in slots)
+            if m & seen:
+                raise ValueError("vos_rle_v: group %d shares a slot with an earlier group" % g)
+            seen |= m
+            masks.append(m)
+        wh = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(G, 2))
+        if (wh < 1).any() or (wh[:, 0] > W).any() or (wh[:, 1] > H).any():
+            raise ValueError("vos_rle_v: a group's size %s does not fit the canvas %d x %d (w x h)" % (wh.tolist(), W, H))
+        ids = np.asarray(object_ids)
+        if ids.shape != (B,) or ids.dtype.kind not in "iu" or (ids < 0).any() or (ids > 255).any():
+            raise ValueError("vos_rle_v: object_ids must be %d integers in 0..255, one per slot" % B)
+
+        def bits(v, what, default):
+            if v is None:
+                return default
+            v = np.asarray(v)
+            if v.shape != (B,):
+                raise ValueError("vos_rle_v: %s must be %d booleans, one per slot" % (what, B))
+            return sum(1 << b for b in range(B) if v[b])
+        self.alive, self.given = bits(alive, "alive", seen), bits(given, "given", 0)
+        if (self.alive | self.given) & ~seen:
+            raise ValueError("vos_rle_v: alive / given name slots outside every group")
+        init = [None] * G if init is None else list(init)
+        if len(init) != G:
+            raise ValueError("vos_rle_v: init must hold one entry per group")
+        for g in range(G):
+            t, (w, h) = init[g], wh[g]
+            if t is None:
+                if self.given & masks[g]:
+                    raise ValueError("vos_rle_v: group %d has given members and no init labels" % g)
+            elif not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w) or \
+                    not t.is_contiguous():
+                raise ValueError("vos_rle_v: init of group %d must be a contiguous uint8 CUDA tensor [%d,%d]" % (g, h, w))
+        if live is None:
+            self.live = (1 << G) - 1
+        else:
+            live = list(live)
+            if len(live) != G:
+                raise ValueError("vos_rle_v: live must hold %d booleans, one per group" % G)
+            self.live = sum(1 << g for g in range(G) if live[g])
+        self.B, self.G, self.W, self.H, self.groups, self.init = B, G, W, H, groups, init
+        self.masks, self.wh = np.ascontiguousarray(masks, dtype=np.uint32), wh
+        self.ids = np.ascontiguousarray(ids.astype(np.uint8))
+        self.ptrs = (ctypes.c_void_p * G)(*[t.data_ptr() if t is not None else None for t in init])
+
+    def tail(self, seg_thr, padding, cap, ws, need, counts, meta):
+        """the arguments the two entries share, from the groups to the stream"""
+        return (self.G, self.masks.ctypes.data, self.wh.ctypes.data, self.ptrs, self.live, float(padding), self.ids.ctypes.data,
+                self.alive, float(seg_thr), self.given, cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr(),
+                _lib.current_stream_ptr())
+
+
+def vos_rle_v(logits, back_boxes, canvas_wh, groups, sizes, object_ids, alive=None, given=None, init=None, live=None, seg_thr=0.35,
+              padding=-1.0, cap=None, counts=None, meta=None):
+    """vos_rle for the objects of several videos in one launch (include/siammask_hip.h: smk_vos_rle_v).  logits [B, ms*ms]: one row
+    per SLOT; groups: the slot lists of the videos (ascending slot order is the object order), sizes: their (w, h), each within
+    canvas_wh; back_boxes: one box per slot (mapped into its group's frame; ignored for a slot in no group).  The other arguments
+    as VosGroups takes them.  The rows of a group's slots are those of vos_rle called at the group's size with the group's logits
+    rows, boxes and ids.  -> (counts int32 CUDA [B,cap], meta int32 CUDA [B,4] = (m, area, h_g, w_g); m = 0: a slot in no group,
+    or of a group that is not live); cap defaults to rle.default_cap of the canvas."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    B = int(logits.shape[0])
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != B:
+        raise ValueError("logits must be [B, ms*ms] with one back_box per slot")
+    v = VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    inv = np.zeros((B, 6), dtype=np.float64)
+    for slots, (w, h) in zip(v.groups, v.wh):
+        for b in slots:
+            inv[b] = invert_affine(crop_back_map(back_boxes[b], (int(w), int(h)))).reshape(6)
+    with torch.cuda.device(logits.device):
+        cap, ws, need, counts, meta = _rle_buffers(logits.device, B, v.W, v.H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_vos_rle_v(logits.data_ptr(), ms, inv.ctypes.data, B, v.W, v.H,
+                                            *v.tail(seg_thr, padding, cap, ws, need, counts, meta)))
+    return counts, meta
+
+
+def vos_rle_dev_v(logits, state, slot, canvas_wh, groups, sizes=None, object_ids=None, alive=None, given=None, init=None, live=None,
+                  seg_thr=0.35, padding=-1.0, head=None, mask_size=None, cap=None, counts=None, meta=None):
+    """vos_rle_v with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of every slot read on the device
+    from the tracker's state block (smk_vos_rle_dev_v).  groups may be a checked VosGroups (the tracker's paste job), the
+    arguments from sizes to live are then unused."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = int(src.shape[0])
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    v = groups if isinstance(groups, VosGroups) else VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    if v.B != B or (v.W, v.H) != (int(canvas_wh[0]), int(canvas_wh[1])):
+        raise ValueError("vos_rle_dev_v: the groups were checked for %d slots on %d x %d" % (v.B, v.W, v.H))
+    with torch.cuda.device(src.device):
+        cap, ws, need, counts, meta = _rle_buffers(src.device, B, v.W, v.H, cap, counts, meta)
+        _lib.check(_lib.lib().smk_vos_rle_dev_v(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, v.W, v.H, *v.tail(seg_thr, padding, cap, ws, need, counts, meta)))
+    return counts, meta
+
+
 def vot_overlap_dev(pred, gt, state, adv_rows=None, out=None, counts=None):
     """vot_overlap with the bounds of pair b taken on the device from record b of the tracker's state block (streams with
     their own frame sizes; include/siammask_hip.h: smk_vot_overlap_dev)"""

@@ -43,6 +43,8 @@ tr.state['im_w'] / ['im_h'] are then per-stream arrays; a slot may be started ag
 track(), gt= / vos= / labels_out= (the objects of VOS share one frame) raise ValueError in this mode.
 A whole dataset of such videos, of different lengths, through the B slots: siammask_amd.dataset.run_videos (the masks then leave as
 run-length codes at each video's own size, through the private _rle_v of enqueue(); the public rle= stays refused under mixed sizes).
+A VOS dataset -- the objects of several videos sharing the B slots, each video fused at its own size into per-object run-length codes:
+siammask_amd.dataset.run_vos (the private _vos_v of enqueue(); gt= / vos= with lists or under mixed sizes stay refused).
 
 The VOT supervised loop (track_vot, :318-365) for B videos in lock-step, still enqueue-only: the overlap of every tracked polygon
 with its annotation is computed on the device (csrc/vot_overlap.hip), the host learns of a loss through a read-back that lags
@@ -121,7 +123,8 @@ def _box_corners(pos, sz):
 # sizes: None, or (mixed sizes) the int32 [B,2] (w, h) of the streams' frames when the frame was enqueued: mask is then the canvas
 # iou: None, or the _Iou of a frame enqueued with iou= (mask is then None for a score-only frame)
 # rle: None, or the _Rle of a frame enqueued with rle= (mask is then None unless a polygon or the masks were asked for)
-_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou rle", defaults=(None, None))
+# vos_v: None, or the _VosV of a frame enqueued with the private _vos_v (mask is then None: the label planes stand in its place)
+_Job = collections.namedtuple("_Job", "logits head slot mask rbox score after adv sizes iou rle vos_v", defaults=(None, None, None))
 # a checked rle= request (_rle_spec): counts per stream, masks wanted; enqueue() adds the frame's counts [B,cap] and meta [B,4]
 # live: None, or (the private _rle_v of enqueue(): streams with their own sizes) the bit mask of the slots that have a video this step
 _Rle = collections.namedtuple("_Rle", "cap masks counts meta live", defaults=(None,))
@@ -131,6 +134,9 @@ _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row label
 # a checked vos['rle'] request (_vos_spec): counts per object, masks / label map wanted beside the counts; enqueue() adds the
 # frame's counts [B,cap] and meta [B,4]
 _LabelRle = collections.namedtuple("_LabelRle", "cap masks labels counts meta")
+# the checked _vos_v of enqueue() (dataset.run_vos: the objects of several videos share the slots): the frame's _LabelRle and the
+# preproc.VosGroups the C entry takes
+_VosV = collections.namedtuple("_VosV", "rle groups")
 # a checked iou= request (_iou_spec): annotation, thresholds, masks wanted, frame scored; enqueue() adds the frame's count row
 _Iou = collections.namedtuple("_Iou", "gt thrs masks scored row")
 _IOU_MAX_THR = 16
@@ -140,13 +146,14 @@ _Event = collections.namedtuple("_Event", "t streams res")            # one star
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
     __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes", "rle",
-                 "label_rle")
+                 "label_rle", "vos_v")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
         self.iou_k = None                                             # thresholds of a chunk enqueued with iou=
         self.rle = None                                               # the _Rle of every frame of a chunk enqueued with rle=
         self.label_rle = None                                         # the _LabelRle of every frame of a chunk enqueued with vos['rle']
+        self.vos_v = False                                            # ... or with _vos_v: the meta rows carry (h, w) per slot as well
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
         self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
@@ -534,8 +541,12 @@ class DeviceTracker(object):
             r.data, r.row_bytes, r.w, r.h = f.data_ptr(), max(int(f.stride(0)), 3 * int(f.shape[1])), int(f.shape[1]), int(f.shape[0])
         return refs
 
-    def _start_mixed(self, frames, streams, bits, hpos, hsz):
-        """start() with a frame of its own size per started stream: the launches of start() through the _v entries"""
+    def _start_mixed(self, frames, streams, bits, hpos, hsz, by_labels=None):
+        """start() with a frame of its own size per started stream: the launches of start() through the _v entries.
+        by_labels (private, dataset.run_vos; hpos / hsz are then None): [(labels uint8 CUDA [h,w] contiguous, ids uint8 [B], slots)],
+        one entry per video that starts objects in this event -- the targets of its slots are the bounding rectangles of
+        labels == ids[slot], taken on the device: smk_label_rects per video into a scratch [B,4], its slots' rows copied on the
+        device into the rectangle table smk_trk_start_v reads.  ONE event whatever the number of videos; the host reads nothing"""
         q, L = self._fr, _lib.lib()
         c, B = q.chunk, q.B
         wh = [(int(f.shape[1]), int(f.shape[0])) for f in frames]
@@ -550,7 +561,14 @@ class DeviceTracker(object):
             self._fr_flush(sp)                                        # (a deferred frame is pasted at the size its slot still has)
             _lib.check(L.smk_frame_sums_v(refs, B, q.sums.data_ptr(), sp))
             res = torch.empty((B, START_ROW), dtype=torch.float64, device=q.device)
-            _lib.check(L.smk_trk_start_v(q.dev.data_ptr(), B, ctypes.byref(q.cfg), bits, None, hpos.ctypes.data, hsz.ctypes.data,
+            for labels, ids, slots in by_labels or ():
+                scratch = torch.empty((B, 4), dtype=torch.int32, device=q.device)
+                _lib.check(L.smk_label_rects(labels.data_ptr(), int(labels.shape[1]), int(labels.shape[0]), ids.ctypes.data, B,
+                                             scratch.data_ptr(), sp))
+                for b in slots:
+                    q.rects[b].copy_(scratch[b])
+            _lib.check(L.smk_trk_start_v(q.dev.data_ptr(), B, ctypes.byref(q.cfg), bits, q.rects.data_ptr() if by_labels else None,
+                                         hpos.ctypes.data if hpos is not None else None, hsz.ctypes.data if hsz is not None else None,
                                          q.sums.data_ptr(), 1, im_wh.ctypes.data, q.win.data_ptr(), res.data_ptr(), sp))
             _lib.check(L.smk_crop_exemplar_dev_v(refs, q.dev.data_ptr(), q.win.data_ptr(), res.data_ptr(), bits, B,
                                                  self.p.exemplar_size, q.z_all.data_ptr(), sp))
@@ -775,6 +793,26 @@ class DeviceTracker(object):
             raise ValueError("vos['rle']['labels']: the label map comes from the scoring launch, which needs gt=")
         return _LabelRle(int(cap), bool(lr.get("masks", False)), bool(lr.get("labels", False)), None, None)
 
+    def _vos_v_spec(self, mixed, want_mask, other, vos_v):
+        """the checked _vos_v of one frame (before anything is launched) -> None, or a _VosV (counts / meta still None).  other:
+        the frame also asks for a polygon, mask_out=, rle= / _rle_v, iou= or carries the hook of run(vot=)"""
+        if vos_v is None:
+            return None
+        q = self._fr
+        if not mixed or other or q.B > 32:
+            raise ValueError("_vos_v comes with a list of frames (up to 32 slots) and nothing else that returns or scores masks")
+        if self.model.variant == "rpn" or not want_mask:
+            raise ValueError("_vos_v needs want_mask and a variant with a mask branch")
+        cap, groups, sizes, ids, alive, given, init, live = vos_v
+        from . import rle as rle_host
+        cap = rle_host.default_cap(q.H, q.W) if cap is None else cap
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= q.H * q.W + 1:
+            raise ValueError("_vos_v: cap must be an integer in 1..%d (the canvas + 1), got %r" % (q.H * q.W + 1, cap))
+        v = preproc.VosGroups(q.B, (q.W, q.H), groups, sizes, ids, alive, given, init, live)
+        if q.chunk.pending and (not q.chunk.vos_v or q.chunk.label_rle[0].cap != int(cap)):
+            raise ValueError("every frame of a chunk carries _vos_v with one cap, or none does")
+        return _VosV(_LabelRle(int(cap), False, False, None, None), v)
+
     def _iou_spec(self, mixed, want_mask, want_polygon, mask_out, scored_vos, iou):
         """the checked iou= request of one frame (before anything is launched) -> None, or an _Iou (row still None)"""
         if iou is None:
@@ -832,7 +870,7 @@ class DeviceTracker(object):
         return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -864,6 +902,11 @@ class DeviceTracker(object):
         with want_polygon smk_paste_mask_dev_v -> rotated box -> smk_rle_encode_v on one canvas the queue keeps, so collect()
         reports no mask either way).  A slot that is not live is tracked, but nothing of its code is computed: n = 0.  The chunk
         rule of rle= holds (every frame, one cap); collect() returns res['rle'] with 'sizes' int32 [T,B,2] (h, w) for 'size'.
+        _vos_v (private, dataset.run_vos): (cap or None, groups, sizes, ids, alive, given, init, live) as preproc.VosGroups takes
+        them, with a LIST of frames -- the slots hold the objects of several videos, every group is fused at its own size and
+        smk_vos_rle_dev_v stands in the paste-back's place: no mask byte, no label byte.  Every frame of a chunk carries it (one
+        cap) or none does; not with want_polygon, mask_out=, gt= / vos= / iou= / rle= / _rle_v.  collect() returns res['label_rle']
+        with 'sizes' int32 [T,B,2] (h, w) for 'size'; n = 0 where a slot is in no live group.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -886,7 +929,7 @@ class DeviceTracker(object):
         want_mask = want_mask and self.model.variant != "rpn"
         want_polygon = want_polygon and want_mask
         self._mask_out(mask_out, want_mask=want_mask)
-        if c.pending and (c.vos_k is not None or c.label_rle is not None) != (vos is not None or gt is not None):
+        if c.pending and (c.vos_k is not None or c.label_rle is not None) != (vos is not None or gt is not None or _vos_v is not None):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
         if c.pending and (c.iou_k is not None) != (iou is not None):
             raise ValueError("every frame of a chunk carries iou=, or none does")
@@ -908,6 +951,8 @@ class DeviceTracker(object):
         if c.pending and c.rle is not None and (c.rle[0].live is None) != (rle.live is None):
             raise ValueError("every frame of a chunk carries _rle_v, or none does")
         iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
+        vv = self._vos_v_spec(mixed, want_mask, want_polygon or mask_out is not None or rle is not None or iou is not None
+                              or _after is not None, _vos_v)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
         L, model = _lib.lib(), self.model
@@ -945,6 +990,11 @@ class DeviceTracker(object):
                 rc, rm = _rle_out if _rle_out is not None else (torch.empty((B, rle.cap), dtype=torch.int32, device=q.device),
                                                                 torch.empty((B, 4), dtype=torch.int32, device=q.device))
                 rle = rle._replace(counts=rc, meta=rm)
+            if vv is not None:
+                rc, rm = _rle_out if _rle_out is not None else (torch.empty((B, vv.rle.cap), dtype=torch.int32, device=q.device),
+                                                                torch.empty((B, 4), dtype=torch.int32, device=q.device))
+                vv = vv._replace(rle=vv.rle._replace(counts=rc, meta=rm))
+                c.labels.append(None)
             dev_ptr = q.dev.data_ptr()
             if mixed:
                 _lib.check(L.smk_crop_resize_dev_v(self._image_refs(frame, list(range(B))), dev_ptr, B, self.p.instance_size,
@@ -975,11 +1025,13 @@ class DeviceTracker(object):
                     mask = q.canvas
                 elif lr is not None and not (want_polygon or lr.masks or mask_out is not None):
                     pass                                              # smk_vos_rle_dev stands in the paste-back's place: likewise
+                elif vv is not None:
+                    pass                                              # smk_vos_rle_dev_v: likewise
                 elif iou is None or iou.masks:                        # (a score-only frame has no mask anywhere)
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
                            q.rbox[blk][i] if want_polygon else None, score, _after, q.rows[blk][i] if _after is not None else None,
-                           sizes if mixed else None, iou, rle)
+                           sizes if mixed else None, iou, rle, vv)
                 if depth:
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
@@ -989,6 +1041,8 @@ class DeviceTracker(object):
                 c.rle = (c.rle or []) + [rle]
             if score is not None and score.rle is not None:
                 c.label_rle = (c.label_rle or []) + [score.rle]
+            if vv is not None:
+                c.label_rle, c.vos_v = (c.label_rle or []) + [vv.rle], True
             c.sizes.append(sizes if mixed else None)
             c.poly.append(bool(want_polygon))
             c.pending = t + 1
@@ -1024,6 +1078,10 @@ class DeviceTracker(object):
             preproc.rle_encode_v(mask, job.sizes, live=live, cap=r.cap, counts=r.counts, meta=r.meta)
         elif r is not None and mask is not None:                      # the bytes exist: encode them, same stream
             preproc.rle_encode(mask, cap=r.cap, counts=r.counts, meta=r.meta)
+        if job.vos_v is not None:                                     # the label planes of every live group, in the paste-back's place
+            vr = job.vos_v.rle
+            preproc.vos_rle_dev_v(logits, q.dev, job.slot, (q.W, q.H), job.vos_v.groups, seg_thr=p.seg_thr, head=head,
+                                  mask_size=self.mask_size, cap=vr.cap, counts=vr.counts, meta=vr.meta)
         if lr is not None and s.labels is None:                       # the fused label planes, in the paste-back's place: no label byte
             preproc.vos_rle_dev(logits, q.dev, job.slot, (q.W, q.H), s.ids, init=s.init, seg_thr=p.seg_thr, head=head,
                                 mask_size=self.mask_size, cap=lr.cap, counts=lr.counts, meta=lr.meta, _bits=(s.bits, s.gbits))
@@ -1110,7 +1168,7 @@ class DeviceTracker(object):
                     vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
                     vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
-                nm = 4 if c.rle is not None and c.rle[0].live is not None else 2      # _rle_v: (h, w) of the meta rows as well
+                nm = 4 if (c.rle is not None and c.rle[0].live is not None) or c.vos_v else 2      # _rle_v / _vos_v: (h, w) as well
                 if enc is not None:                                   # (m, area) of the meta rows ride along as float64 (exact)
                     rmeta = _rle[1] if _rle is not None and _rle[1].shape[0] == T else torch.stack([r.meta for r in enc])
                     rows = torch.cat([rows, rmeta[:, :, :nm].to(torch.float64)], dim=2)
@@ -1128,12 +1186,13 @@ class DeviceTracker(object):
         if T:
             if rle_host is not None:
                 counts = _rle[0] if _rle is not None and _rle[0].shape[0] == T else torch.stack([r.counts for r in enc])
-                res["rle" if c.rle is not None else "label_rle"] = {
+                key = "rle" if c.rle is not None else "label_rle"
+                res[key] = {
                     "counts": counts, "n": np.ascontiguousarray(rle_host[:, :, 0]), "area": np.ascontiguousarray(rle_host[:, :, 1]),
                     "cap": enc[0].cap, "size": (q.H, q.W)}
                 if nm == 4:                                           # per (frame, stream): (h, w) as the kernel read them
-                    del res["rle"]["size"]
-                    res["rle"]["sizes"] = np.ascontiguousarray(rle_host[:, :, 2:4])
+                    del res[key]["size"]
+                    res[key]["sizes"] = np.ascontiguousarray(rle_host[:, :, 2:4])
             masks = c.masks
             if all(m is not None for m in masks):
                 res["mask"] = _masks if _masks is not None and _masks.shape[0] == T else torch.stack(masks)
