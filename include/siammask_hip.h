@@ -448,6 +448,42 @@ int smk_vos_rle_dev_v(const float *logits_dev, const float *head_dev, int score_
                       uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
                       uint32_t *counts_out_dev, int32_t *meta_out_dev, void *stream);
 
+/* ---- the scores of several videos in one launch (additive; smk_version() keeps reporting 1.10, the presence of these symbols is
+ * the probe) --------------------------------------------------------------------------------------------------------------------------
+ * The grouped, per-size forms of smk_vos_score_ex / smk_vos_score_dev_ex (below): the per-frame counts of MultiBatchIouMeter for
+ * the objects of up to B videos that share the B (1..32) slots of a mixed-size batch.  The groups are those of smk_vos_rle_v:
+ * group_masks[g] (non-empty, bits below B, pairwise disjoint), (w_g, h_g) = group_wh[g] within canvas_w x canvas_h (both in
+ * 1..4096), init_labels_dev[g] uint8 [h_g][w_g] or NULL (init_labels_dev itself may be NULL); object_ids[B], alive_mask and
+ * given_mask are per SLOT, live_groups is a bit mask over the groups.  gt_dev[g] is the annotation of group g, uint8 [h_g][w_g] at
+ * pitch w_g (object id per pixel), or NULL: this video is not scored on this step.  group_masks, group_wh and the two pointer
+ * arrays gt_dev / init_labels_dev are HOST arrays that travel as kernel arguments, as thrs and object_ids do: no device table, and
+ * nothing of the caller's host memory is read after the call returns.
+ * For a pixel (x, y) of group g, over the members b of g in ascending slot order: prob_b = bit b of given_mask ?
+ * (init_labels_dev[g][y][x] == object_ids[b] ? 1.0f : 0.0f) : bit b of alive_mask ? the warped probability of slot b's logits row
+ * through slot b's inverse map (inv_map[b] of the host array [B][6], or inv_map[slot] of record b) : -1.0f; best = max_b prob_b,
+ * arg = the first member attaining it (a strict > scan); for each of the n_thr (1..8) thresholds k, above = (double)best >
+ * thrs[k] -- the FLOAT64 comparison of smk_vos_score -- and for each member j of g:
+ *   pred = above && arg == j;  tgt = gt_dev[g][y][x] == object_ids[j];
+ *   counts[j][k][0] += pred && tgt (intersection);  counts[j][k][1] += pred || tgt (union).
+ * A pixel's gt byte is matched against the ids of its OWN group's members only: two videos may use the same id.  The rows of a
+ * group's slots are the rows smk_vos_score_ex gives when called at (w_g, h_g) with the group's logits rows, maps, ids and gt
+ * gathered.  counts_out_dev: int32 [B][n_thr][2] indexed by SLOT, fully defined by the call (zeroed on `stream` by the call
+ * itself), exact and reproducible (integer sums); a slot in no group, or in a group whose live_groups bit is clear or whose gt is
+ * NULL, keeps zeros and nothing of it is computed.  No label byte is written: smk_vos_rle_dev_v has the labels.
+ * Bad arguments -- everything smk_vos_rle_v refuses about slots, groups, sizes, member bits, given_mask bits of a group without
+ * init labels, given_mask or alive_mask bits outside every group, a slot outside 0..1, a null pointer; n_thr outside 1..8, a null
+ * thrs, a null gt_dev, a gt_dev whose entries are ALL NULL, a counts_out_dev that is not 4-byte aligned -- give SMK_E_ARG before
+ * anything is enqueued, the zeroing of the counts included.  No context; asynchronous on `stream`, no host synchronisation. */
+int smk_vos_score_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                    const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *gt_dev,
+                    const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                    uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr, int32_t *counts_out_dev, void *stream);
+int smk_vos_score_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                        int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                        const uint8_t *const *gt_dev, const uint8_t *const *init_labels_dev, uint32_t live_groups, float border,
+                        const uint8_t *object_ids, uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr,
+                        int32_t *counts_out_dev, void *stream);
+
 /* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
  * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
  * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:

@@ -43,7 +43,7 @@ SYMBOLS = (
     "smk_rle_workspace", "smk_rle_encode", "smk_paste_rle_dev", "smk_test_rle_encode",
     "smk_paste_rle_dev_v", "smk_rle_encode_v", "smk_test_rle_encode_v",
     "smk_labels_rle_encode", "smk_vos_rle", "smk_vos_rle_dev",
-    "smk_vos_rle_v", "smk_vos_rle_dev_v",
+    "smk_vos_rle_v", "smk_vos_rle_dev_v", "smk_vos_score_v", "smk_vos_score_dev_v",
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
     "smk_ope_curve", "smk_host_ope_curve",
@@ -204,6 +204,10 @@ def lib():
     rle_v_tail = [ci, vp, vp, vp, u32, cf, vp, u32, cf, u32, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_vos_rle_v.argtypes = [fp, ci, vp, ci, ci, ci] + rle_v_tail
     L.smk_vos_rle_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci] + rle_v_tail
+    # groups (count, masks, sizes, gt pointers, init label pointers, live mask), border, ids, alive, given, thrs, their number, counts, stream
+    score_v_tail = [ci, vp, vp, vp, vp, u32, cf, vp, u32, u32, vp, ci, vp, vp]
+    L.smk_vos_score_v.argtypes = [fp, ci, vp, ci, ci, ci] + score_v_tail
+    L.smk_vos_score_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci] + score_v_tail
     L.smk_vot_traj_overlap.argtypes = [vp] * 8 + [ci] * 5 + [vp, vp, vp]
     L.smk_eao_workspace_bytes.argtypes = [ci, ci]
     L.smk_eao_curve.argtypes = [vp] * 4 + [ci] * 7 + [vp, ctypes.c_size_t, vp, vp, vp, vp]

@@ -435,6 +435,134 @@ int launch_vos_score(const VosParams &p, void *stream) {
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- the counts of G videos in one launch (smk_vos_score_v / smk_vos_score_dev_v) ------------------------------------------------------
+// vos_score_kernel per GROUP of slots, in the frame of rle_bits_labels_v_kernel: blockIdx.z is the group; its member mask, size, gt
+// and init labels are kernarg fields indexed by it (scalar registers).  The grid covers the CANVAS; the three exits -- a clear
+// live_groups bit, no gt, a workgroup wholly outside w_g x h_g -- are block-uniform and stand before the first barrier and the first
+// ballot.  Inside a partial workgroup lanes with x >= w_g reach every ballot with in_x false and the rows stop at h_g, as in the
+// parent.  The members are walked by clearing the lowest set bit of the (scalar) mask, so logits row, record, id, alive and given
+// bit of a slot are scalar; `arg` is the SLOT: the LDS counters are [B][K][2] as the output is and no rank table exists.  A pixel's
+// gt is matched against the ids of its own group's members only.  One global atomic add per non-zero counter per workgroup.
+template <bool DEV, bool GIVEN>
+__global__ __launch_bounds__(256) void vos_score_v_kernel(const VosScoreVParams p) {
+    __shared__ int cnt[TRK_SET_MAX_B * VOS_MAX_THR * 2];
+    const int g = blockIdx.z;
+    if (!((p.live_groups >> g) & 1)) return;
+    const unsigned char *gt = p.gt[g];
+    if (!gt) return;
+    const int W = p.gwh[g][0], H = p.gwh[g][1];
+    if ((int)blockIdx.x * 256 >= W || (int)blockIdx.y * VOS_ROWS >= H) return;
+    const unsigned members = p.gmask[g];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int K = p.n_thr, n = p.B * K * 2;
+    for (int i = tid; i < n; i += 256) cnt[i] = 0;
+    __syncthreads();
+    const int x = blockIdx.x * 256 + tid;
+    const bool in_x = x < W;
+    const int y0 = blockIdx.y * VOS_ROWS, y1 = min(y0 + VOS_ROWS, H);
+    for (int y = y0; y < y1; ++y) {
+        float best = -1.f;
+        int arg = 0, t = -1;
+        unsigned abv = 0;                                             // bit k: (double)best > thr[k]
+        if (in_x) {
+            const size_t px = (size_t)y * W + x;
+            for (unsigned m = members; m; m &= m - 1) {
+                const int b = __ffs(m) - 1;
+                float v = -1.f;
+                bool given = false;
+                if constexpr (GIVEN) {
+                    given = (p.given >> b) & 1;
+                    if (given) v = p.init[g][px] == p.ids[b] ? 1.f : 0.f;
+                }
+                if (!given && ((p.alive >> b) & 1)) {
+                    if constexpr (DEV) {
+                        const smk_trk_stream *s = p.st + b;
+                        const float *lg = p.logits + (size_t)b * p.ms * p.ms;
+                        int ls = 1;
+                        if (p.head_S) {
+                            ls = p.head_S * p.head_S;
+                            const int dy = min(max(s->delta_yx[p.slot][0], 0), p.head_S - 1);
+                            const int dx = min(max(s->delta_yx[p.slot][1], 0), p.head_S - 1);
+                            lg = p.logits + (size_t)b * p.ms * p.ms * ls + dy * p.head_S + dx;
+                        }
+                        v = warped_prob(p, s->inv_map[p.slot], lg, ls, x, y);
+                    } else {
+                        v = warped_prob(p, p.inv_map[b], p.logits + (size_t)b * p.ms * p.ms, 1, x, y);
+                    }
+                }
+                if (m == members || v > best) { best = v; arg = b; }  // np.argmax keeps the first maximum
+            }
+            t = gt[px];
+            for (int k = 0; k < K; ++k) abv |= ((double)best > p.thr[k] ? 1u : 0u) << k;
+        }
+        // predictions: the lanes above some threshold, grouped by arg (a slot of this group)
+        const bool hit = in_x && abv != 0;
+        unsigned long long todo = __ballot(hit);
+        while (todo) {
+            const int a = __builtin_amdgcn_readfirstlane(__shfl(arg, __ffsll((long long)todo) - 1));
+            const bool same = hit && arg == a;
+            todo &= ~__ballot(same);
+            const bool tgt = t == p.ids[a];
+            for (int k = 0; k < K; ++k) {
+                const bool pred = same && ((abv >> k) & 1);
+                const int u = __popcll(__ballot(pred)), it = __popcll(__ballot(pred && tgt));
+                if (lane == 0 && u) {
+                    atomicAdd(&cnt[(a * K + k) * 2 + 1], u);
+                    if (it) atomicAdd(&cnt[(a * K + k) * 2], it);
+                }
+            }
+        }
+        // targets: the lanes grouped by gt; every member with that id takes the pixels its prediction has not counted
+        todo = __ballot(in_x);
+        while (todo) {
+            const int tt = __builtin_amdgcn_readfirstlane(__shfl(t, __ffsll((long long)todo) - 1));
+            const bool same = in_x && t == tt;
+            todo &= ~__ballot(same);
+            for (unsigned m = members; m; m &= m - 1) {
+                const int j = __ffs(m) - 1;
+                if (p.ids[j] != tt) continue;
+                for (int k = 0; k < K; ++k) {
+                    const int u = __popcll(__ballot(same && !(((abv >> k) & 1) && arg == j)));
+                    if (lane == 0 && u) atomicAdd(&cnt[(j * K + k) * 2 + 1], u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int v = cnt[i];
+        if (v) atomicAdd(p.counts + i, v);
+    }
+}
+
+int launch_vos_score_v(const VosScoreVParams &p, void *stream) {
+    if (p.B < 1 || p.B > TRK_SET_MAX_B || p.n_groups < 1 || p.n_groups > p.B || p.n_thr < 1 || p.n_thr > VOS_MAX_THR) return -1;
+    if (p.W < 1 || p.H < 1 || p.W > RLE_MAX_SIDE || p.H > RLE_MAX_SIDE || !p.logits || !p.counts || p.ms < 1) return -1;
+    unsigned seen = 0, given = 0;
+    bool scored = false;
+    for (int g = 0; g < p.n_groups; ++g) {                            // (the entry has said why; nothing out of range is launched)
+        const unsigned m = p.gmask[g];
+        if (!m || (m & seen) || (p.B < 32 && (m >> p.B))) return -1;
+        if (p.gwh[g][0] < 1 || p.gwh[g][1] < 1 || p.gwh[g][0] > p.W || p.gwh[g][1] > p.H) return -1;
+        if ((p.given & m) && !p.init[g]) return -1;
+        seen |= m;
+        scored = scored || p.gt[g];
+        if (((p.live_groups >> g) & 1) && p.gt[g]) given |= p.given & m;
+    }
+    if (((p.given | p.alive) & ~seen) || !scored) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(p.counts, 0, sizeof(int) * 2 * p.B * p.n_thr, s) != hipSuccess) return -4;
+    const dim3 grid((p.W + 255) / 256, (p.H + VOS_ROWS - 1) / VOS_ROWS, p.n_groups);
+    if (given) {
+        if (p.st) hipLaunchKernelGGL((vos_score_v_kernel<true, true>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((vos_score_v_kernel<false, true>), grid, dim3(256), 0, s, p);
+    } else {
+        if (p.st) hipLaunchKernelGGL((vos_score_v_kernel<true, false>), grid, dim3(256), 0, s, p);
+        else      hipLaunchKernelGGL((vos_score_v_kernel<false, false>), grid, dim3(256), 0, s, p);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 // ------------------------------------------------------------------------------------------
 // Per-stream IoU counts (utils/average_meter_helper.py:71-113 IouMeter.add, the per-frame part) fused with the paste-back: the B
 // streams are INDEPENDENT single-object runs (B grid points of one video, tools/tune_vos.py), each scored against gt > 0:

@@ -1127,6 +1127,81 @@ int smk_vos_rle_dev_v(const float *logits_dev, const float *head_dev, int score_
     return 0;
 }
 
+// ---- the counts of G videos in one launch -------------------------------------------------------------------------
+// the checks and the fields both entries share -- the groups as vos_rle_fill_v checks them, then gt, thresholds and the output;
+// everything is refused here, before anything is enqueued (the memset of the counts included)
+static int vos_score_fill_v(const char *who, VosScoreVParams &p, const float *src, int mask_size, int B, int canvas_w, int canvas_h,
+                            int n_groups, const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *gt_dev,
+                            const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                            uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr, int32_t *counts_out_dev) {
+    if (!src || !object_ids || !group_masks || !group_wh || !gt_dev || !thrs || !counts_out_dev)
+        return fail(SMK_E_ARG, "%s: null argument", who);
+    if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d slots (1..%d)", who, B, TRK_SET_MAX_B);
+    if (n_groups < 1 || n_groups > B) return fail(SMK_E_ARG, "%s: %d groups (1..%d, the slots)", who, n_groups, B);
+    if (n_thr < 1 || n_thr > VOS_MAX_THR) return fail(SMK_E_ARG, "%s: %d thresholds (1..%d)", who, n_thr, VOS_MAX_THR);
+    if (mask_size < 1 || canvas_w < 1 || canvas_h < 1 || canvas_w > RLE_MAX_SIDE || canvas_h > RLE_MAX_SIDE)
+        return fail(SMK_E_ARG, "%s: bad geometry (canvas %d x %d in 1..%d, mask %d)", who, canvas_w, canvas_h, RLE_MAX_SIDE, mask_size);
+    if ((uintptr_t)counts_out_dev & 3) return fail(SMK_E_ARG, "%s: misaligned output (4 bytes)", who);
+    memset(&p, 0, sizeof(p));
+    uint32_t seen = 0;
+    bool scored = false;
+    for (int g = 0; g < n_groups; ++g) {
+        const uint32_t m = group_masks[g];
+        const int w = group_wh[2 * g], h = group_wh[2 * g + 1];
+        if (!m) return fail(SMK_E_ARG, "%s: group %d is empty", who, g);
+        if (B < 32 && (m >> B)) return fail(SMK_E_ARG, "%s: group %d (%#x) has member bits at or above %d slots", who, g, m, B);
+        if (m & seen) return fail(SMK_E_ARG, "%s: group %d (%#x) overlaps an earlier group", who, g, m);
+        if (w < 1 || h < 1 || w > canvas_w || h > canvas_h)
+            return fail(SMK_E_ARG, "%s: group %d is %d x %d, the canvas %d x %d", who, g, w, h, canvas_w, canvas_h);
+        const uint8_t *init = init_labels_dev ? init_labels_dev[g] : nullptr;
+        if ((given_mask & m) && !init) return fail(SMK_E_ARG, "%s: given_mask %#x names members of group %d, which has no init labels", who, given_mask, g);
+        seen |= m;
+        scored = scored || gt_dev[g];
+        p.gmask[g] = m; p.gwh[g][0] = w; p.gwh[g][1] = h; p.gt[g] = gt_dev[g]; p.init[g] = init;
+    }
+    if (given_mask & ~seen) return fail(SMK_E_ARG, "%s: given_mask %#x has bits outside every group (%#x)", who, given_mask, seen);
+    if (alive_mask & ~seen) return fail(SMK_E_ARG, "%s: alive_mask %#x has bits outside every group (%#x)", who, alive_mask, seen);
+    if (!scored) return fail(SMK_E_ARG, "%s: no group has a gt: nothing to score", who);
+    p.logits = src; p.counts = counts_out_dev;
+    p.W = canvas_w; p.H = canvas_h; p.ms = mask_size; p.n_groups = n_groups; p.B = B; p.n_thr = n_thr;
+    p.border = border; p.alive = alive_mask; p.given = given_mask; p.live_groups = live_groups;
+    for (int k = 0; k < n_thr; ++k) p.thr[k] = thrs[k];
+    for (int b = 0; b < B; ++b) p.ids[b] = object_ids[b];
+    return 0;
+}
+
+int smk_vos_score_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                    const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *gt_dev,
+                    const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                    uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr, int32_t *counts_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_score_v: null argument");
+    VosScoreVParams p;
+    CHK(vos_score_fill_v("smk_vos_score_v", p, logits_dev, mask_size, B, canvas_w, canvas_h, n_groups, group_masks, group_wh, gt_dev,
+                         init_labels_dev, live_groups, border, object_ids, alive_mask, given_mask, thrs, n_thr, counts_out_dev));
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < 6; ++k) p.inv_map[b][k] = inv_map[6 * b + k];
+    if (launch_vos_score_v(p, stream)) return fail(SMK_E_HIP, "vos_score_v launch failed");
+    return 0;
+}
+
+int smk_vos_score_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                        int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                        const uint8_t *const *gt_dev, const uint8_t *const *init_labels_dev, uint32_t live_groups, float border,
+                        const uint8_t *object_ids, uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr,
+                        int32_t *counts_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_score_dev_v: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_score_dev_v: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_score_dev_v: score_size %d", score_size);
+    VosScoreVParams p;
+    CHK(vos_score_fill_v("smk_vos_score_dev_v", p, head_dev ? head_dev : logits_dev, mask_size, B, canvas_w, canvas_h, n_groups,
+                         group_masks, group_wh, gt_dev, init_labels_dev, live_groups, border, object_ids, alive_mask, given_mask, thrs,
+                         n_thr, counts_out_dev));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_score_v(p, stream)) return fail(SMK_E_HIP, "vos_score_v launch failed");
+    return 0;
+}
+
 int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
                         const void *state_dev, int B, float *overlap_dev, int32_t *counts_dev, void *stream) {
     if (!gt_dev || !overlap_dev || !state_dev || (!pred_dev && !adv_rows_dev)) return fail(SMK_E_ARG, "smk_vot_overlap_dev: null argument");

@@ -362,6 +362,28 @@ struct VosRleVParams {
     double inv_map[TRK_SET_MAX_B][6];
 };
 int launch_vos_rle_v(const VosRleVParams &p, const RleVParams &scan, int B, void *stream);
+// smk_vos_score_v / smk_vos_score_dev_v: launch_vos_score for G groups of slots, the groups as VosRleVParams holds them.  gt[g] is
+// the annotation [h_g][w_g] of group g at pitch w_g, or nullptr: the group is not scored.  A pixel of group g is fused over the
+// members of g and matched against the ids of those members only; `arg` is the SLOT, so counts is [B][n_thr][2] per slot, zeroed
+// in-stream before the launch (a slot that is not scored keeps zeros).  No label byte is written.  Everything travels in the kernarg
+struct VosScoreVParams {
+    const float *logits;            // [B][ms*ms], or the head [B][ms*ms][S][S] when head_S != 0
+    int *counts;                    // [B][n_thr][2] (intersection, union)
+    int W, H, ms, head_S, slot, n_groups, B, n_thr;
+    float border;
+    unsigned alive, given;          // per slot, as VosParams per object
+    unsigned live_groups;           // bit g clear: nothing of group g is computed
+    const smk_trk_stream *st;       // != nullptr: inv_map[slot] / delta_yx[slot] of the state block, inv_map below unused
+    double thr[VOS_MAX_THR];
+    unsigned gmask[TRK_SET_MAX_B];
+    int gwh[TRK_SET_MAX_B][2];
+    const unsigned char *gt[TRK_SET_MAX_B];
+    const unsigned char *init[TRK_SET_MAX_B];      // [h_g][w_g] per group, or nullptr (no given bit in the group)
+    unsigned char ids[TRK_SET_MAX_B];
+    double inv_map[TRK_SET_MAX_B][6];
+};
+static_assert(sizeof(VosScoreVParams) <= 4096, "VosScoreVParams travels as the kernel's arguments");
+int launch_vos_score_v(const VosScoreVParams &p, void *stream);
 struct FrameSumsVParams {
     smk_image_ref im[TRK_SET_MAX_B];
     unsigned long long *sums;       // [n][3]

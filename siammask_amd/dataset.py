@@ -26,6 +26,7 @@ plan_vos() is its scheduler: a video holds n_obj slots for as many steps as it h
 import numpy as np
 
 from . import rle as rle_host
+from . import vos as vos_host
 
 ORDERS = ("given", "longest")
 _ROWS = ("target_pos", "target_sz", "score", "best_id", "polygon", "polygon_found")
@@ -316,7 +317,7 @@ def _vos_video(v, d, B):
     return T, h, w, np.ascontiguousarray(ids.astype(np.uint8)), first, last, init_at
 
 
-def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
+def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=None, thrs=None):
     """The VOS loop of track_vos (tools/test.py:459-520, without an annotation) for a DATASET: the objects of several videos share the
     B slots of ``tracker``, which this call reserves itself on the canvas of the largest h and w.  videos[v] = {'frames': uint8
     CUDA [T,h,w,3], 'object_ids': 1..B ids, 'start' / 'end': {id: frame} (the dataset's dictionaries, as run(vos=) with lifetimes
@@ -329,8 +330,16 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
     (rle.default_cap of the canvas); chunk: steps per collect(), as run_videos (device memory stays within chunk * B * cap * 4
     bytes; the result does not depend on it).  An object that is absent from its init labels starts nothing (started False); its
     planes are unspecified, as run(vos=) with lifetimes leaves them.
+    gt: None, or one entry per video -- None, or its annotation uint8 CUDA [T,h,w] on the frames' device.  Every
+    step scores the videos that have one at their own size in ONE launch right behind the label planes (smk_vos_score_dev_v, the
+    counts of MultiBatchIouMeter at every threshold of thrs: 1..8 float64 values, vos.THRS by default); the count rows of a chunk
+    are one [chunk,B,K,2] tensor and reach the host with the chunk's codes.  A scored video's dictionary gains 'vos_counts' int64
+    [T,O,K,2] and 'mean_iou' float32 [O,K] = vos.mean_iou(counts, start, end, object_ids); the result gains 'thrs' and 'miou'
+    float32 [K] = vos.dataset_mean over the scored videos (None if none is scored; vos.miou_lines prints it).  With gt=None
+    nothing of this is launched, allocated or returned.
     Refused before any launch (ValueError): the rpn variant, a per-stream hp table, a video with more objects than B or with none,
-    an id missing from 'start' / 'end', a start frame outside the video, 'init' of the wrong shape, a bad cap or chunk.
+    an id missing from 'start' / 'end', a start frame outside the video, 'init' of the wrong shape, a bad cap or chunk, a gt list
+    of another length than videos, a gt of the wrong dtype, shape or device, bad thrs, thrs without gt.
     -> {'videos': [per video, in the caller's order: {'slots', 'first_step', 'size': (h, w), 'object_ids', 'label_rle': per frame
     a list of O int64 count arrays (None where n > cap), 'n' / 'area' int32 [T,O], 'started' bool [O]}], 'steps', 'efficiency',
     'events'}; rle.labels_decode(d['label_rle'][t], *d['size']) is frame t's label map, rle.labels_to_coco its submission form."""
@@ -361,6 +370,27 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
     cap = int(cap)
     pl = plan_vos([i[0] for i in info], [i[3].size for i in info], B, order)        # (refuses an unknown order)
     dev = videos[0]["frames"].device
+    thr = None
+    if gt is None:
+        if thrs is not None:
+            raise ValueError("run_vos: thrs without gt: nothing is scored")
+    else:
+        gt = list(gt) if isinstance(gt, (list, tuple)) else None
+        if gt is None or len(gt) != V:
+            raise ValueError("run_vos: gt must hold one entry per video (%d), a tensor or None" % V)
+        for v, t in enumerate(gt):
+            T, h, w = info[v][:3]
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or
+                                  tuple(t.shape) != (T, h, w) or t.device != dev or not t.is_contiguous()):
+                raise ValueError("run_vos: gt of video %d must be a contiguous uint8 CUDA tensor [%d,%d,%d] on the frames' device"
+                                 % (v, T, h, w))
+        try:
+            thr = np.asarray(vos_host.THRS if thrs is None else thrs, dtype=np.float64)
+        except (TypeError, ValueError):
+            thr = None
+        if thr is None or thr.ndim != 1 or not 1 <= thr.size <= 8:
+            raise ValueError("run_vos: thrs must be 1..8 float64 values")
+        thr = np.ascontiguousarray(thr)
     depth = int(getattr(tracker.model, "_pipeline", 0) or 0)
     tracker.reserve(B, Hc, Wc, device=dev)
     if tracker.pipeline and tracker.refine and depth > 1:
@@ -371,10 +401,14 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
             "object_ids": info[v][3].astype(np.int64), "label_rle": [None] * info[v][0],
             "n": np.zeros((info[v][0], info[v][3].size), dtype=np.int32), "area": np.zeros((info[v][0], info[v][3].size), dtype=np.int32)}
            for v in range(V)]
-    last, g0, rows = [None] * B, 0, None
+    if thr is not None:
+        for v in range(V):
+            if gt[v] is not None:
+                out[v]["vos_counts"] = np.zeros((info[v][0], info[v][3].size, thr.size, 2), dtype=np.int64)
+    last, g0, rows, cnt = [None] * B, 0, None, None
     for g in range(pl.G):
         ids, alive, given = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
-        groups, sizes, init, begun = [], [], [], []
+        groups, sizes, init, begun, gts = [], [], [], [], []
         fed = list(last)
         for v, slots in pl.steps[g]:
             T, h, w, vid, first, end, init_at = info[v]
@@ -388,6 +422,7 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
             groups.append(list(slots))
             sizes.append((w, h))
             init.append(init_at(k) if any(given[b] for b in slots) else None)
+            gts.append(gt[v][k] if thr is not None and gt[v] is not None else None)
         for b in range(B):
             if fed[b] is None:                                        # a slot that never had an object: a canvas of zeros
                 fed[b] = torch.zeros((Hc, Wc, 3), dtype=torch.uint8, device=dev)
@@ -395,8 +430,13 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
         if g == g0:                                                   # the chunk's counts and meta rows: ONE tensor each, no stack
             n = min(int(chunk), pl.G - g0)
             rows = (torch.empty((n, B, cap), dtype=torch.int32, device=dev), torch.empty((n, B, 4), dtype=torch.int32, device=dev))
-        tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
-                        _rle_out=(rows[0][g - g0], rows[1][g - g0]))
+            cnt = torch.empty((n, B, thr.size, 2), dtype=torch.int32, device=dev) if thr is not None else None
+        if thr is None:
+            tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
+                            _rle_out=(rows[0][g - g0], rows[1][g - g0]))
+        else:                                                         # ... and the step's count row, right behind the label planes
+            tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
+                            _rle_out=(rows[0][g - g0], rows[1][g - g0]), _vos_gt=(gts, thr, cnt[g - g0]))
         if begun:                                                     # ONE start event for every object that starts on this step
             slots_b = [b for _, _, b in begun]
             frames_b = [videos[v]["frames"][g - int(pl.first_step[v])] for v, _, _ in begun]
@@ -414,7 +454,7 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
             for (_, _, b), f in zip(begun, frames_b):
                 last[b] = f
         if g + 1 - g0 == int(chunk) or g + 1 == pl.G:
-            res = tracker.collect(_rle=rows)
+            res = tracker.collect(_rle=rows) if thr is None else tracker.collect(_rle=rows, _counts=cnt)
             r = res["label_rle"]
             per = rle_host.to_host_v(dict(r, counts=r["counts"][..., :int(min(r["n"].max(), r["cap"]))].cpu().numpy()))
             for t in range(g0, g + 1):
@@ -424,14 +464,23 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256):
                         raise RuntimeError("run_vos: video %d was encoded at another size than its frames'" % v)
                     d["label_rle"][k] = [per[t - g0][b] for b in slots]
                     d["n"][k], d["area"][k] = r["n"][t - g0, slots], r["area"][t - g0, slots]
+                    if "vos_counts" in d:
+                        d["vos_counts"][k] = res["vos_counts"][t - g0, slots]
             for e, objs in zip(res.get("events", []), ev_objs):
                 for (v, j, _), ok in zip(objs, e["started"]):
                     started[v][j] = bool(ok)
                 events.append(dict(e, step=g0 + e["t"], objects=[(v, j) for v, j, _ in objs]))
-            ev_objs, g0, rows, res, r, per = [], g + 1, None, None, None, None
+            ev_objs, g0, rows, cnt, res, r, per = [], g + 1, None, None, None, None, None
     for v in range(V):
         out[v]["started"] = started[v]
-    return {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}
+    result = {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}
+    if thr is not None:                                               # the last lines of the meter (tools/test.py:441-455, :599)
+        for v in range(V):
+            if "vos_counts" in out[v]:
+                out[v]["mean_iou"] = vos_host.mean_iou(out[v]["vos_counts"], videos[v]["start"], videos[v]["end"], out[v]["object_ids"])
+        scored = [d["mean_iou"] for d in out if "mean_iou" in d]
+        result["thrs"], result["miou"] = thr, vos_host.dataset_mean(scored) if scored else None
+    return result
 
 
 def ope_video(d, gt, name):

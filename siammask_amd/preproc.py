@@ -850,6 +850,11 @@ class VosGroups(object):
                 self.alive, float(seg_thr), self.given, cap, ws.data_ptr(), need, counts.data_ptr(), meta.data_ptr(),
                 _lib.current_stream_ptr())
 
+    def score_tail(self, gt_ptrs, thr, padding, counts):
+        """the same for smk_vos_score_v / smk_vos_score_dev_v: gt_ptrs and thr as vos_score_gt returns them"""
+        return (self.G, self.masks.ctypes.data, self.wh.ctypes.data, gt_ptrs, self.ptrs, self.live, float(padding), self.ids.ctypes.data,
+                self.alive, self.given, thr.ctypes.data, int(thr.size), counts.data_ptr(), _lib.current_stream_ptr())
+
 
 def vos_rle_v(logits, back_boxes, canvas_wh, groups, sizes, object_ids, alive=None, given=None, init=None, live=None, seg_thr=0.35,
               padding=-1.0, cap=None, counts=None, meta=None):
@@ -907,6 +912,101 @@ def vos_rle_dev_v(logits, state, slot, canvas_wh, groups, sizes=None, object_ids
             None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
             state.data_ptr(), int(slot), B, v.W, v.H, *v.tail(seg_thr, padding, cap, ws, need, counts, meta)))
     return counts, meta
+
+
+def vos_score_gt(v, gt, thrs, device, idle_ok=False):
+    """the checked annotation and thresholds of vos_score_v / vos_score_dev_v, pure host work: v a checked VosGroups, gt one entry per
+    group -- None (the video is not scored on this step) or a contiguous uint8 CUDA tensor [h_g,w_g] on ``device`` --, at least one
+    of them a tensor; thrs 1..8 float64 values -> (the host array of G device pointers, thrs float64 [K]).  ValueError otherwise.
+    idle_ok (the tracker: a step on which no video has a gt launches nothing): all None gives (None, thrs)."""
+    gt = list(gt) if isinstance(gt, (list, tuple)) else None
+    if gt is None or len(gt) != v.G:
+        raise ValueError("vos_score_v: gt must hold one entry per group (%d), a tensor or None" % v.G)
+    for g, t in enumerate(gt):
+        w, h = (int(n) for n in v.wh[g])
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w)
+                              or not t.is_contiguous() or t.device != device):
+            raise ValueError("vos_score_v: gt of group %d must be a contiguous uint8 CUDA tensor [%d,%d] on the logits' device" % (g, h, w))
+    if all(t is None for t in gt) and not idle_ok:
+        raise ValueError("vos_score_v: no group has a gt: nothing to score")
+    try:
+        thr = np.asarray(thrs, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("vos_score_v: thrs must be 1..8 float64 values")
+    if thrs is None or thr.ndim != 1 or not 1 <= thr.size <= 8:
+        raise ValueError("vos_score_v: thrs must be 1..8 float64 values")
+    thr = np.ascontiguousarray(thr)
+    if all(t is None for t in gt):
+        return None, thr
+    return (ctypes.c_void_p * v.G)(*[t.data_ptr() if t is not None else None for t in gt]), thr
+
+
+def vos_score_out(out, B, K, device):
+    """the checked count tensor of vos_score_v / vos_score_dev_v (allocated when out is None)"""
+    counts = out if out is not None else torch.empty((B, K, 2), dtype=torch.int32, device=device)
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or not counts.is_cuda or not counts.is_contiguous() or \
+            tuple(counts.shape) != (B, K, 2):
+        raise ValueError("vos_score_v: out must be a contiguous int32 CUDA tensor [%d,%d,2]" % (B, K))
+    return counts
+
+
+def vos_score_v(logits, back_boxes, canvas_wh, groups, sizes, gt, object_ids, thrs, alive=None, given=None, init=None, live=None,
+                padding=-1.0, out=None):
+    """vos_score for the objects of several videos in one launch (include/siammask_hip.h: smk_vos_score_v).  logits [B, ms*ms]: one
+    row per SLOT; groups / sizes / object_ids / alive / given / init / live as VosGroups takes them, back_boxes one box per slot
+    (mapped into its group's frame); gt: per group None or its annotation uint8 CUDA [h_g,w_g]; thrs: 1..8 float64 values, shared.
+    The rows of a group's slots are those of smk_vos_score_ex called at the group's size with the group's logits rows, boxes,
+    ids and gt.  -> int32 CUDA [B, K, 2] = (intersection, union); zeros for a slot in no group, or of a group that is not live or
+    has no gt."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    B = int(logits.shape[0])
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != B:
+        raise ValueError("logits must be [B, ms*ms] with one back_box per slot")
+    v = VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    ptrs, thr = vos_score_gt(v, gt, thrs, logits.device)
+    counts = vos_score_out(out, B, int(thr.size), logits.device)
+    inv = np.zeros((B, 6), dtype=np.float64)
+    for slots, (w, h) in zip(v.groups, v.wh):
+        for b in slots:
+            inv[b] = invert_affine(crop_back_map(back_boxes[b], (int(w), int(h)))).reshape(6)
+    with torch.cuda.device(logits.device):
+        _lib.check(_lib.lib().smk_vos_score_v(logits.data_ptr(), ms, inv.ctypes.data, B, v.W, v.H, *v.score_tail(ptrs, thr, padding, counts)))
+    return counts
+
+
+def vos_score_dev_v(logits, state, slot, canvas_wh, groups, gt, thrs, sizes=None, object_ids=None, alive=None, given=None, init=None,
+                    live=None, padding=-1.0, head=None, mask_size=None, out=None):
+    """vos_score_v with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of every slot read on the device
+    from the tracker's state block (smk_vos_score_dev_v).  groups may be a checked VosGroups (the tracker's paste job), the
+    arguments from sizes to live are then unused; gt may be what vos_score_gt returned for it (pointers, thrs), thrs is then unused."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = int(src.shape[0])
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    v = groups if isinstance(groups, VosGroups) else VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    if v.B != B or (v.W, v.H) != (int(canvas_wh[0]), int(canvas_wh[1])):
+        raise ValueError("vos_score_dev_v: the groups were checked for %d slots on %d x %d" % (v.B, v.W, v.H))
+    ptrs, thr = gt if isinstance(gt, tuple) and len(gt) == 2 and isinstance(gt[1], np.ndarray) else vos_score_gt(v, gt, thrs, src.device)
+    counts = vos_score_out(out, B, int(thr.size), src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.lib().smk_vos_score_dev_v(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, v.W, v.H, *v.score_tail(ptrs, thr, padding, counts)))
+    return counts
 
 
 def vot_overlap_dev(pred, gt, state, adv_rows=None, out=None, counts=None):

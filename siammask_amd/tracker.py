@@ -135,8 +135,11 @@ _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row label
 # frame's counts [B,cap] and meta [B,4]
 _LabelRle = collections.namedtuple("_LabelRle", "cap masks labels counts meta")
 # the checked _vos_v of enqueue() (dataset.run_vos: the objects of several videos share the slots): the frame's _LabelRle and the
-# preproc.VosGroups the C entry takes
-_VosV = collections.namedtuple("_VosV", "rle groups")
+# preproc.VosGroups the C entry takes; score: None, or the _VosScore of a frame enqueued with _vos_gt as well
+_VosV = collections.namedtuple("_VosV", "rle groups score", defaults=(None,))
+# the checked _vos_gt of enqueue(): the host array of the groups' gt pointers (None: no group is scored on this frame, the row is
+# zeroed), the thresholds, the frame's count row [B,K,2] and the gt tensors themselves, kept alive until the job has been launched
+_VosScore = collections.namedtuple("_VosScore", "ptrs thrs row keep")
 # a checked iou= request (_iou_spec): annotation, thresholds, masks wanted, frame scored; enqueue() adds the frame's count row
 _Iou = collections.namedtuple("_Iou", "gt thrs masks scored row")
 _IOU_MAX_THR = 16
@@ -146,7 +149,7 @@ _Event = collections.namedtuple("_Event", "t streams res")            # one star
 class _Chunk(object):
     """what has been enqueued since the last collect().  A fresh _Chunk() is the one reset: collect() and a rewind both use it."""
     __slots__ = ("pending", "deferred", "masks", "poly", "labels", "vos_k", "iou_k", "events", "z_snapped", "start", "sizes", "rle",
-                 "label_rle", "vos_v")
+                 "label_rle", "vos_v", "vos_rows")
 
     def __init__(self):
         self.pending, self.deferred, self.vos_k = 0, None, None     # frames; the _Job not pasted yet; thresholds of a scored chunk
@@ -154,6 +157,7 @@ class _Chunk(object):
         self.rle = None                                               # the _Rle of every frame of a chunk enqueued with rle=
         self.label_rle = None                                         # the _LabelRle of every frame of a chunk enqueued with vos['rle']
         self.vos_v = False                                            # ... or with _vos_v: the meta rows carry (h, w) per slot as well
+        self.vos_rows = None                                          # _vos_v with _vos_gt: per frame, the count row [B,K,2] (vos_k = K)
         self.masks, self.poly, self.labels, self.events = [], [], [], []      # per frame: mask, polygon flag, labels; the _Events
         self.z_snapped, self.start = False, None                      # z_snap holds z_all; tr.state at the chunk's start
         self.sizes = []                                               # mixed sizes: per frame, the streams' (w, h) [B,2]
@@ -793,10 +797,13 @@ class DeviceTracker(object):
             raise ValueError("vos['rle']['labels']: the label map comes from the scoring launch, which needs gt=")
         return _LabelRle(int(cap), bool(lr.get("masks", False)), bool(lr.get("labels", False)), None, None)
 
-    def _vos_v_spec(self, mixed, want_mask, other, vos_v):
-        """the checked _vos_v of one frame (before anything is launched) -> None, or a _VosV (counts / meta still None).  other:
-        the frame also asks for a polygon, mask_out=, rle= / _rle_v, iou= or carries the hook of run(vot=)"""
+    def _vos_v_spec(self, mixed, want_mask, other, vos_v, vos_gt=None):
+        """the checked _vos_v [and _vos_gt] of one frame (before anything is launched) -> None, or a _VosV (counts / meta still
+        None, the count row as given).  other: the frame also asks for a polygon, mask_out=, rle= / _rle_v, iou= or carries the
+        hook of run(vot=)"""
         if vos_v is None:
+            if vos_gt is not None:
+                raise ValueError("_vos_gt scores the groups of _vos_v: it comes with it")
             return None
         q = self._fr
         if not mixed or other or q.B > 32:
@@ -811,7 +818,17 @@ class DeviceTracker(object):
         v = preproc.VosGroups(q.B, (q.W, q.H), groups, sizes, ids, alive, given, init, live)
         if q.chunk.pending and (not q.chunk.vos_v or q.chunk.label_rle[0].cap != int(cap)):
             raise ValueError("every frame of a chunk carries _vos_v with one cap, or none does")
-        return _VosV(_LabelRle(int(cap), False, False, None, None), v)
+        score = None
+        if vos_gt is not None:
+            gts, thrs, row = vos_gt
+            ptrs, thr = preproc.vos_score_gt(v, gts, thrs, q.device, idle_ok=True)
+            if row is not None:
+                preproc.vos_score_out(row, q.B, int(thr.size), q.device)
+            score = _VosScore(ptrs, thr, row, list(gts))
+        if q.chunk.pending and ((q.chunk.vos_k is not None) != (score is not None) or
+                                (score is not None and q.chunk.vos_k != int(score.thrs.size))):
+            raise ValueError("every frame of a chunk carries _vos_gt with one number of thresholds, or none does")
+        return _VosV(_LabelRle(int(cap), False, False, None, None), v, score)
 
     def _iou_spec(self, mixed, want_mask, want_polygon, mask_out, scored_vos, iou):
         """the checked iou= request of one frame (before anything is launched) -> None, or an _Iou (row still None)"""
@@ -870,7 +887,7 @@ class DeviceTracker(object):
         return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None, _vos_gt=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -907,6 +924,10 @@ class DeviceTracker(object):
         smk_vos_rle_dev_v stands in the paste-back's place: no mask byte, no label byte.  Every frame of a chunk carries it (one
         cap) or none does; not with want_polygon, mask_out=, gt= / vos= / iou= / rle= / _rle_v.  collect() returns res['label_rle']
         with 'sizes' int32 [T,B,2] (h, w) for 'size'; n = 0 where a slot is in no live group.
+        _vos_gt (private, dataset.run_vos; only with _vos_v): (gt per group: None or uint8 CUDA [h_g,w_g], thrs: 1..8 float64 values,
+        row_out: int32 CUDA [B,K,2] or None) -- smk_vos_score_dev_v right behind smk_vos_rle_dev_v on the same stream scores every
+        group that has a gt against it; a frame whose groups all have None gets a zero row and no launch.  Every frame of a chunk
+        carries it (one K) or none does; collect() returns res['vos_counts'] int64 [T,B,K,2] indexed by slot.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -952,7 +973,7 @@ class DeviceTracker(object):
             raise ValueError("every frame of a chunk carries _rle_v, or none does")
         iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
         vv = self._vos_v_spec(mixed, want_mask, want_polygon or mask_out is not None or rle is not None or iou is not None
-                              or _after is not None, _vos_v)
+                              or _after is not None, _vos_v, _vos_gt)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
         L, model = _lib.lib(), self.model
@@ -994,6 +1015,9 @@ class DeviceTracker(object):
                 rc, rm = _rle_out if _rle_out is not None else (torch.empty((B, vv.rle.cap), dtype=torch.int32, device=q.device),
                                                                 torch.empty((B, 4), dtype=torch.int32, device=q.device))
                 vv = vv._replace(rle=vv.rle._replace(counts=rc, meta=rm))
+                if vv.score is not None and vv.score.row is None:
+                    K = int(vv.score.thrs.size)
+                    vv = vv._replace(score=vv.score._replace(row=torch.empty((B, K, 2), dtype=torch.int32, device=q.device)))
                 c.labels.append(None)
             dev_ptr = q.dev.data_ptr()
             if mixed:
@@ -1043,6 +1067,8 @@ class DeviceTracker(object):
                 c.label_rle = (c.label_rle or []) + [score.rle]
             if vv is not None:
                 c.label_rle, c.vos_v = (c.label_rle or []) + [vv.rle], True
+                if vv.score is not None:
+                    c.vos_rows, c.vos_k = (c.vos_rows or []) + [vv.score.row], int(vv.score.thrs.size)
             c.sizes.append(sizes if mixed else None)
             c.poly.append(bool(want_polygon))
             c.pending = t + 1
@@ -1082,6 +1108,12 @@ class DeviceTracker(object):
             vr = job.vos_v.rle
             preproc.vos_rle_dev_v(logits, q.dev, job.slot, (q.W, q.H), job.vos_v.groups, seg_thr=p.seg_thr, head=head,
                                   mask_size=self.mask_size, cap=vr.cap, counts=vr.counts, meta=vr.meta)
+            sc = job.vos_v.score
+            if sc is not None and sc.ptrs is None:                    # no group has a gt on this frame: a zero row, no launch
+                sc.row.zero_()
+            elif sc is not None:                                      # right behind the label planes, same stream, same records
+                preproc.vos_score_dev_v(logits, q.dev, job.slot, (q.W, q.H), job.vos_v.groups, (sc.ptrs, sc.thrs), None, head=head,
+                                        mask_size=self.mask_size, out=sc.row)
         if lr is not None and s.labels is None:                       # the fused label planes, in the paste-back's place: no label byte
             preproc.vos_rle_dev(logits, q.dev, job.slot, (q.W, q.H), s.ids, init=s.init, seg_thr=p.seg_thr, head=head,
                                 mask_size=self.mask_size, cap=lr.cap, counts=lr.counts, meta=lr.meta, _bits=(s.bits, s.gbits))
@@ -1130,7 +1162,7 @@ class DeviceTracker(object):
                 replay()
                 _lib.check(_lib.lib().smk_seq_sync_check(model._ctx, _lib.current_stream_ptr(), None))
 
-    def collect(self, _masks=None, _labels=None, _rle=None):
+    def collect(self, _masks=None, _labels=None, _rle=None, _counts=None):
         """Join the frames enqueued since the last collect() -- ONE synchronisation -- and return host arrays
         target_pos [T,B,2], target_sz [T,B,2], score [T,B] (float64), best_id [T,B], delta_yx [T,B,2] (int64), crop_box [T,B,4],
         mask (uint8 CUDA [T,B,H,W], None without masks), and for frames enqueued with want_polygon polygon [T,B,4,2] /
@@ -1144,7 +1176,7 @@ class DeviceTracker(object):
         tr.state as T calls of track() would.  Raises SmkError (code E_SEQ) after rewinding the tracker to the chunk's start when
         a persistent-sequence failure was reported: re-run the chunk.  _masks / _labels (private, run()): the [T,B,H,W] / [T,H,W]
         tensors the frames' masks and labels were written into, returned in place of a stack; _rle likewise: (counts [T,B,cap],
-        meta [T,B,4])."""
+        meta [T,B,4]); _counts likewise: the [T,B,K,2] tensor the count rows of a chunk enqueued with _vos_gt were written into."""
         q, st = self._fr, self.state
         if st is None or q is None:
             raise RuntimeError("DeviceTracker.collect(): init() first")
@@ -1165,7 +1197,10 @@ class DeviceTracker(object):
                           for b in q.rbox[:nblk]]
                     rows = torch.cat([rows, torch.cat(rb)[:T]], dim=2)
                 if K is not None:                                     # int32 counts ride along as float64 (exact): [T,B,K*2]
-                    vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
+                    if c.vos_rows is not None:                        # _vos_gt: rows of exactly [B,K,2], one tensor if the caller's
+                        vc = _counts if _counts is not None and _counts.shape[0] == T else torch.stack(c.vos_rows)
+                    else:
+                        vc = torch.cat(counts[:nblk])[:T] if nblk > 1 else counts[0][:T]
                     vc = vc.reshape(T, -1)[:, :B * K * 2].reshape(T, B, K * 2)          # a frame's row is packed [B][K][2]
                     rows = torch.cat([rows, vc.to(torch.float64)], dim=2)
                 nm = 4 if (c.rle is not None and c.rle[0].live is not None) or c.vos_v else 2      # _rle_v / _vos_v: (h, w) as well

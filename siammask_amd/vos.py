@@ -41,6 +41,23 @@ def mean_iou(counts, start=None, end=None, object_ids=None):
     return res
 
 
+def dataset_mean(per_video):
+    """per_video: the float32 [O_v, K] results of mean_iou, one per scored video -> float32 [K], the dataset's mIoU per threshold:
+    np.mean(np.concatenate(iou_lists), axis=0), the very call of tools/test.py:599 -- one row per OBJECT, so a video weighs as many
+    rows as it has objects, and a NaN row (an object with an empty window) makes its column NaN, as it does there."""
+    per_video = [np.asarray(m) for m in per_video]
+    if not per_video:
+        raise ValueError("dataset_mean: at least one scored video")
+    if any(m.ndim != 2 or m.shape[1] != per_video[0].shape[1] for m in per_video):
+        raise ValueError("dataset_mean: every video gives [O_v, K] with one K")
+    return np.mean(np.concatenate(per_video), axis=0)
+
+
+def miou_lines(thrs, miou):
+    """the lines tools/test.py:600 logs for a VOS dataset, one per threshold"""
+    return ["Segmentation Threshold {:.2f} mIoU: {:.3f}".format(thr, iou) for thr, iou in zip(thrs, miou)]
+
+
 def iou_meter(counts, kind="mean", sz=None):
     """counts: host integer array [T', K, 2] = (intersection, union) of the frames handed to IouMeter.add, in order (one stream of
     res['iou_counts']) -> (IouMeter(thrs, sz).value(kind) [K], the meter's table float32 [sz, K]).  sz: the rows of the table
