@@ -484,6 +484,48 @@ int smk_vos_score_dev_v(const float *logits_dev, const float *head_dev, int scor
                         const uint8_t *object_ids, uint32_t alive_mask, uint32_t given_mask, const double *thrs, int n_thr,
                         int32_t *counts_out_dev, void *stream);
 
+/* ---- label maps as PNG-ready zlib streams, deflated on the device (tools/test.py:518-525 --save_mask; additive; smk_version()
+ * keeps reporting 1.10, the presence of these symbols is the probe) ---------------------------------------------------------------
+ * The stream of an H x W uint8 map is the zlib stream a PNG's IDAT chunk holds: 0x78 0x01, ONE deflate block with fixed Huffman
+ * codes over the scanline stream S (per row a filter byte 0, then its W bytes; N = H * (W + 1)), Adler-32 of S.  S is cut into its
+ * maximal runs of equal bytes; a run (v, n) is one literal v, (n - 1) / 258 matches of length 258 at distance 1, and for the rest m
+ * one match of length m (m >= 3) or m literals.  The format is fixed (siammask_amd/csrc/png_deflate.h states it in full): the
+ * device and smk_host_png_encode agree byte for byte, and zlib inflates the stream to S.  Signature, IHDR, PLTE, IEND and the chunk
+ * CRCs are host work on a few KB: siammask_amd.png.to_png.
+ * smk_png_encode: planes_dev uint8 [B][H][W] of ANY byte values (a fused label map, a 0 / 255 mask, ...), one stream per plane.
+ * out_dev: uint8 [B][cap]; meta_out_dev: int32 [B][4] = (n_bytes, n_runs, H, W) with n_bytes ALWAYS the true size of the stream.  If
+ * n_bytes > cap only the first cap bytes of that stream are written -- nothing at or past out_dev + (b + 1) * cap ever is -- and
+ * the caller sees the overflow as n_bytes > cap.  Bytes n_bytes .. cap - 1 are not written.  No atomics, nothing needs zeroing:
+ * every byte below min(n_bytes, cap) is written exactly once and a second call gives the same bytes.
+ * W, H in 1..4096, B in 1..65535, cap in 1..smk_png_worst_bytes(W, H) = 2 + ceil((10 + 9 N) / 8) + 4 (every byte a 9-bit literal;
+ * 0 for a bad geometry).  ws_dev: smk_png_workspace(B, W, H, cap) bytes (per plane a 16-byte head, 8 * (cap + 1) bytes of run table,
+ * one transition bit and one byte per position of S; rounded up to 256; 0 for a bad geometry or cap), 8-byte aligned, owned by the
+ * call until it has completed on `stream`; meta 4-byte aligned.  Bad arguments give SMK_E_ARG before anything is enqueued.  No
+ * context; asynchronous on `stream`, no host synchronisation.
+ * smk_host_png_encode: the CPU twin -- host pointers, the same header code in plain loops, no device, no workspace.
+ * smk_vos_png_v / smk_vos_png_dev_v: the fused label map of every live group of smk_vos_rle_v / smk_vos_rle_dev_v as ONE stream per
+ * group -- byte (x, y) of group g is the LABEL defined there (0, or rank within the group + 1), computed per position: no label byte
+ * is read.  The arguments are those of smk_vos_rle_v / smk_vos_rle_dev_v with cap in BYTES (1..smk_png_worst_bytes of the canvas),
+ * ws_dev smk_png_workspace(B, canvas_w, canvas_h, cap), and out_dev uint8 [B][cap] / meta_out_dev int32 [B][4] in the counts' and
+ * meta's places.  A group's stream and meta row (n_bytes, n_runs, h_g, w_g) are written at the row of its LOWEST member slot; the rows
+ * of its other slots and of groups whose live_groups bit is clear get (0, 0, h_g, w_g), a slot in no group (0, 0, canvas_h,
+ * canvas_w), and no byte.  The stream equals smk_host_png_encode of the map the codes of smk_vos_rle_v decode to.  They refuse
+ * everything smk_vos_rle_v / smk_vos_rle_dev_v refuse, with SMK_E_ARG before anything is enqueued. */
+size_t smk_png_worst_bytes(int W, int H);
+size_t smk_png_workspace(int B, int W, int H, int cap);
+int smk_png_encode(const uint8_t *planes_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes, uint8_t *out_dev,
+                   int32_t *meta_out_dev, void *stream);
+int smk_host_png_encode(const uint8_t *planes, int B, int W, int H, int cap, uint8_t *out, int32_t *meta_out);
+int smk_vos_png_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                  const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *init_labels_dev, uint32_t live_groups,
+                  float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap,
+                  void *ws_dev, size_t ws_bytes, uint8_t *out_dev, int32_t *meta_out_dev, void *stream);
+int smk_vos_png_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                      int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                      const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                      uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
+                      uint8_t *out_dev, int32_t *meta_out_dev, void *stream);
+
 /* ---- VOS scoring fused with the paste-back (tools/test.py:421-456 MultiBatchIouMeter, :480; ABI 1.9, additive) --------
  * smk_vos_score: the per-frame part of MultiBatchIouMeter for the n_obj (1..32) objects that share one W x H frame, without
  * the [O][H][W] probabilities ever reaching memory.  Per frame pixel:

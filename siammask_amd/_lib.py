@@ -44,6 +44,7 @@ SYMBOLS = (
     "smk_paste_rle_dev_v", "smk_rle_encode_v", "smk_test_rle_encode_v",
     "smk_labels_rle_encode", "smk_vos_rle", "smk_vos_rle_dev",
     "smk_vos_rle_v", "smk_vos_rle_dev_v", "smk_vos_score_v", "smk_vos_score_dev_v",
+    "smk_png_worst_bytes", "smk_png_workspace", "smk_png_encode", "smk_host_png_encode", "smk_vos_png_v", "smk_vos_png_dev_v",
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
     "smk_ope_curve", "smk_host_ope_curve",
@@ -204,6 +205,12 @@ def lib():
     rle_v_tail = [ci, vp, vp, vp, u32, cf, vp, u32, cf, u32, ci, vp, ctypes.c_size_t, vp, vp, vp]
     L.smk_vos_rle_v.argtypes = [fp, ci, vp, ci, ci, ci] + rle_v_tail
     L.smk_vos_rle_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci] + rle_v_tail
+    L.smk_png_worst_bytes.argtypes = [ci, ci]
+    L.smk_png_workspace.argtypes = [ci, ci, ci, ci]
+    L.smk_png_encode.argtypes = [vp, ci, ci, ci, ci, vp, ctypes.c_size_t, vp, vp, vp]
+    L.smk_host_png_encode.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+    L.smk_vos_png_v.argtypes = [fp, ci, vp, ci, ci, ci] + rle_v_tail                 # (cap in bytes; a byte stream in the counts' place)
+    L.smk_vos_png_dev_v.argtypes = [fp, fp, ci, ci, vp, ci, ci, ci, ci] + rle_v_tail
     # groups (count, masks, sizes, gt pointers, init label pointers, live mask), border, ids, alive, given, thrs, their number, counts, stream
     score_v_tail = [ci, vp, vp, vp, vp, u32, cf, vp, u32, u32, vp, ci, vp, vp]
     L.smk_vos_score_v.argtypes = [fp, ci, vp, ci, ci, ci] + score_v_tail
@@ -223,7 +230,8 @@ def lib():
         fn = getattr(L, name)
         if name not in ("smk_last_error",):
             fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes",
-                                                        "smk_rle_workspace", "smk_eao_workspace_bytes") else ci
+                                                        "smk_rle_workspace", "smk_eao_workspace_bytes", "smk_png_worst_bytes",
+                                                        "smk_png_workspace") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

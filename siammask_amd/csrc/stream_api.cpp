@@ -1,7 +1,8 @@
 // stream_api.cpp -- the stateless product ABI either side of the network (include/siammask_hip.h): crop / paste / labels,
 // smk_mask_rbox, the tracker state on the device (smk_trk_*), VOS scoring, stream start, the VOT overlap and evaluation, the *_v
-// entries for streams with their own frame sizes -- argument checks and kernargs, one launch each -- and the smk_host_* entries that run the
-// device code's inline functions (tracker_state.h, vot_overlap.h, vot_eval.h, ope_eval.h) on the CPU for the bit-exact host tests.
+// entries for streams with their own frame sizes, label maps as zlib streams (smk_png_*) -- argument checks and kernargs, one launch each --
+// and the smk_host_* entries that run the device code's inline functions (tracker_state.h, vot_overlap.h, vot_eval.h, ope_eval.h,
+// png_deflate.h) on the CPU for the bit-exact host tests.
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -12,6 +13,7 @@
 #include "vot_overlap.h"
 #include "vot_eval.h"
 #include "ope_eval.h"
+#include "png_deflate.h"
 
 using namespace smk;
 
@@ -1047,6 +1049,89 @@ int smk_paste_rle_dev_v(const float *logits_dev, const float *head_dev, int scor
     return 0;
 }
 
+// ---- label maps as PNG-ready zlib streams (png_deflate.h, png_kernels.hip) -----------------------------------------
+static bool png_geometry(int B, int W, int H) {
+    return B >= 1 && B <= 65535 && W >= 1 && H >= 1 && W <= PNG_MAX_SIDE && H <= PNG_MAX_SIDE;
+}
+
+size_t smk_png_worst_bytes(int W, int H) { return png_geometry(1, W, H) ? (size_t)png_worst_bytes(W, H) : 0; }
+
+size_t smk_png_workspace(int B, int W, int H, int cap) {
+    if (!png_geometry(B, W, H) || cap < 1 || cap > png_worst_bytes(W, H)) return 0;
+    return ((size_t)B * png_ws_stride(W, H, cap) + 255) & ~(size_t)255;
+}
+
+// the checks and the fields every device entry shares; everything is refused here, before anything is enqueued
+static int png_fill(const char *who, PngParams &p, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes, uint8_t *out_dev,
+                    int32_t *meta_out_dev) {
+    if (!ws_dev || !out_dev || !meta_out_dev) return fail(SMK_E_ARG, "%s: null argument", who);
+    if (!png_geometry(B, W, H)) return fail(SMK_E_ARG, "%s: bad geometry (B %d in 1..65535, W %d and H %d in 1..%d)", who, B, W, H, PNG_MAX_SIDE);
+    if (cap < 1 || cap > png_worst_bytes(W, H)) return fail(SMK_E_ARG, "%s: cap %d bytes (1..%ld)", who, cap, png_worst_bytes(W, H));
+    if (ws_bytes < smk_png_workspace(B, W, H, cap))
+        return fail(SMK_E_ARG, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, smk_png_workspace(B, W, H, cap));
+    if (((uintptr_t)ws_dev & 7) || ((uintptr_t)meta_out_dev & 3)) return fail(SMK_E_ARG, "%s: misaligned workspace (8 bytes) or meta (4 bytes)", who);
+    memset(&p, 0, sizeof(p));
+    p.ws = (unsigned char *)ws_dev; p.out = out_dev; p.meta = meta_out_dev;
+    p.W = W; p.H = H; p.cap = cap;
+    return 0;
+}
+
+int smk_png_encode(const uint8_t *planes_dev, int B, int W, int H, int cap, void *ws_dev, size_t ws_bytes, uint8_t *out_dev,
+                   int32_t *meta_out_dev, void *stream) {
+    if (!planes_dev) return fail(SMK_E_ARG, "smk_png_encode: null argument");
+    PngParams p;
+    CHK(png_fill("smk_png_encode", p, B, W, H, cap, ws_dev, ws_bytes, out_dev, meta_out_dev));
+    p.planes = planes_dev;
+    if (launch_png(p, B, stream)) return fail(SMK_E_HIP, "png_encode launch failed");
+    return 0;
+}
+
+// the CPU twin: the same header functions in plain loops, no device.  One plane after the other
+int smk_host_png_encode(const uint8_t *planes, int B, int W, int H, int cap, uint8_t *out, int32_t *meta_out) {
+    if (!planes || !out || !meta_out) return fail(SMK_E_ARG, "smk_host_png_encode: null argument");
+    if (!png_geometry(B, W, H))
+        return fail(SMK_E_ARG, "smk_host_png_encode: bad geometry (B %d in 1..65535, W %d and H %d in 1..%d)", B, W, H, PNG_MAX_SIDE);
+    if (cap < 1 || cap > png_worst_bytes(W, H)) return fail(SMK_E_ARG, "smk_host_png_encode: cap %d bytes (1..%ld)", cap, png_worst_bytes(W, H));
+    const long N = png_positions(W, H);
+    std::vector<unsigned char> vals((size_t)N);
+    std::vector<PngRun> runs((size_t)cap + 1);
+    for (int b = 0; b < B; ++b) {
+        for (int y = 0; y < H; ++y) {
+            vals[(size_t)y * (W + 1)] = 0;
+            memcpy(&vals[(size_t)y * (W + 1) + 1], planes + ((size_t)b * H + y) * W, (size_t)W);
+        }
+        unsigned bits = 0;
+        unsigned long long sa = 0, sb = 0, ta, tb;
+        long n_runs = 0, start = 0;
+        for (long i = 1; i <= N; ++i) {
+            if (i < N && vals[i] == vals[i - 1]) continue;            // a transition at i (or the end) closes the run [start, i)
+            if (n_runs <= cap) runs[n_runs] = PngRun{3u + bits, (unsigned)start};
+            bits += png_run_bits(vals[start], (unsigned)(i - start));
+            png_adler_terms(vals[start], (unsigned long long)(i - start), (unsigned long long)start, (unsigned long long)N, &ta, &tb);
+            sa += ta; sb += tb;
+            ++n_runs;
+            start = i;
+        }
+        if (n_runs <= cap) runs[n_runs] = PngRun{3u + bits, (unsigned)N};
+        PngHead hd;
+        hd.end_bits = 3u + bits + 7u;
+        hd.adler = png_adler_finish(sa, sb, (unsigned long long)N);
+        hd.n_runs = (unsigned)n_runs;
+        hd.n_bytes = (unsigned)png_stream_bytes((long)hd.end_bits);
+        const long lim = hd.n_bytes < (unsigned)cap ? (long)hd.n_bytes : (long)cap;
+        const int nrec = (int)(n_runs < cap ? n_runs : cap);
+        uint8_t *o = out + (size_t)b * cap;
+        for (long w = 0; 4 * w < lim; ++w) {
+            const unsigned word = png_word(w, runs.data(), nrec, vals.data(), hd);
+            for (int j = 0; j < 4; ++j)
+                if (4 * w + j < lim) o[4 * w + j] = (uint8_t)(word >> (8 * j));
+        }
+        int32_t *m = meta_out + 4 * b;
+        m[0] = (int32_t)hd.n_bytes; m[1] = (int32_t)n_runs; m[2] = H; m[3] = W;
+    }
+    return 0;
+}
+
 // ---- the label planes of G videos in one launch -----------------------------------------------------------------
 // the checks and the fields both entries share; everything is refused here, before anything is enqueued.  A slot in no group has no
 // size of its own: its meta row reports the canvas
@@ -1054,13 +1139,19 @@ static int vos_rle_fill_v(const char *who, VosRleVParams &p, RleVParams &scan, c
                           int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
                           const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
                           uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
-                          uint32_t *counts_out_dev, int32_t *meta_out_dev) {
+                          uint32_t *counts_out_dev, int32_t *meta_out_dev, PngParams *png = nullptr) {
     if (!src || !object_ids || !group_masks || !group_wh) return fail(SMK_E_ARG, "%s: null argument", who);
     if (B < 1 || B > TRK_SET_MAX_B) return fail(SMK_E_ARG, "%s: %d slots (1..%d)", who, B, TRK_SET_MAX_B);
     if (n_groups < 1 || n_groups > B) return fail(SMK_E_ARG, "%s: %d groups (1..%d, the slots)", who, n_groups, B);
     if (mask_size < 1) return fail(SMK_E_ARG, "%s: bad geometry (mask %d)", who, mask_size);
     RleParams r;
-    CHK(rle_fill(who, r, B, canvas_w, canvas_h, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    if (png) {                                                        // smk_vos_png_*: a byte stream per group in the counts' place
+        memset(&r, 0, sizeof(r));
+        CHK(png_fill(who, *png, B, canvas_w, canvas_h, cap, ws_dev, ws_bytes, (uint8_t *)counts_out_dev, meta_out_dev));
+        png->grouped = 1;
+    } else {
+        CHK(rle_fill(who, r, B, canvas_w, canvas_h, cap, ws_dev, ws_bytes, counts_out_dev, meta_out_dev));
+    }
     memset(&p, 0, sizeof(p));
     memset(&scan, 0, sizeof(scan));
     for (int b = 0; b < B; ++b) { scan.wh[b][0] = canvas_w; scan.wh[b][1] = canvas_h; }
@@ -1080,7 +1171,10 @@ static int vos_rle_fill_v(const char *who, VosRleVParams &p, RleVParams &scan, c
         for (int b = 0; b < B; ++b)
             if ((m >> b) & 1) { scan.wh[b][0] = w; scan.wh[b][1] = h; }
         if ((live_groups >> g) & 1) scan.live |= m;
+        if (png && ((live_groups >> g) & 1)) png->lead |= 1u << __builtin_ctz(m);
     }
+    if (png)
+        for (int b = 0; b < B; ++b) { png->wh[b][0] = scan.wh[b][0]; png->wh[b][1] = scan.wh[b][1]; }
     if (given_mask & ~seen) return fail(SMK_E_ARG, "%s: given_mask %#x has bits outside every group (%#x)", who, given_mask, seen);
     if (alive_mask & ~seen) return fail(SMK_E_ARG, "%s: alive_mask %#x has bits outside every group (%#x)", who, alive_mask, seen);
     p.words = r.words; p.logits = src;
@@ -1199,6 +1293,44 @@ int smk_vos_score_dev_v(const float *logits_dev, const float *head_dev, int scor
     p.head_S = head_dev ? score_size : 0; p.slot = slot;
     p.st = (const smk_trk_stream *)state_dev;
     if (launch_vos_score_v(p, stream)) return fail(SMK_E_HIP, "vos_score_v launch failed");
+    return 0;
+}
+
+// ---- the fused label map of G videos as zlib streams: vos_rle_fill_v's checks with a byte stream per group ------
+int smk_vos_png_v(const float *logits_dev, int mask_size, const double *inv_map, int B, int canvas_w, int canvas_h, int n_groups,
+                  const uint32_t *group_masks, const int32_t *group_wh, const uint8_t *const *init_labels_dev, uint32_t live_groups,
+                  float border, const uint8_t *object_ids, uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap,
+                  void *ws_dev, size_t ws_bytes, uint8_t *out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!inv_map) return fail(SMK_E_ARG, "smk_vos_png_v: null argument");
+    VosRleVParams p;
+    RleVParams scan;
+    PngParams png;
+    CHK(vos_rle_fill_v("smk_vos_png_v", p, scan, logits_dev, mask_size, B, canvas_w, canvas_h, n_groups, group_masks, group_wh,
+                       init_labels_dev, live_groups, border, object_ids, alive_mask, seg_thr, given_mask, cap, ws_dev, ws_bytes,
+                       (uint32_t *)out_dev, meta_out_dev, &png));
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < 6; ++k) p.inv_map[b][k] = inv_map[6 * b + k];
+    if (launch_vos_png_v(p, png, B, stream)) return fail(SMK_E_HIP, "vos_png_v launch failed");
+    return 0;
+}
+
+int smk_vos_png_dev_v(const float *logits_dev, const float *head_dev, int score_size, int mask_size, const void *state_dev, int slot,
+                      int B, int canvas_w, int canvas_h, int n_groups, const uint32_t *group_masks, const int32_t *group_wh,
+                      const uint8_t *const *init_labels_dev, uint32_t live_groups, float border, const uint8_t *object_ids,
+                      uint32_t alive_mask, float seg_thr, uint32_t given_mask, int cap, void *ws_dev, size_t ws_bytes,
+                      uint8_t *out_dev, int32_t *meta_out_dev, void *stream) {
+    if (!state_dev) return fail(SMK_E_ARG, "smk_vos_png_dev_v: null argument");
+    if (slot != 0 && slot != 1) return fail(SMK_E_ARG, "smk_vos_png_dev_v: slot %d (0 or 1)", slot);
+    if (head_dev && (score_size < 1 || score_size > 1024)) return fail(SMK_E_ARG, "smk_vos_png_dev_v: score_size %d", score_size);
+    VosRleVParams p;
+    RleVParams scan;
+    PngParams png;
+    CHK(vos_rle_fill_v("smk_vos_png_dev_v", p, scan, head_dev ? head_dev : logits_dev, mask_size, B, canvas_w, canvas_h, n_groups,
+                       group_masks, group_wh, init_labels_dev, live_groups, border, object_ids, alive_mask, seg_thr, given_mask, cap,
+                       ws_dev, ws_bytes, (uint32_t *)out_dev, meta_out_dev, &png));
+    p.head_S = head_dev ? score_size : 0; p.slot = slot;
+    p.st = (const smk_trk_stream *)state_dev;
+    if (launch_vos_png_v(p, png, B, stream)) return fail(SMK_E_HIP, "vos_png_v launch failed");
     return 0;
 }
 

@@ -25,6 +25,7 @@ plan_vos() is its scheduler: a video holds n_obj slots for as many steps as it h
 """
 import numpy as np
 
+from . import png as png_host
 from . import rle as rle_host
 from . import vos as vos_host
 
@@ -317,7 +318,8 @@ def _vos_video(v, d, B):
     return T, h, w, np.ascontiguousarray(ids.astype(np.uint8)), first, last, init_at
 
 
-def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=None, thrs=None):
+def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=None, thrs=None, png=False, png_cap=None,
+            png_palette=None):
     """The VOS loop of track_vos (tools/test.py:459-520, without an annotation) for a DATASET: the objects of several videos share the
     B slots of ``tracker``, which this call reserves itself on the canvas of the largest h and w.  videos[v] = {'frames': uint8
     CUDA [T,h,w,3], 'object_ids': 1..B ids, 'start' / 'end': {id: frame} (the dataset's dictionaries, as run(vos=) with lifetimes
@@ -337,9 +339,17 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
     [T,O,K,2] and 'mean_iou' float32 [O,K] = vos.mean_iou(counts, start, end, object_ids); the result gains 'thrs' and 'miou'
     float32 [K] = vos.dataset_mean over the scored videos (None if none is scored; vos.miou_lines prints it).  With gt=None
     nothing of this is launched, allocated or returned.
+    png: True -- every step deflates every video's fused label map on the device (smk_vos_png_dev_v behind the
+    label planes, behind the score launch when the step is scored) and every video's dictionary gains 'label_png', per frame the
+    complete 8-bit PNG FILE as bytes (tools/test.py:518-525 --save_mask; a caller writes it under the frame's name; png.decode reads
+    it back) or None where the stream was longer than png_cap, and 'png_bytes' int32 [T], the stream's true size.  png_cap: bytes
+    reserved per stream (png.default_cap of the canvas); the streams of a chunk are ONE [chunk,B,png_cap] uint8 tensor of which
+    only the first max(n_bytes) columns are read back.  png_palette: None (grey, the label is the sample) or uint8 [<= 256,3] for an
+    indexed file (png.davis_palette()).  With png=False nothing of this is launched, allocated or returned.
     Refused before any launch (ValueError): the rpn variant, a per-stream hp table, a video with more objects than B or with none,
     an id missing from 'start' / 'end', a start frame outside the video, 'init' of the wrong shape, a bad cap or chunk, a gt list
-    of another length than videos, a gt of the wrong dtype, shape or device, bad thrs, thrs without gt.
+    of another length than videos, a gt of the wrong dtype, shape or device, bad thrs, thrs without gt, a bad png_cap, a palette
+    that is not uint8 [<= 256,3], png_cap or png_palette without png.
     -> {'videos': [per video, in the caller's order: {'slots', 'first_step', 'size': (h, w), 'object_ids', 'label_rle': per frame
     a list of O int64 count arrays (None where n > cap), 'n' / 'area' int32 [T,O], 'started' bool [O]}], 'steps', 'efficiency',
     'events'}; rle.labels_decode(d['label_rle'][t], *d['size']) is frame t's label map, rle.labels_to_coco its submission form."""
@@ -368,6 +378,16 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
     if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= Hc * Wc + 1 or max(Hc, Wc) > 4096:
         raise ValueError("run_vos: cap must be an integer in 1..%d on a canvas of up to 4096 x 4096, got %r" % (Hc * Wc + 1, cap))
     cap = int(cap)
+    if not png:
+        if png_cap is not None or png_palette is not None:
+            raise ValueError("run_vos: png_cap / png_palette without png: no label map is deflated")
+        pcap = pal = None
+    else:
+        pcap = png_host.default_cap(Hc, Wc) if png_cap is None else png_cap
+        if isinstance(pcap, bool) or not isinstance(pcap, (int, np.integer)) or not 1 <= pcap <= png_host.worst_cap(Hc, Wc):
+            raise ValueError("run_vos: png_cap must be an integer in 1..%d bytes on this canvas, got %r"
+                             % (png_host.worst_cap(Hc, Wc), png_cap))
+        pcap, pal = int(pcap), png_host.check_palette(png_palette)
     pl = plan_vos([i[0] for i in info], [i[3].size for i in info], B, order)        # (refuses an unknown order)
     dev = videos[0]["frames"].device
     thr = None
@@ -401,11 +421,14 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
             "object_ids": info[v][3].astype(np.int64), "label_rle": [None] * info[v][0],
             "n": np.zeros((info[v][0], info[v][3].size), dtype=np.int32), "area": np.zeros((info[v][0], info[v][3].size), dtype=np.int32)}
            for v in range(V)]
+    if png:
+        for v in range(V):
+            out[v]["label_png"], out[v]["png_bytes"] = [None] * info[v][0], np.zeros(info[v][0], dtype=np.int32)
     if thr is not None:
         for v in range(V):
             if gt[v] is not None:
                 out[v]["vos_counts"] = np.zeros((info[v][0], info[v][3].size, thr.size, 2), dtype=np.int64)
-    last, g0, rows, cnt = [None] * B, 0, None, None
+    last, g0, rows, cnt, prow = [None] * B, 0, None, None, None
     for g in range(pl.G):
         ids, alive, given = np.zeros(B, dtype=np.uint8), np.zeros(B, dtype=bool), np.zeros(B, dtype=bool)
         groups, sizes, init, begun, gts = [], [], [], [], []
@@ -431,12 +454,15 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
             n = min(int(chunk), pl.G - g0)
             rows = (torch.empty((n, B, cap), dtype=torch.int32, device=dev), torch.empty((n, B, 4), dtype=torch.int32, device=dev))
             cnt = torch.empty((n, B, thr.size, 2), dtype=torch.int32, device=dev) if thr is not None else None
-        if thr is None:
-            tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
-                            _rle_out=(rows[0][g - g0], rows[1][g - g0]))
-        else:                                                         # ... and the step's count row, right behind the label planes
-            tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
-                            _rle_out=(rows[0][g - g0], rows[1][g - g0]), _vos_gt=(gts, thr, cnt[g - g0]))
+            prow = (torch.empty((n, B, pcap), dtype=torch.uint8, device=dev),
+                    torch.empty((n, B, 4), dtype=torch.int32, device=dev)) if png else None
+        extra = {}
+        if thr is not None:                                           # ... the step's count row, right behind the label planes
+            extra["_vos_gt"] = (gts, thr, cnt[g - g0])
+        if png:                                                       # ... and the step's streams, behind both
+            extra["_png_out"] = (prow[0][g - g0], prow[1][g - g0])
+        tracker.enqueue(list(fed), _vos_v=(cap, groups, sizes, ids, alive, given, init, None),
+                        _rle_out=(rows[0][g - g0], rows[1][g - g0]), **extra)
         if begun:                                                     # ONE start event for every object that starts on this step
             slots_b = [b for _, _, b in begun]
             frames_b = [videos[v]["frames"][g - int(pl.first_step[v])] for v, _, _ in begun]
@@ -457,6 +483,9 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
             res = tracker.collect(_rle=rows) if thr is None else tracker.collect(_rle=rows, _counts=cnt)
             r = res["label_rle"]
             per = rle_host.to_host_v(dict(r, counts=r["counts"][..., :int(min(r["n"].max(), r["cap"]))].cpu().numpy()))
+            if png:                                                   # (collect() has synchronised the stream the launches ran on)
+                pm = prow[1].cpu().numpy()
+                pb = prow[0][..., :int(min(pm[..., 0].max(), pcap))].cpu().numpy()
             for t in range(g0, g + 1):
                 for v, slots in pl.steps[t]:
                     k, d = t - int(pl.first_step[v]), out[v]
@@ -466,11 +495,17 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
                     d["n"][k], d["area"][k] = r["n"][t - g0, slots], r["area"][t - g0, slots]
                     if "vos_counts" in d:
                         d["vos_counts"][k] = res["vos_counts"][t - g0, slots]
+                    if png:                                           # the stream stands in the row of the video's lowest slot
+                        nb, _, ph, pw = (int(x) for x in pm[t - g0, min(slots)])
+                        if (ph, pw) != d["size"] or nb < 1:
+                            raise RuntimeError("run_vos: video %d was deflated at another size than its frames'" % v)
+                        d["png_bytes"][k] = nb
+                        d["label_png"][k] = png_host.to_png(pb[t - g0, min(slots), :nb], ph, pw, pal) if nb <= pcap else None
             for e, objs in zip(res.get("events", []), ev_objs):
                 for (v, j, _), ok in zip(objs, e["started"]):
                     started[v][j] = bool(ok)
                 events.append(dict(e, step=g0 + e["t"], objects=[(v, j) for v, j, _ in objs]))
-            ev_objs, g0, rows, cnt, res, r, per = [], g + 1, None, None, None, None, None
+            ev_objs, g0, rows, cnt, res, r, per, prow = [], g + 1, None, None, None, None, None, None
     for v in range(V):
         out[v]["started"] = started[v]
     result = {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events}

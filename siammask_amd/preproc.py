@@ -914,6 +914,118 @@ def vos_rle_dev_v(logits, state, slot, canvas_wh, groups, sizes=None, object_ids
     return counts, meta
 
 
+# (device, stream, B, W, H, cap) -> the workspace of smk_png_encode / smk_vos_png_*: the rule of _rle_ws, with the cap in the key
+# because the run table is sized by it
+_png_ws = collections.OrderedDict()
+
+
+def _png_buffers(device, B, W, H, cap, out, meta):
+    """the checked cap and the workspace / outputs the PNG wrappers share -> (cap, ws, ws bytes, out uint8 [B,cap], meta [B,4])"""
+    from . import png
+    L = _lib.lib()
+    worst = L.smk_png_worst_bytes(W, H)
+    if worst == 0 or B < 1:
+        raise ValueError("png: B >= 1 and H, W in 1..4096, got B = %d, %d x %d" % (B, H, W))
+    cap = png.default_cap(H, W) if cap is None else cap
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= worst:
+        raise ValueError("png: cap must be an integer in 1..%d bytes, got %r" % (worst, cap))
+    cap = int(cap)
+    need = L.smk_png_workspace(B, W, H, cap)
+    key = (device.index, _lib.current_stream_ptr().value, B, W, H, cap)
+    ws = _png_ws.get(key)
+    if ws is None:
+        ws = _png_ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
+        while len(_png_ws) > _RLE_WS_MAX:
+            _png_ws.popitem(last=False)
+    else:
+        _png_ws.move_to_end(key)
+    if out is None:
+        out = torch.empty((B, cap), dtype=torch.uint8, device=device)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (B, cap):
+        raise ValueError("png: out must be a contiguous uint8 CUDA tensor [%d,%d]" % (B, cap))
+    if meta is None:
+        meta = torch.empty((B, 4), dtype=torch.int32, device=device)
+    elif meta.dtype != torch.int32 or not meta.is_cuda or not meta.is_contiguous() or tuple(meta.shape) != (B, 4):
+        raise ValueError("png: meta must be a contiguous int32 CUDA tensor [%d,4]" % B)
+    return cap, ws, need, out, meta
+
+
+def png_encode(planes, cap=None, out=None, meta=None):
+    """The zlib streams of byte maps, deflated on the device (include/siammask_hip.h: smk_png_encode).  planes: uint8 CUDA [B,H,W] or
+    [H,W] of ANY byte values -- a fused label map, a 0 / 255 mask --, H and W up to 4096.  cap: bytes reserved per stream
+    (png.default_cap(H, W)).  -> (out uint8 CUDA [B,cap], meta int32 CUDA [B,4] = (n_bytes, n_runs, H, W)): out[b, :n_bytes] is
+    what a PNG's IDAT chunk holds (png.to_png writes the file); n_bytes > cap reports an overflow (only cap bytes were written).
+    Bytes past n_bytes are not written.  png.encode_host_v is the CPU twin: the same bytes."""
+    _need_cuda(planes, "planes")
+    if planes.dtype != torch.uint8 or planes.dim() not in (2, 3):
+        raise ValueError("planes must be uint8 [B,H,W] or [H,W]")
+    m = planes.contiguous()
+    if m.dim() == 2:
+        m = m[None]
+    B, H, W = (int(v) for v in m.shape)
+    with torch.cuda.device(m.device):
+        cap, ws, need, out, meta = _png_buffers(m.device, B, W, H, cap, out, meta)
+        _lib.check(_lib.lib().smk_png_encode(m.data_ptr(), B, W, H, cap, ws.data_ptr(), need, out.data_ptr(), meta.data_ptr(),
+                                             _lib.current_stream_ptr()))
+    return out, meta
+
+
+def vos_png_v(logits, back_boxes, canvas_wh, groups, sizes, object_ids, alive=None, given=None, init=None, live=None, seg_thr=0.35,
+              padding=-1.0, cap=None, out=None, meta=None):
+    """vos_rle_v whose result is ONE zlib stream per group: the fused label map of every live group, deflated as png_encode
+    deflates its bytes, without a label byte being read (smk_vos_png_v).  Arguments as for vos_rle_v; cap in bytes
+    (png.default_cap of the canvas).  -> (out uint8 CUDA [B,cap], meta int32 CUDA [B,4] = (n_bytes, n_runs, h_g, w_g)): a group's
+    stream stands in the row of its LOWEST slot; n_bytes = 0 in every other row."""
+    _need_cuda(logits, "logits")
+    logits = logits.contiguous().float()
+    B = int(logits.shape[0])
+    ms = int(round(logits[0].numel() ** 0.5))
+    if ms * ms != logits[0].numel() or len(back_boxes) != B:
+        raise ValueError("logits must be [B, ms*ms] with one back_box per slot")
+    v = VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    inv = np.zeros((B, 6), dtype=np.float64)
+    for slots, (w, h) in zip(v.groups, v.wh):
+        for b in slots:
+            inv[b] = invert_affine(crop_back_map(back_boxes[b], (int(w), int(h)))).reshape(6)
+    with torch.cuda.device(logits.device):
+        cap, ws, need, out, meta = _png_buffers(logits.device, B, v.W, v.H, cap, out, meta)
+        _lib.check(_lib.lib().smk_vos_png_v(logits.data_ptr(), ms, inv.ctypes.data, B, v.W, v.H,
+                                            *v.tail(seg_thr, padding, cap, ws, need, out, meta)))
+    return out, meta
+
+
+def vos_png_dev_v(logits, state, slot, canvas_wh, groups, sizes=None, object_ids=None, alive=None, given=None, init=None, live=None,
+                  seg_thr=0.35, padding=-1.0, head=None, mask_size=None, cap=None, out=None, meta=None):
+    """vos_png_v with the inverse map inv_map[slot] (and, with head, the column delta_yx[slot]) of every slot read on the device
+    from the tracker's state block (smk_vos_png_dev_v).  groups may be a checked VosGroups (the tracker's paste job), the
+    arguments from sizes to live are then unused."""
+    src = head if head is not None else logits
+    _need_cuda(src, "logits")
+    _need_cuda(state, "state")
+    if src.dtype != torch.float32 or not src.is_contiguous():
+        raise ValueError("logits / head must be contiguous float32")
+    B = int(src.shape[0])
+    S = 0
+    if head is not None:
+        S = int(head.shape[-1])
+        ms = int(mask_size or round(head.shape[1] ** 0.5))
+        if head.dim() != 4 or head.shape[2] != S or ms * ms != head.shape[1]:
+            raise ValueError("head must be [B, ms*ms, S, S]")
+    else:
+        ms = int(mask_size or round(logits[0].numel() ** 0.5))
+        if ms * ms != logits[0].numel():
+            raise ValueError("logits must be [B, ms*ms]")
+    v = groups if isinstance(groups, VosGroups) else VosGroups(B, canvas_wh, groups, sizes, object_ids, alive, given, init, live)
+    if v.B != B or (v.W, v.H) != (int(canvas_wh[0]), int(canvas_wh[1])):
+        raise ValueError("vos_png_dev_v: the groups were checked for %d slots on %d x %d" % (v.B, v.W, v.H))
+    with torch.cuda.device(src.device):
+        cap, ws, need, out, meta = _png_buffers(src.device, B, v.W, v.H, cap, out, meta)
+        _lib.check(_lib.lib().smk_vos_png_dev_v(
+            None if head is not None else logits.data_ptr(), head.data_ptr() if head is not None else None, S, ms,
+            state.data_ptr(), int(slot), B, v.W, v.H, *v.tail(seg_thr, padding, cap, ws, need, out, meta)))
+    return out, meta
+
+
 def vos_score_gt(v, gt, thrs, device, idle_ok=False):
     """the checked annotation and thresholds of vos_score_v / vos_score_dev_v, pure host work: v a checked VosGroups, gt one entry per
     group -- None (the video is not scored on this step) or a contiguous uint8 CUDA tensor [h_g,w_g] on ``device`` --, at least one

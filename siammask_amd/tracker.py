@@ -135,8 +135,9 @@ _Score = collections.namedtuple("_Score", "gt ids thrs bits gbits init row label
 # frame's counts [B,cap] and meta [B,4]
 _LabelRle = collections.namedtuple("_LabelRle", "cap masks labels counts meta")
 # the checked _vos_v of enqueue() (dataset.run_vos: the objects of several videos share the slots): the frame's _LabelRle and the
-# preproc.VosGroups the C entry takes; score: None, or the _VosScore of a frame enqueued with _vos_gt as well
-_VosV = collections.namedtuple("_VosV", "rle groups score", defaults=(None,))
+# preproc.VosGroups the C entry takes; score: None, or the _VosScore of a frame enqueued with _vos_gt as well; png: None, or the
+# checked _png_out of the frame, (bytes uint8 [B,cap], meta int32 [B,4])
+_VosV = collections.namedtuple("_VosV", "rle groups score png", defaults=(None, None))
 # the checked _vos_gt of enqueue(): the host array of the groups' gt pointers (None: no group is scored on this frame, the row is
 # zeroed), the thresholds, the frame's count row [B,K,2] and the gt tensors themselves, kept alive until the job has been launched
 _VosScore = collections.namedtuple("_VosScore", "ptrs thrs row keep")
@@ -797,13 +798,15 @@ class DeviceTracker(object):
             raise ValueError("vos['rle']['labels']: the label map comes from the scoring launch, which needs gt=")
         return _LabelRle(int(cap), bool(lr.get("masks", False)), bool(lr.get("labels", False)), None, None)
 
-    def _vos_v_spec(self, mixed, want_mask, other, vos_v, vos_gt=None):
-        """the checked _vos_v [and _vos_gt] of one frame (before anything is launched) -> None, or a _VosV (counts / meta still
-        None, the count row as given).  other: the frame also asks for a polygon, mask_out=, rle= / _rle_v, iou= or carries the
-        hook of run(vot=)"""
+    def _vos_v_spec(self, mixed, want_mask, other, vos_v, vos_gt=None, png_out=None):
+        """the checked _vos_v [, _vos_gt and _png_out] of one frame (before anything is launched) -> None, or a _VosV (counts /
+        meta still None, the count row as given).  other: the frame also asks for a polygon, mask_out=, rle= / _rle_v, iou= or
+        carries the hook of run(vot=)"""
         if vos_v is None:
             if vos_gt is not None:
                 raise ValueError("_vos_gt scores the groups of _vos_v: it comes with it")
+            if png_out is not None:
+                raise ValueError("_png_out deflates the label maps of _vos_v: it comes with it")
             return None
         q = self._fr
         if not mixed or other or q.B > 32:
@@ -828,7 +831,19 @@ class DeviceTracker(object):
         if q.chunk.pending and ((q.chunk.vos_k is not None) != (score is not None) or
                                 (score is not None and q.chunk.vos_k != int(score.thrs.size))):
             raise ValueError("every frame of a chunk carries _vos_gt with one number of thresholds, or none does")
-        return _VosV(_LabelRle(int(cap), False, False, None, None), v, score)
+        if png_out is not None:
+            from . import png as png_host
+            ok = isinstance(png_out, (tuple, list)) and len(png_out) == 2 and all(isinstance(t, torch.Tensor) for t in png_out)
+            if ok:
+                pb, pm = png_out
+                ok = pb.is_cuda and pm.is_cuda and pb.device == q.device and pm.device == q.device and pb.dtype == torch.uint8 and \
+                    pm.dtype == torch.int32 and pb.is_contiguous() and pm.is_contiguous() and pb.dim() == 2 and \
+                    int(pb.shape[0]) == q.B and 1 <= int(pb.shape[1]) <= png_host.worst_cap(q.H, q.W) and tuple(pm.shape) == (q.B, 4)
+            if not ok:
+                raise ValueError("_png_out: (uint8 CUDA [%d,cap], int32 CUDA [%d,4]) on the tracker's device, contiguous, cap in 1..%d "
+                                 "bytes" % (q.B, q.B, png_host.worst_cap(q.H, q.W)))
+            png_out = (pb, pm)
+        return _VosV(_LabelRle(int(cap), False, False, None, None), v, score, png_out)
 
     def _iou_spec(self, mixed, want_mask, want_polygon, mask_out, scored_vos, iou):
         """the checked iou= request of one frame (before anything is launched) -> None, or an _Iou (row still None)"""
@@ -887,7 +902,7 @@ class DeviceTracker(object):
         return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None, _vos_gt=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None, _vos_gt=None, _png_out=None):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -928,6 +943,10 @@ class DeviceTracker(object):
         row_out: int32 CUDA [B,K,2] or None) -- smk_vos_score_dev_v right behind smk_vos_rle_dev_v on the same stream scores every
         group that has a gt against it; a frame whose groups all have None gets a zero row and no launch.  Every frame of a chunk
         carries it (one K) or none does; collect() returns res['vos_counts'] int64 [T,B,K,2] indexed by slot.
+        _png_out (private, dataset.run_vos; only with _vos_v): (bytes uint8 CUDA [B,cap], meta int32 CUDA [B,4]), the frame's rows
+        of the caller's tensors -- smk_vos_png_dev_v on the same stream right behind the label planes (behind the score launch when
+        the step is scored) deflates every live group's fused label map into the row of the group's lowest slot (siammask_amd.png);
+        it warps every pixel once more.  The caller reads its tensors behind collect(): nothing of them comes back from it.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
         -> the frame's index in the chunk that collect() returns."""
@@ -973,7 +992,7 @@ class DeviceTracker(object):
             raise ValueError("every frame of a chunk carries _rle_v, or none does")
         iou = self._iou_spec(mixed, want_mask, want_polygon, mask_out, vos is not None or gt is not None, iou)
         vv = self._vos_v_spec(mixed, want_mask, want_polygon or mask_out is not None or rle is not None or iou is not None
-                              or _after is not None, _vos_v, _vos_gt)
+                              or _after is not None, _vos_v, _vos_gt, _png_out)
         score = None if mixed else self._vos_spec(frame.dim(), want_mask, gt, vos, labels_out)
         frame = list(frame) if mixed else frame.contiguous()
         L, model = _lib.lib(), self.model
@@ -1114,6 +1133,10 @@ class DeviceTracker(object):
             elif sc is not None:                                      # right behind the label planes, same stream, same records
                 preproc.vos_score_dev_v(logits, q.dev, job.slot, (q.W, q.H), job.vos_v.groups, (sc.ptrs, sc.thrs), None, head=head,
                                         mask_size=self.mask_size, out=sc.row)
+            if job.vos_v.png is not None:                             # the same labels once more, as one zlib stream per group
+                pb, pm = job.vos_v.png
+                preproc.vos_png_dev_v(logits, q.dev, job.slot, (q.W, q.H), job.vos_v.groups, seg_thr=p.seg_thr, head=head,
+                                      mask_size=self.mask_size, cap=int(pb.shape[1]), out=pb, meta=pm)
         if lr is not None and s.labels is None:                       # the fused label planes, in the paste-back's place: no label byte
             preproc.vos_rle_dev(logits, q.dev, job.slot, (q.W, q.H), s.ids, init=s.init, seg_thr=p.seg_thr, head=head,
                                 mask_size=self.mask_size, cap=lr.cap, counts=lr.counts, meta=lr.meta, _bits=(s.bits, s.gbits))
