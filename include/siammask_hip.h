@@ -798,6 +798,39 @@ int smk_ope_curve(const double *pred_dev, const double *gt_dev, const int32_t *o
                   int V, const double *thr_overlap, int K1, const double *thr_error, int K2, int quantise, int32_t *counts_dev,
                   double *iou_dev, double *dist_dev, void *stream);
 
+/* ---- the supervised VOT loop of a DATASET run: overlap, decision and the evaluator's rows per slot (additive; smk_version() keeps
+ * reporting 1.10, the presence of this symbol is the probe) ------------------------------------------------------------------
+ * track_vot (tools/test.py:318-365) for videos that move through the B slots of one tracker: smk_vot_overlap_dev with the
+ * decision made on the device, next to the overlap, and every result written where the evaluator (smk_vot_traj_overlap,
+ * smk_eao_curve) reads it -- the frames of the V videos concatenated, N rows in all, row n = offsets[v] + t.
+ * Slot b (B in 1..32) carries HOST values that travel as kernel arguments (no device table, nothing of the caller's host memory
+ * is read after the call returns): row_host[b] = its frame's row n, vid_host[b] = its video v, t_host[b] = the frame's index
+ * in its video (>= 1: frame 0 initialises and is never stepped), and bit b of live_mask.  vstate_dev int32 [V][2] =
+ * (start_frame, lost_times) per video, zeroed by the caller before the video's first step; only the slot that currently runs
+ * video v touches row v, in stream order.
+ * Per live slot, in this order:
+ *   t <  start_frame (inside a skip window): code_dev[n] <- 0, nothing else; no overlap is computed.
+ *   t == start_frame (the frame of a re-initialisation): code_dev[n] <- 1, nothing else.
+ *   otherwise the frame is tracked: the prediction's corners are taken as smk_vot_overlap_dev takes them (pred_dev rows of stride
+ *     8 or 12 per SLOT, the box of the advance row where a stride-12 row's `found` is not positive, the clipped state with
+ *     pred_dev NULL), the bounds from record b of state_dev clamped into 1..4096, the annotation is gt_dev[n] (f64 [N][8]), the
+ *     reference's FIRST polygon.  overlap_dev[n] (f32 [N]) <- the overlap, counts_dev[n] (int32 [N][4], may be NULL) <- the four
+ *     counts of smk_vot_overlap, poly_dev[n] (f64 [N][8]) <- the eight corners that were used.  An overlap that is not exactly
+ *     0 (NaN included, as `if b_overlap:`): code_dev[n] <- -1.  Exactly 0, a loss: code_dev[n] <- 2 and vstate_dev[v] <-
+ *     (t + skip, lost_times + 1).
+ *   in every live case start_out_dev[b] (int32 [B]) <- the video's start_frame AFTER the decision: the row a caller's lagging
+ *     read-back takes to learn that frame t + skip re-initialises.
+ * A slot whose live bit is clear writes nothing at all.  Every store is a plain store by one lane; no atomics, nothing is zeroed,
+ * a second call on the same state behaves as the next step would.  code_dev is int8 [N].
+ * SMK_E_ARG before anything is enqueued: a null pointer (counts_dev excepted; pred_dev only with adv_rows_dev), pred_stride
+ * other than 8 / 12, B outside 1..32, live_mask bits at or above B, N or V below 1, a live row outside 0..N-1, a live vid outside
+ * 0..V-1, a live t below 1, two live slots with the same vid or the same row, skip outside 1..65535, a misaligned pointer.
+ * No context; asynchronous on `stream`, no host synchronisation, no workspace. */
+int smk_vot_step_rows_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
+                          const void *state_dev, int B, const int32_t *row_host, const int32_t *vid_host, const int32_t *t_host,
+                          uint32_t live_mask, int N, int V, int skip, int32_t *vstate_dev, int8_t *code_dev, double *poly_dev,
+                          float *overlap_dev, int32_t *counts_dev, int32_t *start_out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,13 @@ int smk_host_trk_start_v(void *state, int B, const smk_trk_cfg *cfg, uint32_t st
  * (csrc/vot_overlap.h), rows looped by one thread.  pred, gt: f64 [n][8] corners; overlap f32 [n]; counts int32 [n][4] (may be
  * NULL) as for smk_vot_overlap. */
 int smk_host_vot_overlap(const double *pred, const double *gt, int n, int im_w, int im_h, float *overlap, int32_t *counts);
+/* smk_vot_step_rows_dev on HOST memory: the same checks, the same decision function (csrc/vot_overlap.h: vot_step_phase,
+ * vot_step_decide) and the overlap of smk_host_vot_overlap, slots looped in ascending order by one thread.  im_wh int32 [B][2] =
+ * (w, h), the image size of slot b in place of the state records (clamped into 1..4096 as the kernel clamps a record). */
+int smk_host_vot_step_rows(const double *pred, int pred_stride, const double *adv_rows, const double *gt, const int32_t *im_wh,
+                           int B, const int32_t *row, const int32_t *vid, const int32_t *t, uint32_t live_mask, int N, int V,
+                           int skip, int32_t *vstate, int8_t *code, double *poly, float *overlap, int32_t *counts,
+                           int32_t *start_out);
 
 /* which path each stream took in the last smk_mask_rbox_ex(mode = SMK_RBOX_CYCLES) call on workspace `ws_dev` (same B, W, H):
  * paths_host [B] = 0 parallel contour area, 1 serial trace (bounding rectangle beyond SMK_RBOX_STATE_CAP).  Synchronises the

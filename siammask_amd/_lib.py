@@ -48,6 +48,7 @@ SYMBOLS = (
     "smk_vot_traj_overlap", "smk_eao_workspace_bytes", "smk_eao_curve",
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
     "smk_ope_curve", "smk_host_ope_curve",
+    "smk_vot_step_rows_dev", "smk_host_vot_step_rows",
 )
 
 
@@ -223,6 +224,9 @@ def lib():
     L.smk_host_eao_curve.argtypes = [vp] * 3 + [ci] * 6 + [vp] * 5 + [ci]
     L.smk_ope_curve.argtypes = [vp] * 4 + [ci] * 3 + [vp, ci, vp, ci, ci] + [vp] * 4
     L.smk_host_ope_curve.argtypes = [vp] * 3 + [ci] * 3 + [vp, ci, vp, ci, ci] + [vp] * 3
+    # pred, stride, adv, gt, state | im_wh, B, row, vid, t, live, N, V, skip, vstate, code, poly, overlap, counts, start_out[, stream]
+    L.smk_vot_step_rows_dev.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, u32, ci, ci, ci] + [vp] * 7
+    L.smk_host_vot_step_rows.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, u32, ci, ci, ci] + [vp] * 6
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]

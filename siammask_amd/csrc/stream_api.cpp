@@ -1350,4 +1350,62 @@ int smk_vot_overlap_dev(const double *pred_dev, int pred_stride, const double *a
     return 0;
 }
 
+// ---- the supervised loop of a dataset run: overlap, decision and the evaluator's rows per slot (vot_overlap.hip) ----
+// the checks the device entry and its host twin share; fills p on success
+static int vot_step_fill(const char *who, VotStepParams &p, const double *pred, int pred_stride, const double *adv, const double *gt,
+                         int B, const int32_t *row, const int32_t *vid, const int32_t *t, uint32_t live_mask, int N, int V, int skip,
+                         int32_t *vstate, int8_t *code, double *poly, float *overlap, int32_t *counts, int32_t *start_out) {
+    if (!gt || !row || !vid || !t || !vstate || !code || !poly || !overlap || !start_out || (!pred && !adv))
+        return fail(SMK_E_ARG, "%s: null argument", who);
+    if (pred && pred_stride != 8 && pred_stride != 12)
+        return fail(SMK_E_ARG, "%s: pred_stride %d (8 corners, or the 12 of smk_mask_rbox)", who, pred_stride);
+    if (B < 1 || B > VOT_STEP_SLOTS) return fail(SMK_E_ARG, "%s: %d slots (1..%d)", who, B, VOT_STEP_SLOTS);
+    if (B < 32 && (live_mask >> B)) return fail(SMK_E_ARG, "%s: live_mask has bits at or above B = %d", who, B);
+    if (N < 1 || V < 1) return fail(SMK_E_ARG, "%s: N = %d rows, V = %d videos", who, N, V);
+    if (skip < 1 || skip > 65535) return fail(SMK_E_ARG, "%s: skip %d (1..65535)", who, skip);
+    if ((uintptr_t)pred % 8 || (uintptr_t)adv % 8 || (uintptr_t)gt % 8 || (uintptr_t)poly % 8 || (uintptr_t)vstate % 4 ||
+        (uintptr_t)overlap % 4 || (uintptr_t)counts % 4 || (uintptr_t)start_out % 4)
+        return fail(SMK_E_ARG, "%s: misaligned argument", who);
+    for (int b = 0; b < B; ++b) {
+        p.row[b] = 0; p.vid[b] = 0; p.t[b] = 1;
+        if (!(live_mask >> b & 1u)) continue;
+        if (row[b] < 0 || row[b] >= N) return fail(SMK_E_ARG, "%s: slot %d: row %d outside 0..%d", who, b, row[b], N - 1);
+        if (vid[b] < 0 || vid[b] >= V) return fail(SMK_E_ARG, "%s: slot %d: video %d outside 0..%d", who, b, vid[b], V - 1);
+        if (t[b] < 1 || t[b] > INT32_MAX - 65535) return fail(SMK_E_ARG, "%s: slot %d: local frame %d (>= 1)", who, b, t[b]);
+        for (int a = 0; a < b; ++a)
+            if ((live_mask >> a & 1u) && (vid[a] == vid[b] || row[a] == row[b]))
+                return fail(SMK_E_ARG, "%s: slots %d and %d share a video or a row", who, a, b);
+        p.row[b] = row[b]; p.vid[b] = vid[b]; p.t[b] = t[b];
+    }
+    for (int b = B; b < VOT_STEP_SLOTS; ++b) { p.row[b] = 0; p.vid[b] = 0; p.t[b] = 1; }
+    p.pred = pred; p.adv = adv; p.gt = gt; p.vstate = vstate; p.code = code; p.poly = poly; p.overlap = overlap; p.counts = counts;
+    p.start_out = start_out; p.pred_stride = pred ? pred_stride : 0; p.B = B; p.skip = skip; p.live = live_mask;
+    return 0;
+}
+
+int smk_vot_step_rows_dev(const double *pred_dev, int pred_stride, const double *adv_rows_dev, const double *gt_dev,
+                          const void *state_dev, int B, const int32_t *row_host, const int32_t *vid_host, const int32_t *t_host,
+                          uint32_t live_mask, int N, int V, int skip, int32_t *vstate_dev, int8_t *code_dev, double *poly_dev,
+                          float *overlap_dev, int32_t *counts_dev, int32_t *start_out_dev, void *stream) {
+    if (!state_dev || (uintptr_t)state_dev % 8) return fail(SMK_E_ARG, "smk_vot_step_rows_dev: null or misaligned state");
+    VotStepParams p;
+    CHK(vot_step_fill("smk_vot_step_rows_dev", p, pred_dev, pred_stride, adv_rows_dev, gt_dev, B, row_host, vid_host, t_host, live_mask,
+                      N, V, skip, vstate_dev, code_dev, poly_dev, overlap_dev, counts_dev, start_out_dev));
+    if (!live_mask) return 0;                                         // no live slot writes nothing: nothing to launch
+    if (launch_vot_step_rows(p, state_dev, stream)) return fail(SMK_E_HIP, "vot_step_rows launch failed");
+    return 0;
+}
+
+int smk_host_vot_step_rows(const double *pred, int pred_stride, const double *adv_rows, const double *gt, const int32_t *im_wh,
+                           int B, const int32_t *row, const int32_t *vid, const int32_t *t, uint32_t live_mask, int N, int V,
+                           int skip, int32_t *vstate, int8_t *code, double *poly, float *overlap, int32_t *counts,
+                           int32_t *start_out) {
+    if (!im_wh) return fail(SMK_E_ARG, "smk_host_vot_step_rows: null argument");
+    VotStepParams p;
+    CHK(vot_step_fill("smk_host_vot_step_rows", p, pred, pred_stride, adv_rows, gt, B, row, vid, t, live_mask, N, V, skip, vstate,
+                      code, poly, overlap, counts, start_out));
+    for (int b = 0; b < B; ++b) vot_step_serial(p, b, im_wh[2 * b], im_wh[2 * b + 1]);
+    return 0;
+}
+
 }  // extern "C"

@@ -245,5 +245,56 @@ SMK_VOT_HD void vot_pred_corners(const double *pred, int pred_stride, const doub
     for (int k = 0; k < 8; ++k) c[k] = row[k];
 }
 
+// ---- the supervised loop's decision per slot (tools/test.py:322-365), once for host and device -------------------------------
+// vstate row of a video: (start_frame, lost_times).  vot_step_phase: what local frame t is BEFORE any overlap is looked at.
+constexpr int VOT_STEP_SLOTS = 32;
+enum { VOT_STEP_SKIP = 0, VOT_STEP_INIT = 1, VOT_STEP_TRACK = 2 };
+SMK_VOT_HD int vot_step_phase(int t, int start_frame) {
+    return t < start_frame ? VOT_STEP_SKIP : (t == start_frame ? VOT_STEP_INIT : VOT_STEP_TRACK);
+}
+// a tracked frame's overlap -> its code; a loss (exactly 0; NaN is "not lost", `if b_overlap:`) moves the video's start frame
+// `skip` frames on and counts
+SMK_VOT_HD int vot_step_decide(float ov, int t, int skip, int32_t *vs) {
+    if (!(ov == 0.0f)) return -1;
+    vs[0] = t + skip;
+    vs[1] = vs[1] + 1;
+    return 2;
+}
+
+struct VotStepParams {
+    const double *pred, *adv, *gt;  // pred / adv per SLOT as VotParams; gt [N][8] per dataset row
+    int32_t *vstate;                // [V][2]
+    int8_t *code;                   // [N]
+    double *poly;                   // [N][8]
+    float *overlap;                 // [N]
+    int32_t *counts;                // [N][4] or nullptr
+    int32_t *start_out;             // [B]
+    int pred_stride, B, skip;
+    uint32_t live;
+    int row[VOT_STEP_SLOTS], vid[VOT_STEP_SLOTS], t[VOT_STEP_SLOTS];
+};
+int launch_vot_step_rows(const VotStepParams &p, const void *state, void *stream);
+
+// the whole step of one slot on one thread (the host entry); im_w, im_h as the kernel clamps the record's
+SMK_VOT_HD void vot_step_serial(const VotStepParams &p, int b, int im_w, int im_h) {
+    if (!(p.live >> b & 1u)) return;
+    const int n = p.row[b], t = p.t[b];
+    int32_t *vs = p.vstate + 2 * (size_t)p.vid[b];
+    const int phase = vot_step_phase(t, vs[0]);
+    if (phase != VOT_STEP_TRACK) {
+        p.code[n] = (int8_t)phase;                                    // (VOT_STEP_SKIP / VOT_STEP_INIT are the codes 0 / 1)
+        p.start_out[b] = vs[0];
+        return;
+    }
+    double c[8];
+    vot_pred_corners(p.pred, p.pred_stride, p.adv, b, c);
+    const float ov = vot_overlap_serial(p.gt + 8 * (size_t)n, c, v_imin(v_imax(im_w, 1), VOT_MAX_DIM),
+                                        v_imin(v_imax(im_h, 1), VOT_MAX_DIM), p.counts ? p.counts + 4 * (size_t)n : nullptr);
+    p.overlap[n] = ov;
+    for (int k = 0; k < 8; ++k) p.poly[8 * (size_t)n + k] = c[k];
+    p.code[n] = (int8_t)vot_step_decide(ov, t, p.skip, vs);
+    p.start_out[b] = vs[0];
+}
+
 }  // namespace smk
 #endif

@@ -22,6 +22,14 @@ and leaves as one run-length code per object per frame.
     rle.labels_decode(d['label_rle'][t], *d['size'])            # frame t's label map; rle.labels_to_coco: the submission dicts
 
 plan_vos() is its scheduler: a video holds n_obj slots for as many steps as it has frames, first fit on the lowest free slots.
+
+VOT datasets: the supervised loop of track_vot -- an overlap of exactly 0 is a loss, the video skips 5 frames and is
+re-initialised -- through the same slots and the same plan(); overlap, decision and the evaluator's rows are made on the device.
+
+    res = dataset.run_vot(tr, videos, gt)                       # gt[v]: float64 [T_v,8] corners (or [T_v,4] rectangles)
+    d = res['videos'][v]                                        # code [T_v], polygon [T_v,4,2], overlap [T_v], lost_times
+    dataset.vot_lines(d)                                        # the lines of <video>_001.txt
+    dataset.eval_vot(res, dataset='VOT2018')                    # evaluate.vot on the tables the run left on the device
 """
 import numpy as np
 
@@ -31,6 +39,7 @@ from . import vos as vos_host
 
 ORDERS = ("given", "longest")
 _ROWS = ("target_pos", "target_sz", "score", "best_id", "polygon", "polygon_found")
+_VOT_ROWS = ("target_pos", "target_sz", "score", "best_id")           # run_vot: the polygons come from the device table instead
 
 
 class Plan(object):
@@ -516,6 +525,232 @@ def run_vos(tracker, videos, B=None, order="longest", cap=None, chunk=256, gt=No
         scored = [d["mean_iou"] for d in out if "mean_iou" in d]
         result["thrs"], result["miou"] = thr, vos_host.dataset_mean(scored) if scored else None
     return result
+
+
+# ---- VOT datasets: the supervised loop through the B slots, decided on the device ------------------------------
+def vot_starts(row, refills, ring_row, lengths, skip):
+    """The start() merge rule of one step of run_vot, pure numpy.  row: int [B,2] = (video, local frame) per slot, -1 where idle
+    (plan().table[g]); refills: the plan's (slot, video) pairs started behind this step; ring_row: the [B] start frames the device
+    reported behind step g - skip (None before step `skip`); lengths [V].  A slot at local frame t is re-initialised behind this
+    step if and only if t > skip and ring_row[slot] == t (a loss on frame t - skip); one that falls on the video's last frame is
+    dropped -- the slot is free behind this step, a refill takes it.  -> [(slot, video, frame)] in slot order, the ONE start()
+    call of the step: re-initialisations on their frame t, refills on frame 0."""
+    out = {}
+    for b, (v, t) in enumerate(np.asarray(row).reshape(-1, 2).tolist()):
+        if v >= 0 and t > skip and ring_row is not None and int(ring_row[b]) == t and t < int(lengths[v]) - 1:
+            out[b] = (b, v, t)
+    for s, v in refills:
+        if s in out:
+            raise RuntimeError("run_vot: slot %d is re-initialised and refilled behind one step" % s)
+        out[int(s)] = (int(s), int(v), 0)
+    return [out[b] for b in sorted(out)]
+
+
+def run_vot(tracker, videos, gt, B=None, order="longest", skip=5, rle=False, chunk=256):
+    """The supervised loop of track_vot (tools/test.py:318-365, `--dataset VOT2018`) for a DATASET: every video runs once through the
+    B slots of ``tracker`` as plan() places it -- a video holds its slot for exactly T_v - 1 steps whatever it loses, the frames of
+    a skip window are stepped through -- and after every tracked frame the overlap of the polygon with the annotation, the
+    decision (an overlap of exactly 0 is a loss, the video skips `skip` frames and is re-initialised) and the rows of the result
+    are made on the device (smk_vot_step_rows_dev in the frame's hook, behind its rotated box).  The host only learns what it
+    needs to launch start(): the [B] start frames of every step are copied asynchronously into a pinned ring of skip + 1 rows,
+    and before step g is enqueued the host waits for the event of step g - skip alone (a loss on frame t takes effect on frame
+    t + skip).  The re-initialisations (on videos[v][t], from vot.axis_aligned_bbox(gt[v][t])) and the plan's refills of one
+    step are ONE start() call.
+    videos[v]: as run_videos takes them; gt[v]: float64 [T_v,8] corners or [T_v,4] rectangles (evaluate.corners), all finite; video
+    v starts on frame 0 from axis_aligned_bbox(gt[v][0]).  rle: False, True or {'cap': n} as run_videos -- the masks of the
+    stepped frames as run-length codes at the video's size; no mask is returned either way (polygons come through one re-used
+    canvas [B,Hc,Wc]).  chunk: steps per collect(); the result does not depend on it.  Device memory beyond the chunk's rows: the
+    tables gt [N,8], code [N], polygon [N,8], overlap [N] over the N = sum(T_v) frames and vstate [V,2], allocated once, read
+    back once at the end.
+    Refused before any launch (ValueError): a per-stream hp table, the rpn variant, a video of fewer than 2 frames, gt[v] not
+    [T_v, 8 or 4] or not finite, skip < 1, more than 32 slots, a frame of a list video of another size than its frame 0, a
+    canvas above 4096.
+    -> {'videos': [per video, in the caller's order: code int8 [T_v] (1 init, 2 lost, 0 skipped, -1 tracked), polygon float64
+    [T_v,4,2] (the corners used on codes -1 and 2, zeros elsewhere), overlap float32 [T_v] (likewise), lost_times, size (h, w),
+    slot, first_step, target_pos, target_sz, score, best_id over [T_v - 1, ...] (frame t + 1; unspecified where its code is not
+    -1 / 2)[, rle: T_v - 1 count arrays (frame t + 1; None where n > cap), n, area]], 'steps', 'efficiency', 'events',
+    'packed': evaluate.pack's dictionary for one tracker -- host arrays from the read-back, 'dev' the device tables themselves, so
+    that evaluate.vot(res['packed'], dataset=...) uploads nothing (eval_vot fills the names)}"""
+    import torch
+    from . import evaluate, preproc, vot as votmod
+    videos = list(videos)
+    V = len(videos)
+    lengths = [len(v) for v in videos]
+    if V and min(lengths) < 2:
+        raise ValueError("run_vot: every video has at least 2 frames (frame 0 initialises), video %d has %d"
+                         % (int(np.argmin(lengths)), min(lengths)))
+    if tracker.get_hp() is not None:
+        raise ValueError("run_vot: the tracker holds a per-stream hp table; its rows belong to slots and videos move between "
+                         "slots (set_hp(None) first)")
+    if tracker.model.variant == "rpn":
+        raise ValueError("run_vot: the supervised loop compares the polygon of the mask: a variant with a mask branch")
+    if isinstance(skip, bool) or int(skip) != skip or not 1 <= skip <= 65535:
+        raise ValueError("run_vot: skip must be an integer in 1..65535, got %r" % (skip,))
+    skip = int(skip)
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError("run_vot: chunk >= 1 steps, got %r" % (chunk,))
+    rle_on = rle is not None and rle is not False
+    if rle_on and rle is not True and (not isinstance(rle, dict) or set(rle) - {"cap"}):
+        raise ValueError("run_vot: rle = True, False or {'cap': counts per stream}")
+    try:
+        gt = list(gt)
+    except TypeError:
+        gt = None
+    if gt is None or len(gt) != V:
+        raise ValueError("run_vot: gt must hold one annotation array per video (%d)" % V)
+    gts = []
+    for v in range(V):
+        g = np.asarray(gt[v], dtype=np.float64)
+        if g.ndim != 2 or g.shape[0] != lengths[v] or g.shape[1] not in (4, 8) or not np.isfinite(g).all():
+            raise ValueError("run_vot: gt[%d] must be %d x 8 (or 4) finite values, got %s" % (v, lengths[v], g.shape))
+        gts.append(evaluate.corners(g))
+    Bq = min(int(getattr(tracker.model, "_max_batch", 1)), V, 32) if B is None else B
+    if isinstance(Bq, bool) or int(Bq) != Bq or Bq > 32:
+        raise ValueError("run_vot: up to 32 slots, got %r" % (B,))
+    B = int(Bq)
+    pl = plan(lengths, B, order)                                      # (refuses an empty list, B < 1, an unknown order)
+    sizes = [_video_size(videos, v) for v in range(V)]
+    Hc, Wc = max(h for h, _ in sizes), max(w for _, w in sizes)
+    if max(Hc, Wc) > 4096:
+        raise ValueError("run_vot: a canvas of up to 4096 x 4096, the videos need %d x %d" % (Hc, Wc))
+    cap = None
+    if rle_on:
+        cap = rle_host.default_cap(Hc, Wc) if rle is True or rle.get("cap") is None else rle["cap"]
+        if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= Hc * Wc + 1:
+            raise ValueError("run_vot: rle['cap'] must be an integer in 1..%d, got %r" % (Hc * Wc + 1, cap))
+    box = [{0: votmod.axis_aligned_bbox(gts[v][0])} for v in range(V)]          # (v, frame) -> cx, cy, w, h of a start
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    N = int(offsets[-1])
+    depth = int(getattr(tracker.model, "_pipeline", 0) or 0)
+    dev = videos[0][0].device
+    tracker.reserve(B, Hc, Wc, device=dev)
+    if tracker.pipeline and tracker.refine and depth > 1:
+        tracker.model.set_pipeline(depth)
+
+    code0 = np.zeros(N, dtype=np.int8)
+    code0[offsets[:-1]] = 1                                           # frame 0 of every video: the init frame is never stepped
+    ring_n = skip + 1                                                 # row g is consumed before step g + skip + 1 writes it again
+    with torch.cuda.device(dev):
+        gt_dev = torch.from_numpy(np.ascontiguousarray(np.concatenate(gts))).to(dev)
+        code_dev = torch.from_numpy(code0).to(dev)
+        poly_dev = torch.zeros((N, 8), dtype=torch.float64, device=dev)
+        ov_dev = torch.zeros(N, dtype=torch.float32, device=dev)
+        vstate = torch.zeros((V, 2), dtype=torch.int32, device=dev)
+        start_dev = torch.zeros((ring_n, B), dtype=torch.int32, device=dev)
+        ring = torch.zeros((ring_n, B), dtype=torch.int32).pin_memory()
+    done = [None] * pl.G                                              # step -> the event behind the copy into its ring row
+
+    def rows_behind(g, live):
+        """the hook of step g's paste job, behind its rotated box on the same stream"""
+        tab = pl.table[g].astype(np.int64)
+        vid, t = np.where(live, tab[:, 0], 0), np.where(live, tab[:, 1], 1)
+        row = np.where(live, offsets[vid] + t, 0)
+        out, host, event = start_dev[g % ring_n], ring[g % ring_n], done[g]
+
+        def after(rbox, adv):
+            preproc.vot_step_rows(rbox, gt_dev, tracker._fr.dev, row, vid, t, live, skip, vstate, code_dev, poly_dev, ov_dev, out,
+                                  adv_rows=adv)
+            host.copy_(out, non_blocking=True)                        # the lagging read-back: [B] start frames into pinned memory
+            event.record(torch.cuda.current_stream())
+        return after
+
+    def start(triples):
+        fr = [videos[v][t] for _, v, t in triples]
+        for _, v, t in triples:
+            if t not in box[v]:
+                box[v][t] = votmod.axis_aligned_bbox(gts[v][t])
+        bx = np.array([box[v][t] for _, v, t in triples], dtype=np.float64).reshape(-1, 4)
+        tracker.start(fr, [s for s, _, _ in triples], pos=bx[:, 0:2], sz=bx[:, 2:4])
+        started.append([(v, t) for _, v, t in triples])
+        for (s, _, _), f in zip(triples, fr):
+            last[s] = f
+
+    started, events, acc, g0, rows = [], [], _Gather(pl), 0, None
+    last = [None] * B
+    start([(s, v, 0) for s, v in pl.initial])
+    for g in range(pl.G):
+        live = np.array([pl.table[g, b, 0] >= 0 for b in range(B)], dtype=bool)
+        ring_row = None
+        if g >= skip and (pl.table[g, :, 1] > skip).any():            # a slot at t <= skip cannot have a re-initialisation due
+            if skip == 1:                                             # the paste-back of step g - 1 may still be deferred (pipelined)
+                tracker._fr_flush()
+            done[g - skip].synchronize()
+            ring_row = ring[(g - skip) % ring_n].numpy().copy()
+            done[g - skip] = None
+        for b in range(B):
+            if live[b]:
+                last[b] = videos[pl.table[g, b, 0]][int(pl.table[g, b, 1])]
+            elif last[b] is None:
+                last[b] = torch.zeros((Hc, Wc, 3), dtype=torch.uint8, device=dev)
+        if rle_on and g == g0:                                        # the chunk's counts and meta rows: ONE tensor each, no stack
+            n = min(int(chunk), pl.G - g0)
+            rows = (torch.empty((n, B, cap), dtype=torch.int32, device=dev), torch.empty((n, B, 4), dtype=torch.int32, device=dev))
+        done[g] = torch.cuda.Event()
+        tracker.enqueue(list(last), want_mask=True, want_polygon=True, _after=rows_behind(g, live), _canvas=True,
+                        _rle_v=(cap, [bool(x) for x in live]) if rle_on else None,
+                        _rle_out=(rows[0][g - g0], rows[1][g - g0]) if rle_on else None)
+        todo = vot_starts(pl.table[g], pl.starts[g], ring_row, lengths, skip)
+        if todo:
+            start(todo)
+        if g + 1 - g0 == int(chunk) or g + 1 == pl.G:
+            res = tracker.collect(_rle=rows)
+            res.pop("mask", None)
+            r = res.get("rle")
+            if r is not None:
+                k = int(min(r["n"].max(), r["cap"]))
+                res["rle"] = dict(r, counts=r["counts"][..., :k].cpu().numpy())
+            acc.add({k: res[k] for k in _VOT_ROWS + ("rle",) if k in res})
+            for e, vs in zip(res.get("events", []), started):
+                events.append(dict(e, step=g0 + e["t"], videos=[v for v, _ in vs], frames=[t for _, t in vs]))
+            started, g0, rows, res, r = [], g + 1, None, None, None
+    with torch.cuda.device(dev):                                      # the tables: read back once, in one synchronisation
+        host = [torch.empty(x.shape, dtype=x.dtype, pin_memory=True) for x in (code_dev, poly_dev, ov_dev, vstate)]
+        for h, x in zip(host, (code_dev, poly_dev, ov_dev, vstate)):
+            h.copy_(x, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+    code, poly, ov, vs = (h.numpy().copy() for h in host)
+    per = acc.videos()
+    out = []
+    for v in range(V):
+        a, b = int(offsets[v]), int(offsets[v + 1])
+        d = {"code": code[a:b].copy(), "polygon": poly[a:b].reshape(-1, 4, 2).copy(), "overlap": ov[a:b].copy(),
+             "lost_times": int(vs[v, 1]), "size": sizes[v], "slot": per[v]["slot"], "first_step": per[v]["first_step"]}
+        d.update({k: per[v][k] for k in _VOT_ROWS})
+        if rle_on:
+            d.update({k: per[v][k] for k in ("rle", "n", "area")})
+            if (per[v]["sizes"] != np.asarray(sizes[v])).any():
+                raise RuntimeError("run_vot: video %d was encoded at another size than its frames'" % v)
+        out.append(d)
+    wh = np.array([(w, h) for h, w in sizes], dtype=np.int32).reshape(-1, 2)
+    packed = {"names": ["%d" % v for v in range(V)], "offsets": offsets.astype(np.int32), "wh": wh, "code": code[None],
+              "polygon": poly[None], "gt": np.ascontiguousarray(np.concatenate(gts)),
+              "video_of": np.repeat(np.arange(V, dtype=np.int32), lengths)}
+    with torch.cuda.device(dev):
+        packed["dev"] = {"code": code_dev[None], "polygon": poly_dev[None], "gt": gt_dev,
+                         "video_of": torch.from_numpy(packed["video_of"]).to(dev),
+                         "offsets": torch.from_numpy(packed["offsets"]).to(dev), "wh": torch.from_numpy(wh).to(dev)}
+    return {"videos": out, "steps": pl.G, "efficiency": pl.efficiency, "events": events, "packed": packed}
+
+
+def vot_lines(d):
+    """the lines track_vot writes to <video>_001.txt for one video of run_vot (tools/test.py:403-406): the code as an integer on
+    init / lost / skipped frames, the polygon's eight values (vot.format_value) on tracked ones"""
+    from . import vot as votmod
+    return [",".join(votmod.format_value(x) for x in np.asarray(d["polygon"][t]).reshape(-1)) if c == votmod.TRACKED else "%d" % int(c)
+            for t, c in enumerate(np.asarray(d["code"]).tolist())]
+
+
+def eval_vot(res, names=None, **kw):
+    """evaluate.vot of a run_vot result on the tables the run left on the device (nothing is uploaded again); names: one per video
+    (default: its index as text); every other keyword is evaluate.vot's (dataset=, low=, high=, ...)"""
+    from . import evaluate
+    packed = dict(res["packed"])
+    if names is not None:
+        names = [str(n) for n in names]
+        if len(names) != len(packed["names"]) or len(set(names)) != len(names):
+            raise ValueError("eval_vot: %d distinct names, one per video" % len(packed["names"]))
+        packed["names"] = names
+    return evaluate.vot(packed, **kw)
 
 
 def ope_video(d, gt, name):

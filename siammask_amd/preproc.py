@@ -1169,3 +1169,58 @@ def vot_overlap(pred, gt, im_wh, adv_rows=None, out=None, counts=None, _state=No
         else:
             _lib.check(_lib.lib().smk_vot_overlap(*(shared + (B, int(im_wh[0]), int(im_wh[1])) + tail)))
     return out
+
+
+def vot_step_rows(pred, gt, state, row, vid, t, live, skip, vstate, code, poly, overlap, start_out, adv_rows=None, counts=None):
+    """One step of the supervised VOT loop for the B slots of a dataset run (include/siammask_hip.h: smk_vot_step_rows_dev): the
+    overlap of smk_vot_overlap_dev, track_vot's decision behind it on the device, and every result in the evaluator's
+    concatenated layout.  pred: float64 CUDA [B,8] / [B,4,2] / [B,12] per SLOT, or None with adv_rows (float64 CUDA [B,16]); gt:
+    float64 CUDA [N,8], the dataset's annotations; state: the tracker's state block (B records).  row / vid / t: B host integers --
+    the slot's row of the tables, its video and the frame's index in it (>= 1); live: B booleans (a slot that is not live writes
+    nothing); skip: frames skipped after a loss.  vstate int32 CUDA [V,2] (start_frame, lost_times), code int8 CUDA [N], poly float64
+    CUDA [N,8], overlap float32 CUDA [N], counts int32 CUDA [N,4] or None, start_out int32 CUDA [B] (the video's start frame after
+    the decision).  Enqueue-only; the library refuses bad rows (SmkError) before anything is enqueued."""
+    for name, a in (("gt", gt), ("state", state), ("vstate", vstate), ("code", code), ("poly", poly), ("overlap", overlap),
+                    ("start_out", start_out)):
+        _need_cuda(a, name)
+    row, vid, t = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (row, vid, t))
+    B = int(row.size)
+    live = np.asarray(live, dtype=bool).reshape(-1)
+    if not 1 <= B <= 32 or vid.size != B or t.size != B or live.size != B:
+        raise ValueError("vot_step_rows: row, vid, t and live hold one value per slot, 1..32 slots")
+    if gt.dtype != torch.float64 or gt.dim() != 2 or gt.shape[1] != 8 or not gt.is_contiguous():
+        raise ValueError("gt must be a contiguous float64 CUDA tensor [N,8]")
+    N = int(gt.shape[0])
+    stride = 0
+    if pred is not None:
+        _need_cuda(pred, "pred")
+        if pred.dtype != torch.float64 or pred.dim() not in (2, 3) or pred.shape[0] != B or not pred.is_contiguous() or \
+                pred[0].numel() not in (8, 12):
+            raise ValueError("pred must be a contiguous float64 CUDA tensor [%d,8], [%d,4,2] or [%d,12]" % (B, B, B))
+        stride = int(pred[0].numel())
+    elif adv_rows is None:
+        raise ValueError("vot_step_rows: pred, or adv_rows for the box of the state")
+    if adv_rows is not None:
+        _need_cuda(adv_rows, "adv_rows")
+        if adv_rows.dtype != torch.float64 or tuple(adv_rows.shape) != (B, 16) or not adv_rows.is_contiguous():
+            raise ValueError("adv_rows must be a contiguous float64 CUDA tensor [%d,16]" % B)
+    # (smk_trk_state_bytes counts two float64 behind every record; the kernel reads the B records alone)
+    if state.numel() * state.element_size() < int(_lib.lib().smk_trk_state_bytes(B)) - 16 * B or not state.is_contiguous():
+        raise ValueError("state must hold the %d records of the slots" % B)
+    if vstate.dtype != torch.int32 or vstate.dim() != 2 or vstate.shape[1] != 2 or vstate.shape[0] < 1 or not vstate.is_contiguous():
+        raise ValueError("vstate must be a contiguous int32 CUDA tensor [V,2]")
+    for name, a, dt, shape in (("code", code, torch.int8, (N,)), ("poly", poly, torch.float64, (N, 8)),
+                               ("overlap", overlap, torch.float32, (N,)), ("start_out", start_out, torch.int32, (B,)),
+                               ("counts", counts, torch.int32, (N, 4))):
+        if a is None and name == "counts":
+            continue
+        if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != dt or tuple(a.shape) != shape or not a.is_contiguous():
+            raise ValueError("%s must be a contiguous %s CUDA tensor %s" % (name, dt, list(shape)))
+    bits = sum(1 << b for b in range(B) if live[b])
+    with torch.cuda.device(gt.device):
+        _lib.check(_lib.lib().smk_vot_step_rows_dev(
+            pred.data_ptr() if pred is not None else None, stride, adv_rows.data_ptr() if adv_rows is not None else None,
+            gt.data_ptr(), state.data_ptr(), B, row.ctypes.data, vid.ctypes.data, t.ctypes.data, bits, N, int(vstate.shape[0]),
+            int(skip), vstate.data_ptr(), code.data_ptr(), poly.data_ptr(), overlap.data_ptr(),
+            counts.data_ptr() if counts is not None else None, start_out.data_ptr(), _lib.current_stream_ptr()))
+    return overlap

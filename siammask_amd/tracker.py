@@ -902,7 +902,8 @@ class DeviceTracker(object):
         return _Rle(int(cap), bool(rle.get("masks", False)), None, None)
 
     def enqueue(self, frame, want_mask=True, want_polygon=False, mask_out=None, gt=None, vos=None, labels_out=None, _after=None,
-                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None, _vos_gt=None, _png_out=None):
+                _unsized=False, iou=None, rle=None, _rle_out=None, _rle_v=None, _vos_v=None, _vos_gt=None, _png_out=None,
+                _canvas=False):
         """Enqueue one frame on the current stream: crop (window from the device state) -> network + decode (+ Refine) ->
         advance + plan -> paste-back (map from the device state) [-> rotated box] [-> VOS scoring].  No host synchronisation of
         any kind.  mask_out: a contiguous uint8 CUDA tensor [B,im_h,im_w] the frame's mask is written into.
@@ -949,6 +950,9 @@ class DeviceTracker(object):
         it warps every pixel once more.  The caller reads its tensors behind collect(): nothing of them comes back from it.
         _after (private, tracker_loops.run_vot): the hook of the frame's _Job.  _unsized (private, run_vot's frame 0, which every
         stream steps over BEFORE it is started on it): a list's frames need not have the slots' sizes, only fit the canvas.
+        _canvas (private, dataset.run_vot; with a LIST of frames and want_polygon, without mask_out=): the frame's masks live on the
+        ONE canvas the queue keeps, re-used by every step in stream order, also without _rle_v -- collect() reports no mask -- and
+        the hook of _after composes with _rle_v (it runs behind the rotated box and the per-size encoder of the same job).
         -> the frame's index in the chunk that collect() returns."""
         q = self._fr
         if self.state is None or q is None:
@@ -973,6 +977,8 @@ class DeviceTracker(object):
             raise ValueError("every frame of a chunk is scored (gt=, vos=), or none is")
         if c.pending and (c.iou_k is not None) != (iou is not None):
             raise ValueError("every frame of a chunk carries iou=, or none does")
+        if _canvas and (not mixed or not want_polygon or mask_out is not None or B > 32):
+            raise ValueError("_canvas comes with a list of frames (up to 32 streams) and want_polygon, without mask_out=")
         live = None
         if _rle_v is not None:                                        # the per-size codes: rle= itself stays refused under mixed sizes
             if (rle is not None and rle is not False) or not mixed or mask_out is not None or B > 32:
@@ -985,7 +991,7 @@ class DeviceTracker(object):
         if c.pending and (c.rle is not None) != (rle is not None and rle is not False):
             raise ValueError("every frame of a chunk carries rle=, or none does")
         rle = self._rle_spec(mixed and _rle_v is None, want_mask,
-                             vos is not None or gt is not None or iou is not None or _after is not None, rle)
+                             vos is not None or gt is not None or iou is not None or (_after is not None and not _canvas), rle)
         if _rle_v is not None:
             rle = rle._replace(live=sum(1 << b for b in range(B) if live[b]))
         if c.pending and c.rle is not None and (c.rle[0].live is None) != (rle.live is None):
@@ -1070,6 +1076,10 @@ class DeviceTracker(object):
                     pass                                              # smk_vos_rle_dev stands in the paste-back's place: likewise
                 elif vv is not None:
                     pass                                              # smk_vos_rle_dev_v: likewise
+                elif _canvas:                                         # the same ONE canvas without a code (dataset.run_vot, rle=False)
+                    if q.canvas is None:
+                        q.canvas = torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
+                    mask = q.canvas
                 elif iou is None or iou.masks:                        # (a score-only frame has no mask anywhere)
                     mask = mask_out if mask_out is not None else torch.empty((B, H, W), dtype=torch.uint8, device=q.device)
                 job = _Job(out["refine"] if self.refine else None, None if self.refine else out["mask"], slot, mask,
@@ -1079,7 +1089,7 @@ class DeviceTracker(object):
                     c.deferred = job                                  # pasted behind the NEXT step (or by start() / collect())
                 else:
                     self._fr_paste(job, sp)
-            c.masks.append(mask if rle is None or rle.live is None else None)
+            c.masks.append(mask if (rle is None or rle.live is None) and not _canvas else None)
             if rle is not None:                                       # (beside the frame count: a launch that raised leaves no row)
                 c.rle = (c.rle or []) + [rle]
             if score is not None and score.rle is not None:
