@@ -831,6 +831,42 @@ int smk_vot_step_rows_dev(const double *pred_dev, int pred_stride, const double 
                           uint32_t live_mask, int N, int V, int skip, int32_t *vstate_dev, int8_t *code_dev, double *poly_dev,
                           float *overlap_dev, int32_t *counts_dev, int32_t *start_out_dev, void *stream);
 
+/* ---- frames enter as JPEG: a baseline decoder on the device (additive; smk_version() keeps reporting 1.10, the
+ * presence of these symbols is the probe) ----------------------------------------------------------------------------------------
+ * File bytes in, uint8 BGR [h][w][3] frames out -- what every entry point of the tracker takes -- with libjpeg's default integer
+ * arithmetic (islow IDCT, fancy chroma upsampling, table colour conversion): the pixels equal cv2.imread's.  Accepted: SOF0 / SOF1,
+ * 8 bits, Huffman, one interleaved scan, grey or YCbCr with luma sampling 1x1, 2x1 or 2x2, 8-bit DQT, DRI / RSTn, w and h in
+ * 1..4096.  siammask_amd/csrc/jpeg_decode.h states the format, the descriptor columns and the arithmetic in full.
+ * smk_host_jpeg_parse: one file -> desc_out int32 [32] (the format columns and the file's length), its table blob
+ * (smk_jpeg_tables_bytes() bytes, 4-byte aligned; files with the same DQT / DHT segments give the same blob) and the offsets of its
+ * entropy segments (seg_out, seg_cap entries of room; at most (w / 8) (h / 8) rounded up are written).  Returns 0, 1 for a file
+ * outside the scope above (progressive, arithmetic, lossless, 12-bit, 16-bit DQT, 4 components, an Adobe transform, other
+ * samplings, several scans, DNL, a size outside 1..4096), 2 for a file whose headers are cut or contradict themselves -- the reason
+ * through smk_last_error -- and SMK_E_ARG for a null pointer, a short or misaligned table buffer or too little segment room.  It
+ * never reads at or past data + len.  A file cut inside its entropy data parses; its decode reports a status.
+ * smk_jpeg_workspace: lays n_images parsed rows out as one call -- WRITES their columns for the running segment and block counts
+ * -- and returns the workspace bytes (0: a null pointer, n_images outside 1..65535, a row whose format columns are out of range).
+ * The caller fills the file offset, the table offset (bytes into tables_dev, a multiple of 4), the output pointer (two words) and
+ * the bytes between output rows (>= 3 w), and uploads the rows and the concatenated segment offsets.
+ * smk_jpeg_decode: ONE memset and THREE launches for all images (one lane per entropy segment; eight lanes per 8x8 block; one lane
+ * per pixel).  desc is the host copy of desc_dev: every column is checked against bytes_len, n_seg, tables_len, ws_bytes before
+ * anything is enqueued (SMK_E_ARG); segment offsets are clamped into their image's entropy data on the device.  ws_dev 256-byte
+ * aligned, owned by the call until it has completed on `stream`.  meta_out_dev int32 [n_images][4] = (status, h, w, segments);
+ * status 0 is a clean decode, else bits 1 (a bit pattern that is no code), 2 (a run past coefficient 63), 4 (the data ended inside
+ * a block), 8 (fewer restart segments than the image needs): such an image has unspecified pixels inside its own h x w and disturbs
+ * nothing else.  Bytes outside an image's h x w x 3 are never written (a pitched view into a canvas works).  No context;
+ * asynchronous on `stream`, no host synchronisation.
+ * smk_host_jpeg_decode: the CPU twin -- host pointers, the same header code in plain loops, no device; out_h x out_w must be the
+ * file's size; returns what smk_host_jpeg_parse returns. */
+size_t smk_jpeg_tables_bytes(void);
+int smk_host_jpeg_parse(const uint8_t *data, size_t len, int32_t *desc_out, void *tables_out, size_t tables_bytes, int32_t *seg_out,
+                        size_t seg_cap);
+size_t smk_jpeg_workspace(int32_t *desc, int n_images);
+int smk_jpeg_decode(const uint8_t *bytes_dev, size_t bytes_len, const int32_t *desc, const int32_t *desc_dev, const int32_t *seg_dev,
+                    size_t n_seg, const void *tables_dev, size_t tables_len, int n_images, void *ws_dev, size_t ws_bytes,
+                    int32_t *meta_out_dev, void *stream);
+int smk_host_jpeg_decode(const uint8_t *data, size_t len, uint8_t *out, int64_t pitch, int out_h, int out_w, int32_t *meta_out);
+
 #ifdef __cplusplus
 }
 #endif

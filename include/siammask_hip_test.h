@@ -259,6 +259,11 @@ int smk_host_eao_curve(const float *ov_eao, const int8_t *code, const int32_t *o
 int smk_host_ope_curve(const double *pred, const double *gt, const int32_t *offsets, int N, int G, int V, const double *thr_overlap,
                        int K1, const double *thr_error, int K2, int quantise, int32_t *counts, double *iou_out, double *dist_out);
 
+/* Measurement only (tools/measure/gpu_jpeg_cost.py): which stages smk_jpeg_decode launches from now on, process-wide -- bit 0 the
+ * entropy decode, bit 1 the IDCT, bit 2 upsampling and colour; the memset always runs.  7 is the product's value and the default;
+ * a stage left out leaves its outputs as they are, so the frames of such a call mean nothing.  A mask outside 0..7: SMK_E_ARG. */
+int smk_test_jpeg_stages(int mask);
+
 #ifdef __cplusplus
 }
 #endif

@@ -49,6 +49,7 @@ SYMBOLS = (
     "smk_host_vot_quantise", "smk_host_vot_traj_overlap", "smk_host_eao_curve",
     "smk_ope_curve", "smk_host_ope_curve",
     "smk_vot_step_rows_dev", "smk_host_vot_step_rows",
+    "smk_jpeg_tables_bytes", "smk_host_jpeg_parse", "smk_jpeg_workspace", "smk_jpeg_decode", "smk_host_jpeg_decode", "smk_test_jpeg_stages",
 )
 
 
@@ -227,6 +228,13 @@ def lib():
     # pred, stride, adv, gt, state | im_wh, B, row, vid, t, live, N, V, skip, vstate, code, poly, overlap, counts, start_out[, stream]
     L.smk_vot_step_rows_dev.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, u32, ci, ci, ci] + [vp] * 7
     L.smk_host_vot_step_rows.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, u32, ci, ci, ci] + [vp] * 6
+    sz = ctypes.c_size_t
+    L.smk_jpeg_tables_bytes.argtypes = []
+    L.smk_host_jpeg_parse.argtypes = [vp, sz, vp, vp, sz, vp, sz]
+    L.smk_jpeg_workspace.argtypes = [vp, ci]
+    L.smk_jpeg_decode.argtypes = [vp, sz, vp, vp, vp, sz, vp, sz, ci, vp, sz, vp, vp]
+    L.smk_host_jpeg_decode.argtypes = [vp, sz, vp, i64, ci, ci, vp]
+    L.smk_test_jpeg_stages.argtypes = [ci]
     L.smk_op_conv_seq.argtypes = [ctypes.POINTER(SeqOp), ci, fp, ci, ctypes.POINTER(ctypes.c_float), fp, ip, vp]
     L.smk_host_plan_seq.argtypes = [ctypes.POINTER(SeqOp), ci, ci, ip, ip, ip]
     L.smk_bench_conv.argtypes = [ci, ci, gp, ci, ci, ctypes.POINTER(ctypes.c_float), vp]
@@ -235,7 +243,7 @@ def lib():
         if name not in ("smk_last_error",):
             fn.restype = ctypes.c_size_t if name in ("smk_mask_rbox_workspace", "smk_mask_rbox_workspace_ex", "smk_trk_state_bytes",
                                                         "smk_rle_workspace", "smk_eao_workspace_bytes", "smk_png_worst_bytes",
-                                                        "smk_png_workspace") else ci
+                                                        "smk_png_workspace", "smk_jpeg_tables_bytes", "smk_jpeg_workspace") else ci
     _lib = L
     # SMK_TUNE="key=value,key=value": library tuning knobs from the environment (A/B runs of the test-suite)
     for kv in filter(None, os.environ.get("SMK_TUNE", "").split(",")):

@@ -1224,3 +1224,96 @@ def vot_step_rows(pred, gt, state, row, vid, t, live, skip, vstate, code, poly, 
             int(skip), vstate.data_ptr(), code.data_ptr(), poly.data_ptr(), overlap.data_ptr(),
             counts.data_ptr() if counts is not None else None, start_out.data_ptr(), _lib.current_stream_ptr()))
     return overlap
+
+
+# ---- frames enter as JPEG (include/siammask_hip.h: smk_jpeg_decode) ---------------------------------------------
+_jpeg_ws = {}                                                         # (device, stream) -> the workspace, grown on demand
+
+
+def _align(n, a=256):
+    return (n + a - 1) // a * a
+
+
+def jpeg_decode(list_of_bytes, out=None, device=None):
+    """Baseline JPEG files to BGR frames on the device.  list_of_bytes: the files' bytes (or jpeg.parse results), any mix of
+    sizes and samplings, 1..65535 of them.  The host parses them (C++, microseconds each; jpeg.Unsupported / jpeg.Corrupt before any
+    launch), stages descriptors, segment offsets, tables and file bytes in ONE pinned buffer, and the device gets one copy, one
+    memset and three launches for all images.  out: None (the frames are views of one allocation) or one uint8 CUDA tensor [h,w,3]
+    per image whose pixels are 3 contiguous bytes and whose rows are contiguous (a pitched view into a canvas works: bytes outside
+    h x w are not written).  -> (frames: a list of uint8 CUDA [h,w,3] BGR, equal to cv2.imread of the file; meta: int32 CUDA [N,4] =
+    (status, h, w, segments), status 0 for a clean decode -- an image with another status has unspecified pixels and disturbs no
+    other image).  Asynchronous on the current stream; nothing is read back."""
+    from . import jpeg
+    L = _lib.lib()
+    ps = [jpeg.parse(b) for b in list_of_bytes]
+    N = len(ps)
+    if not 1 <= N <= 65535:
+        raise ValueError("jpeg_decode: 1..65535 images per call, got %d" % N)
+    if out is not None:
+        out = list(out)
+        if len(out) != N:
+            raise ValueError("jpeg_decode: %d out tensors for %d images" % (len(out), N))
+        for n, (o, p) in enumerate(zip(out, ps)):
+            _need_cuda(o, "out[%d]" % n)
+            if o.dtype != torch.uint8 or tuple(o.shape) != (p.h, p.w, 3) or o.stride(2) != 1 or o.stride(1) != 3 or \
+                    (p.h > 1 and o.stride(0) < 3 * p.w) or o.stride(0) >= 1 << 31:
+                raise ValueError("jpeg_decode: out[%d] must be uint8 [%d,%d,3] with contiguous pixels and rows" % (n, p.h, p.w))
+        device = out[0].device
+    device = torch.device("cuda") if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("jpeg_decode runs on the MI355X only: device must be a CUDA(HIP) device")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    desc = np.stack([p.desc for p in ps])
+    blobs, toff = {}, []
+    for p in ps:                                                      # the frames of one video share their tables: one upload
+        if p.tables not in blobs:
+            blobs[p.tables] = (len(blobs), p.tables)
+        toff.append(blobs[p.tables][0])
+    tb = L.smk_jpeg_tables_bytes()
+    desc[:, jpeg.TABLE_OFF] = np.asarray(toff, dtype=np.int64) * tb
+    lens = np.asarray([len(p.data) for p in ps], dtype=np.int64)
+    foff = np.concatenate([[0], np.cumsum((lens + 3) // 4 * 4)])
+    if foff[-1] >= 1 << 31:
+        raise ValueError("jpeg_decode: %d file bytes in one call (below 2 GiB)" % foff[-1])
+    desc[:, jpeg.FILE_OFF] = foff[:-1]
+    ws_need = L.smk_jpeg_workspace(desc.ctypes.data, N)
+    if ws_need == 0:
+        raise ValueError("jpeg_decode: the descriptors are out of range")
+    seg = np.concatenate([p.seg for p in ps]).astype(np.int32)
+    with torch.cuda.device(device):
+        if out is None:
+            sizes = [_align(p.h * p.w * 3) for p in ps]
+            buf = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+            out, o0 = [], 0
+            for p, s in zip(ps, sizes):
+                out.append(buf[o0:o0 + p.h * p.w * 3].view(p.h, p.w, 3))
+                o0 += s
+        ptrs = np.asarray([o.data_ptr() for o in out], dtype=np.uint64)
+        desc[:, jpeg.OUT_LO] = (ptrs & np.uint64(0xffffffff)).astype(np.uint32).view(np.int32)
+        desc[:, jpeg.OUT_HI] = (ptrs >> np.uint64(32)).astype(np.uint32).view(np.int32)
+        desc[:, jpeg.PITCH] = [o.stride(0) if p.h > 1 else 3 * p.w for o, p in zip(out, ps)]
+        # one pinned buffer: [descriptors][segment offsets][tables][files]
+        o_seg = _align(desc.nbytes)
+        o_tab = o_seg + _align(seg.nbytes)
+        o_byt = o_tab + _align(len(blobs) * tb)
+        total = o_byt + _align(int(foff[-1]))
+        pin = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        h = pin.numpy()
+        h[:desc.nbytes] = desc.view(np.uint8).reshape(-1)
+        h[o_seg:o_seg + seg.nbytes] = seg.view(np.uint8)
+        for k, blob in blobs.values():
+            h[o_tab + k * tb:o_tab + (k + 1) * tb] = np.frombuffer(blob, dtype=np.uint8)
+        for p, o in zip(ps, foff[:-1]):
+            h[o_byt + int(o):o_byt + int(o) + len(p.data)] = np.frombuffer(p.data, dtype=np.uint8)
+        stage = torch.empty(total, dtype=torch.uint8, device=device)
+        stage.copy_(pin, non_blocking=True)
+        key = (device.index, _lib.current_stream_ptr().value)
+        ws = _jpeg_ws.get(key)
+        if ws is None or ws.numel() < ws_need:
+            ws = _jpeg_ws[key] = torch.empty(_align(ws_need, 1 << 20), dtype=torch.uint8, device=device)
+        meta = torch.empty((N, 4), dtype=torch.int32, device=device)
+        base = stage.data_ptr()
+        _lib.check(L.smk_jpeg_decode(base + o_byt, int(foff[-1]), desc.ctypes.data, base, base + o_seg, seg.size, base + o_tab,
+                                     len(blobs) * tb, N, ws.data_ptr(), ws.numel(), meta.data_ptr(), _lib.current_stream_ptr()))
+    return out, meta
