@@ -43,6 +43,11 @@ extern "C" {
  *   "chain_mask" 0|1|2 (fp16 frame step: the 63x63 mask head in a launch of its own | inside the Refine chain launch, chain_mask_kernel
  *   (default) | the same with the mask head on the generic 128x128 implicit-GEMM tiles, there and in its own launch, instead of the
  *   stationary-pixel tile of mask_head_tile.inc; bit-identical logits).
+ *   "chain_split" 0|1|2|4 (fp16 Refine chain: workgroups per stream -- row bands of its four fine layers post1, h0.0, h0.2, post2; 0 = the
+ *   rule (default: 4 while B * 4 workgroups fit one round of the CUs, else 2, else 1) | forced; 1 = one workgroup per stream, the
+ *   parity tests' reference arm; bit-identical logits for every value; read at launch / graph capture).
+ *   "mask_nsplit" 0..15 (A/B knob: channel ranges per 128-pixel tile of the stationary-pixel mask head; 0 = the rules of conv_igemm.hip: one
+ *   round of the free CUs where the launch has the chip, >= 80 workgroups where it ends a pipelined tail beside the next frame's front end).
  *   "a_stage" 0|1 (conv_wreg_kernel / conv_seq_kernel producers: activation rows by LDS-DMA with the swizzle on the source
  *   address | global -> VGPR in ascending lane order, swizzle applied by ds_write_b128; same LDS image, bit-identical results).
  *   "seq_fuse" 0..3 (conv_seq_kernel: a Bottleneck's conv3 + the 1x1 convolution that reads it -- the next block's conv1, adjust -- as
@@ -196,6 +201,10 @@ int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *syn
  * engine's table of arena tensors the way smk_create allocates it -- elements per image, one plane (a split-operand context stores
  * two), aliased buffers counted once.  Lets the CPU test-suite pin the sizes. */
 int smk_host_arena_elems(int dtype, int variant, int pipe_depth, uint64_t *elems_per_image);
+
+/* Host only: the output rows band s of S (1, 2, 4) computes in the split Refine chain -- out = [y0, y1) of post1, h0.0, h0.2 (61 rows
+ * each) and post2 (127 rows), from the very function the kernel compiles (csrc/chain_rows.h). */
+int smk_host_chain_rows(int S, int s, int out[8]);
 
 /* Host only: the scalar stage of the tracker (smk_trk_plan / smk_trk_advance) on HOST memory -- the very inline functions the
  * device kernels compile (csrc/tracker_state.h), so that the CPU test-suite can hold them bit for bit against the host loop of

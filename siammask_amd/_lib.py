@@ -29,7 +29,7 @@ SYMBOLS = (
     "smk_version", "smk_last_error", "smk_create", "smk_destroy", "smk_set_weight",
     "smk_finalize_weights", "smk_template", "smk_track", "smk_refine", "smk_set_decode_params", "smk_decode", "smk_step", "smk_set_graph_mode", "smk_seq_status", "smk_seq_sync_check", "smk_set_result_ring", "smk_result_ring_cursor", "smk_set_pipeline", "smk_pipeline_join", "smk_pipeline_observe",
     "smk_debug_read", "smk_debug_seq_inject", "smk_tune", "smk_tune_get", "smk_profile", "smk_profile_dump", "smk_op_conv2d_ex", "smk_op_conv2d", "smk_op_dw_xcorr",
-    "smk_op_maxpool3x3s2", "smk_op_stem_pool", "smk_op_l1_block", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_host_arena_elems", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
+    "smk_op_maxpool3x3s2", "smk_op_stem_pool", "smk_op_l1_block", "smk_op_conv_seq", "smk_host_conv2d_ex", "smk_host_plan_conv", "smk_host_plan_seq", "smk_host_arena_elems", "smk_host_chain_rows", "smk_bench_conv", "smk_packed_size", "smk_export_packed",
     "smk_import_packed", "smk_crop_resize", "smk_paste_mask", "smk_paste_labels", "smk_mask_rbox_workspace", "smk_mask_rbox",
     "smk_trk_state_bytes", "smk_trk_set", "smk_trk_plan", "smk_trk_advance", "smk_crop_resize_dev", "smk_paste_mask_dev",
     "smk_vos_score", "smk_vos_score_dev", "smk_host_trk_plan", "smk_host_trk_advance",
@@ -147,6 +147,7 @@ def lib():
     L.smk_host_conv2d_ex.argtypes = [gp, fp, fp, fp, fp, vp, fp]
     L.smk_host_plan_conv.argtypes = [gp, ci, ci, ip, ip, ip, ip]
     L.smk_host_arena_elems.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_uint64)]
+    L.smk_host_chain_rows.argtypes = [ci, ci, ip]
     L.smk_packed_size.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
     L.smk_export_packed.argtypes = [vp, vp, ctypes.c_uint64]
     L.smk_import_packed.argtypes = [vp, vp, ctypes.c_uint64]

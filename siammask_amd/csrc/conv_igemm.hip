@@ -1015,13 +1015,14 @@ int launch_conv_halo(const ConvParams &p, int dtype, int bm, void *stream) {
 // refine_chain_kernel occupies B of the 256 CUs for ~44 us (one workgroup per stream, custom.py:150-153 is a dependent
 // chain); the mask head (256 -> 3969 1x1 convolution, custom.py:185, 79 MB of fp32 logits at B = 8) is bound by its
 // stores and by nothing on the Refine path -- it only needs head.0's output.  As two launches they cost ~44 + ~40 us
-// back to back.  Here workgroups [0, B) run the chain (all 1024 threads) and the others run the mask head: one tile of
+// back to back.  Here workgroups [0, B * S) run the chain (all 1024 threads; S row bands per stream, chain_rows.h) and the others run the mask head: one tile of
 // mask_head_tile.inc each (128 stationary pixels x a range of channel blocks, all sixteen waves) -- or, on the generic
 // path (smk_tune chain_mask = 2, shapes the tile does not cover), TWO 128x128 implicit-GEMM tiles each (threads 0-511 /
 // 512-1023, an LDS half each; both halves execute the same number of barriers).  Cross-stream forks in the captured graph were the
 // measured alternative: hipGraphLaunch then costs ~1 ms of host time per replay.
 // ---------------------------------------------------------------------------------------------
 }  // namespace smk
+#include "chain_rows.h"
 namespace smk {
 #include "refine_chain_body.inc"
 #include "mask_head_tile.inc"
@@ -1033,13 +1034,14 @@ static_assert(MH_LDS <= CM_LDS, "the stationary-pixel mask-head tile fits the fu
 // two generic 128x128 tile bodies
 __global__ __launch_bounds__(1024) void chain_mask_kernel(const RefineChainParams rp, const ConvBatch cb, const int mh_nsplit) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[CM_LDS];
-    if ((int)blockIdx.x < rp.B) {
+    const int chain_wgs = rp.B * rp.S;               // S row bands per stream (chain_rows.h)
+    if ((int)blockIdx.x < chain_wgs) {
         refine_chain_body<false>(rp, (int)blockIdx.x, smem);
     } else if (mh_nsplit > 0) {
-        mask_head_tile(cb.p[0], (int)blockIdx.x - rp.B, mh_nsplit, smem);
+        mask_head_tile(cb.p[0], (int)blockIdx.x - chain_wgs, mh_nsplit, smem);
     } else {
         const int half = threadIdx.x >> 9;
-        const int bx = 2 * ((int)blockIdx.x - rp.B) + half;
+        const int bx = 2 * ((int)blockIdx.x - chain_wgs) + half;
         if (bx < cb.start[cb.n])                       // (odd tile count -- refused by the launcher: the last workgroup would run one tile)
             conv_igemm_body<_Float16, 2, 2, 1, 128, OUT_NCHW_F32, 2>(cb, bx, 0, half * 512, smem + half * CM_CONV_LDS);
     }
@@ -1084,6 +1086,7 @@ int mask_head_nsplit(const ConvParams &p, int cus) {
     const int ptiles = (p.M + MH_PX - 1) / MH_PX, nblk = (p.N + 31) / 32;
     int cap = nblk / 8;
     if (cap < 1) cap = 1;
+    if (g_tune.mask_nsplit > 0) return g_tune.mask_nsplit < cap ? g_tune.mask_nsplit : cap;      // (A/B knob)
     if (ptiles * 2 <= cus) {
         const int ns = cus / ptiles;
         return ns < cap ? ns : cap;
@@ -1096,6 +1099,22 @@ int mask_head_nsplit(const ConvParams &p, int cus) {
         if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
     }
     return best;
+}
+
+// Channel ranges per pixel tile where the launch shares the chip with the NEXT frame's front end (the end of a pipelined tail).  There
+// every mask-head workgroup keeps its CU from the front end for the length of the launch (143 KB of LDS, 16 waves), and the front
+// end -- not the tail -- is the later of the two at the main gate: the head is better off LONGER on a third of the chip than short on
+// all of it.  MH_SHARED_WGS workgroups at least: B = 8 -> 40 x 2 = 80, B = 16 -> 79 x 2 = 158.  Measured (profiles/chain_split_ab.txt,
+// B = 8 step against the parent's 0.5279-0.5328 ms): 40 workgroups 0.533-0.539, 80 0.5138-0.5157, 120 0.515-0.528, 160 0.524-0.533,
+// 200 (one round of what the chain leaves, the stand-alone rule) 0.522-0.531; B = 16: 79 / 158 1.003-1.010, 237 1.025-1.026 = the parent's.
+constexpr int MH_SHARED_WGS = 80;
+static int mask_head_nsplit_shared(const ConvParams &p) {
+    const int ptiles = (p.M + MH_PX - 1) / MH_PX, nblk = (p.N + 31) / 32;
+    int cap = nblk / 8;
+    if (cap < 1) cap = 1;
+    if (g_tune.mask_nsplit > 0) return g_tune.mask_nsplit < cap ? g_tune.mask_nsplit : cap;      // (A/B knob)
+    const int ns = (MH_SHARED_WGS + ptiles - 1) / ptiles;
+    return ns < cap ? ns : cap;
 }
 
 // Streaming (nt) or plain stores.  One dword per lane, the tile's stores are faster plain -- alone on the chip 22.7 us plain
@@ -1117,18 +1136,22 @@ int launch_mask_head(const ConvParams &p0, void *stream) {
 
 // cb: ONE f16 problem with the NCHW f32 epilogue (the mask head): mask_head_tile where the caller asks for it (stationary != 0) and
 // the tile covers the problem, else 128x128 tiles
-int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, int stationary, void *stream) {
-    if (rp.v2_cs != 32 || rp.v1_cs != 16 || rp.v0_cs != 8 || cb.n != 1) return -1;
+int launch_chain_mask(const RefineChainParams &rp0, ConvBatch &cb, int stationary, void *stream) {
+    if (rp0.v2_cs != 32 || rp0.v1_cs != 16 || rp0.v0_cs != 8 || cb.n != 1 || rp0.B < 1) return -1;
     ConvParams &p = cb.p[0];
     if (p.out_mode != OUT_NCHW_F32 || p.groups > 1) return -1;
+    RefineChainParams rp = rp0;
+    rp.S = chain_split_rule(rp.B, 256, g_tune.chain_split);
+    const int chain_wgs = rp.B * rp.S;
     if (stationary && mask_head_eligible(p, DT_F16)) {
-        const int nsplit = mask_head_nsplit(p, 256 - rp.B > 64 ? 256 - rp.B : 64);
+        // serial step: one round of the CUs the chain's workgroups leave; pipelined tail (its last launch carries tail_sem): the shared-chip rule
+        const int nsplit = rp.tail_sem ? mask_head_nsplit_shared(p) : mask_head_nsplit(p, 256 - chain_wgs > 64 ? 256 - chain_wgs : 64);
         const int ptiles = (p.M + MH_PX - 1) / MH_PX;
         cb.start[0] = 0;
         for (int i = 1; i <= CONV_BATCH_MAX; ++i) cb.start[i] = ptiles * nsplit;
         p.ksplit = 1;
         p.nt_store = mask_head_nt(p);
-        hipLaunchKernelGGL(chain_mask_kernel, dim3(rp.B + ptiles * nsplit), dim3(1024), 0, (hipStream_t)stream, rp, cb, nsplit);
+        hipLaunchKernelGGL(chain_mask_kernel, dim3(chain_wgs + ptiles * nsplit), dim3(1024), 0, (hipStream_t)stream, rp, cb, nsplit);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
     const int tiles = ((p.M + 127) / 128) * ((p.Nst + 127) / 128);
@@ -1140,7 +1163,7 @@ int launch_chain_mask(const RefineChainParams &rp, ConvBatch &cb, int stationary
     cb.start[0] = 0;
     for (int i = 1; i <= CONV_BATCH_MAX; ++i) cb.start[i] = tiles;
     p.ksplit = 1;
-    hipLaunchKernelGGL(chain_mask_kernel, dim3(rp.B + (tiles + 1) / 2), dim3(1024), 0, (hipStream_t)stream, rp, cb, 0);
+    hipLaunchKernelGGL(chain_mask_kernel, dim3(chain_wgs + (tiles + 1) / 2), dim3(1024), 0, (hipStream_t)stream, rp, cb, 0);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -11,7 +11,7 @@
 //   conv_launch.cpp    ConvEnv, conv_params, conv_work, launch_plan
 //   conv_plan.cpp      which kernel and tile a convolution gets, the marks on a sequence list (conv_plan.h; no HIP call)
 //   tune.cpp           smk_tune / smk_tune_get and the KNOBS table
-//   op_api.cpp         smk_op_*, smk_bench_conv, smk_host_conv2d_ex, smk_host_plan_conv, smk_host_plan_seq
+//   op_api.cpp         smk_op_*, smk_bench_conv, smk_host_conv2d_ex, smk_host_plan_conv, smk_host_plan_seq, smk_host_chain_rows
 //   stream_api.cpp     the stateless product entries: crop / paste / labels, smk_mask_rbox, smk_trk_*, smk_host_trk_*,
 //                      smk_vos_score*, stream start, smk_vot_overlap*, the *_v entries
 //
@@ -1238,6 +1238,7 @@ static int seq_refine(smk_ctx *c, StepRec &rec, int B, float *out, hipStream_t s
         rp.v2_cs = V2.C; rp.v1_cs = V1.C; rp.v0_cs = V0.C;
         rp.out = out;
         rp.B = B;
+        rp.S = 0;                                        // (workgroups per stream: the launcher's rule, smk_tune "chain_split")
         rp.clk = nullptr;
         rp.ring = nullptr; rp.ring_cursor = nullptr; rp.ring_done = nullptr; rp.ring_rows = 0;
         rp.tail_sem = nullptr;

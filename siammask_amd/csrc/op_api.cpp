@@ -1,6 +1,6 @@
 // op_api.cpp -- the entry points of include/siammask_hip_test.h that need no context: single operations on caller tensors
 // (smk_op_*: unit parity of the kernels), smk_bench_conv, and the host-only walks and planners the CPU tests pin the engine's
-// choices with (smk_host_conv2d_ex, smk_host_plan_conv, smk_host_plan_seq).  They pack, plan and launch through the code the
+// choices with (smk_host_conv2d_ex, smk_host_plan_conv, smk_host_plan_seq, smk_host_chain_rows).  They pack, plan and launch through the code the
 // engine uses (weight_pack.cpp, conv_plan.cpp, conv_launch.cpp).
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/siammask_hip_test.h"
+#include "chain_rows.h"
 #include "engine_internal.h"
 
 using namespace smk;
@@ -746,6 +747,18 @@ int smk_host_plan_seq(const smk_seq_op *ops, int n, int grid, int *cfg, int *syn
         sync[i] = rec[i].L.sync;
         a_stage[i] = rec[i].L.a_stage;
     }
+    return 0;
+}
+
+// the row bands of the split Refine chain: chain_rows.h's function, the one refine_chain_body.inc compiles
+int smk_host_chain_rows(int S, int s, int out[8]) {
+    if (!out) return fail(SMK_E_ARG, "smk_host_chain_rows: null argument");
+    if (!chain_split_valid(S) || s < 0 || s >= S) return fail(SMK_E_ARG, "smk_host_chain_rows: band %d of %d (1, 2 or 4 bands)", s, S);
+    const ChainRows r = chain_rows(S, s);
+    out[0] = r.post1[0]; out[1] = r.post1[1];
+    out[2] = r.h00[0]; out[3] = r.h00[1];
+    out[4] = r.h02[0]; out[5] = r.h02[1];
+    out[6] = r.post2[0]; out[7] = r.post2[1];
     return 0;
 }
 

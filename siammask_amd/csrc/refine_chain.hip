@@ -1,5 +1,6 @@
 // refine_chain.hip -- the sequential tail of Refine (experiments/siammask_sharp/custom.py:150-153) as ONE
-// launch, one workgroup per stream, every intermediate activation resident in LDS (fp16 path).
+// launch, S workgroups per stream (row bands of the four fine layers, chain_rows.h; S = 1: one workgroup), every intermediate
+// activation resident in LDS (fp16 path).
 //
 //   out = post0(up31(h2(deconv_out) + V2))      h2 = conv3x3+ReLU, conv3x3+ReLU   (32 ch @ 15x15)
 //   out = post1(up61(h1(out)        + V1))      h1 = ...                          (16 ch @ 31x31)
@@ -22,6 +23,7 @@
 // fp16 exactly where the per-layer path stores fp16 activations, so the two paths share rounding points.
 #include <hip/hip_runtime.h>
 
+#include "chain_rows.h"
 #include "smk_kernels.h"
 
 namespace smk {
@@ -34,10 +36,14 @@ __global__ __launch_bounds__(1024) void refine_chain_kernel(const RefineChainPar
     refine_chain_body<TIMED>(p, (int)blockIdx.x, smem);
 }
 
-int launch_refine_chain(const RefineChainParams &p, void *stream) {
-    if (p.v2_cs != 32 || p.v1_cs != 16 || p.v0_cs != 8) return -1;      // the layouts v_load assumes
-    if (p.clk) hipLaunchKernelGGL(refine_chain_kernel<true>, dim3(p.B), dim3(RC_NT), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(refine_chain_kernel<false>, dim3(p.B), dim3(RC_NT), 0, (hipStream_t)stream, p);
+// Row bands (chain_rows.h): the four fine layers -- 21 of the unsplit chain's 37 us, instruction-issue bound on ONE CU -- on S CUs
+// per stream while B * S workgroups fit one round of the 256 CUs (measured: profiles/chain_split_ab.txt)
+int launch_refine_chain(const RefineChainParams &p0, void *stream) {
+    if (p0.v2_cs != 32 || p0.v1_cs != 16 || p0.v0_cs != 8 || p0.B < 1) return -1;      // the layouts v_load assumes
+    RefineChainParams p = p0;
+    p.S = chain_split_rule(p.B, 256, g_tune.chain_split);
+    if (p.clk) hipLaunchKernelGGL(refine_chain_kernel<true>, dim3(p.B * p.S), dim3(RC_NT), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(refine_chain_kernel<false>, dim3(p.B * p.S), dim3(RC_NT), 0, (hipStream_t)stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

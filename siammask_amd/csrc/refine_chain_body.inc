@@ -129,14 +129,17 @@ __device__ __forceinline__ void zero_image(_Float16 *img) {
 //   FCIN/FCOUT  the layer after that: its fetch to `wfar` starts before this layer's arithmetic (a layer can
 //               be shorter than one global-memory round trip, two never are)
 //   VH/VC       V_x for the layer after this one: global -> registers -> the image `vimg` likewise
+//   y0, y1      output rows this workgroup computes (chain_rows.h; the coarse layers: all of them).  A pixel's arithmetic does not
+//               depend on which pixels share its fragment or its workgroup: any band is bit-identical to the whole image's rows.
 template <int CIN, int COUT, int H, int SRC, bool RELU, bool RES, bool OUT_GLOBAL, int NCIN, int NCOUT, int FCIN,
           int FCOUT, int VH, int VC>
 __device__ __forceinline__ void chain_layer(const _Float16 *in, _Float16 *out, const _Float16 *wl, _Float16 *wl_next,
                                             const WR<NCIN, NCOUT> &wnext, const RefineChainLayer &Lfar,
                                             WR<FCIN, FCOUT> &wfar, const _Float16 *vsrc, _Float16 *vimg,
-                                            const int *tab, float *gout) {
+                                            const int *tab, float *gout, const int y0 = 0, const int y1 = H) {
     typedef WGeo<CIN, COUT> WG;
-    constexpr int KSTEPS = WG::KSTEPS, KP = WG::KP, NT = WG::NT, M = H * H, MT = (M + 15) / 16;
+    constexpr int KSTEPS = WG::KSTEPS, KP = WG::KP, NT = WG::NT;
+    const int M0 = y0 * H, M = y1 * H, MT = (M - M0 + 15) / 16;      // this workgroup's pixels: rows [y0, y1)
     constexpr int HI = SRC > 0 ? SRC : H, W2 = HI + 2;       // input image geometry (bordered width)
     constexpr int WO = H + 2;
     constexpr bool PRELOAD = KSTEPS * NT <= 10;
@@ -183,7 +186,7 @@ __device__ __forceinline__ void chain_layer(const _Float16 *in, _Float16 *out, c
     }
 
     for (int mt = wave; mt < MT; mt += RC_NT / 64) {
-        int m = mt * 16 + fr;
+        int m = M0 + mt * 16 + fr;
         m = m < M ? m : M - 1;
         const int oy = m / H, ox = m - oy * H;
         // element offset (halfs) of this lane's K slice in the bordered input image
@@ -206,12 +209,12 @@ __device__ __forceinline__ void chain_layer(const _Float16 *in, _Float16 *out, c
             }
         }
         // ---- epilogue: C^T[row = channel 4 kq + i][col = pixel fr]: this lane's pixel is the one its fragment reads addressed (oy, ox)
-        const bool px_ok = mt * 16 + fr < M;
+        const bool px_ok = M0 + mt * 16 + fr < M;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int n = nt * 16 + 4 * kq;
             if (OUT_GLOBAL) {
-                if (n == 0 && px_ok) gout[mt * 16 + fr] = acc[nt][0] + bias4[nt][0];
+                if (n == 0 && px_ok) gout[M0 + mt * 16 + fr] = acc[nt][0] + bias4[nt][0];
             } else if (n < COUT && px_ok) {
                 static_assert(OUT_GLOBAL || COUT % 4 == 0, "four channels per lane");
                 _Float16 *o = out + ((oy + 1) * WO + ox + 1) * COUT + n;
@@ -245,9 +248,10 @@ template <int COUT, int H, int SRC, bool RELU, bool RES, bool OUT_GLOBAL, int NC
 __device__ __forceinline__ void chain_layer_c4(const _Float16 *in, _Float16 *out, const _Float16 *wl, _Float16 *wl_next,
                                                const WR<NCIN, NCOUT> &wnext, const RefineChainLayer &Lfar,
                                                WR<FCIN, FCOUT> &wfar, const _Float16 *vsrc, _Float16 *vimg,
-                                               const int *tab, float *gout, _Float16 *gout16 = nullptr) {
+                                               const int *tab, float *gout, _Float16 *gout16, const int y0, const int y1) {
     typedef WGeo<4, COUT> WG;
-    constexpr int KP = WG::KP, M = H * H;
+    constexpr int KP = WG::KP;
+    const int M0 = y0 * H, M = y1 * H;                         // this workgroup's pixels: rows [y0, y1)
     constexpr int HI = SRC > 0 ? SRC : H, W2 = HI + 2, WO = H + 2;
     static_assert(COUT == 4 || COUT == 1, "output channels");
     const int tid = threadIdx.x;
@@ -272,7 +276,7 @@ __device__ __forceinline__ void chain_layer_c4(const _Float16 *in, _Float16 *out
             wv[co][t][1] = half2v{w4[2], w4[3]};
         }
     }
-    for (int px = tid; px < M; px += RC_NT) {
+    for (int px = M0 + tid; px < M; px += RC_NT) {
         const int oy = px / H, ox = px - oy * H;
         float acc[COUT];
 #pragma unroll
@@ -337,9 +341,14 @@ __device__ __forceinline__ void chain_layer_c4(const _Float16 *in, _Float16 *out
 
 }  // namespace
 
-// TIMED: stream 0 also records a timestamp per layer (SMK_CHAIN_CLK=1; see engine.cpp)
+// TIMED: stream 0's first workgroup also records a timestamp per layer (SMK_CHAIN_CLK=1; see engine.cpp)
+// wg: chain workgroup of the launch, 0 .. B * S - 1 = (band wg / B of stream wg % B) -- a stream's S workgroups land on one XCD at
+// B = 8 and share its L2 for V_x.  Every workgroup runs deconv-input .. h1.2 whole (cheap, and every band reads all of h1.2 + V1
+// through the upsampling); post1 .. post2 on its band's rows only (chain_rows.h).  No workgroup waits for another.
 template <bool TIMED>
-__device__ __forceinline__ void refine_chain_body(const RefineChainParams &p, const int b, unsigned char *smem) {
+__device__ __forceinline__ void refine_chain_body(const RefineChainParams &p, const int wg, unsigned char *smem) {
+    const int s = wg / p.B, b = wg - s * p.B;
+    const ChainRows R = chain_rows(p.S, s);
     _Float16 *bA = (_Float16 *)smem, *bB = (_Float16 *)(smem + RC_BUF), *bC = (_Float16 *)(smem + 2 * RC_BUF);
     _Float16 *w0 = (_Float16 *)(smem + 3 * RC_BUF), *w1 = (_Float16 *)(smem + 3 * RC_BUF + RC_WSTAGE);
     const _Float16 *v2 = (const _Float16 *)p.v2 + (size_t)b * (225 * 32);
@@ -349,7 +358,7 @@ __device__ __forceinline__ void refine_chain_body(const RefineChainParams &p, co
     _Float16 *gout16 = nullptr;
     if (p.ring) gout16 = p.ring + ((size_t)(*(volatile const unsigned *)p.ring_cursor % (unsigned)p.ring_rows) * p.B + b) * (127 * 127);
     int *tab = (int *)(smem + 3 * RC_BUF + 2 * RC_WSTAGE);
-    unsigned long long *clk = TIMED && p.clk && b == 0 && threadIdx.x == 0 ? p.clk : nullptr;
+    unsigned long long *clk = TIMED && p.clk && wg == 0 && threadIdx.x == 0 ? p.clk : nullptr;
     if (TIMED && clk) clk[0] = wall_clock64();
     // weights of layer i+1 / i+2 in flight (registers) while layer i computes
     WRegs<32, 32> r1;
@@ -383,17 +392,17 @@ __device__ __forceinline__ void refine_chain_body(const RefineChainParams &p, co
     if (TIMED && clk) clk[5] = wall_clock64();
     chain_layer<16, 16, 31, 0, true, true, false, 16, 4, 4, 4, 0, 0>(bB, bC, w0, w1, r5, p.L[6], r6, nullptr, nullptr, tab, nullptr);  // h1.2 + V1
     if (TIMED && clk) clk[6] = wall_clock64();
-    chain_layer<16, 4, 61, 31, false, false, false, 4, 4, 4, 4, 0, 0>(bC, bA, w1, w0, r6, p.L[7], r7, nullptr, nullptr, tab, nullptr);  // post1(up61)
+    chain_layer<16, 4, 61, 31, false, false, false, 4, 4, 4, 4, 0, 0>(bC, bA, w1, w0, r6, p.L[7], r7, nullptr, nullptr, tab, nullptr, R.post1[0], R.post1[1]);  // post1(up61)
     if (TIMED && clk) clk[7] = wall_clock64();
-    chain_layer_c4<4, 61, 0, true, false, false, 4, 4, 4, 1, 61, 4>(bA, bB, w0, w1, r7, p.L[8], r8, v0, bC, tab, nullptr);  // h0.0
+    chain_layer_c4<4, 61, 0, true, false, false, 4, 4, 4, 1, 61, 4>(bA, bB, w0, w1, r7, p.L[8], r8, v0, bC, tab, nullptr, nullptr, R.h00[0], R.h00[1]);  // h0.0
     if (TIMED && clk) clk[8] = wall_clock64();
-    chain_layer_c4<4, 61, 0, true, true, false, 4, 1, 0, 0, 0, 0>(bB, bC, w1, w0, r8, p.L[8], none, nullptr, nullptr, tab, nullptr);  // h0.2 + V0
+    chain_layer_c4<4, 61, 0, true, true, false, 4, 1, 0, 0, 0, 0>(bB, bC, w1, w0, r8, p.L[8], none, nullptr, nullptr, tab, nullptr, nullptr, R.h02[0], R.h02[1]);  // h0.2 + V0
     if (TIMED && clk) clk[9] = wall_clock64();
-    chain_layer_c4<1, 127, 61, false, false, true, 0, 0, 0, 0, 0, 0>(bC, nullptr, w0, nullptr, none, p.L[8], none, nullptr, nullptr, tab, gout, gout16);  // post2
+    chain_layer_c4<1, 127, 61, false, false, true, 0, 0, 0, 0, 0, 0>(bC, nullptr, w0, nullptr, none, p.L[8], none, nullptr, nullptr, tab, gout, gout16, R.post2[0], R.post2[1]);  // post2
     if (TIMED && clk) clk[10] = wall_clock64();
-    if (p.ring && threadIdx.x == 0) {                // the last stream's workgroup advances the ring's cursor
+    if (p.ring && threadIdx.x == 0) {                // the last of the B * S chain workgroups to arrive advances the ring's cursor
         const unsigned prev = __hip_atomic_fetch_add(p.ring_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (prev == (unsigned)p.B - 1) {
+        if (prev == (unsigned)(p.B * p.S) - 1) {
             __hip_atomic_store(p.ring_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_add(p.ring_cursor, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }

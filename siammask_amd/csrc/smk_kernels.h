@@ -188,6 +188,8 @@ struct Tuning {
                                // 128 / 64 force that workgroup height)
     int halo_db = 1;           // halo kernel: double-buffered patch when the launch has at most one workgroup per CU
     int chain = 1;             // fp16: Refine's sequential tail as one launch (refine_chain_kernel)
+    int chain_split = 0;       // workgroups per stream of that chain (row bands of its four fine layers, chain_rows.h): 0 = the rule (chain_split_rule), 1 | 2 | 4
+                               // forced; 1 is the unsplit form of rounds 1-6 and the parity tests' reference arm (every value is bit-identical)
     int ksplit = 0;            // split-K across workgroups: 0 off (default: measured a net loss at B=8, +1 % at B=1,
                                // see pick_ksplit), 1 auto (long-K few-tile launches), 2 / 4 forced (tests)
     int xc_ch = 64;            // dw_xcorr, banded kernel: channels per workgroup (64 or 32)
@@ -202,6 +204,7 @@ struct Tuning {
     int chain_mask = 1;        // fused frame step, fp16: the mask head runs inside the Refine chain launch (chain_mask_kernel); 2 = the same with the mask
                                // head on the generic 128x128 implicit-GEMM tiles, there and in its stand-alone launch, instead of the stationary-pixel
                                // tile of mask_head_tile.inc (A/B and parity arm: the logits are bit-identical)
+    int mask_nsplit = 0;       // A/B knob: channel ranges per 128-pixel tile of the stationary-pixel mask head, 0 = the rule (mask_head_nsplit), 1..15 forced
     int nchw_tn_major = 1;     // large NCHW f32 outputs (the 63x63 mask logits): tn-major tile order (see conv_params)
     int merge = 1;             // share one launch between independent convolutions (ds+c1, cls3+loc3, Refine windows): 0 never, 1 up to
                                // merge_max_batch streams (beyond it every member fills the chip by itself), 2 always
@@ -457,9 +460,10 @@ struct RefineChainParams {
     RefineChainLayer L[9];                // h2.0 h2.2 post0 h1.0 h1.2 post1 h0.0 h0.2 post2
     float *out;                           // [B][127*127] f32
     int B;
+    int S;                                // workgroups per stream (1, 2, 4): row bands of post1 .. post2 (chain_rows.h); filled by the launchers
     unsigned long long *clk;              // optional [11]: 100 MHz timestamps of workgroup 0 at the layer boundaries
-    // result ring folded into the chain: post2 also stores fp16 logits into row (*ring_cursor % ring_rows); the last workgroup
-    // to finish advances the cursor (every workgroup reads it at its start, the advance needs every workgroup's arrival)
+    // result ring folded into the chain: post2 also stores fp16 logits into row (*ring_cursor % ring_rows); the last of the B * S chain
+    // workgroups to finish advances the cursor (every workgroup reads it at its start, the advance needs every workgroup's arrival)
     _Float16 *ring;                       // [rows][B][127*127] or nullptr
     int *ring_cursor;
     unsigned *ring_done;

@@ -83,6 +83,13 @@ static const Knob KNOBS[] = {
     {"measure_build", &g_measure_build, nullptr, KNOB_RAW, nullptr},
 };
 
+// The Refine tail's geometry knobs (chain_rows.h, conv_igemm.hip) in a table of their own: tests/test_host_logic.py pins the number of rows
+// of KNOBS above; these two are read back by tests/test_chain_rows_host.py.
+static const Knob TAIL_KNOBS[] = {
+    {"chain_split", &g_tune.chain_split, "0|1|2|4", KNOB_RAW, nullptr},
+    {"mask_nsplit", &g_tune.mask_nsplit, "0..15", KNOB_RAW, nullptr},
+};
+
 static bool knob_accepts(const char *spec, int v) {
     if (!strcmp(spec, "*")) return true;
     for (const char *t = spec; t; t = strchr(t, '|') ? strchr(t, '|') + 1 : nullptr) {
@@ -99,6 +106,8 @@ static bool knob_accepts(const char *spec, int v) {
 
 static const Knob *find_knob(const char *key) {
     for (const Knob &k : KNOBS)
+        if (!strcmp(key, k.name)) return &k;
+    for (const Knob &k : TAIL_KNOBS)
         if (!strcmp(key, k.name)) return &k;
     return nullptr;
 }
